@@ -15,16 +15,18 @@ update -- random-init weights. Compute dtype: bf16 by default (BASELINE.json
 configs 2/3 "default config bf16": bf16 MFMA operands, fp32 accumulation,
 activations, master weights and optimizer state; two kernels per step at every
 W, the gradient exchange over xGMI folded into the second); ``--precision fp32``
-is the reference model's own dtype. The headline run is followed by the same
+is the reference model's own dtype. A plain run does only what the headline figure
+needs: set up, warm up, time the K steps, write the outputs (``--dump-outputs``) and
+print the JSON line. With ``--full`` the headline run is followed by the same
 measurement of the fp32 engine (same steps / warmup / protocol), reported as
 config.fp32_samples_per_s / config.fp32_ms_per_step: a same-dtype comparison with
-the reference every run (``--no-fp32-companion`` skips it).
+the reference (``--no-fp32-companion`` skips it there too).
 
 Scaling modes:
   weak (default)  per-GPU batch fixed at --batch (32 = the reference's batch), global batch = 32*N
   reference       global batch 32 split across ranks (src/trainer.py:62-64)
 
-Usage:  python bench.py --gpus N --steps K --warmup W
+Usage:  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   N > 1 under a launcher (torch.distributed.run / torchrun): one rank per GPU over RCCL.
   N > 1 without one: bench.py starts torch.distributed.run --nproc-per-node N itself.
 
@@ -32,6 +34,12 @@ Timing: every hipGraph the K timed steps replay is captured and uploaded before 
 region (a capture counter is checked after it); wall time between barrier+synchronize pairs is
 reported. The LeNet timed region holds no hipEvent (two timing-event records cost ~30 us of wall
 time per region here); per-kernel device time comes from rocprofv3 (profiles/).
+
+``--dump-outputs DIR``: after the timed steps, what the timed path left its caller in the last
+step is written as DIR/<name>.npy (float32 / float64; rank 0): the parameters, the last step's
+loss and per-sample statistics or logits, the accumulated statistics. At most 64 MB in all: a
+larger array is stored as a fixed seeded sample of its elements. Inputs, initial weights and
+augmentation are seeded, so two builds run with the same arguments can be compared file by file.
 
 BASELINE.json config 5 ("large" fp8: 24L/1024H BERT encoder, OCP fp8 forward/dgrad GEMMs with
 delayed scaling): ``--model large [--grad-accum N]`` (``--model bert-large`` = same model in bf16).
@@ -57,8 +65,16 @@ BASELINE_SAMPLES_PER_S = 892.0  # BASELINE.md headline (CPU, batch 32)
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3000)
-    ap.add_argument("--warmup", type=int, default=300)
+    ap.add_argument("--steps", type=int, default=None,
+                    help="timed steps (default 3000; 20 for the BERT models, 50 on CPU)")
+    ap.add_argument("--warmup", type=int, default=None,
+                    help="untimed steps before them (default 300; 5 for the BERT models and on CPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline run, also run the measurements its figure does not need "
+                         "(LeNet bf16: the fp32 engine under the same protocol, config.fp32_*)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step left its caller as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB in all)")
     ap.add_argument("--batch", type=int, default=None,
                     help="per-GPU batch (weak) / global batch (reference); default 32 (LeNet), "
                          "1536 (bert-base: 228 GiB), 256 (bert-large), 512 (large fp8: 245 GiB of HBM)")
@@ -91,7 +107,7 @@ def parse():
                          "operands, fp32 accumulation / activations / masters / optimizer state; 2 kernels "
                          "per step) or fp32 (the reference model's dtype; 4 kernels per step)")
     ap.add_argument("--no-fp32-companion", action="store_true",
-                    help="LeNet bf16: skip the fp32 engine measurement that follows the headline run")
+                    help="LeNet bf16 with --full: skip the fp32 engine measurement that follows the headline run")
     ap.add_argument("--transport", choices=["auto", "xgmi-loopback", "rccl-loopback"], default="auto",
                     help="LeNet, 1 GPU: time the data-parallel step against this rank itself (xgmi-loopback: "
                          "the bf16 two-launch exchange step; rccl-loopback: a real ncclAllReduce in the graph)")
@@ -135,6 +151,7 @@ def bench_bert(args, world, rank, dev):
 
     accum = max(1, args.grad_accum)
     ce = CrossEntropyLoss()
+    last = {}  # --dump-outputs: the last step's logits and loss
 
     def run(n, start):
         for i in range(n):
@@ -144,10 +161,13 @@ def bench_bert(args, world, rank, dev):
                 sync = a == accum - 1
                 ctxm = ddp.no_sync() if (world > 1 and not sync) else contextlib.nullcontext()
                 with ctxm:
-                    loss = ce(fwd(ids[j]), labels[j])  # native fused softmax-CE (src/trainer.py:141-142)
+                    logits = fwd(ids[j])
+                    loss = ce(logits, labels[j])  # native fused softmax-CE (src/trainer.py:141-142)
                     (loss / accum if accum > 1 else loss).backward()
                 loss_acc.add_(loss.detach())
             opt.step()
+        if args.dump_outputs and n:
+            last.update(logits=logits.detach(), loss=loss.detach())
 
     run(args.warmup, 0)
     torch.cuda.synchronize()
@@ -170,6 +190,10 @@ def bench_bert(args, world, rank, dev):
     elapsed = float(t.item())
     total = per_gpu * world * args.steps * accum
     value = total / elapsed
+    if args.dump_outputs and last:
+        _dump_outputs(args.dump_outputs, rank, {"params": _flat_params(model.parameters()),
+                                                "last_logits": last["logits"], "last_loss": last["loss"],
+                                                "loss_sum": loss_acc})
     comm = None
     if world > 1 and hasattr(ddp, "comm_stats"):
         comm = ddp.comm_stats()  # bucket layout + comm backend; hipEvent timings with --ddp-timing
@@ -263,6 +287,35 @@ def _emit(out, rank, args):
                 f.write(line + "\n")
 
 
+DUMP_LIMIT_BYTES = 64 * 2 ** 20  # --dump-outputs: all files together
+
+
+def _flat_params(params):
+    import torch
+    return torch.cat([p.detach().reshape(-1).float() for p in params])
+
+
+def _dump_outputs(dump_dir, rank, arrays):
+    """--dump-outputs: ``arrays`` {name: tensor} as DIR/<name>.npy on rank 0, float64 kept and
+    everything else as float32. Each array may take an equal share of 3/4 of the 64 MB limit; a
+    larger one is stored as a fixed sample of its flattened elements (sorted indices drawn with a
+    CPU generator seeded by the array's size alone, so two builds sample the same elements)."""
+    if not dump_dir or rank != 0:
+        return
+    import numpy as np
+    import torch
+    os.makedirs(dump_dir, exist_ok=True)
+    share = DUMP_LIMIT_BYTES * 3 // 4 // max(1, len(arrays))
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t if t.dtype == torch.float64 else t.float()
+        if t.numel() * t.element_size() > share:
+            g = torch.Generator().manual_seed(t.numel())
+            idx = torch.randint(0, t.numel(), (share // t.element_size(),), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(dump_dir, name + ".npy"), t.cpu().numpy())
+
+
 def bench_cpu(args, world, rank):
     """BASELINE config 1 (tiny/default LeNet on CPU, gloo): plumbing path with stock torch ops,
     the native DDP bucket engine over gloo and the flat optimizer's CPU implementation."""
@@ -283,14 +336,18 @@ def bench_cpu(args, world, rank):
     xs = torch.randn(4, per_gpu, 3, 32, 32, generator=g)
     ys = torch.randint(0, 10, (4, per_gpu), generator=g)
     loss_acc = torch.zeros(())
+    last = {}  # --dump-outputs: the last step's logits and loss
 
     def run(n, start):
         for i in range(n):
             opt.zero_grad(set_to_none=False)
-            loss = F.cross_entropy(fwd(xs[(start + i) % 4]), ys[(start + i) % 4])
+            logits = fwd(xs[(start + i) % 4])
+            loss = F.cross_entropy(logits, ys[(start + i) % 4])
             loss.backward()
             opt.step()
             loss_acc.add_(loss.detach())
+        if args.dump_outputs and n:
+            last.update(logits=logits.detach(), loss=loss.detach())
 
     run(args.warmup, 0)
     if world > 1:
@@ -305,6 +362,10 @@ def bench_cpu(args, world, rank):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     value = per_gpu * world * args.steps / elapsed
+    if args.dump_outputs and last:
+        _dump_outputs(args.dump_outputs, rank, {"params": _flat_params(model.parameters()),
+                                                "last_logits": last["logits"], "last_loss": last["loss"],
+                                                "loss_sum": loss_acc})
     return {
         "metric": "samples/sec/node", "value": round(value, 1), "unit": "samples/s", "n_gpus": world,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
@@ -318,7 +379,7 @@ def bench_cpu(args, world, rank):
     }
 
 
-def bench_lenet(args, world, rank, dev, backend, precision):
+def bench_lenet(args, world, rank, dev, backend, precision, dump_dir=None):
     """The LeNet headline (BASELINE.json metric): the fused step engine on an HBM-resident
     synthetic dataset, every hipGraph captured before the timed region."""
     import torch
@@ -436,6 +497,11 @@ def bench_lenet(args, world, rank, dev, backend, precision):
     # sanity: training actually ran (finite loss accumulated on device); transport healthy
     loss_sum = float(engine.stats[0].item())
     engine.check_transport()
+    if dump_dir and args.steps > 0:
+        # what the engine's caller holds after the last timed step: the fp32 parameters, the loss and
+        # accuracy sums over every step run, the last step's per-sample (loss / B, hit / B)
+        _dump_outputs(dump_dir, rank, {"params": _flat_params(model.parameters()), "stats": engine.stats,
+                                       "last_step_sample_stats": engine.bufs["cestat"]})
     value = total_samples / elapsed
     ms_per_step = elapsed / args.steps * 1e3
     nodes = engine.eng.graph_nodes(engine._train_mode(), per_gpu, spg) if use_graph else 0
@@ -486,6 +552,15 @@ def bench_lenet(args, world, rank, dev, backend, precision):
     return out
 
 
+def _default_steps(args, steps, warmup):
+    """--steps / --warmup as given; when neither is, this mode's defaults (one alone leaves the
+    other at the LeNet default)."""
+    if args.steps is None and args.warmup is None:
+        args.steps, args.warmup = steps, warmup
+    args.steps = 3000 if args.steps is None else args.steps
+    args.warmup = 300 if args.warmup is None else args.warmup
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -521,8 +596,7 @@ def main():
     if args.device == "cpu" or not torch.cuda.is_available():
         if world > 1:
             dist.init_process_group("gloo")
-        if args.steps == 3000 and args.warmup == 300:
-            args.steps, args.warmup = 50, 5
+        _default_steps(args, 50, 5)
         _emit(bench_cpu(args, world, rank), rank, args)
         if world > 1:
             dist.barrier()
@@ -540,8 +614,7 @@ def main():
         world = dist.get_world_size()
 
     if args.model in ("bert-base", "bert-tiny", "bert-large", "large"):
-        if args.steps == 3000 and args.warmup == 300:  # LeNet-sized defaults -> BERT-sized
-            args.steps, args.warmup = 20, 5
+        _default_steps(args, 20, 5)  # BERT-sized
         r = bench_bert(args, world, rank, dev)
         r["config"]["host_sync"] = "spin" if spin else "default"
         _emit(r, rank, args)
@@ -550,9 +623,10 @@ def main():
             dist.destroy_process_group()
         return
 
-    out = bench_lenet(args, world, rank, dev, backend, args.precision)
+    _default_steps(args, 3000, 300)
+    out = bench_lenet(args, world, rank, dev, backend, args.precision, dump_dir=args.dump_outputs)
     out["config"]["host_sync"] = "spin" if spin else "default"
-    if args.precision == "bf16" and not args.no_fp32_companion:
+    if args.full and args.precision == "bf16" and not args.no_fp32_companion:
         # same-dtype comparison with the reference (fp32), same protocol, after the headline run
         comp = bench_lenet(args, world, rank, dev, backend, "fp32")
         out["config"]["fp32_samples_per_s"] = comp["value"]
