@@ -1,7 +1,9 @@
 """Per-phase timing of the bf16 per-sample LeNet kernel (lenet_mfma.hip, LENET_TRACE): block 0
 stores s_memtime stamps at every phase boundary (each stamp adds a barrier, so the sum runs a
 little over the untraced kernel). Needs a trace build (-DMLT_LENET_TRACE_BUILD=1: the stamps are
-compiled out of the shipped kernel). Usage: python benchmarks/lenet_bf16_phases.py [batch] [--jsonl F]"""
+compiled out of the shipped kernel). With the split tail (two blocks per sample; MLT_LENET_SPLIT=0
+turns it off) block 0 is role D's, whose conv1 wgrad runs on waves 7-13, and the role-W blocks' end
+times are reported against it. Usage: python benchmarks/lenet_bf16_phases.py [batch] [--jsonl F]"""
 import json
 import os
 import sys
@@ -98,6 +100,19 @@ ks_end = max(e for _, e in ks)
 print(f"KS blocks: start spread {(max(a for a, _ in ks) - t0) * 10} ns, block time "
       f"{min(e - a for a, e in ks) * 10}..{max(e - a for a, e in ks) * 10} ns, last end at {(ks_end - t0) * 10} ns")
 rec["ks_block_ns"] = [[(a - t0) * 10, (e - t0) * 10] for a, e in ks]
+# split tail (two blocks per sample): the phases above are role D's block 0; the role-W blocks'
+# wall clock follows role D's in the per-block slots (sample i: slot 600 + 2 (B + i))
+rec["split"] = split = bool(eng.eng.split_active(B))
+if split:
+    kwr = [(tr[600 + 2 * (B + i)], tr[601 + 2 * (B + i)]) for i in range(B) if B + i < 200]
+    if kwr and all(a and e for a, e in kwr):
+        print(f"split: role W of sample 0 ends {(kwr[0][1] - ks[0][1]) * 10} ns after role D's block 0 ends "
+              f"(negative: before); role W blocks start {(min(a for a, _ in kwr) - t0) * 10}.."
+              f"{(max(a for a, _ in kwr) - t0) * 10} ns, end {(min(e for _, e in kwr) - t0) * 10}.."
+              f"{(max(e for _, e in kwr) - t0) * 10} ns after the first role D start")
+        rec["ks_role_w_block_ns"] = [[(a - t0) * 10, (e - t0) * 10] for a, e in kwr]
+        rec["role_w_end_minus_role_d_end_ns"] = (kwr[0][1] - ks[0][1]) * 10
+        ks_end = max(ks_end, max(e for _, e in kwr))
 if kw:
     k0 = min(a for a, _ in kw)
     print(f"KW blocks ({nkw}): first start {(k0 - ks_end) * 10} ns after the last KS end; start spread "

@@ -1071,6 +1071,9 @@ class LeNetEngine {
       P_.prep = get("prep", at::kByte, B * 8192).data_ptr<uint8_t>();
       P_.pmeta = get("pmeta", at::kLong, B * 4).data_ptr<int64_t>();
     }
+    // bf16 per-sample kernel with two blocks per sample where eligible (MLT_LENET_SPLIT=0: off, for A/B)
+    const char* se = std::getenv("MLT_LENET_SPLIT");
+    split_ = !(se && std::string(se) == "0");
     A_ = LeNetAug{};
     O_ = LeNetOpt{};
   }
@@ -1185,6 +1188,22 @@ class LeNetEngine {
     graphs_.clear();
   }
   bool fused_dp() const { return fused_dp_; }
+  // bf16 training step: two blocks per sample in the per-sample kernel (the launch still falls back
+  // to one where the split is not eligible: split_active)
+  void set_split(bool s) {
+    split_ = s;
+    graphs_.clear();
+  }
+  bool split() const { return split_; }
+  // what a bf16 training launch at batch B would do with the current dataset / buffers
+  bool split_active(int B) const {
+    if (prec_ != 1 || B <= 0 || B > max_b_) return false;
+    return lenet_mfma_split_active(split_bits(LENET_FWD | LENET_CE | LENET_BWD), B, P_, A_);
+  }
+  // (the switch travels to the bf16 step's launch as an internal mode bit; no other kernel sees it)
+  int split_bits(int mode) const {
+    return split_ || prec_ != 1 || !(mode & LENET_BWD) ? mode : mode | LENET_NOSPLIT;
+  }
 
   void check_mode(int mode, int B) const {
     TORCH_CHECK(B > 0 && B <= max_b_, "batch ", B, " outside [1, ", max_b_, "]");
@@ -1205,7 +1224,7 @@ class LeNetEngine {
     check_mode(mode, B);
     const bool mf = prec_ == 1 && (mode & LENET_BWD);
     if (mf) launch_lenet_mfma_pack(cfg_, P_, O_, cur_stream());  // shadow / fragment image from the masters
-    launch_step(cfg_, mode, B, P_, A_, O_, comm_, xgmi_, cur_stream(), mf, fused_dp_);
+    launch_step(cfg_, split_bits(mode), B, P_, A_, O_, comm_, xgmi_, cur_stream(), mf, fused_dp_);
   }
 
   // transport bring-up: the batch reductions of the current activation / slab buffers into the
@@ -1277,9 +1296,10 @@ class LeNetEngine {
     XgmiAllReduce* xgmi = xgmi_;
     const bool mf = prec_ == 1 && (mode & LENET_BWD);
     const bool fused = fused_dp_;
+    const int lmode = split_bits(mode);
     g->capture([&](hipStream_t s) {
       // (no pack here: replay() re-packs when the host changed the masters since the last pack)
-      for (int i = 0; i < nsteps; ++i) launch_step(cfg, mode, B, P, A, O, comm, xgmi, s, mf, fused);
+      for (int i = 0; i < nsteps; ++i) launch_step(cfg, lmode, B, P, A, O, comm, xgmi, s, mf, fused);
     });
     graphs_[key(mode, B, nsteps)] = std::move(g);
   }
@@ -1331,6 +1351,7 @@ class LeNetEngine {
   std::map<int64_t, std::unique_ptr<HipGraph>> graphs_;
   int prec_ = 0;
   bool fused_dp_ = true;
+  bool split_ = true;
   int64_t shadow_n_ = 0;
   Tensor master_;          // the fp32 masters (version counter: host-side changes)
   int64_t pack_ver_ = -1;  // master_._version() at the last pack
@@ -1467,6 +1488,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("set_comm", &LeNetEngine::set_comm)
       .def("set_xgmi", &LeNetEngine::set_xgmi)
       .def_property("fused_dp", &LeNetEngine::fused_dp, &LeNetEngine::set_fused_dp)
+      .def("set_split", &LeNetEngine::set_split)
+      .def("split", &LeNetEngine::split)
+      .def("split_active", &LeNetEngine::split_active, py::arg("B"))
       .def("clear_aug", &LeNetEngine::clear_aug)
       .def("set_ctrl", &LeNetEngine::set_ctrl)
       .def("set_opt", &LeNetEngine::set_opt)

@@ -42,6 +42,7 @@ enum LeNetMode : int {
   LENET_PROBE_NOF1T = 1 << 17,  // role A skips the fc1 dgrad (transposed) weight fetch
   LENET_PROBE_NOF1W = 1 << 18,  // role B skips the fc1 forward weight fetch
   LENET_PROBE_NOF2 = 1 << 19,   // fc2 forward + dgrad weight fetches skipped
+  LENET_NOSPLIT = 1 << 20,      // internal: the bf16 per-sample kernel runs one block per sample (engine switch off)
 };
 
 struct LeNetPtrs {
@@ -107,6 +108,8 @@ void launch_head_cls_bwd(const float* dlogits, const float* pooled, const float*
 // reductions / optimizer). Needs stage2 / meta2 / stepinfo / shadow, and slab1 >= B * slab floats.
 void launch_lenet_mfma(int cfg, int mode, int B, const LeNetPtrs& P, const LeNetAug& A, const LeNetOpt& O,
                        hipStream_t stream);
+// whether that step's per-sample kernel would run two blocks per sample at batch B (split tail)
+bool lenet_mfma_split_active(int mode, int B, const LeNetPtrs& P, const LeNetAug& A);
 int lenet_mfma_slab_floats(int cfg);
 int lenet_mfma_kw_blocks(int cfg);  // grid of the batch-reduction / optimizer kernel
 // data-parallel bf16 step: optimizer update from the all-reduced gradient + bf16 shadow + fragment

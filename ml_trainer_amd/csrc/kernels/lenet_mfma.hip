@@ -4,15 +4,16 @@
 namespace mlt {
 namespace lm {
 void launch_ms(int cfg, int mode, int B, const LeNetPtrs& P, const LeNetAug& A, const LeNetOpt& O, hipStream_t st) {
-  const float inv_B = 1.f / (float)B;
   if (cfg == LENET_TINY)
-    hipLaunchKernelGGL(lenet_ms<DmTiny>, dim3(B), dim3(kT), 0, st, P.stage2, P.meta2, A.ctrl, P.wimg, P.metaN, mode,
-                       inv_B, P, A, O, B);
+    launch_ms_t<DmTiny>(mode, B, P, A, O, st);
   else
-    hipLaunchKernelGGL(lenet_ms<DmDefault>, dim3(B), dim3(kT), 0, st, P.stage2, P.meta2, A.ctrl, P.wimg, P.metaN, mode,
-                       inv_B, P, A, O, B);
+    launch_ms_t<DmDefault>(mode, B, P, A, O, st);
 }
 }  // namespace lm
+
+bool lenet_mfma_split_active(int mode, int B, const LeNetPtrs& P, const LeNetAug& A) {
+  return lm::split_eligible(mode, B, P, A);
+}
 
 void launch_lenet_mfma_reduce(int cfg, int B, const LeNetPtrs& P, const LeNetOpt& O, const XgmiFused* X,
                               hipStream_t stream) {

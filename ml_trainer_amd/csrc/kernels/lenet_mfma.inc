@@ -10,6 +10,9 @@
 //       pixels the previous KW's prep blocks made (tag hit: one load); without prep buffers the
 //       NEXT step's raw image is gathered (epoch permutation -> dataset row) and staged by an
 //       otherwise idle wave instead.
+//       lenet_ms<D, true> (grid 2 B, where 2 B fits the CUs): a second CU per sample recomputes the
+//       chain up to the fc1 dgrad and takes the stores, the staging and the conv2 wgrad off the
+//       first one's conv2 dgrad -> conv1 wgrad chain (see the kernel).
 //       The ~250 KB of fc weight fragments a CU fetches per step are the other cost besides the
 //       latency chain (a CU's vector memory path moves ~35 B/clk and a wave stalls while its loads
 //       queue), so fetches go to waves without work in that phase: waves 8-15 fetch fc1 while 0-7
@@ -414,8 +417,29 @@ __device__ __forceinline__ void pool4(f32x4 a, float bias, float& pv, uint8_t& c
 // ---------------------------------------------------------------------------
 // KS: the per-sample chain
 // ---------------------------------------------------------------------------
-// The per-sample kernel of the two-launch step (grid B).
-template <class D>
+// The per-sample kernel of the two-launch step (grid B; SPLIT: grid 2 B).
+//
+// SPLIT: two workgroups per sample, on two CUs. Blocks [0, B) are role D (dgrad), blocks [B, 2 B)
+// role W (wgrad) of sample blockIdx.x - B. Both run P0 .. P8 on the same inputs with the same
+// arithmetic, so each holds bit for bit what the single block holds; then the tail's two independent
+// halves part ways: role D runs the conv2 dgrad -> conv1 wgrad chain (the critical path), role W
+// everything else (the stores for KW, the next-step staging, the conv2 wgrad) and returns. The two
+// blocks of a sample never synchronise or communicate: no flag, counter or poll.
+// Global memory audit (SPLIT): every location is written by exactly one role, and nothing one role
+// writes is read by the other role in the same launch.
+//   written by role W only: stage2 / meta2 / metaN rows b (staging wave 7); p2, h1, h2, dh2, logits,
+//     dlogits, cestat rows b (P5); dflat, dh1 rows b, targets[b], stepinfo (block B: b == 0) (P10);
+//     slab1 row b, the conv2 part [S2OFF, S2OFF + S2)
+//   written by role D only: slab1 row b, the conv1 part [0, S1); the LENET_TRACE phase stamps (block 0)
+//   written by both, to distinct slots: the LENET_TRACE per-block wall clock (slot by blockIdx.x)
+//   read by both: ctrl, pmeta / prep rows b (written by KW only), wimg, shadow, the biases, x, perm,
+//     data, dtargets, targets[b] (read only without a dataset, written only with one)
+//   read by role W only: metaN row b (its own staging wave, before that wave rewrites it), lr table
+//   the one conflict: with a dataset but without prep buffers P0 reads stage2 / meta2 rows b, which
+//     the staging wave rewrites later -- ordered inside one block, a race across two. The host never
+//     launches SPLIT there (split_eligible). Without a dataset P0 still loads those rows (unused),
+//     but nothing stages, so nothing writes them.
+template <class D, bool SPLIT>
 // The pointers the first loads need lead the argument list as plain scalars: the file is built with
 // kernarg preloading (build.py), so they arrive in SGPRs with the wave instead of behind an s_load
 // of the kernarg segment (aggregates are never preloaded).
@@ -431,7 +455,12 @@ __global__ __launch_bounds__(kT) void lenet_ms(uint8_t* __restrict__ pstage2, in
   __shared__ S L;
   // w is wave-uniform: readfirstlane makes the per-wave role branches scalar (uniform) branches,
   // so a role's pending loads never force waits on the other roles' code paths
-  const int b = (int)blockIdx.x, t = threadIdx.x, lane = t & 63, g = lane >> 4, m = lane & 15;
+  // the role is block-uniform (an SGPR); without SPLIT every block does both halves of the tail
+  // (doW / doD fold to true)
+  const int bi = (int)blockIdx.x;
+  const bool roleW = SPLIT && bi >= B;
+  const bool doW = !SPLIT || roleW, doD = !SPLIT || !roleW;
+  const int b = roleW ? bi - B : bi, t = threadIdx.x, lane = t & 63, g = lane >> 4, m = lane & 15;
   const int w = __builtin_amdgcn_readfirstlane(t >> 6);
   // LENET_TRACE: s_memtime stamps of block 0 per phase (P.trace: 32 8-byte slots; 100 MHz wall
   // stamps at 14, 15; sub-phase stamps at 16..)
@@ -516,7 +545,7 @@ __global__ __launch_bounds__(kT) void lenet_ms(uint8_t* __restrict__ pstage2, in
   }
   // next-step staging wave (see P3): wave 15 (role B) when this kernel gathers its own input next
   // step, else wave 7 (role A, idle in P3 .. P4c) for the prep blocks of this step's batch reduction
-  const bool stage_on = aug && w == (pre_on ? 7 : 15);
+  const bool stage_on = aug && doW && w == (pre_on ? 7 : 15);
   // (vector loads, issued before the bulk: scalar ones would be waited for by every LDS barrier's
   // lgkmcnt(0), and the staging decision they feed is taken in P2, off the critical path)
   longlong2 mN01 = make_longlong2(-1, -1);
@@ -670,11 +699,13 @@ __global__ __launch_bounds__(kT) void lenet_ms(uint8_t* __restrict__ pstage2, in
   stamp(2);
 
   // conv2 dgrad fragments (to LDS in P10; loading them later, in P6, measured slower: r6d)
-  const uint4 wid = __builtin_bit_cast(uint4, ld16(pwimg, (unsigned)(kW2D + 8 * min(t, WID - 1))));
+  // (SPLIT: role D's alone -- role W runs no dgrad)
+  uint4 wid = make_uint4(0u, 0u, 0u, 0u);
+  if (doD) wid = __builtin_bit_cast(uint4, ld16(pwimg, (unsigned)(kW2D + 8 * min(t, WID - 1))));
   // the step's lr for KW's optimizer context (stepinfo, stored in P10): a vector load issued here, so
   // that no wave waits on a load round trip at the end of the kernel (the step counters arrived in P1)
   float lr_step = O.h.lr;
-  if (b == 0 && t == 0 && P.stepinfo && O.lr_ptr) lr_step = O.lr_ptr[O.lr_table ? sie : 0];
+  if (doW && b == 0 && t == 0 && P.stepinfo && O.lr_ptr) lr_step = O.lr_ptr[O.lr_table ? sie : 0];
 
   // ---- P3-P7 as two wave roles (the same barrier sequence in both), then P8 on every wave ---------
   // waves 0-7 fetch the fc3 / fc2 dgrad fragments during conv2 and run that dgrad chain; waves 8-15
@@ -909,7 +940,9 @@ __global__ __launch_bounds__(kT) void lenet_ms(uint8_t* __restrict__ pstage2, in
     // dgrad (role B has no load outstanding since P3): p2 on waves 8-14, the rest on wave 15
     // (spread over all 512 role-B threads, both LDS reads in flight before the stores, it measured
     // 0.1 us per step slower: profiles/r6/lenet_rb_store_ab_r6t.jsonl)
-    if (w < 15) {
+    // (SPLIT: role W's alone)
+    if (!doW) {
+    } else if (w < 15) {
       for (int e = t - 512; e < FLAT; e += 448) P.p2[(int64_t)b * FLAT + e] = L.f32[e];
     } else {
       for (int e = lane; e < F1; e += 64) P.h1[(int64_t)b * F1 + e] = L.sh1[e];
@@ -940,25 +973,27 @@ __global__ __launch_bounds__(kT) void lenet_ms(uint8_t* __restrict__ pstage2, in
   stamp(22);
   {
     {
+      // (SPLIT: a role fills only the images its own tail reads -- dch and d1 feed the dgrad chain
+      // of role D, dcc the conv2 wgrad of role W; the values written are the same either way)
       constexpr int NPIX = 18 * DCHS;  // dch border: the pixels outside [4, 14) x [4, 14), 2 uint4 each
-      for (int e = t; e < 2 * NPIX; e += kT) {
+      for (int e = t; doD && e < 2 * NPIX; e += kT) {
         const int pix = e >> 1, Y = pix / DCHS, X = pix - DCHS * Y;
         if (Y < 4 || Y >= 14 || X < 4 || X >= 14)
           reinterpret_cast<uint4*>(L.v.k.dch)[2 * pix + (e & 1)] = make_uint4(0u, 0u, 0u, 0u);
       }
       static_assert(DCCS == 24, "dcc pad layout");
-      for (int e = t; e < 160 * 7; e += kT) {  // dcc columns 10 .. 23 of its 160 rows (7 u32)
+      for (int e = t; doW && e < 160 * 7; e += kT) {  // dcc columns 10 .. 23 of its 160 rows (7 u32)
         const int r = e / 7, k = e - 7 * r;
         reinterpret_cast<unsigned*>(L.v.k.dcc + r * DCCS + 10)[k] = 0u;
       }
       constexpr int D1Q = D::C1 * D1S * 2 / 16;
       static_assert((D::C1 * D1S * 2) % 16 == 0, "d1 zero fill");
-      for (int e = t; e < D1Q; e += kT) reinterpret_cast<uint4*>(L.v.k.d1)[e] = make_uint4(0u, 0u, 0u, 0u);
+      for (int e = t; doD && e < D1Q; e += kT) reinterpret_cast<uint4*>(L.v.k.d1)[e] = make_uint4(0u, 0u, 0u, 0u);
       if constexpr (C2 < 16) {  // channels C2 .. 15 of both images' interior cells (tiny config)
         for (int e = t; e < 100 * (16 - C2); e += kT) {
           const int oc = C2 + e / 100, q = e % 100, Y = q / 10, X = q - 10 * Y;
-          L.v.k.dch[((Y + 4) * DCHS + X + 4) * 16 + oc] = 0;
-          L.v.k.dcc[(oc * 10 + Y) * DCCS + X] = 0;
+          if (doD) L.v.k.dch[((Y + 4) * DCHS + X + 4) * 16 + oc] = 0;
+          if (doW) L.v.k.dcc[(oc * 10 + Y) * DCCS + X] = 0;
         }
       }
     }
@@ -974,12 +1009,12 @@ __global__ __launch_bounds__(kT) void lenet_ms(uint8_t* __restrict__ pstage2, in
         for (int q = 0; q < F1M::B1K; ++q) acc = mfma(ah[q], f1t_frag<F1, FLAT>(L.u.f1img, tile, q), acc);
         const int c = 16 * tile + m;
         if (c < FLAT) {  // (oc < C2)
-          if (g == 0) L.df[c] = acc[0];
+          if (doW && g == 0) L.df[c] = acc[0];  // (stored as dflat in P10)
           const int oc = c / 25, cell = c - 25 * oc, py = cell / 5, pxx = cell - 5 * py;
           const int Y = 2 * py + (g >> 1), X = 2 * pxx + (g & 1);
           const uint16_t o = (int)L.i2[c] == g ? f32_to_bf16(acc[0]) : (uint16_t)0;
-          L.v.k.dch[((Y + 4) * DCHS + X + 4) * 16 + oc] = o;
-          L.v.k.dcc[(oc * 10 + Y) * DCCS + X] = o;
+          if (doD) L.v.k.dch[((Y + 4) * DCHS + X + 4) * 16 + oc] = o;
+          if (doW) L.v.k.dcc[(oc * 10 + Y) * DCCS + X] = o;
         }
       }
     }
@@ -991,11 +1026,16 @@ __global__ __launch_bounds__(kT) void lenet_ms(uint8_t* __restrict__ pstage2, in
   // ---- P10: the conv2 dgrad fragments to LDS (their slot aliased the fc1 image, read until P8);
   //      the last activations / gradients and the step context for KW stored (no load of this
   //      kernel is waited for after this point)
-  if (t < WID) reinterpret_cast<uint4*>(L.u.b.w2d)[t] = wid;
+  //      (SPLIT: the fragments are role D's, the stores role W's)
+  if (doD && t < WID) reinterpret_cast<uint4*>(L.u.b.w2d)[t] = wid;
   static_assert(FLAT <= 512 && F1 <= 512, "P10 store mapping");
-  if (t < FLAT) P.dflat[(int64_t)b * FLAT + t] = L.df[t];
-  else if (t >= 512 && t < 512 + F1) P.dh1[(int64_t)b * F1 + t - 512] = L.sdh1[t - 512];
-  if (t == 0) {
+  if (!doW) {
+  } else if (t < FLAT) {
+    P.dflat[(int64_t)b * FLAT + t] = L.df[t];
+  } else if (t >= 512 && t < 512 + F1) {
+    P.dh1[(int64_t)b * F1 + t - 512] = L.sdh1[t - 512];
+  }
+  if (doW && t == 0) {
     if (aug && P.targets) P.targets[b] = tgt;  // (inspection; nothing downstream reads it)
     if (b == 0 && P.stepinfo) {  // the step's optimizer context for KW (lr from the device table, Adam's t)
       P.stepinfo[0] = step;
@@ -1003,8 +1043,6 @@ __global__ __launch_bounds__(kT) void lenet_ms(uint8_t* __restrict__ pstage2, in
       P.stepinfo[2] = (int64_t)__float_as_uint(lr_step);
     }
   }
-  lbar();
-  stamp(6);
 
   // ---- P11: conv2 dgrad (waves 0-6) -> liveness mask -> unpooled conv1 grad d1 -----------------
   //           conv2 wgrad of the sample (waves 7-15) -> slab
@@ -1012,8 +1050,15 @@ __global__ __launch_bounds__(kT) void lenet_ms(uint8_t* __restrict__ pstage2, in
   // (in channel, x parity), K = (kh, u, oc16) with kw = u - 1 + dx: 7 tiles x 15 k-steps
   // (the operand reads of both roles issued 4 k-steps / a whole tile ahead, pinned with
   // sched_group_barrier, measured 0.1 us per step slower: profiles/r6/lenet_p11_prefetch_ab_r6p.jsonl)
+  // (re-tried in the split kernel's role D, the wgrad waves gone from its CU: the dgrad's reads 4
+  // k-steps ahead end the MFMAs of waves 0-3 at ~1000 instead of ~1400 cycles, but waves 4-6 --
+  // second on their SIMDs -- and the d1 scatter still close the phase at 3392 vs 3396 cycles;
+  // 15.05 vs 15.05 us per step: profiles/r7/lenet_split_p11_ahead_ab.jsonl)
+  // SPLIT: role D runs the dgrad on waves 0-6 while its waves 7-13 read the input rows of their
+  // conv1 wgrad (P13) into registers; role W runs the wgrad's 10 tiles on waves 6-15, one each (a
+  // tile is one wave's own accumulator chain: the same bits on any wave), and returns.
   float* slab = P.slab1 + (int64_t)b * D::SLABN;
-  if (w < 7) {
+  auto dgrad = [&]() __attribute__((always_inline)) {
     const int pidx = min(16 * w + m, 97), Y = pidx % 14, xp = pidx / 14;
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -1037,12 +1082,10 @@ __global__ __launch_bounds__(kT) void lenet_ms(uint8_t* __restrict__ pstage2, in
         }
       }
     }
-  } else {
-    // 10 M-tiles over waves 7-15 (wave 7: two): tile tt = (kw, half); rows (ic, kh) = 16 * half + m;
-    // row 31 of tile 1 = ones (bias). Wave 15's staging stores were issued in P10.
-    const int t0 = w - 7, t1 = w == 7 ? 2 : w - 6;
-    for (int tt0 = t0; tt0 < t1; ++tt0) {
-      const int tt = w == 7 && tt0 == 1 ? 9 : tt0;
+  };
+  // conv2 wgrad M-tile tt = (kw, half); rows (ic, kh) = 16 * half + m; row 31 of tile 1 = ones (bias)
+  auto wgrad_tile = [&](int tt) __attribute__((always_inline)) {
+    {
       // the window shift kw is wave-uniform: one dispatch per tile, then a branch-free unrolled
       // K loop with the shift as a compile-time constant (a switch inside the loop cost a branch
       // and an lgkmcnt(0) wait per step)
@@ -1077,21 +1120,42 @@ __global__ __launch_bounds__(kT) void lenet_ms(uint8_t* __restrict__ pstage2, in
         default: tile(std::integral_constant<int, 4>{}); break;
       }
     }
-  }
-  wstamp(3);
-  lbar();
-  stamp(7);
-
-  // ---- P13: conv1 wgrad (waves 0-6: 4 output rows Y each, all 5 kw tiles) ---------------------
+  };
+  // LENET_TRACE: this block's wall clock (slots 600 + 2 blockIdx (+1); SPLIT: role W's blocks follow
+  // role D's, so slot 600 + 2 B (+1) is when the role-W block of sample 0 started / ended)
+  auto block_clock = [&]() {
+    if constexpr (!kTraceBuild) return;
+    if (!((mode & LENET_TRACE) && P.trace && bi < 200)) return;
+    lbar();
+    if (t == 0) {
+      reinterpret_cast<unsigned long long*>(P.trace)[600 + 2 * bi] = tb0;
+      reinterpret_cast<unsigned long long*>(P.trace)[601 + 2 * bi] = __builtin_amdgcn_s_memrealtime();
+    }
+  };
+  auto p11_end = [&]() __attribute__((always_inline)) {
+    wstamp(3);
+    lbar();
+    stamp(7);
+  };
+  // ---- P13: conv1 wgrad (7 waves: 4 output rows Y each, all 5 kw tiles) -----------------------
   // One read of the input rows (lo / hi) and of the gradient row feeds the five kw-shifted
   // windows' MFMAs: 84 operand reads in all (450 with one tile per wave); the 7 row-range partials
   // are summed in a fixed order. (Split over 14 waves -- kw 0-2 / 3-4 -- it measured slower: the
   // second group re-reads the rows, r6e.)
-  if (w < kP13W) {
+  // input rows of row range `slot`, row yy (they do not depend on d1)
+  auto c1w_row = [&](int slot, int yy, u32x4& lo, u32x4& hi) __attribute__((always_inline)) {
     const int c = m / 5, kh = m - 5 * c;
     const bool valid = m < 15;
+    const uint16_t* xrow = L.xc + ((valid ? c : 0) * 32 + (valid ? kh : 0)) * XCS + 8 * g;
+    const int Y = (28 / kP13W) * slot + yy;
+    lo = *reinterpret_cast<const u32x4*>(xrow + Y * XCS);
+    hi = *reinterpret_cast<const u32x4*>(xrow + Y * XCS + 8);
+  };
+  // row range `slot` -> partial slot `slot`; PRE: the input rows are already in plo / phi
+  auto c1w = [&](int slot, auto PREc, const u32x4* plo, const u32x4* phi) __attribute__((always_inline)) {
+    constexpr bool PRE = decltype(PREc)::value;
+    const bool valid = m < 15;
     const int x0 = 8 * g;
-    const uint16_t* xrow = L.xc + ((valid ? c : 0) * 32 + (valid ? kh : 0)) * XCS + x0;
     const uint16_t* drow = L.v.k.d1 + min(m, C1 - 1) * D1S + x0;
     constexpr u32x4 ONES = {0x3F803F80u, 0x3F803F80u, 0x3F803F80u, 0x3F803F80u};  // bias row (m = 15, kw = 0)
     const u32x4 Z = {0u, 0u, 0u, 0u};
@@ -1100,10 +1164,16 @@ __global__ __launch_bounds__(kT) void lenet_ms(uint8_t* __restrict__ pstage2, in
     for (int k = 0; k < 5; ++k) acc[k] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int yy = 0; yy < 28 / kP13W; ++yy) {
-      const int Y = (28 / kP13W) * w + yy;
+      const int Y = (28 / kP13W) * slot + yy;
       u32x4 bq = *reinterpret_cast<const u32x4*>(drow + Y * 32);
       if (m >= C1) bq = Z;
-      const u32x4 lo = *reinterpret_cast<const u32x4*>(xrow + Y * XCS), hi = *reinterpret_cast<const u32x4*>(xrow + Y * XCS + 8);
+      u32x4 lo, hi;
+      if constexpr (PRE) {
+        lo = plo[yy];
+        hi = phi[yy];
+      } else {
+        c1w_row(slot, yy, lo, hi);
+      }
       acc[0] = mfma(valid ? fshift<0>(lo, hi) : (m == 15 ? ONES : Z), bq, acc[0]);
       acc[1] = mfma(valid ? fshift<1>(lo, hi) : Z, bq, acc[1]);
       acc[2] = mfma(valid ? fshift<2>(lo, hi) : Z, bq, acc[2]);
@@ -1113,7 +1183,43 @@ __global__ __launch_bounds__(kT) void lenet_ms(uint8_t* __restrict__ pstage2, in
 #pragma unroll
     for (int kw = 0; kw < 5; ++kw)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) L.u.b.scr[((w * 5 + kw) * 16 + 4 * g + r) * 16 + m] = acc[kw][r];
+      for (int r = 0; r < 4; ++r) L.u.b.scr[((slot * 5 + kw) * 16 + 4 * g + r) * 16 + m] = acc[kw][r];
+  };
+  if constexpr (SPLIT) {
+    if (roleW) {  // (its operands, dcc and p1c, were complete at the barrier that closed P8)
+      if (w >= 6) wgrad_tile(w - 6);
+      wstamp(3);
+      block_clock();
+      return;
+    }
+    lbar();
+    stamp(6);
+    // three wave groups with the same barrier sequence
+    if (w < 7) {
+      dgrad();
+      p11_end();
+    } else if (w < 7 + kP13W) {
+      // conv1 wgrad on waves 7-13: the input rows during P11, the d1 rows and the MFMAs after it
+      u32x4 xlo[28 / kP13W], xhi[28 / kP13W];
+#pragma unroll
+      for (int yy = 0; yy < 28 / kP13W; ++yy) c1w_row(w - 7, yy, xlo[yy], xhi[yy]);
+      p11_end();
+      c1w(w - 7, std::true_type{}, xlo, xhi);
+    } else {
+      p11_end();
+    }
+  } else {
+    lbar();
+    stamp(6);
+    if (w < 7) {
+      dgrad();
+    } else {
+      // 10 M-tiles over waves 7-15 (wave 7: two). Wave 15's staging stores were issued in P10.
+      const int t0 = w - 7, t1 = w == 7 ? 2 : w - 6;
+      for (int tt0 = t0; tt0 < t1; ++tt0) wgrad_tile(w == 7 && tt0 == 1 ? 9 : tt0);
+    }
+    p11_end();
+    if (w < kP13W) c1w(w, std::false_type{}, nullptr, nullptr);
   }
   wstamp(4);
   lbar();
@@ -1133,13 +1239,7 @@ __global__ __launch_bounds__(kT) void lenet_ms(uint8_t* __restrict__ pstage2, in
   if (kTraceBuild && (mode & LENET_TRACE) && b == 0 && t < 32 && P.trace) reinterpret_cast<unsigned long long*>(P.trace)[t] = L.tr[t];
   if (kTraceBuild && (mode & LENET_TRACE) && b == 0 && t < 96 && P.trace)
     reinterpret_cast<unsigned long long*>(P.trace)[1024 + t] = (&L.wtr[0][0])[t];
-  if (kTraceBuild && (mode & LENET_TRACE) && P.trace && b < 200) {  // per-block wall clock: slots 600 + 2 b (+1)
-    lbar();
-    if (t == 0) {
-      reinterpret_cast<unsigned long long*>(P.trace)[600 + 2 * b] = tb0;
-      reinterpret_cast<unsigned long long*>(P.trace)[601 + 2 * b] = __builtin_amdgcn_s_memrealtime();
-    }
-  }
+  block_clock();
 }
 
 // ---------------------------------------------------------------------------
@@ -1934,12 +2034,44 @@ inline int nprep(const LeNetPtrs& P, const LeNetAug& A, int B) {
   return (A.data && A.perm && P.prep && P.pmeta && P.dtargets && P.stepinfo && P.stage2 && P.meta2) ? B : 0;
 }
 
+// compute units of the current device, queried once per device
+inline int device_cus() {
+  static int cus[64] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+  if (cus[dev] == 0) {
+    int n = 0;
+    cus[dev] = hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0 ? n : -1;
+  }
+  return cus[dev] > 0 ? cus[dev] : 0;
+}
+
+// Whether a per-sample launch at batch B runs two blocks per sample (lenet_ms<D, true>): a whole
+// training step (no internal partial mode), the engine's switch on (LENET_NOSPLIT clear), nothing
+// the kernel reads is written by it (the audit above lenet_ms: with a dataset the inputs must come
+// from the prep buffers), and both blocks of every sample resident at once -- a second round of
+// blocks would cost more than the split saves.
+inline bool split_eligible(int mode, int B, const LeNetPtrs& P, const LeNetAug& A) {
+  if (!(mode & LENET_BWD) || (mode & (LENET_NOSPLIT | LENET_FROM_P1 | LENET_K4WG))) return false;
+  if (A.data && !(P.prep && P.pmeta)) return false;
+  return B > 0 && 2 * B <= device_cus();
+}
+
+template <class D>
+void launch_ms_t(int mode, int B, const LeNetPtrs& P, const LeNetAug& A, const LeNetOpt& O, hipStream_t st) {
+  const float inv_B = 1.f / (float)B;
+  if (split_eligible(mode, B, P, A))
+    hipLaunchKernelGGL((lenet_ms<D, true>), dim3(2 * B), dim3(kT), 0, st, P.stage2, P.meta2, A.ctrl, P.wimg, P.metaN,
+                       mode, inv_B, P, A, O, B);
+  else
+    hipLaunchKernelGGL((lenet_ms<D, false>), dim3(B), dim3(kT), 0, st, P.stage2, P.meta2, A.ctrl, P.wimg, P.metaN,
+                       mode, inv_B, P, A, O, B);
+}
+
 template <class D>
 void run(int mode, int B, const LeNetPtrs& P, const LeNetAug& A, const LeNetOpt& O, hipStream_t st) {
   mode |= probe_bits();
-  const float inv_B = 1.f / (float)B;
-  hipLaunchKernelGGL(lenet_ms<D>, dim3(B), dim3(kT), 0, st, P.stage2, P.meta2, A.ctrl, P.wimg, P.metaN, mode, inv_B, P,
-                     A, O, B);
+  launch_ms_t<D>(mode, B, P, A, O, st);
   const int nblk = mw_conv_blocks<D>() + mw_fc_blocks<D>() + 1;
   hipLaunchKernelGGL(lenet_mw<D>, dim3(nblk + nprep(P, A, B)), dim3(kWgT), 0, st, P.slab1, P.p2, P.dh1, P.h1, P.dh2,
                      mode, B, P, O, A.ctrl, A);

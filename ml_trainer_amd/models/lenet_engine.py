@@ -8,7 +8,9 @@ zero_grad -> H2D -> forward -> CE -> loss.item() -> backward (DDP all-reduce)
   (csrc/kernels/lenet_mfma.inc). ``lenet_ms``: one CU per sample (the sample's
   input -- RandomCrop/HFlip/Normalize of the HBM-resident uint8 image, prepared by
   the previous step's second kernel -- conv/fc forward on MFMA, softmax-CE, the
-  whole backward of the sample, its weight-gradient slab). ``lenet_mw``: the batch
+  whole backward of the sample, its weight-gradient slab; a second CU per sample
+  takes half of the backward tail where 2 x batch fits the CUs, ``set_split``).
+  ``lenet_mw``: the batch
   reductions in sample order, the on-device loss/accuracy sums, the fused optimizer
   update of the fp32 masters + bf16 shadow + fragment images, and (on CUs those
   leave idle) the NEXT step's augmented inputs. fp32 (the reference dtype): four
@@ -402,6 +404,18 @@ class LeNetStepEngine:
     def read_stats(self, n_batches: int):
         s = self.stats.cpu().tolist()
         return s[0] / max(n_batches, 1), s[1] / max(n_batches, 1)
+
+    def set_split(self, on: bool) -> None:
+        """bf16 step: run ``lenet_ms`` with two workgroups per sample (one carries the conv2 dgrad
+        -> conv1 wgrad chain, the other the stores, the staging and the conv2 wgrad) wherever a
+        launch is eligible -- see ``split_active``. Default: on unless MLT_LENET_SPLIT=0. Results
+        are bitwise the same either way; the captured graphs are dropped."""
+        self.eng.set_split(bool(on))
+
+    def split_active(self, B: int) -> bool:
+        """Whether a bf16 training step at batch ``B`` would run split: the switch is on, with a
+        dataset attached the prep buffers are in use, and ``2 * B`` fits the device's CUs."""
+        return bool(self.eng.split_active(int(B)))
 
     # ------------------------------------------------------------------ steps
     @property
