@@ -43,20 +43,8 @@ static void check_dev(const Tensor& t, const char* name, at::ScalarType st, int6
 static OptHyper make_hyper(int kind, double lr, double momentum, double dampening, double wd, double beta1,
                            double beta2, double eps, double lr_decay, double grad_scale, bool nesterov,
                            bool maximize) {
-  OptHyper h;
-  h.kind = kind;
-  h.lr = (float)lr;
-  h.momentum = (float)momentum;
-  h.dampening = (float)dampening;
-  h.weight_decay = (float)wd;
-  h.beta1 = (float)beta1;
-  h.beta2 = (float)beta2;
-  h.eps = (float)eps;
-  h.lr_decay = (float)lr_decay;
-  h.grad_scale = (float)grad_scale;
-  h.nesterov = nesterov ? 1 : 0;
-  h.maximize = maximize ? 1 : 0;
-  return h;
+  return make_opt_hyper(kind, lr, momentum, dampening, wd, beta1, beta2, eps, lr_decay, grad_scale, nesterov,
+                        maximize);
 }
 
 void flat_optim(Tensor p, Tensor g, c10::optional<Tensor> s1, c10::optional<Tensor> s2, int kind, double lr,
@@ -118,7 +106,9 @@ void sq_norm(Tensor x, Tensor out) {
   TORCH_CHECK(x.numel() % 4 == 0, "sq_norm needs numel % 4 == 0");
   check_dev(x, "x", at::kFloat, x.numel());
   check_dev(out, "out", at::kFloat, 1, 4);
-  launch_sq_norm(x.data_ptr<float>(), x.numel(), out.data_ptr<float>(), cur_stream());
+  // per-block partials (summed in block order by a second launch); stream-ordered scratch
+  Tensor part = at::empty({sq_norm_partials_needed()}, x.options());
+  launch_sq_norm(x.data_ptr<float>(), x.numel(), part.data_ptr<float>(), out.data_ptr<float>(), cur_stream());
 }
 
 void clip_coef(Tensor sq, double max_norm, Tensor coef, Tensor total) {

@@ -17,7 +17,10 @@ void launch_flat_optim(float* p, const float* g, float* s1, float* s2, int64_t n
                        const float* lr_ptr, const int64_t* lr_index_ptr, const int64_t* step_ptr, float t_host,
                        uint16_t* shadow_bf16, const float* coef_ptr, hipStream_t stream,
                        const unsigned* skip = nullptr);  // skip: no update while *skip != 0
-void launch_sq_norm(const float* x, int64_t n, float* out, hipStream_t stream);
+// out[0] = sum of squares of x[0..n): per-block partials into `part` (sq_norm_partials_needed() floats,
+// contents irrelevant), then summed in block order -> bitwise reproducible. out is overwritten.
+int sq_norm_partials_needed();
+void launch_sq_norm(const float* x, int64_t n, float* part, float* out, hipStream_t stream);
 void launch_clip_coef(const float* sq, float max_norm, float* coef, float* total_norm, hipStream_t stream);
 void launch_cast_bf16(const float* x, uint16_t* y, int64_t n, hipStream_t stream);
 // dst[C][R] = src[R][C], bf16 (transpose.hip)

@@ -19,13 +19,43 @@ struct OptHyper {
   float momentum;
   float dampening;
   float weight_decay;
-  float beta1, beta2, eps;
+  // The betas are kept as their complements, rounded to fp32 once from the host's doubles
+  // (make_opt_hyper). Kept as (float)beta, 1.f - (float)0.999 is off by 1.3e-5 relative (beta's rounding
+  // error against a difference a thousand times smaller), which went straight into exp_avg_sq and,
+  // through 1 - powf(beta, t), into the bias corrections. From the complement all come out right:
+  // beta = 1.f - omb rounds to (float)beta for beta >= 0.5 (within 3e-8 of it below), and
+  // 1 - beta^t = -expm1f(t * log1pf(-omb)) has no cancellation.
+  float omb1, omb2;    // 1 - beta1, 1 - beta2
+  float eps;
   float lr_decay;      // adagrad
   float grad_scale;    // multiply incoming grads (e.g. 1/world or 1/loss_scale)
   int nesterov;
   int maximize;
   int kind;
 };
+
+// The one place that fills an OptHyper from a user's (double) hyper-parameters.
+inline OptHyper make_opt_hyper(int kind, double lr, double momentum, double dampening, double weight_decay,
+                               double beta1, double beta2, double eps, double lr_decay, double grad_scale,
+                               bool nesterov, bool maximize) {
+  OptHyper h;
+  h.kind = kind;
+  h.lr = (float)lr;
+  h.momentum = (float)momentum;
+  h.dampening = (float)dampening;
+  h.weight_decay = (float)weight_decay;
+  h.omb1 = (float)(1.0 - beta1);
+  h.omb2 = (float)(1.0 - beta2);
+  h.eps = (float)eps;
+  h.lr_decay = (float)lr_decay;
+  h.grad_scale = (float)grad_scale;
+  h.nesterov = nesterov ? 1 : 0;
+  h.maximize = maximize ? 1 : 0;
+  return h;
+}
+
+// 1 - beta^t from omb = 1 - beta (beta = 0: log1pf(-1) = -inf, expm1f(-inf) = -1, correction 1)
+__device__ __forceinline__ float opt_bias_correction(float omb, float t) { return -expm1f(t * log1pf(-omb)); }
 
 // One element update. s1/s2 are the optimizer state slots for this element:
 //   SGD: s1 = momentum buffer; Adam/AdamW/Adamax: s1 = exp_avg, s2 = exp_avg_sq / exp_inf;
@@ -54,10 +84,10 @@ __device__ __forceinline__ void opt_update_k(const OptHyper& h, float lr, float 
     } else {
       if (h.weight_decay != 0.f) g = fmaf(h.weight_decay, p, g);
     }
-    s1 = fmaf(h.beta1, s1, (1.f - h.beta1) * g);
-    s2 = fmaf(h.beta2, s2, (1.f - h.beta2) * g * g);
-    const float bc1 = 1.f - powf(h.beta1, t);
-    const float bc2 = 1.f - powf(h.beta2, t);
+    s1 = fmaf(h.omb1, g - s1, s1);  // torch's lerp_(g, 1 - beta1)
+    s2 = fmaf(1.f - h.omb2, s2, h.omb2 * g * g);
+    const float bc1 = opt_bias_correction(h.omb1, t);
+    const float bc2 = opt_bias_correction(h.omb2, t);
     const float step_size = lr / bc1;
     const float denom = sqrtf(s2) / sqrtf(bc2) + h.eps;
     p = fmaf(-step_size, s1 / denom, p);
@@ -68,9 +98,9 @@ __device__ __forceinline__ void opt_update_k(const OptHyper& h, float lr, float 
     p = fmaf(-clr, g / (sqrtf(s1) + h.eps), p);
   } else if constexpr (K == OPT_ADAMAX) {
     if (h.weight_decay != 0.f) g = fmaf(h.weight_decay, p, g);
-    s1 = fmaf(h.beta1, s1, (1.f - h.beta1) * g);
-    s2 = fmaxf(h.beta2 * s2, fabsf(g) + h.eps);
-    const float clr = lr / (1.f - powf(h.beta1, t));
+    s1 = fmaf(h.omb1, g - s1, s1);  // torch's lerp_(g, 1 - beta1)
+    s2 = fmaxf((1.f - h.omb2) * s2, fabsf(g) + h.eps);
+    const float clr = lr / opt_bias_correction(h.omb1, t);
     p = fmaf(-clr, s1 / s2, p);
   }
 }

@@ -55,8 +55,12 @@ __global__ __launch_bounds__(256) void flat_optim_kernel(float* __restrict__ p, 
   }
 }
 
-// sum of squares of a flat fp32 buffer -> out[0] (atomic, caller zeroes out)
-__global__ __launch_bounds__(256) void sq_norm_kernel(const float* __restrict__ x, int64_t n4, float* out) {
+constexpr int kSqNormMaxBlocks = 512;
+
+// sum of squares of a flat fp32 buffer, two fixed-order stages (bitwise reproducible, like the
+// loss reductions in losses.hip): (1) each block writes its partial to part[blockIdx.x];
+__global__ __launch_bounds__(256) void sq_norm_partial_kernel(const float* __restrict__ x, int64_t n4,
+                                                              float* __restrict__ part) {
   __shared__ float red[4];
   const float4* x4 = reinterpret_cast<const float4*>(x);
   float acc = 0.f;
@@ -65,7 +69,17 @@ __global__ __launch_bounds__(256) void sq_norm_kernel(const float* __restrict__ 
     acc += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
   }
   acc = block_sum(acc, red);
-  if (threadIdx.x == 0) atomicAdd(out, acc);
+  if (threadIdx.x == 0) part[blockIdx.x] = acc;
+}
+
+// (2) one block sums the nb partials in index order -> out[0] (overwritten: no zeroing by the caller)
+__global__ __launch_bounds__(256) void sq_norm_final_kernel(const float* __restrict__ part, int nb,
+                                                            float* __restrict__ out) {
+  __shared__ float red[4];
+  float acc = 0.f;
+  for (int i = threadIdx.x; i < nb; i += 256) acc += part[i];
+  acc = block_sum(acc, red);
+  if (threadIdx.x == 0) *out = acc;
 }
 
 // clip coefficient: coef = min(1, max_norm / (sqrt(sq) + 1e-6))  (torch.nn.utils.clip_grad_norm_)
@@ -104,11 +118,13 @@ void launch_flat_optim(float* p, const float* g, float* s1, float* s2, int64_t n
                      lr_index_ptr, step_ptr, t_host, shadow, coef_ptr, skip);
 }
 
-void launch_sq_norm(const float* x, int64_t n, float* out, hipStream_t stream) {
+int sq_norm_partials_needed() { return kSqNormMaxBlocks; }
+
+void launch_sq_norm(const float* x, int64_t n, float* part, float* out, hipStream_t stream) {
   const int64_t n4 = n / 4;
-  if (n4 == 0) return;
-  hipLaunchKernelGGL(sq_norm_kernel, dim3(grid_for(n4) > 512 ? 512 : grid_for(n4)), dim3(256), 0, stream, x, n4,
-                     out);
+  const int nb = n4 == 0 ? 0 : (grid_for(n4) > kSqNormMaxBlocks ? kSqNormMaxBlocks : grid_for(n4));
+  if (nb > 0) hipLaunchKernelGGL(sq_norm_partial_kernel, dim3(nb), dim3(256), 0, stream, x, n4, part);
+  hipLaunchKernelGGL(sq_norm_final_kernel, dim3(1), dim3(256), 0, stream, part, nb, out);
 }
 
 void launch_clip_coef(const float* sq, float max_norm, float* coef, float* total_norm, hipStream_t stream) {

@@ -182,7 +182,7 @@ def _cpu_update(h, t, p, g, s1, s2) -> None:
             p.mul_(1 - lr * wd)
         elif wd:
             g = g + wd * p
-        s1.mul_(h["beta1"]).add_(g, alpha=1 - h["beta1"])
+        s1.lerp_(g, 1 - h["beta1"])
         s2.mul_(h["beta2"]).addcmul_(g, g, value=1 - h["beta2"])
         bc1 = 1 - h["beta1"] ** t
         bc2 = 1 - h["beta2"] ** t
@@ -197,7 +197,7 @@ def _cpu_update(h, t, p, g, s1, s2) -> None:
     elif k == 4:
         if wd:
             g = g + wd * p
-        s1.mul_(h["beta1"]).add_(g, alpha=1 - h["beta1"])
+        s1.lerp_(g, 1 - h["beta1"])
         torch.maximum(s2.mul_(h["beta2"]), g.abs().add_(h["eps"]), out=s2)
         p.addcdiv_(s1, s2, value=-lr / (1 - h["beta1"] ** t))
 
@@ -266,11 +266,13 @@ def build_optimizer(name: str, params, lr: float, momentum: float = 0.9, weight_
 
 def clip_grad_norm_flat(flat: FlatParams, max_norm: float) -> torch.Tensor:
     """torch.nn.utils.clip_grad_norm_ over a flat gradient buffer: one fused
-    sum-of-squares kernel + one scale, no host sync (returns the device norm)."""
+    sum-of-squares kernel + one scale, no host sync (returns the device norm). The sum runs in a
+    fixed order (per-block partials added in block order): norm and clipped gradients are bitwise
+    reproducible from run to run."""
     g = flat.grad
     if g.is_cuda:
         C = require_native()
-        sq = torch.zeros(1, dtype=torch.float32, device=g.device)
+        sq = torch.empty(1, dtype=torch.float32, device=g.device)  # overwritten by sq_norm
         coef = torch.empty(1, dtype=torch.float32, device=g.device)
         total = torch.empty(1, dtype=torch.float32, device=g.device)
         C.sq_norm(g, sq)

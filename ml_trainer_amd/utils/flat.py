@@ -57,6 +57,7 @@ class FlatParams:
                 _OWNER[id(p)] = self
         self.shadow: Optional[torch.Tensor] = None  # bf16 copy of `data` for mixed-precision compute
         self._shadow_ver = -1
+        self._shadow_pvers: List[int] = []  # each parameter's version counter when the shadow was cast
         self.generation = 0  # bumped by every optimizer update (keys caches of derived weight copies)
         self.grad_ready_hooks: List = []  # called as hook(p) when a fused kernel wrote p's gradient
 
@@ -132,27 +133,34 @@ class FlatParams:
 
     def refresh_shadow(self) -> torch.Tensor:
         """(Re)build the bf16 shadow when the fp32 master changed outside the fused optimizer
-        (load_state_dict, manual edits bump the tensor version counter; the optimizer kernel
-        writes the shadow itself and leaves the counter alone)."""
+        (load_state_dict, manual edits bump a tensor version counter; the optimizer kernel
+        writes the shadow itself and leaves the counters alone). An edit of ``data`` bumps
+        ``data._version``; an edit through a parameter (``load_state_dict``, ``p.mul_()``) bumps only
+        that parameter's own counter, since ``p.data = view`` does not share the buffer's: both are
+        compared."""
         if self.shadow is None:
             self.shadow = torch.empty(self.numel, dtype=torch.bfloat16, device=self.device)
             self._shadow_ver = -1
-        if self._shadow_ver != self.data._version:
+        if self._shadow_ver != self.data._version or self._shadow_pvers != [p._version for p in self.params]:
             if self.device.type == "cuda":
                 from ml_trainer_amd.ops._ext import require_native
                 require_native().cast_bf16(self.data, self.shadow)
             else:
                 self.shadow.copy_(self.data)
-            self._shadow_ver = self.data._version
+            self.mark_shadow_fresh()
         return self.shadow
 
     def shadow_view(self, p: torch.Tensor) -> torch.Tensor:
-        sh = self.refresh_shadow()
-        o, n = self.segment(p)
-        return sh[o:o + n].view(p.shape)
+        i = self._index[id(p)]
+        # per-weight hot path: this parameter's counter and the buffer's; anything else -> full check
+        if self.shadow is None or self._shadow_ver != self.data._version or self._shadow_pvers[i] != p._version:
+            self.refresh_shadow()
+        o = self.offsets[i]
+        return self.shadow[o:o + p.numel()].view(p.shape)
 
     def mark_shadow_fresh(self) -> None:
         self._shadow_ver = self.data._version
+        self._shadow_pvers = [p._version for p in self.params]
 
     def state_dict_views(self) -> List[torch.Tensor]:
         return [self.data[o:o + p.numel()].view_as(p) for p, o in zip(self.params, self.offsets)]

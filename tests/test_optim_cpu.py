@@ -70,6 +70,27 @@ def test_works_with_lr_schedulers():
     assert o.param_groups[0]["lr"] == pytest.approx(0.125)
 
 
+def test_shadow_follows_edits_through_parameters():
+    """``p.data = view`` gives a parameter its own version counter: load_state_dict or an in-place
+    edit of a parameter leaves ``fp.data._version`` alone and must still invalidate the bf16 shadow."""
+    m = torch.nn.Linear(6, 3)
+    fp = FlatParams(m.parameters())
+
+    def fresh():
+        return torch.equal(fp.refresh_shadow(), fp.data.to(torch.bfloat16)) and all(
+            torch.equal(fp.shadow_view(p), p.detach().to(torch.bfloat16)) for p in m.parameters())
+
+    assert fresh()
+    m.load_state_dict({k: v + 1.0 for k, v in m.state_dict().items()})
+    assert torch.equal(fp.shadow_view(m.weight), m.weight.detach().to(torch.bfloat16))
+    assert fresh()
+    with torch.no_grad():
+        m.bias.mul_(3.0)
+    assert torch.equal(fp.shadow_view(m.bias), m.bias.detach().to(torch.bfloat16))
+    fp.data.mul_(1.5)
+    assert fresh()
+
+
 def test_clip_grad_norm_flat_cpu():
     m = torch.nn.Linear(10, 10)
     fp = FlatParams(m.parameters())

@@ -69,3 +69,20 @@ def test_pointwise_any_size(dev, n, kind, seed):
     loss.backward()
     ref.backward()
     torch.testing.assert_close(p.grad, p2.grad, rtol=1e-6, atol=1e-9)
+
+
+@_S
+@given(n4=st.integers(1, 70_000), kind=st.sampled_from(["sgd", "adam", "adamw", "adagrad", "adamax"]),
+       seed=st.integers(0, 1000))
+def test_flat_optim_any_size(dev, n4, kind, seed):
+    """Two steps of the flat optimizer kernel at any float4 count vs fp64 torch.optim, under the error
+    budget of tests/test_optim_gpu.py (fp32 torch.optim is the yardstick)."""
+    from ml_trainer_amd.ops._ext import require_native
+    from tests.test_optim_gpu import (CASE_BY_ID, CASE_OF_KIND, budget_ratio, kernel_run, make_inputs,
+                                      torch_run)
+    _, _, hp = CASE_BY_ID[CASE_OF_KIND[kind]]
+    p0, grads = make_inputs(4 * n4, 2, seed)
+    K = kernel_run(require_native(), dev, kind, hp, p0, grads)
+    R = torch_run(kind, hp, p0, grads, torch.float64)
+    T = torch_run(kind, hp, p0, grads, torch.float32)
+    budget_ratio(f"{kind} n4={n4} seed={seed} p", K[0], R[0], T[0])
