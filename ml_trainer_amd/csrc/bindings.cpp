@@ -1394,7 +1394,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   }, py::arg("M"), py::arg("N"), py::arg("K"), py::arg("cfg") = -1, py::arg("splits") = 0);
   m.def("set_gemm_split_mode", &set_gemm_split_mode, py::arg("mode"));
   m.def("set_gemm_w4q8", &set_gemm_w4q8, py::arg("on"));
-  m.def("set_lenet_variant", &set_lenet_variant, py::arg("variant"));
   m.def("lenet_mfma_wimg_elems", &lenet_mfma_wimg_elems);
   m.def("lenet_mfma_trace_build", &lenet_mfma_trace_build);
   // host-side completion waits of a device: spin (lowest latency; the launch-bound LeNet step
@@ -1408,7 +1407,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lenet_mfma_slab_floats", &lenet_mfma_slab_floats, py::arg("cfg"));
   m.def("lenet_mfma_kw_blocks", &lenet_mfma_kw_blocks, py::arg("cfg"));
   m.def("lenet_mfma_xch_granules", &lenet_mfma_xch_granules, py::arg("cfg"));
-  m.def("get_lenet_variant", &get_lenet_variant);
   m.def("fp8_cast", &fp8_cast, py::arg("x"), py::arg("y"), py::arg("scale"), py::arg("amax") = py::none(),
         py::arg("fmt") = 0);
   m.def("fp8_amax", &fp8_amax);

@@ -35,11 +35,9 @@ enum LeNetMode : int {
   LENET_CE = 2,         // softmax-CE loss + dlogits + loss/accuracy accumulation
   LENET_BWD = 4,        // dlogits -> all parameter gradients
   LENET_OPT = 8,        // fused optimizer update inside the weight-gradient kernel (single process only)
-  LENET_REDUCE = 16,    // (kept for API compatibility: the conv1 reduction always happens inside K5)
-  LENET_TRACE = 256,    // fused kernel: block 0 stores per-phase clock64() stamps into slab1 (K5 skipped)
-  LENET_SKIP_CONV1 = 512, LENET_SKIP_CONV2 = 1024, LENET_SKIP_FC = 2048,  // K5 roles skipped (profiling)
-  LENET_K4WG = 4096,    // internal: K4 wrote the conv wgrad slabs, K5 only reduces them
-  LENET_FROM_P1 = 8192, // internal: the per-sample kernel starts from p1 (conv2 -> fc chain) and stops there
+  LENET_REDUCE = 16,    // data-parallel step (LeNetEngine): all-reduce the flat gradient after the backward
+                        // kernels, then the flat optimizer update; exclusive with LENET_OPT
+  LENET_TRACE = 256,    // bf16 kernels only (MLT_LENET_TRACE_BUILD): phase stamps into LeNetPtrs::trace
   LENET_STATS_DEFER = 16384,  // internal: CE writes per-sample loss / hit to cestat; K4 sums them in sample order
   // timing probes of the bf16 per-sample kernel (wrong numerics: profiling only; env MLT_LENET_PROBE)
   LENET_PROBE_NOF1T = 1 << 17,  // role A skips the fc1 dgrad (transposed) weight fetch
@@ -56,7 +54,7 @@ struct LeNetPtrs {
   int64_t* targets;          // [B] class ids (written by conv1 in the augment path)
   const int64_t* dtargets;   // dataset targets [N] (augment path)
   double* stats;             // [2]: sum over batches of batch-mean loss, of batch accuracy
-  unsigned* counters;        // [>= C1+1] zero-initialised arrival counters (K5 last-arriver reductions)
+  unsigned* counters;        // [>= C1+1] zero-initialised; only [C1] is used: K5's launch-wide arrival counter
   uint8_t* stage;            // [B][3072] raw uint8 images of the next step (nullptr: no staging)
   int64_t* stage_meta;       // [B][4] (perm position, dataset row, target, 0) of each staged image; -1 = empty
   double* cestat;            // [B][2] per-sample (loss / B, hit / B) for the fixed-order stats sum (or nullptr)
@@ -132,8 +130,6 @@ void launch_lenet_mfma_reduce(int cfg, int B, const LeNetPtrs& P, const LeNetOpt
 int64_t lenet_mfma_xch_granules(int cfg);  // granules per parity the fused exchange needs
 // shadow + wimg from the fp32 masters (O.p)
 void launch_lenet_mfma_pack(int cfg, const LeNetPtrs& P, const LeNetOpt& O, hipStream_t stream);
-void set_lenet_variant(int v);  // 0 default (4 launches), 1 fully fused per-sample chain, 2 split conv2 / fc
-int get_lenet_variant();
 
 // Standalone GPU augmentation (RandomCrop(32,pad) + HFlip + ToTensor + Normalize) for the
 // generic (non-LeNet) device data path: out [B,3,32,32] fp32.

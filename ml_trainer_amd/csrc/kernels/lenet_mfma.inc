@@ -177,10 +177,7 @@ constexpr int DCCS = 24;         // [oc][Y][X] conv2-output grad: row stride (co
 constexpr int D1S = 28 * 32 + 16;  // [oc][Y][X32] unpooled conv1 grad: channel stride (conv1 wgrad B, 1-way vs 5)
 constexpr int kWgT = 256;        // KW threads
 constexpr int kP13W = 7;         // conv1 wgrad waves (28 output rows / 4 each)
-#ifndef MLT_KC1W
-#define MLT_KC1W 8  // (build-time A/B knob)
-#endif
-constexpr int kC1W = MLT_KC1W;   // conv1 forward waves (the fc1 forward waves 8-15 fetch weights meanwhile)
+constexpr int kC1W = 8;          // conv1 forward waves (the fc1 forward waves 8-15 fetch weights meanwhile)
 #ifndef MLT_LENET_TRACE_BUILD
 #define MLT_LENET_TRACE_BUILD 0  // 1: the LENET_TRACE stamps are compiled in (benchmarks/lenet_bf16_phases.py)
 #endif
@@ -191,13 +188,6 @@ constexpr bool kTraceBuild = MLT_LENET_TRACE_BUILD != 0;
 // (the per-sample slabs and the update's outputs as streaming -- nontemporal -- stores, to take
 // them out of the end-of-kernel L2 writeback, measured 1.1 us per step SLOWER: r6v,
 // profiles/r6/lenet_nt_store_ab_r6v.jsonl)
-#ifndef MLT_LENET_CNTWAIT
-#define MLT_LENET_CNTWAIT 0  // (build-time A/B knob) counted vmcnt before P4a: leave the fc2 / fc3 loads in flight
-#endif
-constexpr bool kCountedWait = MLT_LENET_CNTWAIT != 0;
-#ifndef MLT_F1_SWZ
-#define MLT_F1_SWZ 0  // (build-time A/B knob) 1: the bank-model layout of f1_chunk (measured 0.1 us slower, r6g)
-#endif
 
 // ---------------------------------------------------------------------------
 // fc layers on the matrix cores: y = W x for ONE sample, its input row x (bf16 in LDS, zero past K
@@ -236,20 +226,13 @@ __device__ __forceinline__ float row_dot(const u32x4 (&f)[KS], const uint16_t* x
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 // LDS fc1 image: W1 row r, 16-byte chunk c (8 bf16, c < FLAT / 8) at image chunk
-//   r * F1S + (r & 3) + (c ^ X(r)),  F1S = FLAT / 8 + 3,  X(r) = (r >> 3) & 1 (0 for an odd chunk count)
-// -- chosen by a bank model of both readers (P4a: rows 16 tn + m, chunk 4 q + g, ds_read_b128; P8:
-// 8-byte transposed reads of rows 32 q + 8 g + qq (+4), ds_read_b64_tr_b16): 482 / 425 LDS cycles
-// against an ideal 416 / 400 per step, where round 5's layout (F1S = FLAT / 8 + 1, shift r & 1, no
-// XOR) made the row-wise reads of the fc1 forward 2-way (832).
+//   r * F1S + (r & 1) + c,  F1S = FLAT / 8 + 1
+// Its readers: P4a (rows 16 tn + m, chunk 4 q + g, ds_read_b128) and P8 (8-byte transposed reads of
+// rows 32 q + 8 g + qq (+4), ds_read_b64_tr_b16). (A layout chosen by a bank model of both, F1S =
+// FLAT / 8 + 3 with shift r & 3 and an XOR swizzle, measured 0.1 us per step slower, r6g.)
 template <int FLAT>
 __device__ __forceinline__ int f1_chunk(int r, int c) {
-  constexpr int NCH = FLAT / 8;
-  if constexpr (MLT_F1_SWZ) {
-    const int x = (NCH % 2 == 0) ? ((r >> 3) & 1) : 0;
-    return r * (NCH + 3) + (r & 3) + (c ^ x);
-  } else {
-    return r * (NCH + 1) + (r & 1) + c;
-  }
+  return r * (FLAT / 8 + 1) + (r & 1) + c;
 }
 template <int F1, int FLAT>
 __device__ __forceinline__ u32x4 f1t_frag(const uint16_t* img, int tile, int q) {
@@ -307,9 +290,9 @@ template <class D>
 struct KsLds {
   using F = Fc<D>;
   static constexpr int SCR = kP13W * 5 * 256;
-  // fc1 weight image [F1 rows][F1S 16-byte chunks], layout f1_chunk (row r: chunks (r & 3) .. +
-  // FLAT/8 - 1, XOR-swizzled by (r >> 3) & 1; the other chunks are padding)
-  static constexpr int F1S = D::FLAT / 8 + (MLT_F1_SWZ ? 3 : 1);
+  // fc1 weight image [F1 rows][F1S 16-byte chunks], layout f1_chunk (row r: chunks (r & 1) .. +
+  // FLAT/8 - 1; the other chunk is padding)
+  static constexpr int F1S = D::FLAT / 8 + 1;
   // filled by LDS-DMA (1 KiB = 64 chunks per wave-instruction, lane-linear): F1NI instructions, the
   // last one's lanes past the image land in the padding
   static constexpr int F1NCH = D::F1 * F1S, F1NI = (F1NCH + 63) / 64;
@@ -521,9 +504,8 @@ __global__ __launch_bounds__(kT) void lenet_ms(uint8_t* __restrict__ pstage2, in
     for (int i = w - F1M::W1F; i < S::F1NI; i += 16 - F1M::W1F) {  // wave-uniform i: the LDS base
       // image chunk q -> (row r, chunk c) of W1 (the inverse of f1_chunk); pad chunks re-read chunk 0
       const int q = min(64 * i + lane, S::F1NCH - 1), r = q / S::F1S;
-      const int loc = q - r * S::F1S - (MLT_F1_SWZ ? (r & 3) : (r & 1));
-      const int x = (MLT_F1_SWZ && (FLAT / 8) % 2 == 0) ? ((r >> 3) & 1) : 0;
-      const int src = (loc >= 0 && loc < FLAT / 8) ? (loc ^ x) : 0;
+      const int loc = q - r * S::F1S - (r & 1);
+      const int src = (loc >= 0 && loc < FLAT / 8) ? loc : 0;
       __builtin_amdgcn_global_load_lds((const void*)(W1 + r * FLAT + src * 8),
                                        (__attribute__((address_space(3))) void*)(L.u.f1img + 64 * 8 * i), 16, 0, 0);
     }
@@ -851,20 +833,8 @@ __global__ __launch_bounds__(kT) void lenet_ms(uint8_t* __restrict__ pstage2, in
       }
     }
     wstamp(1);
-    // the fc1 image's LDS-DMA (issued by these waves in P1 / P2) has landed: a COUNTED wait that
-    // leaves the loads issued after it -- the fc2 / fc3 fragments of this role, and the one conv2
-    // dgrad fragment of every thread issued in between -- in flight except that fragment (vmcnt
-    // retires in issue order); the fc fragments are waited for at their use in P4b / P4c, so the
-    // fc1 forward starts as soon as its own weights are in
-    if (stage_on || !kCountedWait) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    } else if (w >= F1M::W2F && w < F1M::W2F + F1M::T2) {
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(F1M::K2) : "memory");
-    } else if (w == F1M::W3F) {
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(F1M::K3) : "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
+    // the fc1 image's LDS-DMA (issued by these waves in P1 / P2) has landed
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     lbar();
     stamp(3);
     if (w >= F1M::W1F) {  // P4a: fc1 forward (the last T1 waves), B fragments = W1 rows from the image
@@ -1478,11 +1448,6 @@ __host__ __device__ constexpr int mw_fc_blocks() {
 // The exchange's granule space (per parity): the conv elements by their lane index e, then 256
 // granules per fc weight-gradient wave, lane-contiguous -- every publish / poll instruction of a wave
 // touches 64 consecutive granules (512 bytes) instead of 16 rows x 32 bytes.
-#ifdef MLT_XCH_FLAT
-constexpr bool kXchFlat = true;
-#else
-constexpr bool kXchFlat = false;
-#endif
 template <class D>
 __host__ __device__ constexpr int64_t xch_fc_base() {
   return ((int64_t)D::S1 + D::S2 + 63) / 64 * 64;
@@ -1538,16 +1503,14 @@ __device__ __forceinline__ void fc_wgrad(const Xch<WT>& xc, int64_t gbase, int t
   float gb = acc[0];
   if constexpr (Xch<WT>::on) {  // data-parallel: this lane's elements summed over the ranks
     if (wrow) {
-      // (MLT_XCH_FLAT: the round-4 layout, granule = flat parameter offset -- PMC A/B only)
-      constexpr int GS = kXchFlat ? 1 : 64;
-      const int64_t gi = kXchFlat ? iw : gbase + lane;
-      xc.template put4<GS>(gi, gv);
+      const int64_t gi = gbase + lane;
+      xc.template put4<64>(gi, gv);
       float o[4] = {gv.x, gv.y, gv.z, gv.w}, r[4];
-      if (!xc.template get<4, GS>(gi, o, r)) return;
+      if (!xc.template get<4, 64>(gi, o, r)) return;
       gv = make_float4(r[0], r[1], r[2], r[3]);
     }
     if (brow) {
-      const int64_t gi = kXchFlat ? ib : gbase + lane;  // (a bias lane holds no weight values: slot 0 is free)
+      const int64_t gi = gbase + lane;  // (a bias lane holds no weight values: slot 0 is free)
       xc.put1(gi, gb);
       float r;
       if (!xc.template get<1>(gi, &gb, &r)) return;
@@ -1648,7 +1611,7 @@ __device__ __forceinline__ void upd_wave(int v, int mode, const LeNetPtrs& P, co
       for (int u = 0; u < 32; ++u) gsum += b0 + u < B ? vv[u] : 0.f;
     }
     if constexpr (Xch<WT>::on) {  // data-parallel: summed over the ranks
-      const int64_t gi = kXchFlat ? dst : e;  // granule = the lane's element index: lane-contiguous
+      const int64_t gi = e;  // granule = the lane's element index: lane-contiguous
       xc.put1(gi, gsum);
       float r;
       if (!xc.template get<1>(gi, &gsum, &r)) return;
@@ -1843,7 +1806,6 @@ __device__ __forceinline__ Xch<XT> make_xch(const XgmiFused& X, int vb, uint64_t
     if (q == X.rank) xc.mine = xc.gr[q];
   }
   if constexpr (Xch<XT>::TWO) {
-    static_assert(!kXchFlat, "two-phase exchange: lane-contiguous granules only");
 #pragma unroll
     for (int q = 0; q < WT; ++q) {
       xc.rd[q] = X.gran[q] + 2 * X.cap + half;  // the reduced granules follow the granules
@@ -2047,12 +2009,12 @@ inline int device_cus() {
 }
 
 // Whether a per-sample launch at batch B runs two blocks per sample (lenet_ms<D, true>): a whole
-// training step (no internal partial mode), the engine's switch on (LENET_NOSPLIT clear), nothing
+// training step, the engine's switch on (LENET_NOSPLIT clear), nothing
 // the kernel reads is written by it (the audit above lenet_ms: with a dataset the inputs must come
 // from the prep buffers), and both blocks of every sample resident at once -- a second round of
 // blocks would cost more than the split saves.
 inline bool split_eligible(int mode, int B, const LeNetPtrs& P, const LeNetAug& A) {
-  if (!(mode & LENET_BWD) || (mode & (LENET_NOSPLIT | LENET_FROM_P1 | LENET_K4WG))) return false;
+  if (!(mode & LENET_BWD) || (mode & LENET_NOSPLIT)) return false;
   if (A.data && !(P.prep && P.pmeta)) return false;
   return B > 0 && 2 * B <= device_cus();
 }

@@ -102,7 +102,8 @@ def lenet_buffers(cfg_id: int, B: int, device) -> Dict[str, torch.Tensor]:
         "i2": torch.empty(_align4(B * flat), dtype=torch.uint8, device=device),
         "targets": torch.zeros(B, dtype=torch.int64, device=device),
         "stats": torch.zeros(2, dtype=torch.float64, device=device),
-        # arrival counters of the in-launch last-arriver reductions (zeroed once; reset by the kernel)
+        # arrival counters (zeroed once; reset by the kernel): the weight-gradient launch's last block
+        # to arrive advances the step counters
         "counters": torch.zeros(16, dtype=torch.int32, device=device),
         # next-step input staging (engine path): K4 gathers the raw uint8 images of the NEXT step
         # into `stage`, tagged in `stage_meta` [B][4] = (perm position, dataset row, target, 0);
