@@ -38,7 +38,7 @@ for name, M, N, K in shapes:
     B = torch.randn(N, K, device=dev).to(torch.float8_e4m3fn)
     wg = name.endswith("wgrad")
     out = torch.zeros(M, N, dtype=torch.float32 if wg else torch.bfloat16, device=dev)
-    variants = {"planner": {}, "cfg1": {"cfg": 1}, "cfg5": {"cfg": 5}, "cfg6": {"cfg": 6}}
+    variants = {"planner": {}, "cfg1": {"cfg": 1}, "cfg5": {"cfg": 5}}
     best = {k: 1e9 for k in variants}
     for _ in range(3):
         for k, kw in variants.items():

@@ -1,8 +1,8 @@
 """Where the fp8 quantising FFN1 GEMM's time goes (large config shape: M tokens x 4096, K = 1024):
 the plain GEMM on the 4-wave kernel (cfg 7) and on the ping-pong kernel (cfg 5), each with the
 bf16 bias + GELU epilogue (pre-activation saved), and the quantising (q8) epilogues of gemm_f8_q
-(fp8 Y + Y^T + amax): FFN1's GELU and FFN2-dgrad's dGELU (+ column sums). MLT_GEMM_W4Q8=0 puts the
-q8 forms on the ping-pong kernel instead of the 4-wave one. One JSON line. FFN_TOKENS (default 262144)."""
+(fp8 Y + Y^T + amax): FFN1's GELU and FFN2-dgrad's dGELU (+ column sums). One JSON
+line. FFN_TOKENS (default 262144)."""
 import json
 import os
 import sys

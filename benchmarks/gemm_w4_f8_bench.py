@@ -1,5 +1,5 @@
-"""fp8 GEMM: config 7 (4-wave asm loop on the block-scaled MFMA) vs configs 5 / 6 (ping-pong /
-persistent ping-pong) and the bf16 config 7, on the `large` (24L / 1024H / FFN 4096) shapes at 128K
+"""fp8 GEMM: config 7 (4-wave asm loop on the block-scaled MFMA) vs config 5 (ping-pong) and
+the bf16 config 7, on the `large` (24L / 1024H / FFN 4096) shapes at 128K
 tokens and a square; interleaved rounds, random operands, one JSON line per shape."""
 import json
 import os
@@ -39,7 +39,6 @@ for name, M, N, K in shapes:
     out = torch.empty(M, N, dtype=torch.bfloat16, device=dev)
     fns = {"f8_cfg7": lambda: C.gemm_f8(A8, B8, out, 0, 0, one, one, cfg=7),
            "f8_cfg5": lambda: C.gemm_f8(A8, B8, out, 0, 0, one, one, cfg=5),
-           "f8_cfg6": lambda: C.gemm_f8(A8, B8, out, 0, 0, one, one, cfg=6),
            "bf16_cfg7": lambda: C.gemm(A16, B16, out, False, False, cfg=7),
            "bf16_torch": lambda: torch.matmul(A16, B16.t(), out=out)}
     best = {k: 1e9 for k in fns}

@@ -1,6 +1,6 @@
 """Weight-gradient GEMMs (BERT-base shapes at GEMM_BENCH_TOKENS tokens, A [K][M], B [K][N], fp32
-accumulate into the gradient) through the planner (cfg 7 split-K by default; MLT_GEMM_W4=0: the
-8-wave split-K tiles) and torch.matmul (hipBLASLt, bf16 out). One JSON line per shape."""
+accumulate into the gradient) through the planner (cfg 7 split-K) and torch.matmul (hipBLASLt,
+bf16 out). One JSON line per shape."""
 import json
 import os
 import sys
@@ -36,6 +36,6 @@ for name, M, N in [("qkv_wgrad", 2304, 768), ("out_wgrad", 768, 768), ("ffn1_wgr
     t = min(timeit(lambda: C.gemm(A, B, out, True, True, accumulate=True)) for _ in range(2))
     ob = torch.empty(M, N, dtype=torch.bfloat16, device=dev)
     tt = min(timeit(lambda: torch.matmul(A.t(), B, out=ob)) for _ in range(2))
-    print(json.dumps({"shape": name, "M": M, "N": N, "K": T, "w4_env": os.environ.get("MLT_GEMM_W4", "1"),
+    print(json.dumps({"shape": name, "M": M, "N": N, "K": T,
                       "plan": list(C.gemm_plan(True, True, M, N, T)), "ms": round(t, 4), "tflops": round(fl / t / 1e9, 1),
                       "torch_tflops": round(fl / tt / 1e9, 1)}), flush=True)

@@ -326,12 +326,17 @@ void mcrmse(Tensor p, Tensor t, Tensor col, Tensor out) {
 // bf16 GEMM
 // ----------------------------------------------------------------------------
 static const uint16_t* bf16_ptr(const Tensor& t) { return reinterpret_cast<const uint16_t*>(t.data_ptr()); }
+// a forced GEMM configuration: 6 was the persistent ping-pong kernel, whose number stays unused
+static void check_gemm_cfg(int cfg) {
+  TORCH_CHECK(cfg != 6, "GEMM configuration 6 (persistent ping-pong) was retired; use 5 (ping-pong) or 7 (4-wave)");
+}
 
 // A, B, C are 2-D (row-major, unit column stride). a_mn / b_mn describe the storage:
 //   A: [M,K] (a_mn=0) or [K,M] (a_mn=1);  B: [N,K] (b_mn=0) or [K,N] (b_mn=1);  C: [M,N].
 void gemm(Tensor A, Tensor B, Tensor C, bool a_mn, bool b_mn, c10::optional<Tensor> bias, c10::optional<Tensor> aux,
           c10::optional<Tensor> res, double alpha, int mode, bool accumulate, int cfg, int splits,
           c10::optional<Tensor> colsum_out, bool colsum_accumulate) {
+  check_gemm_cfg(cfg);
   TORCH_CHECK(A.dim() == 2 && B.dim() == 2 && C.dim() == 2, "gemm operands must be 2-D");
   TORCH_CHECK(A.scalar_type() == at::kBFloat16 && B.scalar_type() == at::kBFloat16, "gemm A/B must be bf16");
   TORCH_CHECK(C.scalar_type() == at::kBFloat16 || C.scalar_type() == at::kFloat, "gemm C must be bf16 or fp32");
@@ -414,6 +419,7 @@ static const uint8_t* u8(const Tensor& t) { return reinterpret_cast<const uint8_
 void gemm_f8(Tensor A, Tensor B, Tensor C, int fmt_a, int fmt_b, Tensor inv_scale_a, Tensor inv_scale_b,
              c10::optional<Tensor> bias, c10::optional<Tensor> aux, c10::optional<Tensor> res, double alpha, int mode,
              bool accumulate, int cfg, int splits) {
+  check_gemm_cfg(cfg);
   TORCH_CHECK(A.dim() == 2 && B.dim() == 2 && C.dim() == 2, "gemm_f8 operands must be 2-D");
   TORCH_CHECK(is_fp8_storage(A) && is_fp8_storage(B), "gemm_f8 A/B must be fp8 (or uint8) storage");
   TORCH_CHECK((fmt_a == 0 || fmt_a == 1) && (fmt_b == 0 || fmt_b == 1) && !(fmt_a == 1 && fmt_b == 1),
@@ -610,6 +616,7 @@ void fp8_update_scale(Tensor hist, Tensor amax, Tensor scale, Tensor inv_scale, 
 }
 
 py::tuple gemm_plan(bool a_mn, bool b_mn, int64_t M, int64_t N, int64_t K, int cfg, int splits, bool accumulate) {
+  check_gemm_cfg(cfg);
   const GemmPlan p = plan_gemm_bf16(a_mn, b_mn, (int)M, (int)N, (int)K, cfg, splits, accumulate ? 1 : 0);
   return py::make_tuple(p.cfg, p.splits, p.ksteps, p.ws_floats, p.ext);
 }
@@ -1389,6 +1396,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("out_amax"), py::arg("bias") = py::none(), py::arg("aux") = py::none(), py::arg("mode") = 0,
         py::arg("colsum_out") = py::none(), py::arg("colsum_accumulate") = false);
   m.def("gemm_f8_plan", [](int64_t M, int64_t N, int64_t K, int cfg, int splits) {
+    check_gemm_cfg(cfg);
     const GemmPlan p = plan_gemm_f8((int)M, (int)N, (int)K, cfg, splits);
     return py::make_tuple(p.cfg, p.splits, p.ksteps, p.ws_floats, p.ext);
   }, py::arg("M"), py::arg("N"), py::arg("K"), py::arg("cfg") = -1, py::arg("splits") = 0);

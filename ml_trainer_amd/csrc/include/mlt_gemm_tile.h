@@ -1,5 +1,5 @@
-// Fragment / staging helpers shared by the 256-wide bf16 / fp8 GEMM kernels (gemm_tile.hip:
-// one tile per workgroup; gemm_persist.hip: persistent tile loop with register epilogue).
+// Fragment / staging helpers of the 256-wide bf16 / fp8 GEMM kernels (gemm_tile.hip), and the
+// host interface of the 4-wave kernel (gemm_w4.hip) that gemm_tile.hip dispatches to.
 #pragma once
 #include "mlt_common.h"
 
@@ -97,11 +97,6 @@ __device__ __forceinline__ i32x8 tfrag_f8(const uint8_t* lds, int row) {
 }
 
 struct GemmEpi;
-// gemm_persist.hip (planner cfg 6): persistent 256x256 tile loop, register epilogue, splits = 1
-template <bool AM, bool BNL, typename OutT, int F8A, int F8B>
-void launch_gemm_persist(const uint8_t* A, const uint8_t* B, OutT* C, int M, int N, int K, int64_t lda, int64_t ldb,
-                         int64_t ldc, const GemmEpi& e, int group_m, int max_blocks, hipStream_t st);
-
 // gemm_w4.hip (planner cfg 7): 4-wave 256x256x64 tile, generated-asm main loop, k-contiguous A,
 // B k-contiguous or (b_mn) n-contiguous
 bool gemm_w4_supported(int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc, int out_bytes, const GemmEpi& e,

@@ -167,7 +167,9 @@ void launch_mcrmse(const float* p, const float* t, int64_t B, int C, float* col,
 // Kernel choice per shape: cfg 0 = 128x128 register-staged kernel (any K % 8 == 0), cfg 1..4 =
 // 256x256 / 256x128 / 128x256 / 256x192 global_load_lds kernels (K % 64 == 0) with split-K
 // (deterministic in-launch slab reduction; needs ws_floats of fp32 workspace from the caller;
-// tile counters come from an internal self-resetting pool when cnt == nullptr).
+// tile counters come from an internal self-resetting pool when cnt == nullptr), cfg 5 = 256x256
+// ping-pong kernel, cfg 7 = 4-wave asm kernel (gemm_w4.hip). cfg 6 (a persistent ping-pong kernel)
+// is retired: the number stays unused and the bindings reject it.
 struct GemmPlan {
   int cfg;
   int splits;
@@ -179,7 +181,7 @@ struct GemmPlan {
 GemmPlan plan_gemm_bf16(int a_mn, int b_mn, int M, int N, int K, int force_cfg, int force_splits,
                         int accumulate = 0);
 void set_gemm_split_mode(int mode);  // -1 planner, 0 in-kernel last-arriver, 1 external reduce
-void set_gemm_w4q8(int on);          // gemm_f8_q GELU: 1 4-wave kernel, 0 ping-pong, -1 env
+void set_gemm_w4q8(int on);          // gemm_f8_q GELU: 1 4-wave kernel, 0 ping-pong, -1 default (1)
 void launch_gemm_bf16(const GemmPlan& plan, int a_mn, int b_mn, bool out_f32, const uint16_t* A, const uint16_t* B,
                       void* C, int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc, const float* bias,
                       const uint16_t* aux, int64_t ldaux, const uint16_t* res, int64_t ldres, float alpha, int mode,

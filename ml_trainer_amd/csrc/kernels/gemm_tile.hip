@@ -33,14 +33,11 @@
 
 namespace mlt {
 
-// exact GELU / GELU' at the bf16 input points for the quantising epilogue (scripts/gen_gelu_table.py;
-// the 4-wave kernel's epilogues use the same tables, gemm_w4.hip). Build switch -DMLT_Q8_GELU_TAB=0:
-// the A&S erf polynomial of mlt_gemm.h. Same-box A/B at the large config's FFN (262 K tokens,
+// The quantising epilogue takes exact GELU / GELU' at the bf16 input points from tables
+// (scripts/gen_gelu_table.py; the 4-wave kernel's epilogues use the same tables, gemm_w4.hip).
+// Against a two-wide erf polynomial at the large config's FFN (262 K tokens,
 // profiles/r5/fp8_q8_gelu_tab_ab.jsonl): q8 GELU forward 2.37 -> 2.28 ms, q8 dGELU 2.49-2.50 ->
 // 2.37-2.38 ms; fp8 `large` 1,183-1,184 -> 1,202-1,205 samples/s.
-#ifndef MLT_Q8_GELU_TAB
-#define MLT_Q8_GELU_TAB 1
-#endif
 
 template <int V>
 using PIC = std::integral_constant<int, V>;
@@ -399,7 +396,7 @@ __device__ __forceinline__ void q8_quadrant(uint8_t* __restrict__ C, int64_t ldc
     const int gn = gn0 + c16;
     if (epi.mode == 1) {  // GELU: save the bf16 pre-activation, activate its rounded value
       uint16_t* ap = const_cast<uint16_t*>(epi.aux) + gm * epi.ldaux + gn;
-      uint32_t pr[8];  // (two-wide GELU, mlt_gemm.h)
+      uint32_t pr[8];
 #pragma unroll
       for (int q = 0; q < 8; ++q) pr[q] = cvt_pk_bf16(f32x2{v[2 * q], v[2 * q + 1]});
       reinterpret_cast<uint4*>(ap)[0] = make_uint4(pr[0], pr[1], pr[2], pr[3]);
@@ -409,12 +406,8 @@ __device__ __forceinline__ void q8_quadrant(uint8_t* __restrict__ C, int64_t ldc
         f32x2 x2[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) x2[q] = unpack_bf16x2(pr[4 * hh + q]);
-        if constexpr (MLT_Q8_GELU_TAB) {
 #pragma unroll
-          for (int q = 0; q < 4; ++q) x2[q] = x2[q] * gelu_tab2(pr[4 * hh + q], tab);
-        } else {
-          gelu2<4>(x2);
-        }
+        for (int q = 0; q < 4; ++q) x2[q] = x2[q] * gelu_tab2(pr[4 * hh + q], tab);
 #pragma unroll
         for (int q = 0; q < 4; ++q) v[8 * hh + 2 * q] = x2[q].x, v[8 * hh + 2 * q + 1] = x2[q].y;
       }
@@ -425,14 +418,8 @@ __device__ __forceinline__ void q8_quadrant(uint8_t* __restrict__ C, int64_t ldc
 #pragma unroll
       for (int hh = 0; hh < 2; ++hh) {
         f32x2 x2[4];
-        if constexpr (MLT_Q8_GELU_TAB) {
 #pragma unroll
-          for (int q = 0; q < 4; ++q) x2[q] = gelu_tab2(w[4 * hh + q], tab);
-        } else {
-#pragma unroll
-          for (int q = 0; q < 4; ++q) x2[q] = unpack_bf16x2(w[4 * hh + q]);
-          gelu_grad2<4>(x2);
-        }
+        for (int q = 0; q < 4; ++q) x2[q] = gelu_tab2(w[4 * hh + q], tab);
 #pragma unroll
         for (int q = 0; q < 4; ++q) v[8 * hh + 2 * q] *= x2[q].x, v[8 * hh + 2 * q + 1] *= x2[q].y;
       }
@@ -514,7 +501,7 @@ __global__ __launch_bounds__(T_NT, 1) void gemm_pp_kernel(const uint8_t* __restr
   const int wr = wid >> 2, wc = wid & 3;
   const int nk = K / (F8 ? 128 : T_BK);
   const int kt0 = ksplit * ksteps, kt1 = min(nk, kt0 + ksteps);
-  if constexpr (sizeof(OutT) == 1 && MLT_Q8_GELU_TAB) {  // quantising GELU / dGELU epilogue: its table
+  if constexpr (sizeof(OutT) == 1) {  // quantising GELU / dGELU epilogue: its table
     if (epi.mode == 1 || epi.mode == 2) gelu_tab_load(smem + 2 * BUF, epi.mode == 2, T_NT);
   }
 
@@ -849,19 +836,14 @@ const CfgDesc kCfg[kNumCfg] = {{128, 128, 0.62e15 / kCUs, 2, 1.0e-6},
                                {128, 256, 0.92e15 / kCUs, 1, 1.0e-6},
                                {256, 192, 1.05e15 / kCUs, 1, 1.0e-6},
                                {256, 256, 1.335e15 / kCUs, 1, 2.5e-6},   // 5: ping-pong
-                               {256, 256, 1.335e15 / kCUs, 1, 5.6e-6},   // 6: persistent ping-pong (fill once)
+                               {0, 0, 0.0, 0, 0.0},                      // 6: retired (the bindings reject it)
                                {256, 256, 1.335e15 / kCUs, 1, 2.5e-6}};  // 7: 4-wave asm main loop (gemm_w4.hip)
+constexpr int kRetiredCfg = 6;
+constexpr int kLastFittedCfg = 5;  // plan_tiles searches 1..5; cfg 7 is placed by plan_gemm_bf16 / plan_gemm_f8
 
-// split-K combine override: -1 planner, 0 in-kernel, 1 external (env MLT_GEMM_SPLIT_EXT, or
-// set_gemm_split_mode() from tests / benchmarks)
-int g_split_mode = -2;
-int gemm_split_mode() {
-  if (g_split_mode == -2) {
-    const char* v = getenv("MLT_GEMM_SPLIT_EXT");
-    g_split_mode = v ? atoi(v) : -1;
-  }
-  return g_split_mode;
-}
+// split-K combine override: -1 planner, 0 in-kernel, 1 external (set_gemm_split_mode() from tests /
+// benchmarks)
+int g_split_mode = -1;
 
 // Cost of combining split-K partials (fitted to benchmarks/wgrad_bench.py on MI355X). In-kernel:
 // the last-arriving block of each tile reads every slab of its tile on its own -- measured
@@ -889,7 +871,6 @@ double est_time(int cfg, int splits, int M, int N, int K, int kstep, double spee
   const double fixed = c.fixed;
   const double t_block = 2.0 * c.bm * c.bn * kstep * ks / (speed * c.rate / c.per_cu) + fixed;
   double t = rounds * t_block;
-  if (cfg == 6) t = rounds * (t_block - fixed) + fixed;  // prologue / epilogue overlap the next tile
   if (splits > 1) t += split_cost(cfg, splits, M, N, nullptr);
   return t;
 }
@@ -898,6 +879,13 @@ double est_time(int cfg, int splits, int M, int N, int K, int kstep, double spee
 // overrides). 4 measured >= 8 everywhere on MI355X (profiles/gemm_group_m_r2.txt: BERT-base b512
 // +1.0 %, fp8 large b512 +1.1 %, BERT-base b128 equal); 16 lost 2-3 % at b128 (ab_gemm_group_m.txt)
 constexpr int kGroupM = 4;
+int gemm_group_m() {
+  static const int group_m = [] {
+    const char* v = getenv("MLT_GEMM_GROUP_M");
+    return v ? atoi(v) : kGroupM;
+  }();
+  return group_m;
+}
 // cfg 7 runs one 256 x 256 tile per workgroup and never splits K: below about one tile per CU the
 // split-K tiles win (the fp8 weight gradients of the `large` config: 16-256 tiles at K = 256K
 // tokens ran 1,064 -> 621 samples/s end to end when cfg 7 took them)
@@ -926,26 +914,20 @@ void w4_pick_splits(int tiles, int nk, int M, int N, int& bs, int& bks) {
 }
 
 GemmPlan plan_tiles(int M, int N, int K, int force_cfg, int force_splits, int kstep, bool allow_legacy,
-                    bool allow_pp = true, bool allow_persist = true) {
+                    bool allow_pp = true) {
   GemmPlan p{0, 1, 0, 0, 0};
   const bool big_ok = K % kstep == 0 && K >= kstep && M >= 64 && N >= 64;
   const double speed = kstep == 128 ? 1.8 : 1.0;
   int best_cfg = 0, best_s = 1;
   if (force_cfg >= 0) {
-    best_cfg = (force_cfg >= 1 && force_cfg < kNumCfg && big_ok) ? force_cfg : 0;
-    if (best_cfg == 6 && !allow_persist) best_cfg = 1;
-    best_s = best_cfg ? (force_splits > 0 && best_cfg < 6 ? force_splits : 1) : 1;
+    best_cfg = (force_cfg >= 1 && force_cfg < kNumCfg && force_cfg != kRetiredCfg && big_ok) ? force_cfg : 0;
+    best_s = best_cfg ? (force_splits > 0 && best_cfg <= kLastFittedCfg ? force_splits : 1) : 1;
   } else if (big_ok) {
     double best = allow_legacy ? est_time(0, 1, M, N, K, 64, 1.0) : 1e30;
     const int nk = K / kstep;
-    for (int cfg = 1; cfg < kNumCfg; ++cfg)
+    for (int cfg = 1; cfg <= kLastFittedCfg; ++cfg)
       for (int s = 1; s <= 16; ++s) {
         if (cfg == 5 && !allow_pp) break;
-        // persistent ping-pong (cfg 6): only when forced. It won 4-12 % on the fp8 K = 768 / 1024
-        // shapes while the tile kernels stored 8 bytes per lane; with their 16-byte-store
-        // epilogue the ping-pong tile beats it by 13-20 % there (profiles/gemm_epi16_64k_tokens.jsonl,
-        // profiles/fp8_cfg_large_131k_tokens.jsonl), and at K >= 3072 it already lost by 8-11 %.
-        if (cfg >= 6) break;
         if (s > nk) break;
         const int ks = (nk + s - 1) / s;
         if ((int64_t)ks * (s - 1) >= nk) continue;  // no empty split
@@ -957,10 +939,7 @@ GemmPlan plan_tiles(int M, int N, int K, int force_cfg, int force_splits, int ks
           best_s = s;
         }
       }
-    if (force_splits > 0 && best_cfg) {
-      if (best_cfg == 6) best_cfg = 1;  // an explicit split-K request takes the split-capable tile
-      best_s = force_splits;
-    }
+    if (force_splits > 0 && best_cfg) best_s = force_splits;
   }
   p.cfg = best_cfg;
   p.splits = best_s;
@@ -972,8 +951,7 @@ GemmPlan plan_tiles(int M, int N, int K, int force_cfg, int force_splits, int ks
     const int64_t tiles = (int64_t)((M + c.bm - 1) / c.bm) * ((N + c.bn - 1) / c.bn);
     if (p.splits > 1) {
       split_cost(best_cfg, p.splits, M, N, &p.ext);
-      const int mode = gemm_split_mode();
-      if (mode >= 0) p.ext = (mode > 0 && N % 4 == 0) ? 1 : 0;
+      if (g_split_mode >= 0) p.ext = (g_split_mode > 0 && N % 4 == 0) ? 1 : 0;
       if (p.ext) {
         p.ws_floats = (int64_t)p.splits * M * N;
         p.cnt_ints = 0;
@@ -1016,19 +994,15 @@ void launch_tile(const GemmPlan& p, const uint8_t* A, const uint8_t* B, OutT* C,
     attr_set = true;
   }
   const int tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
-  static const int group_m = [] {
-    const char* v = getenv("MLT_GEMM_GROUP_M");
-    return v ? atoi(v) : kGroupM;
-  }();
   hipLaunchKernelGGL(kern, dim3(tiles, p.splits), dim3(T_NT), G::SMEM, st, A, B, C, M, N, K, lda, ldb, ldc, e, ws,
-                     cnt, p.ksteps, group_m);
+                     cnt, p.ksteps, gemm_group_m());
 }
 
 template <bool AM, bool BNL, typename OutT, int F8A, int F8B>
 void launch_pp(const GemmPlan& p, const uint8_t* A, const uint8_t* B, OutT* C, int M, int N, int K, int64_t lda,
                int64_t ldb, int64_t ldc, const GemmEpi& e, float* ws, unsigned* cnt, hipStream_t st) {
   // two K-tiles; the epilogue image (8 x 64 x 36 fp32) fits inside; + the GELU table (quantising epilogue)
-  constexpr int SMEM = 2 * 4 * 16384 + (sizeof(OutT) == 1 && MLT_Q8_GELU_TAB ? kGeluTabBytes : 0);
+  constexpr int SMEM = 2 * 4 * 16384 + (sizeof(OutT) == 1 ? kGeluTabBytes : 0);
   auto kern = gemm_pp_kernel<AM, BNL, OutT, F8A, F8B>;
   static bool attr_set = false;
   if (!attr_set) {
@@ -1036,78 +1010,46 @@ void launch_pp(const GemmPlan& p, const uint8_t* A, const uint8_t* B, OutT* C, i
     attr_set = true;
   }
   const int tiles = ((M + 255) / 256) * ((N + 255) / 256);
-  static const int group_m = [] {
-    const char* v = getenv("MLT_GEMM_GROUP_M");
-    return v ? atoi(v) : kGroupM;
-  }();
   hipLaunchKernelGGL(kern, dim3(tiles, p.splits), dim3(T_NT), SMEM, st, A, B, C, M, N, K, lda, ldb, ldc, e, ws, cnt,
-                     p.ksteps, group_m);
+                     p.ksteps, gemm_group_m());
 }
 
 template <bool AM, bool BNL, typename OutT, int F8A, int F8B>
 void launch_cfg(const GemmPlan& p, const uint8_t* A, const uint8_t* B, OutT* C, int M, int N, int K, int64_t lda,
                 int64_t ldb, int64_t ldc, const GemmEpi& e, float* ws, unsigned* cnt, hipStream_t st) {
+  static_assert(sizeof(OutT) == 2 || sizeof(OutT) == 4, "bf16 or fp32 output (fp8 outputs: launch_gemm_f8_q)");
   switch (p.cfg) {
     case 1: launch_tile<256, 256, 2, AM, BNL, OutT, F8A, F8B>(p, A, B, C, M, N, K, lda, ldb, ldc, e, ws, cnt, st); break;
     case 2: launch_tile<256, 128, 4, AM, BNL, OutT, F8A, F8B>(p, A, B, C, M, N, K, lda, ldb, ldc, e, ws, cnt, st); break;
     case 3: launch_tile<128, 256, 2, AM, BNL, OutT, F8A, F8B>(p, A, B, C, M, N, K, lda, ldb, ldc, e, ws, cnt, st); break;
     case 4: launch_tile<256, 192, 4, AM, BNL, OutT, F8A, F8B>(p, A, B, C, M, N, K, lda, ldb, ldc, e, ws, cnt, st); break;
     case 5: launch_pp<AM, BNL, OutT, F8A, F8B>(p, A, B, C, M, N, K, lda, ldb, ldc, e, ws, cnt, st); break;
-    case 6:
-      // persistent ping-pong (gemm_persist.hip): k-contiguous A, an even K-tile count, no split
-      if constexpr (!AM) {
-        if ((K / (F8A >= 0 ? 128 : T_BK)) % 2 == 0 && p.splits == 1) {
-          static const int group_m = [] {
-            const char* v = getenv("MLT_GEMM_GROUP_M");
-            return v ? atoi(v) : kGroupM;
-          }();
-          launch_gemm_persist<AM, BNL, OutT, F8A, F8B>(A, B, C, M, N, K, lda, ldb, ldc, e, group_m, kCUs, st);
-          break;
-        }
-      }
-      launch_pp<AM, BNL, OutT, F8A, F8B>(p, A, B, C, M, N, K, lda, ldb, ldc, e, ws, cnt, st);
-      break;
-    case 7:
-      // 4-wave asm main loop (gemm_w4.hip): bf16, k-contiguous A, full 256 tiles
-      if constexpr (!AM && F8A < 0 && (sizeof(OutT) == 2 || sizeof(OutT) == 4)) {
-        if (p.splits == 1 && gemm_w4_supported(M, N, K, lda, ldb, ldc, (int)sizeof(OutT), e, BNL)) {
-          static const int group_m = [] {
-            const char* v = getenv("MLT_GEMM_GROUP_M");
-            return v ? atoi(v) : kGroupM;
-          }();
-          launch_gemm_w4<OutT>(A, B, C, M, N, K, lda, ldb, ldc, e, group_m, BNL, st);
-          break;
-        }
-      } else if constexpr (AM && BNL && F8A < 0 && (sizeof(OutT) == 2 || sizeof(OutT) == 4)) {
-        // weight gradients: both operands transposed in LDS, split-K raw partials (external reduce)
-        if (gemm_w4_wgrad_supported(M, N, K, lda, ldb, ldc, (int)sizeof(OutT), e, p.splits, p.ksteps) &&
-            (p.splits == 1 || (ws != nullptr && cnt == nullptr))) {
-          static const int group_m = [] {
-            const char* v = getenv("MLT_GEMM_GROUP_M");
-            return v ? atoi(v) : kGroupM;
-          }();
-          launch_gemm_w4_wgrad<OutT>(A, B, C, ws, M, N, K, lda, ldb, ldc, e, group_m, p.splits, p.ksteps, st);
-          break;
-        }
-        launch_tile<256, 256, 2, AM, BNL, OutT, F8A, F8B>(p, A, B, C, M, N, K, lda, ldb, ldc, e, ws, cnt, st);
-        break;
-      } else if constexpr (!AM && !BNL && F8A >= 0 && (sizeof(OutT) == 2 || sizeof(OutT) == 4)) {
-        static const int group_m = [] {
-          const char* v = getenv("MLT_GEMM_GROUP_M");
-          return v ? atoi(v) : kGroupM;
-        }();
-        if (p.splits == 1 && gemm_w4_f8_supported(M, N, K, lda, ldb, ldc, (int)sizeof(OutT), e)) {
-          launch_gemm_w4_f8<OutT, F8A, F8B>(A, B, C, M, N, K, lda, ldb, ldc, e, group_m, st);
-          break;
-        }
+    case 7: {
+      // 4-wave asm main loop (gemm_w4.hip): for this layout, the matching 4-wave form when it covers
+      // the call; otherwise the fallback tile
+      const int gm = gemm_group_m();
+      if constexpr (F8A >= 0) {
+        // fp8 (both operands k-contiguous): unsplit, or split-K raw partials for the external reduce
+        if (p.splits == 1 && gemm_w4_f8_supported(M, N, K, lda, ldb, ldc, (int)sizeof(OutT), e))
+          return launch_gemm_w4_f8<OutT, F8A, F8B>(A, B, C, M, N, K, lda, ldb, ldc, e, gm, st);
         if (p.splits > 1 && ws != nullptr && cnt == nullptr &&
-            gemm_w4_f8_splitk_supported(M, N, K, lda, ldb, p.splits, p.ksteps)) {
-          launch_gemm_w4_f8_splitk<F8A, F8B>(A, B, ws, M, N, K, lda, ldb, group_m, p.splits, p.ksteps, st);
-          break;
-        }
+            gemm_w4_f8_splitk_supported(M, N, K, lda, ldb, p.splits, p.ksteps))
+          return launch_gemm_w4_f8_splitk<F8A, F8B>(A, B, ws, M, N, K, lda, ldb, gm, p.splits, p.ksteps, st);
+      } else if constexpr (!AM) {
+        // forward / input gradient: k-contiguous A, full 256 tiles, no split
+        if (p.splits == 1 && gemm_w4_supported(M, N, K, lda, ldb, ldc, (int)sizeof(OutT), e, BNL))
+          return launch_gemm_w4<OutT>(A, B, C, M, N, K, lda, ldb, ldc, e, gm, BNL, st);
+      } else if constexpr (BNL) {
+        // weight gradients: both operands transposed in LDS, split-K raw partials (external reduce);
+        // the ping-pong fit does not cover them, so their fallback is the 256 x 256 tile
+        if (gemm_w4_wgrad_supported(M, N, K, lda, ldb, ldc, (int)sizeof(OutT), e, p.splits, p.ksteps) &&
+            (p.splits == 1 || (ws != nullptr && cnt == nullptr)))
+          return launch_gemm_w4_wgrad<OutT>(A, B, C, ws, M, N, K, lda, ldb, ldc, e, gm, p.splits, p.ksteps, st);
+        return launch_tile<256, 256, 2, AM, BNL, OutT, F8A, F8B>(p, A, B, C, M, N, K, lda, ldb, ldc, e, ws, cnt, st);
       }
       launch_pp<AM, BNL, OutT, F8A, F8B>(p, A, B, C, M, N, K, lda, ldb, ldc, e, ws, cnt, st);
       break;
+    }
     default: break;
   }
 }
@@ -1141,7 +1083,7 @@ void launch_split_reduce(const GemmPlan& p, const float* ws, OutT* C, int M, int
 
 void set_gemm_split_mode(int mode) { g_split_mode = mode; }
 
-// which kernel runs gemm_f8_q's GELU epilogue: 1 the 4-wave one, 0 the ping-pong one, -1 MLT_GEMM_W4Q8
+// which kernel runs gemm_f8_q's GELU epilogue: 1 the 4-wave one, 0 the ping-pong one, -1 the default (1)
 static int g_w4q8 = -1;
 void set_gemm_w4q8(int on) { g_w4q8 = on; }
 
@@ -1151,20 +1093,16 @@ GemmPlan plan_gemm_bf16(int a_mn, int b_mn, int M, int N, int K, int force_cfg, 
   // only with split-K partials, whose external reduce accumulates; otherwise the fitted planner)
   // the 4-wave asm kernel (cfg 7) takes every k-contiguous-A (forward / input-gradient) shape it
   // covers: 3-17 % over the ping-pong tile on the BERT forward shapes, 98-101 % of hipBLASLt at
-  // 4096^3 / 8192^3 (profiles/r4/gemm_w4_*.jsonl). MLT_GEMM_W4=0 restores the fitted planner.
-  static const bool w4 = [] {
-    const char* v = getenv("MLT_GEMM_W4");
-    return !(v && atoi(v) == 0);
-  }();
+  // 4096^3 / 8192^3 (profiles/r4/gemm_w4_*.jsonl).
   // (only with enough tiles to fill the chip: few-tile / long-K shapes keep the split-K planner)
-  if (w4 && !accumulate && force_cfg < 0 && force_splits <= 0 && a_mn == 0 && M % 256 == 0 && N % 256 == 0 &&
+  if (!accumulate && force_cfg < 0 && force_splits <= 0 && a_mn == 0 && M % 256 == 0 && N % 256 == 0 &&
       K % 128 == 0 && K >= 256 && (int64_t)(M / 256) * (N / 256) >= kW4MinTiles) {
     GemmPlan p{7, 1, K / 64, 0, 0};
     return p;
   }
   // weight gradients (both operands mn-contiguous, few tiles, K = tokens): cfg 7 with split-K raw
   // partials reduced by one grid-wide launch; splits from a rounds x K-steps + reduce-traffic model
-  if (w4 && force_cfg < 0 && force_splits <= 0 && a_mn == 1 && b_mn == 1 && M % 256 == 0 && N % 256 == 0 &&
+  if (force_cfg < 0 && force_splits <= 0 && a_mn == 1 && b_mn == 1 && M % 256 == 0 && N % 256 == 0 &&
       K % 128 == 0 && K >= 256) {
     int bs = 0, bks = 0;
     w4_pick_splits((M / 256) * (N / 256), K / 64, M, N, bs, bks);
@@ -1176,23 +1114,18 @@ GemmPlan plan_gemm_bf16(int a_mn, int b_mn, int M, int N, int K, int force_cfg, 
   }
   // the ping-pong kernel's fit covers the k-contiguous-A (forward / dgrad) shapes; weight
   // gradients (A = dY^T, mn-contiguous) stay on the 256-wide tiles with split-K
-  return plan_tiles(M, N, K, force_cfg, force_splits, 64, true, a_mn == 0, a_mn == 0);
+  return plan_tiles(M, N, K, force_cfg, force_splits, 64, true, a_mn == 0);
 }
 
 GemmPlan plan_gemm_f8(int M, int N, int K, int force_cfg, int force_splits) {
-  // the 4-wave asm kernel's fp8 form (cfg 7) where it applies; MLT_GEMM_W4=0 / MLT_GEMM_W4F8=0 opt out
-  static const bool w4 = [] {
-    const char* v = getenv("MLT_GEMM_W4");
-    const char* v8 = getenv("MLT_GEMM_W4F8");
-    return !(v && atoi(v) == 0) && !(v8 && atoi(v8) == 0);
-  }();
-  if (w4 && force_cfg < 1 && force_splits <= 0 && M % 256 == 0 && N % 256 == 0 && K % 256 == 0 && K >= 512 &&
+  // the 4-wave asm kernel's fp8 form (cfg 7) where it applies
+  if (force_cfg < 1 && force_splits <= 0 && M % 256 == 0 && N % 256 == 0 && K % 256 == 0 && K >= 512 &&
       (int64_t)(M / 256) * (N / 256) >= kW4MinTiles) {
     GemmPlan p{7, 1, K / 128, 0, 0};
     return p;
   }
   // few tiles, long K (the fp8 weight gradients): cfg 7 split-K raw partials + the external reduce
-  if (w4 && force_cfg < 1 && force_splits <= 0 && M % 256 == 0 && N % 256 == 0 && N % 4 == 0 && K % 256 == 0 &&
+  if (force_cfg < 1 && force_splits <= 0 && M % 256 == 0 && N % 256 == 0 && N % 4 == 0 && K % 256 == 0 &&
       K >= 1024) {
     int bs = 0, bks = 0;
     w4_pick_splits((M / 256) * (N / 256), K / 128, M, N, bs, bks);
@@ -1276,26 +1209,17 @@ void launch_gemm_f8_q(int fmt_a, int fmt_b, const uint8_t* A, const uint8_t* B, 
   e.q_amax = out_amax;
   e.q_colpart = colpart;
   e.q_fmt = out_fmt;
-  // the 4-wave kernel's quantising epilogues when they fit (MLT_GEMM_W4Q8=0 / set_gemm_w4q8(0): the
+  // the 4-wave kernel's quantising epilogues when they fit (set_gemm_w4q8(0): the
   // ping-pong kernel's): 1.93 vs 2.27 ms per FFN1 (GELU) call and 1.97 vs 2.37 ms per FFN2-dgrad
   // (dGELU) call of the fp8 `large` step (262144 x 4096 x 1024), 1,262 vs 1,204 samples/s for the
   // step (profiles/r5/fp8_q8_w4_ab.jsonl). Its first form, Y^T stored as 64 rows x 16 bytes per
   // instruction, took 2.63 ms: the 4-wave epilogue is not hidden behind another wave group's main
   // loop, so the Y^T pass is stored as 16 columns x 64 contiguous bytes per instruction instead.
   // (Round 4's 4-wave q8 form, on the erf GELU, had lost too: 2.73 vs 2.43 ms.)
-  if (g_w4q8 < 0) {
-    const char* v = getenv("MLT_GEMM_W4Q8");
-    g_w4q8 = (v && atoi(v) == 0) ? 0 : 1;
-  }
-  // raster group width 4 (MLT_GEMM_W4Q8_GROUP_M overrides): in isolation 2 M-tiles ran the GELU
+  // raster group width kGroupM = 4 as everywhere else: in isolation 2 M-tiles ran the GELU
   // form faster (1.91 vs 1.96 ms) and the dGELU form slower (2.08 vs 1.97), 8 / 16 lost on both;
   // in the fp8 `large` step GELU at 2 lost (1,254 vs 1,263 samples/s) -- profiles/r5/fp8_q8_w4_group_m.jsonl
-  static const int q_group_m = [] {
-    const char* v = getenv("MLT_GEMM_W4Q8_GROUP_M");
-    return v ? atoi(v) : 0;
-  }();
-  const int gm_q = q_group_m > 0 ? q_group_m : kGroupM;
-  if (g_w4q8 && launch_gemm_w4_f8_q(fmt_a, A, B, Y, M, N, K, lda, ldb, ldy, e, gm_q, st)) return;
+  if (g_w4q8 != 0 && launch_gemm_w4_f8_q(fmt_a, A, B, Y, M, N, K, lda, ldb, ldy, e, gemm_group_m(), st)) return;
   GemmPlan p{5, 1, K / 128, 0, 0};
   if (fmt_a == 0 && fmt_b == 0)
     launch_pp<false, false, uint8_t, 0, 0>(p, A, B, Y, M, N, K, lda, ldb, ldy, e, nullptr, nullptr, st);

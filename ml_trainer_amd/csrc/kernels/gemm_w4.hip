@@ -44,17 +44,14 @@ __device__ __forceinline__ uint32_t pack2(uint16_t lo, uint16_t hi) { return (ui
 constexpr int kW4Pitch = 132, kW4Smem = 4 * 64 * kW4Pitch * 4 > 131072 ? 4 * 64 * kW4Pitch * 4 : 131072;
 
 // GELU / GELU' of the (b)GELU epilogues from exact tables at the bf16 input points (scripts/
-// gen_gelu_table.py: layout, accuracy, why) instead of the A&S erf of mlt_gemm.h; the table sits in
-// LDS behind the epilogue images (158,736 B of the 160 KB). Build switch -DMLT_W4_GELU_TAB=0: the
-// erf polynomial. Same-box A/B at 256 K tokens (profiles/r5/gemm_gelu_tab_attn_pkf32_ab.jsonl): bias +
-// GELU 832 -> 862-870 TF, dGELU 839-842 -> 914-917, dGELU + column sums 809-812 -> 880-887 (plain
-// epilogue 1,097-1,107); BERT-base 3,038-3,040 -> 3,070-3,074 samples/s.
-#ifndef MLT_W4_GELU_TAB
-#define MLT_W4_GELU_TAB 1
-#endif
+// gen_gelu_table.py: layout, accuracy, why) instead of an erf polynomial; the table sits in
+// LDS behind the epilogue images (158,736 B of the 160 KB). Against a two-wide erf polynomial at
+// 256 K tokens (profiles/r5/gemm_gelu_tab_attn_pkf32_ab.jsonl): bias + GELU 832 -> 862-870 TF, dGELU
+// 839-842 -> 914-917, dGELU + column sums 809-812 -> 880-887 (plain epilogue 1,097-1,107); BERT-base
+// 3,038-3,040 -> 3,070-3,074 samples/s.
 template <int EK>
-constexpr bool w4_gelu_tab() {
-  return MLT_W4_GELU_TAB && (w4_gel<EK>() || w4_dgel<EK>());
+constexpr bool w4_gelu_tab() {  // a GELU / dGELU epilogue
+  return w4_gel<EK>() || w4_dgel<EK>();
 }
 template <int EK>
 constexpr int w4_smem() {
@@ -140,7 +137,7 @@ __device__ __forceinline__ void w4_epilogue(OutT* __restrict__ C, int64_t ldc, c
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[e] = v[e] * alpha + bs[e];
       if constexpr (w4_gel<EK>()) {  // keep the (bf16-rounded) pre-activation for the backward
-        uint32_t a[4];                // (two-wide GELU: this epilogue is VALU-bound, mlt_gemm.h)
+        uint32_t a[4];
         f32x2 x2[4];
 #pragma unroll
         for (int q2 = 0; q2 < 4; ++q2) {
@@ -149,26 +146,16 @@ __device__ __forceinline__ void w4_epilogue(OutT* __restrict__ C, int64_t ldc, c
         }
         *reinterpret_cast<uint4*>(const_cast<uint16_t*>(epi.aux) + (int64_t)gm * epi.ldaux + gn) =
             make_uint4(a[0], a[1], a[2], a[3]);
-        if constexpr (w4_gelu_tab<EK>()) {
 #pragma unroll
-          for (int q2 = 0; q2 < 4; ++q2) x2[q2] = x2[q2] * gelu_tab2(a[q2], smem + kW4Smem);
-        } else {
-          gelu2<4>(x2);
-        }
+        for (int q2 = 0; q2 < 4; ++q2) x2[q2] = x2[q2] * gelu_tab2(a[q2], smem + kW4Smem);
 #pragma unroll
         for (int q2 = 0; q2 < 4; ++q2) v[2 * q2] = x2[q2].x, v[2 * q2 + 1] = x2[q2].y;
       } else if constexpr (w4_dgel<EK>()) {
         const uint4 sv = sd[0][it % SB];
         f32x2 x2[4];
-        if constexpr (w4_gelu_tab<EK>()) {
-          const uint32_t sw4[4] = {sv.x, sv.y, sv.z, sv.w};
+        const uint32_t sw4[4] = {sv.x, sv.y, sv.z, sv.w};
 #pragma unroll
-          for (int q2 = 0; q2 < 4; ++q2) x2[q2] = gelu_tab2(sw4[q2], smem + kW4Smem);
-        } else {
-          x2[0] = unpack_bf16x2(sv.x), x2[1] = unpack_bf16x2(sv.y), x2[2] = unpack_bf16x2(sv.z);
-          x2[3] = unpack_bf16x2(sv.w);
-          gelu_grad2<4>(x2);
-        }
+        for (int q2 = 0; q2 < 4; ++q2) x2[q2] = gelu_tab2(sw4[q2], smem + kW4Smem);
 #pragma unroll
         for (int q2 = 0; q2 < 4; ++q2) {
           const f32x2 gv = f32x2{v[2 * q2], v[2 * q2 + 1]} * x2[q2];
@@ -414,12 +401,11 @@ __global__ __launch_bounds__(256, 1) void gemm_w4f8_kernel(const uint8_t* __rest
   }
 }
 
-// Persistent by default: 256 workgroups (one per CU), XCD x walking ITS contiguous run of tile ids
+// Persistent above 256 tiles (w4_grid): 256 workgroups (one per CU), XCD x walking ITS contiguous run of tile ids
 // (the run xcd_remap gives it in a one-tile-per-workgroup launch, so the L2 reuse pattern is kept),
 // the next tile's DMAs issued right behind the previous epilogue's stores: +0.5-2 % per shape,
 // BERT-base 2,925 / 2,932 -> 2,945 / 2,956 (profiles/r4/gemm_w4_persist_xcd_ab.jsonl). (A first
 // persistent version striding ids by 256 broke that locality and lost: QKV 950 vs 988 TF.)
-// MLT_W4_PERSIST=0: one tile per workgroup.
 template <typename OutT, int EK, bool AN, bool BN>
 __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(const uint8_t* __restrict__ A, const uint8_t* __restrict__ B,
                                                          OutT* __restrict__ C, int M, int N, int nk, int ksteps,
@@ -447,6 +433,9 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(const uint8_t* __restri
   }
 }
 
+// workgroups per split: persistent (one per CU) once an unsplit launch has more tiles than CUs
+static int w4_grid(int tiles, int splits) { return splits == 1 && tiles > 256 ? 256 : tiles; }
+
 template <typename OutT, int EK, bool AN, bool BN>
 static void launch_w4_ek(const uint8_t* A, const uint8_t* B, OutT* C, int M, int N, int K, int64_t lda, int64_t ldb,
                          int64_t ldc, const GemmEpi& e, int group_m, int splits, int ksteps, int64_t cstride,
@@ -458,12 +447,7 @@ static void launch_w4_ek(const uint8_t* A, const uint8_t* B, OutT* C, int M, int
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
     attr_set = true;
   }
-  const int tiles = (M / 256) * (N / 256);
-  static const bool persist = [] {
-    const char* v = getenv("MLT_W4_PERSIST");
-    return !(v && atoi(v) == 0);
-  }();
-  const int grid = persist && splits == 1 && tiles > 256 ? 256 : tiles;
+  const int grid = w4_grid((M / 256) * (N / 256), splits);
   hipLaunchKernelGGL(kern, dim3(grid, splits), dim3(256), SMEM, st, A, B, C, M, N, K / 64, ksteps, lda, ldb, ldc,
                      cstride, e, group_m);
 }
@@ -551,12 +535,7 @@ static void launch_w4f8_ek(const uint8_t* A, const uint8_t* B, OutT* C, int M, i
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
     attr_set = true;
   }
-  static const bool persist = [] {
-    const char* v = getenv("MLT_W4_PERSIST");
-    return !(v && atoi(v) == 0);
-  }();
-  const int tiles = (M / 256) * (N / 256);
-  const int grid = persist && splits == 1 && tiles > 256 ? 256 : tiles;
+  const int grid = w4_grid((M / 256) * (N / 256), splits);
   hipLaunchKernelGGL(kern, dim3(grid, splits), dim3(256), SMEM, st, A, B, C, M, N, K / 128,
                      ksteps > 0 ? ksteps : K / 128, lda, ldb, ldc, cstride, e, group_m);
 }

@@ -84,7 +84,7 @@ __device__ __forceinline__ f32x2 gelu_tab2(uint32_t u2, const uint8_t* tab) {
   return f32x2{*reinterpret_cast<const float*>(tab + (w & 0xffffu)), *reinterpret_cast<const float*>(tab + (w >> 16))};
 }
 // the same index for one bf16 (bits b), and the scalar / two-wide lookups from global memory (the
-// general, persistent and split-K-reduce epilogues: L1/L2-resident table, no LDS copy)
+// general and split-K-reduce epilogues: L1/L2-resident table, no LDS copy)
 __device__ __forceinline__ uint32_t gelu_tab_index(uint32_t b) {
   const uint32_t m = b & 0x7fffu;
   const uint32_t i = m > MLT_GELU_TAB_LO - 1 ? min(m - (MLT_GELU_TAB_LO - 1), (uint32_t)MLT_GELU_TAB_NR + 1) : 0u;

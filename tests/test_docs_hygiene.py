@@ -23,3 +23,18 @@ def test_no_one_launch_step_left():
     src = open(os.path.join(REPO, "ml_trainer_amd", "csrc", "bindings.cpp")).read()
     assert "onelaunch" not in src and "MLT_LENET_ONELAUNCH" not in src
     assert not hasattr(le.LeNetStepEngine, "flush") and not hasattr(le.LeNetStepEngine, "sync_error")
+
+
+def test_no_retired_gemm_paths_left():
+    """The persistent ping-pong GEMM (config 6), the erf-polynomial GELU fork and the switches of
+    settled A/Bs are gone from the native sources; the raster override is read in one place."""
+    csrc = os.path.join(REPO, "ml_trainer_amd", "csrc")
+    assert not glob.glob(os.path.join(csrc, "kernels", "gemm_persist*.hip"))
+    text = {}
+    for d, _, files in os.walk(csrc):
+        for f in files:
+            text[os.path.join(d, f)] = open(os.path.join(d, f), errors="replace").read()
+    for name in ("MLT_W4_GELU_TAB", "MLT_Q8_GELU_TAB", "MLT_W4_PERSIST", "MLT_GEMM_W4F8", "MLT_GEMM_W4Q8_GROUP_M",
+                 "MLT_GEMM_SPLIT_EXT", "gelu_grad2", "launch_gemm_persist"):
+        assert not [p for p, s in text.items() if name in s], name
+    assert sum(s.count('getenv("MLT_GEMM_GROUP_M")') for s in text.values()) == 1

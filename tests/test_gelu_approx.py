@@ -1,23 +1,19 @@
-"""CPU check of the two-wide A&S GELU / GELU' formula (mlt_gemm.h: phi_tail2 / gelu2 / gelu_grad2), the
-build-switch alternative of the 4-wave and quantising epilogues (-DMLT_W4_GELU_TAB=0 /
--DMLT_Q8_GELU_TAB=0); the default epilogues use the exact tables (tests/test_gelu_table.py).
+"""CPU record of the two-wide A&S GELU / GELU' polynomial that the 4-wave and quantising epilogues
+used before the exact tables (tests/test_gelu_table.py) replaced it. The device code is gone
+(docs/ARCHITECTURE.md says why tables are used); this file keeps the accuracy bound of the formula
+until a later clean-up removes it together with its last mention.
 
-The device code evaluates erf by Abramowitz & Stegun 7.1.26 with the 0.5 and 1/sqrt(2) folded
-into the constants:
+The formula evaluates erf by Abramowitz & Stegun 7.1.26 with the 0.5 and 1/sqrt(2) folded into
+the constants:
     q = Phi(-|x|) = t * h(t) * exp2(-x^2 log2(e) / 2),  t = 1 / (1 + p |x| / sqrt 2)
     gelu(x)  = fma(-|x|, q, (x + |x|) / 2)
     gelu'(x) = fma(x / sqrt(2 pi), e^{-x^2/2}, 0.5 + copysign(0.5 - q, x))
-This test replays that sequence in float32 numpy (exact division / exp2 standing in for v_rcp /
-v_exp, which are within 1 ulp) and bounds its error against the exact erf GELU, so a change of a
-constant or of the sequence in the header has a reference to fail against.
+This test replays that sequence in float32 numpy and bounds its error against the exact erf GELU.
 """
 import math
-from pathlib import Path
 
 import numpy as np
 from scipy.special import erf
-
-HDR = Path(__file__).resolve().parents[1] / "ml_trainer_amd" / "csrc" / "include" / "mlt_gemm.h"
 
 
 def _device_gelu(x):
@@ -51,11 +47,3 @@ def test_gelu_formula_matches_exact_erf_gelu():
     assert abs(g[0]) < 1e-30 and g[-1] == np.float32(12.0)
     assert abs(gp[0]) < 1e-29 and gp[-1] == 1.0
     assert np.all(np.isfinite(g)) and np.all(np.isfinite(gp))
-
-
-def test_header_carries_the_tested_constants():
-    src = HDR.read_text()
-    for c in ("0.3275911f", "1.061405429f", "-1.453152027f", "1.421413741f", "-0.284496736f", "0.254829592f",
-              "0.3989422804014327f", "1.4426950408889634f"):
-        assert src.count(c) >= 1, c  # the two-wide form (the scalar paths use the exact tables)
-    assert "pk_fma(-ax[i], q[i], (x[i] + ax[i]) * f32x2(0.5f))" in src

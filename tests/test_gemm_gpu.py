@@ -141,7 +141,7 @@ def test_identity_asymmetric_tile(dev):
     M = 256
     A = torch.eye(M, dtype=torch.bfloat16, device=dev)
     B = (torch.arange(M * 128, device=dev).view(128, M) % 251).to(torch.bfloat16)
-    for cfg in (1, 2, 3, 4, 5, 6):
+    for cfg in (1, 2, 3, 4, 5):
         out = torch.empty(M, 128, dtype=torch.float32, device=dev)
         C.gemm(A, B, out, False, False, cfg=cfg)
         torch.testing.assert_close(out, B.float().t())
@@ -212,60 +212,125 @@ def test_split_k_external_reduce_bitwise(dev, cfg):
     torch.testing.assert_close(outs[1][0], A.float().t() @ B.float() + 0.25, rtol=2e-3, atol=2e-2)
 
 
-@pytest.mark.parametrize("b_mn", [0, 1])
-def test_persistent_kernel(dev, b_mn):
-    """Config 6 (persistent tile loop, next tile's first K-step staged under the current tile's
-    last MFMAs, register epilogue from swapped-operand C^T fragments): more tiles than CUs (every
-    workgroup walks several), M / N tails, a strided A, every epilogue, bf16 and fp32 outputs."""
+def test_forced_config_6_is_rejected(dev):
+    """Configuration 6 (the persistent ping-pong kernel) is retired: forcing it raises instead of
+    running another kernel, from both GEMM entry points and both planners, and nothing is launched
+    (the output keeps its NaN fill)."""
     C = require_native()
-    M, N, K = 8200, 2312, 256  # 33 x 10 = 330 tiles > 256 workgroups; tails in M and N; 4 K-tiles
-    g = torch.Generator().manual_seed(50 + b_mn)
-    A = _mk((M, K + 64), dev, g)[:, :K]
-    B = _mk((K, N) if b_mn else (N, K), dev, g)
-    ref = _ref(A, B, 0, b_mn)
-    assert C.gemm_plan(False, bool(b_mn), M, N, K, 6, 0)[0] == 6
-    for out_dtype in (torch.bfloat16, torch.float32):
-        out = torch.empty(M, N, dtype=out_dtype, device=dev)
-        C.gemm(A, B, out, False, bool(b_mn), cfg=6)
-        tol = 2e-2 if out_dtype == torch.bfloat16 else 2e-3
-        torch.testing.assert_close(out.float(), ref, rtol=tol, atol=tol * 8)
-    bias = torch.randn(N, device=dev)
-    out = torch.empty(M, N, dtype=torch.bfloat16, device=dev)
-    aux = torch.empty(M, N, dtype=torch.bfloat16, device=dev)
-    C.gemm(A, B, out, False, bool(b_mn), bias=bias, aux=aux, mode=1, cfg=6)
-    torch.testing.assert_close(aux.float(), ref + bias, rtol=2e-2, atol=0.15)
-    torch.testing.assert_close(out.float(), torch.nn.functional.gelu(aux.float()), rtol=2e-2, atol=0.15)
-    res = _mk((M, N), dev, g)
-    C.gemm(A, B, out, False, bool(b_mn), res=res, alpha=0.5, cfg=6)
-    torch.testing.assert_close(out.float(), 0.5 * ref + res.float(), rtol=2e-2, atol=0.15)
-    acc = torch.ones(M, N, device=dev)
-    C.gemm(A, B, acc, False, bool(b_mn), accumulate=True, cfg=6)
-    torch.testing.assert_close(acc, ref + 1, rtol=2e-3, atol=2e-2)
-    pre = _mk((M, N), dev, g)
-    C.gemm(A, B, out, False, bool(b_mn), aux=pre, mode=2, cfg=6)
-    x = pre.float()
-    dg = 0.5 * (1 + torch.erf(x * 0.7071067811865476)) + x * torch.exp(-0.5 * x * x) * 0.3989422804014327
-    torch.testing.assert_close(out.float(), ref * dg, rtol=2e-2, atol=0.15)
-
-
-def test_persistent_kernel_repeatable_full_chip(dev):
-    """Race screen for the cross-tile pipeline: repeated full-chip runs are bit-identical, and
-    agree with the one-tile-per-workgroup kernel to fp32 rounding."""
-    C = require_native()
-    M, N, K = 8192, 2304, 768
-    g = torch.Generator().manual_seed(77)
-    A = _mk((M, K), dev, g)
-    B = _mk((N, K), dev, g)
-    ref = torch.empty(M, N, device=dev)
-    C.gemm(A, B, ref, False, False, cfg=1)
-    first = None
-    for _ in range(6):
-        out = torch.full((M, N), float("nan"), device=dev)
+    M = 256
+    A = torch.eye(M, dtype=torch.bfloat16, device=dev)
+    B = (torch.arange(M * 128, device=dev).view(128, M) % 251).to(torch.bfloat16)
+    out = torch.full((M, 128), float("nan"), device=dev)
+    one = torch.ones(1, device=dev)
+    with pytest.raises(RuntimeError, match="retired"):
         C.gemm(A, B, out, False, False, cfg=6)
-        if first is None:
-            first = out.clone()
-        assert torch.equal(out, first)
-    torch.testing.assert_close(first, ref, rtol=1e-5, atol=1e-4)
+    with pytest.raises(RuntimeError, match="retired"):
+        C.gemm_f8(A.to(torch.float8_e4m3fn), B.to(torch.float8_e4m3fn), out, 0, 0, one, one, cfg=6)
+    with pytest.raises(RuntimeError, match="retired"):
+        C.gemm_plan(False, False, M, 128, M, 6, 0)
+    with pytest.raises(RuntimeError, match="retired"):
+        C.gemm_f8_plan(M, 128, M, 6, 0)
+    torch.cuda.synchronize()
+    assert torch.isnan(out).all()
+
+
+# (call, args) -> (cfg, splits, ksteps, ws_floats, ext), recorded from the build before the retired
+# configuration 6 and the MLT_GEMM_W4 / MLT_GEMM_W4F8 / MLT_GEMM_SPLIT_EXT switches were removed.
+# gemm_plan args: a_mn, b_mn, M, N, K, cfg, splits, accumulate; gemm_f8_plan args: M, N, K.
+# BERT-base and `large` weights at 65536 and 262144 tokens: forward (0,0), input gradient (0,1),
+# weight gradient (1,1, plain and accumulating); four shapes that miss configuration 7; the fp8
+# `large` forward and weight-gradient shapes.
+_PINNED_PLANS = [
+    ("gemm_plan", (False, False, 65536, 2304, 768, -1, 0, False), (7, 1, 12, 0, 0)),
+    ("gemm_plan", (False, True, 65536, 768, 2304, -1, 0, False), (7, 1, 36, 0, 0)),
+    ("gemm_plan", (True, True, 2304, 768, 65536, -1, 0, False), (7, 9, 114, 15925248, 1)),
+    ("gemm_plan", (True, True, 2304, 768, 65536, -1, 0, True), (7, 9, 114, 15925248, 1)),
+    ("gemm_plan", (False, False, 262144, 2304, 768, -1, 0, False), (7, 1, 12, 0, 0)),
+    ("gemm_plan", (False, True, 262144, 768, 2304, -1, 0, False), (7, 1, 36, 0, 0)),
+    ("gemm_plan", (True, True, 2304, 768, 262144, -1, 0, False), (7, 9, 456, 15925248, 1)),
+    ("gemm_plan", (True, True, 2304, 768, 262144, -1, 0, True), (7, 9, 456, 15925248, 1)),
+    ("gemm_plan", (False, False, 65536, 768, 768, -1, 0, False), (7, 1, 12, 0, 0)),
+    ("gemm_plan", (False, True, 65536, 768, 768, -1, 0, False), (7, 1, 12, 0, 0)),
+    ("gemm_plan", (True, True, 768, 768, 65536, -1, 0, False), (7, 27, 38, 15925248, 1)),
+    ("gemm_plan", (True, True, 768, 768, 65536, -1, 0, True), (7, 27, 38, 15925248, 1)),
+    ("gemm_plan", (False, False, 262144, 768, 768, -1, 0, False), (7, 1, 12, 0, 0)),
+    ("gemm_plan", (False, True, 262144, 768, 768, -1, 0, False), (7, 1, 12, 0, 0)),
+    ("gemm_plan", (True, True, 768, 768, 262144, -1, 0, False), (7, 28, 148, 16515072, 1)),
+    ("gemm_plan", (True, True, 768, 768, 262144, -1, 0, True), (7, 28, 148, 16515072, 1)),
+    ("gemm_plan", (False, False, 65536, 3072, 768, -1, 0, False), (7, 1, 12, 0, 0)),
+    ("gemm_plan", (False, True, 65536, 768, 3072, -1, 0, False), (7, 1, 48, 0, 0)),
+    ("gemm_plan", (True, True, 3072, 768, 65536, -1, 0, False), (7, 7, 148, 16515072, 1)),
+    ("gemm_plan", (True, True, 3072, 768, 65536, -1, 0, True), (7, 7, 148, 16515072, 1)),
+    ("gemm_plan", (False, False, 262144, 3072, 768, -1, 0, False), (7, 1, 12, 0, 0)),
+    ("gemm_plan", (False, True, 262144, 768, 3072, -1, 0, False), (7, 1, 48, 0, 0)),
+    ("gemm_plan", (True, True, 3072, 768, 262144, -1, 0, False), (7, 7, 586, 16515072, 1)),
+    ("gemm_plan", (True, True, 3072, 768, 262144, -1, 0, True), (7, 7, 586, 16515072, 1)),
+    ("gemm_plan", (False, False, 65536, 768, 3072, -1, 0, False), (7, 1, 48, 0, 0)),
+    ("gemm_plan", (False, True, 65536, 3072, 768, -1, 0, False), (7, 1, 12, 0, 0)),
+    ("gemm_plan", (True, True, 768, 3072, 65536, -1, 0, False), (7, 7, 148, 16515072, 1)),
+    ("gemm_plan", (True, True, 768, 3072, 65536, -1, 0, True), (7, 7, 148, 16515072, 1)),
+    ("gemm_plan", (False, False, 262144, 768, 3072, -1, 0, False), (7, 1, 48, 0, 0)),
+    ("gemm_plan", (False, True, 262144, 3072, 768, -1, 0, False), (7, 1, 12, 0, 0)),
+    ("gemm_plan", (True, True, 768, 3072, 262144, -1, 0, False), (7, 7, 586, 16515072, 1)),
+    ("gemm_plan", (True, True, 768, 3072, 262144, -1, 0, True), (7, 7, 586, 16515072, 1)),
+    ("gemm_plan", (False, False, 65536, 3072, 1024, -1, 0, False), (7, 1, 16, 0, 0)),
+    ("gemm_plan", (False, True, 65536, 1024, 3072, -1, 0, False), (7, 1, 48, 0, 0)),
+    ("gemm_plan", (True, True, 3072, 1024, 65536, -1, 0, False), (7, 5, 206, 15728640, 1)),
+    ("gemm_plan", (True, True, 3072, 1024, 65536, -1, 0, True), (7, 5, 206, 15728640, 1)),
+    ("gemm_plan", (False, False, 262144, 3072, 1024, -1, 0, False), (7, 1, 16, 0, 0)),
+    ("gemm_plan", (False, True, 262144, 1024, 3072, -1, 0, False), (7, 1, 48, 0, 0)),
+    ("gemm_plan", (True, True, 3072, 1024, 262144, -1, 0, False), (7, 16, 256, 50331648, 1)),
+    ("gemm_plan", (True, True, 3072, 1024, 262144, -1, 0, True), (7, 16, 256, 50331648, 1)),
+    ("gemm_plan", (False, False, 65536, 1024, 1024, -1, 0, False), (7, 1, 16, 0, 0)),
+    ("gemm_plan", (False, True, 65536, 1024, 1024, -1, 0, False), (7, 1, 16, 0, 0)),
+    ("gemm_plan", (True, True, 1024, 1024, 65536, -1, 0, False), (7, 16, 64, 16777216, 1)),
+    ("gemm_plan", (True, True, 1024, 1024, 65536, -1, 0, True), (7, 16, 64, 16777216, 1)),
+    ("gemm_plan", (False, False, 262144, 1024, 1024, -1, 0, False), (7, 1, 16, 0, 0)),
+    ("gemm_plan", (False, True, 262144, 1024, 1024, -1, 0, False), (7, 1, 16, 0, 0)),
+    ("gemm_plan", (True, True, 1024, 1024, 262144, -1, 0, False), (7, 16, 256, 16777216, 1)),
+    ("gemm_plan", (True, True, 1024, 1024, 262144, -1, 0, True), (7, 16, 256, 16777216, 1)),
+    ("gemm_plan", (False, False, 65536, 4096, 1024, -1, 0, False), (7, 1, 16, 0, 0)),
+    ("gemm_plan", (False, True, 65536, 1024, 4096, -1, 0, False), (7, 1, 64, 0, 0)),
+    ("gemm_plan", (True, True, 4096, 1024, 65536, -1, 0, False), (7, 4, 256, 16777216, 1)),
+    ("gemm_plan", (True, True, 4096, 1024, 65536, -1, 0, True), (7, 4, 256, 16777216, 1)),
+    ("gemm_plan", (False, False, 262144, 4096, 1024, -1, 0, False), (7, 1, 16, 0, 0)),
+    ("gemm_plan", (False, True, 262144, 1024, 4096, -1, 0, False), (7, 1, 64, 0, 0)),
+    ("gemm_plan", (True, True, 4096, 1024, 262144, -1, 0, False), (7, 4, 1024, 16777216, 1)),
+    ("gemm_plan", (True, True, 4096, 1024, 262144, -1, 0, True), (7, 4, 1024, 16777216, 1)),
+    ("gemm_plan", (False, False, 65536, 1024, 4096, -1, 0, False), (7, 1, 64, 0, 0)),
+    ("gemm_plan", (False, True, 65536, 4096, 1024, -1, 0, False), (7, 1, 16, 0, 0)),
+    ("gemm_plan", (True, True, 1024, 4096, 65536, -1, 0, False), (7, 4, 256, 16777216, 1)),
+    ("gemm_plan", (True, True, 1024, 4096, 65536, -1, 0, True), (7, 4, 256, 16777216, 1)),
+    ("gemm_plan", (False, False, 262144, 1024, 4096, -1, 0, False), (7, 1, 64, 0, 0)),
+    ("gemm_plan", (False, True, 262144, 4096, 1024, -1, 0, False), (7, 1, 16, 0, 0)),
+    ("gemm_plan", (True, True, 1024, 4096, 262144, -1, 0, False), (7, 4, 1024, 16777216, 1)),
+    ("gemm_plan", (True, True, 1024, 4096, 262144, -1, 0, True), (7, 4, 1024, 16777216, 1)),
+    ("gemm_plan", (False, False, 520, 264, 1000, -1, 0, False), (0, 1, 0, 0, 0)),
+    ("gemm_plan", (False, False, 8, 8, 8, -1, 0, False), (0, 1, 0, 0, 0)),
+    ("gemm_plan", (False, False, 4096, 2304, 256, -1, 0, False), (4, 1, 4, 0, 0)),  # 144 tiles < the 240-tile gate
+    ("gemm_plan", (True, True, 768, 520, 4096, -1, 0, False), (2, 13, 5, 5191680, 1)),
+    ("gemm_f8_plan", (65536, 3072, 1024), (7, 1, 8, 0, 0)),
+    ("gemm_f8_plan", (262144, 3072, 1024), (7, 1, 8, 0, 0)),
+    ("gemm_f8_plan", (65536, 1024, 1024), (7, 1, 8, 0, 0)),
+    ("gemm_f8_plan", (262144, 1024, 1024), (7, 1, 8, 0, 0)),
+    ("gemm_f8_plan", (65536, 4096, 1024), (7, 1, 8, 0, 0)),
+    ("gemm_f8_plan", (262144, 4096, 1024), (7, 1, 8, 0, 0)),
+    ("gemm_f8_plan", (65536, 1024, 4096), (7, 1, 32, 0, 0)),
+    ("gemm_f8_plan", (262144, 1024, 4096), (7, 1, 32, 0, 0)),
+    ("gemm_f8_plan", (3072, 1024, 262144), (7, 16, 128, 50331648, 1)),
+    ("gemm_f8_plan", (1024, 1024, 262144), (7, 16, 128, 16777216, 1)),
+    ("gemm_f8_plan", (4096, 1024, 262144), (7, 4, 512, 16777216, 1)),
+    ("gemm_f8_plan", (1024, 4096, 262144), (7, 4, 512, 16777216, 1)),
+]
+
+
+def test_planner_choices_pinned(dev):
+    """The planners (host arithmetic only) choose what they chose before the dispatch clean-up."""
+    C = require_native()
+    assert len({want[0] for _, _, want in _PINNED_PLANS}) >= 3  # the grid reaches several kernels,
+    assert any(want[1] > 1 and want[4] == 1 for _, _, want in _PINNED_PLANS)  # split-K and its external reduce
+    for call, args, want in _PINNED_PLANS:
+        assert tuple(getattr(C, call)(*args)) == want, (call, args)
 
 
 @pytest.mark.parametrize("b_mn", [0, 1])
@@ -413,7 +478,7 @@ def test_gelu_epilogues_same_bits_on_every_kernel(dev, mode):
     """Every GEMM kernel's GELU (mode 1) / dGELU (mode 2) epilogue multiplies by the same exact table
     entry (csrc/include/mlt_gelu_table.inc; LDS copy in the 4-wave kernel, global memory elsewhere):
     with operands whose products and sums are exact in fp32 (so every kernel reaches the same
-    pre-activation whatever its accumulation order), the 4-wave, ping-pong, tile, persistent and
+    pre-activation whatever its accumulation order), the 4-wave, ping-pong, tile and
     general kernels and the split-K reduce all write identical bits, which also match torch's erf
     GELU within bf16 rounding."""
     C = require_native()
@@ -425,7 +490,7 @@ def test_gelu_epilogues_same_bits_on_every_kernel(dev, mode):
     bias = (torch.randn(N, generator=g) * 2).to(dev)
     pre = (torch.randn(M, N, generator=g) * 2).to(torch.bfloat16).to(dev)
     outs = {}
-    for cfg, splits in ((7, 0), (5, 0), (1, 0), (6, 0), (0, 0), (1, 2)):
+    for cfg, splits in ((7, 0), (5, 0), (1, 0), (0, 0), (1, 2)):
         out = torch.empty(M, N, dtype=torch.bfloat16, device=dev)
         if mode == 1:
             aux = torch.empty(M, N, dtype=torch.bfloat16, device=dev)
