@@ -4,6 +4,7 @@ baseline of the same model (torch.autocast + SDPA + hipBLASLt) for comparison.
 
     python benchmarks/bert_bench.py --model bert-base --batch 16 --seq 512 --steps 10
     python benchmarks/bert_bench.py --impl torch      # eager PyTorch baseline
+    python benchmarks/bert_bench.py --impl native --dropout 0.1   # hidden dropout in the LayerNorm kernels
 
 Prints one JSON line per run (samples/s, tokens/s, ms/step, model TFLOP/s).
 Synthetic token ids, random-init weights (no network).
@@ -28,7 +29,10 @@ def run(args):
     from ml_trainer_amd.ops.optim import FusedAdamW
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
-    cfg = bert_config(args.model, **({"layers": args.layers} if args.layers else {}))
+    over = {"layers": args.layers} if args.layers else {}
+    if args.dropout:
+        over["hidden_dropout"] = args.dropout
+    cfg = bert_config(args.model, **over)
     m = BertClassifier(cfg).to(dev)
     if args.impl == "native":
         opt = FusedAdamW(m.parameters(), lr=1e-4, weight_decay=0.01)
@@ -57,7 +61,7 @@ def run(args):
     tokens = args.batch * args.seq
     flops = m.flops_per_token(args.seq) * tokens
     rec = {"bench": "bert_train_step", "impl": args.impl, "model": args.model, "layers": cfg.layers,
-           "batch": args.batch, "seq": args.seq, "ms_per_step": dt * 1e3, "samples_per_s": args.batch / dt,
+           "batch": args.batch, "seq": args.seq, "dropout": args.dropout, "ms_per_step": dt * 1e3, "samples_per_s": args.batch / dt,
            "tokens_per_s": tokens / dt, "model_tflops": flops / dt / 1e12, "loss": float(loss.detach()),
            "peak_mem_gb": torch.cuda.max_memory_allocated() / 2 ** 30}
     print(json.dumps(rec), flush=True)
@@ -73,6 +77,7 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--impl", choices=["native", "torch", "both"], default="both")
+    ap.add_argument("--dropout", type=float, default=0.0, help="hidden dropout probability (default 0.0)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     recs = []

@@ -14,7 +14,8 @@ CIFAR-shaped dataset and says so in the log.
 
 Extension flags (not in the reference): ``--model`` (default/tiny/bert-base/
 large), ``--synthetic``, ``--per_device_batch``, ``--no_engine``,
-``--no_parallel``, ``--resume``, ``--amp bf16``, ``--precision bf16``, ``--metrics_jsonl``, ``--log_jsonl``, ``--zero_stage``, ``--async_checkpoint``.
+``--no_parallel``, ``--resume``, ``--amp bf16``, ``--precision bf16``, ``--metrics_jsonl``, ``--log_jsonl``, ``--zero_stage``, ``--async_checkpoint``,
+``--dropout`` (BERT hidden dropout).
 """
 from __future__ import annotations
 
@@ -62,8 +63,11 @@ def main(args):
     from ml_trainer_amd.models import build_model
     from ml_trainer_amd.trainer import Trainer
     torch.manual_seed(args.seed)
-    model = build_model(args.model)
-    if args.model in ("default", "tiny", "lenet"):
+    lenet = args.model in ("default", "tiny", "lenet")
+    if lenet and args.dropout:
+        raise ValueError("--dropout applies to the BERT models; the LeNet models have no dropout")
+    model = build_model(args.model, **({"hidden_dropout": args.dropout} if args.dropout else {}))
+    if lenet:
         datasets = build_datasets(args)
     else:  # BERT configs: synthetic token classification (no network for GLUE downloads)
         from ml_trainer_amd.data.text import SyntheticTextClassification
@@ -129,6 +133,9 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--data_dir", type=str, default=os.environ.get("SM_CHANNEL_TRAIN", "cifar10-dataset"))
     # extensions
     parser.add_argument("--model", type=str, default="default", help="default|tiny|bert-base|large")
+    parser.add_argument("--dropout", type=float, default=0.0,
+                        help="BERT hidden dropout probability (embedding, attention-output and FFN-output "
+                             "sites; default: 0.0). An error for the LeNet models")
     parser.add_argument("--synthetic", action="store_true", help="use the seeded synthetic dataset")
     parser.add_argument("--synthetic_size", type=int, default=0)
     parser.add_argument("--seq_len", type=int, default=512)

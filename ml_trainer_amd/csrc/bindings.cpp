@@ -656,14 +656,61 @@ void ln_fwd(Tensor X, Tensor gamma, Tensor beta, Tensor Y, Tensor mean, Tensor r
                 mean.data_ptr<float>(), rstd.data_ptr<float>(), rows, (int)D, (float)eps, cur_stream());
 }
 
+// One dropout site's kernel arguments: thr = min(int(p * 2^32), 0xFFFFFFFF) (keep iff word >= thr),
+// scale = 1 / (1 - p) in double rounded once to fp32 -- the values ops/dropout.py computes.
+static DropArgs make_drop_args(double p, int64_t seed, int64_t site, int64_t rank) {
+  TORCH_CHECK(p >= 0.0 && p < 1.0, "dropout probability must satisfy 0 <= p < 1, got ", p);
+  TORCH_CHECK(site >= 0 && site <= 0xFFFFFFFFLL && rank >= 0 && rank <= 0xFFFFFFFFLL,
+              "dropout site / rank must fit 32 bits");
+  const double t = p * 4294967296.0;
+  DropArgs d;
+  d.thr = t >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)t;
+  d.scale = (float)(1.0 / (1.0 - p));
+  d.seed_lo = (uint32_t)((uint64_t)seed & 0xFFFFFFFFull);
+  d.seed_hi = (uint32_t)((uint64_t)seed >> 32);
+  d.site = (uint32_t)site;
+  d.rank = (uint32_t)rank;
+  return d;
+}
+
+// out = keep ? bf16(x * scale) : 0 over a contiguous bf16 tensor (flat element index = mask index)
+void dropout(Tensor x, Tensor out, double p, int64_t seed, int64_t site, int64_t rank) {
+  TORCH_CHECK(x.numel() % 8 == 0, "dropout needs numel % 8 == 0, got ", x.numel());
+  check_dev(x, "x", at::kBFloat16, 0, 16);
+  check_dev(out, "out", at::kBFloat16, x.numel(), 16);
+  TORCH_CHECK(out.numel() == x.numel(), "dropout: out must have x's size");
+  launch_dropout(bf16_ptr(x), (uint16_t*)out.data_ptr(), x.numel(), make_drop_args(p, seed, site, rank),
+                 cur_stream());
+}
+
+// Z = bf16(dropout(Y0) + RES); Y, mean, rstd = LayerNorm(Z)
+void dropout_add_ln_fwd(Tensor Y0, Tensor RES, Tensor gamma, Tensor beta, Tensor Z, Tensor Y, Tensor mean,
+                        Tensor rstd, double eps, double p, int64_t seed, int64_t site, int64_t rank) {
+  const int64_t D = gamma.numel(), rows = Y0.numel() / std::max<int64_t>(D, 1);
+  TORCH_CHECK(D % 256 == 0 && D >= 256 && D <= 1024, "LayerNorm width must be 256/512/768/1024");
+  check_bf16_2d(Y0, "Y0", rows, D);
+  check_bf16_2d(RES, "RES", rows, D);
+  check_bf16_2d(Z, "Z", rows, D);
+  check_bf16_2d(Y, "Y", rows, D);
+  check_dev(gamma, "gamma", at::kFloat, D);
+  check_dev(beta, "beta", at::kFloat, D);
+  check_dev(mean, "mean", at::kFloat, rows, 4);
+  check_dev(rstd, "rstd", at::kFloat, rows, 4);
+  launch_dropout_add_ln_fwd(bf16_ptr(Y0), bf16_ptr(RES), gamma.data_ptr<float>(), beta.data_ptr<float>(),
+                            (uint16_t*)Z.data_ptr(), (uint16_t*)Y.data_ptr(), mean.data_ptr<float>(),
+                            rstd.data_ptr<float>(), rows, (int)D, (float)eps, make_drop_args(p, seed, site, rank),
+                            cur_stream());
+}
+
 int64_t ln_partial_blocks(int64_t rows) { return ln_bwd_partial_blocks(rows); }
 int64_t ln_q8_partial_blocks(int64_t rows) { return ln_bwd_q8_partial_blocks(rows); }
 
 // dxsum (optional): column sums of DX (bias gradient of the producing linear layer), accumulated
-// into when dxsum_acc.
+// into when dxsum_acc. dxm (optional, needs dxsum, excludes dres): X was dropout(linear) + residual
+// at site (p, seed, site, rank); dxm gets mask * scale * DX and dxsum its column sums instead of DX's.
 void ln_bwd(Tensor DY, Tensor X, Tensor gamma, Tensor mean, Tensor rstd, Tensor DX, Tensor part, Tensor dgamma,
             Tensor dbeta, bool accumulate, c10::optional<Tensor> dres, c10::optional<Tensor> dxsum,
-            bool dxsum_acc) {
+            bool dxsum_acc, c10::optional<Tensor> dxm, double p, int64_t seed, int64_t site, int64_t rank) {
   const int64_t D = gamma.numel(), rows = X.numel() / std::max<int64_t>(D, 1);
   TORCH_CHECK(D % 256 == 0 && D >= 256 && D <= 1024, "LayerNorm width must be 256/512/768/1024");
   check_bf16_2d(X, "X", rows, D);
@@ -684,6 +731,16 @@ void ln_bwd(Tensor DY, Tensor X, Tensor gamma, Tensor mean, Tensor rstd, Tensor 
   if (dres.has_value()) {
     check_bf16_2d(*dres, "dres", rows, D);
     dr = bf16_ptr(*dres);
+  }
+  if (dxm.has_value()) {
+    TORCH_CHECK(dxs != nullptr && dr == nullptr, "ln_bwd: dxm needs dxsum and takes no dres");
+    check_bf16_2d(*dxm, "dxm", rows, D);
+    launch_ln_bwd_dropout(bf16_ptr(DY), bf16_ptr(X), gamma.data_ptr<float>(), mean.data_ptr<float>(),
+                          rstd.data_ptr<float>(), (uint16_t*)DX.data_ptr(), (uint16_t*)dxm->data_ptr(),
+                          part.data_ptr<float>(), dgamma.data_ptr<float>(), dbeta.data_ptr<float>(), rows, (int)D,
+                          accumulate ? 1 : 0, dxs, dxsum_acc ? 1 : 0, make_drop_args(p, seed, site, rank),
+                          cur_stream());
+    return;
   }
   launch_ln_bwd(bf16_ptr(DY), bf16_ptr(X), gamma.data_ptr<float>(), mean.data_ptr<float>(), rstd.data_ptr<float>(),
                 (uint16_t*)DX.data_ptr(), part.data_ptr<float>(), dgamma.data_ptr<float>(), dbeta.data_ptr<float>(),
@@ -1434,7 +1491,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("dxsum_acc"), py::arg("Y8"), py::arg("YT8"), py::arg("scale"), py::arg("amax"));
   m.def("ln_bwd", &ln_bwd, py::arg("DY"), py::arg("X"), py::arg("gamma"), py::arg("mean"), py::arg("rstd"),
         py::arg("DX"), py::arg("part"), py::arg("dgamma"), py::arg("dbeta"), py::arg("accumulate") = false,
-        py::arg("dres") = py::none(), py::arg("dxsum") = py::none(), py::arg("dxsum_acc") = false);
+        py::arg("dres") = py::none(), py::arg("dxsum") = py::none(), py::arg("dxsum_acc") = false,
+        py::arg("dxm") = py::none(), py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("site") = 0,
+        py::arg("rank") = 0);
+  m.def("dropout", &dropout, py::arg("x"), py::arg("out"), py::arg("p"), py::arg("seed"), py::arg("site"),
+        py::arg("rank"));
+  m.def("dropout_add_ln_fwd", &dropout_add_ln_fwd, py::arg("Y0"), py::arg("RES"), py::arg("gamma"), py::arg("beta"),
+        py::arg("Z"), py::arg("Y"), py::arg("mean"), py::arg("rstd"), py::arg("eps"), py::arg("p"), py::arg("seed"),
+        py::arg("site"), py::arg("rank"));
   m.def("ln_partial_blocks", &ln_partial_blocks);
   m.def("embed_fwd", &embed_fwd);
   m.def("embed_bwd", &embed_bwd);

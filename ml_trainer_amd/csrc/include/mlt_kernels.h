@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "mlt_optim.h"
+#include "mlt_philox.h"
 
 namespace mlt {
 
@@ -285,6 +286,18 @@ int ln_bwd_partial_blocks(int64_t rows);
 void launch_ln_bwd(const uint16_t* DY, const uint16_t* X, const float* gamma, const float* mean, const float* rstd,
                    uint16_t* DX, float* part, float* dgamma, float* dbeta, int64_t rows, int D, int accumulate,
                    const uint16_t* DRES, float* dxsum, int dxsum_acc, hipStream_t st);
+// Hidden dropout (mlt_philox.h) fused into the LayerNorm kernels. Forward: Z = bf16(dropout(Y0) +
+// RES), Y / mean / rstd = LayerNorm(Z). Backward: launch_ln_bwd's DX and partials, plus DXM =
+// mask * scale * DX (the dY of the linear that produced Y0) whose column sums go to dxsum.
+void launch_dropout_add_ln_fwd(const uint16_t* Y0, const uint16_t* RES, const float* gamma, const float* beta,
+                               uint16_t* Z, uint16_t* Y, float* mean, float* rstd, int64_t rows, int D, float eps,
+                               DropArgs dr, hipStream_t st);
+void launch_ln_bwd_dropout(const uint16_t* DY, const uint16_t* X, const float* gamma, const float* mean,
+                           const float* rstd, uint16_t* DX, uint16_t* DXM, float* part, float* dgamma, float* dbeta,
+                           int64_t rows, int D, int accumulate, float* dxsum, int dxsum_acc, DropArgs dr,
+                           hipStream_t st);
+// out = keep ? bf16(x * scale) : 0 over numel (% 8 == 0) contiguous bf16 elements (dropout.hip)
+void launch_dropout(const uint16_t* x, uint16_t* out, int64_t numel, DropArgs dr, hipStream_t st);
 // LayerNorm backward that also quantises dx (the next fp8 GEMM's dY): e5m2 Y8 [rows, D] + YT8
 // [D, rows] with scale *qscale, amax into qamax's slots; dxsum required. false: shape not covered
 int ln_bwd_q8_partial_blocks(int64_t rows);

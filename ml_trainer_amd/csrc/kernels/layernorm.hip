@@ -12,6 +12,7 @@
 #include "mlt_common.h"
 #include "mlt_kernels.h"
 #include "mlt_fp8.h"
+#include "mlt_philox.h"
 
 namespace mlt {
 
@@ -28,17 +29,13 @@ __device__ __forceinline__ void load_row(const uint16_t* __restrict__ p, float (
   }
 }
 
+// LayerNorm of one row held in registers (x: the wave's E values per lane): statistics, Y, mean / rstd
 template <int VPL>
-__global__ __launch_bounds__(256) void ln_fwd_kernel(const uint16_t* __restrict__ X, const float* __restrict__ gamma,
-                                                     const float* __restrict__ beta, uint16_t* __restrict__ Y,
-                                                     float* __restrict__ mean, float* __restrict__ rstd, int64_t rows,
-                                                     float eps) {
+__device__ __forceinline__ void ln_fwd_row(const float (&x)[VPL * 4], const float* __restrict__ gamma,
+                                           const float* __restrict__ beta, uint16_t* __restrict__ Y,
+                                           float* __restrict__ mean, float* __restrict__ rstd, int64_t row, float eps) {
   constexpr int D = VPL * 256, E = VPL * 4;
   const int lane = threadIdx.x & 63;
-  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  float x[E];
-  load_row<VPL>(X + row * D, x);
   float s = 0.f;
 #pragma unroll
   for (int i = 0; i < E; ++i) s += x[i];
@@ -68,25 +65,87 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const uint16_t* __restrict_
   }
 }
 
+template <int VPL>
+__global__ __launch_bounds__(256) void ln_fwd_kernel(const uint16_t* __restrict__ X, const float* __restrict__ gamma,
+                                                     const float* __restrict__ beta, uint16_t* __restrict__ Y,
+                                                     float* __restrict__ mean, float* __restrict__ rstd, int64_t rows,
+                                                     float eps) {
+  constexpr int D = VPL * 256, E = VPL * 4;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  float x[E];
+  load_row<VPL>(X + row * D, x);
+  ln_fwd_row<VPL>(x, gamma, beta, Y, mean, rstd, row, eps);
+}
+
+// Z = bf16(dropout(Y0) + RES), Y = LayerNorm(Z): the hidden dropout and the residual add of a
+// post-LN sub-layer in the pass that normalises their sum. Y0 is the linear's output (bias
+// included, no residual). The statistics and Y come from the bf16-rounded Z through ln_fwd_row,
+// so Y / mean / rstd are bitwise what ln_fwd_kernel gives on Z, and the backward recomputes xhat
+// from the saved Z. The mask is recomputed from (row, column), nothing is stored (mlt_philox.h).
+template <int VPL>
+__global__ __launch_bounds__(256) void dropout_add_ln_fwd_kernel(
+    const uint16_t* __restrict__ Y0, const uint16_t* __restrict__ RES, const float* __restrict__ gamma,
+    const float* __restrict__ beta, uint16_t* __restrict__ Z, uint16_t* __restrict__ Y, float* __restrict__ mean,
+    float* __restrict__ rstd, int64_t rows, float eps, DropArgs dr) {
+  constexpr int D = VPL * 256, E = VPL * 4;
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  float x[E];
+#pragma unroll
+  for (int v = 0; v < VPL; ++v) {
+    const ushort4 a = reinterpret_cast<const ushort4*>(Y0 + row * D)[lane + 64 * v];
+    const ushort4 r = reinterpret_cast<const ushort4*>(RES + row * D)[lane + 64 * v];
+    const Philox4 w = drop_words((uint64_t)row * (D / 4) + lane + 64 * v, dr);
+    // __fmul_rn: the scaled value is rounded to fp32 before the add (no fma contraction)
+    ushort4 z;
+    z.x = f32_to_bf16((w.x >= dr.thr ? __fmul_rn(bf16_to_f32(a.x), dr.scale) : 0.f) + bf16_to_f32(r.x));
+    z.y = f32_to_bf16((w.y >= dr.thr ? __fmul_rn(bf16_to_f32(a.y), dr.scale) : 0.f) + bf16_to_f32(r.y));
+    z.z = f32_to_bf16((w.z >= dr.thr ? __fmul_rn(bf16_to_f32(a.z), dr.scale) : 0.f) + bf16_to_f32(r.z));
+    z.w = f32_to_bf16((w.w >= dr.thr ? __fmul_rn(bf16_to_f32(a.w), dr.scale) : 0.f) + bf16_to_f32(r.w));
+    reinterpret_cast<ushort4*>(Z + row * D)[lane + 64 * v] = z;
+    x[4 * v + 0] = bf16_to_f32(z.x);
+    x[4 * v + 1] = bf16_to_f32(z.y);
+    x[4 * v + 2] = bf16_to_f32(z.z);
+    x[4 * v + 3] = bf16_to_f32(z.w);
+  }
+  ln_fwd_row<VPL>(x, gamma, beta, Y, mean, rstd, row, eps);
+}
+
 // dx = rstd * (dy*g - mean(dy*g) - xhat * mean(dy*g*xhat)); partial dgamma/dbeta per block.
 // DXS: also emit per-block column sums of the (bf16-rounded) dx -- the bias gradient of the
 // linear layer whose output (plus residual) fed this LayerNorm, fused here for free.
-template <int VPL, bool DXS>
+// DROP (with DXS, without DRES): the LayerNorm's input was dropout(linear) + residual
+// (dropout_add_ln_fwd_kernel). DX is the residual's gradient as before; the linear's dY is
+// DXM = keep ? bf16(dx_bf16 * scale) : 0 with the forward's mask, and the column sums are DXM's.
+// The dropout arguments are a trailing pack (one LnBwdDrop when DROP, empty otherwise), so the
+// instantiations without dropout keep the argument list, and with it the code, they had before.
+struct LnBwdDrop {
+  uint16_t* DXM;
+  DropArgs dr;
+};
+__device__ __forceinline__ const LnBwdDrop& ln_bwd_drop_arg(const LnBwdDrop& d) { return d; }
+
+template <int VPL, bool DXS, bool DROP = false, typename... DropT>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const uint16_t* __restrict__ DY, const uint16_t* __restrict__ X,
                                                      const float* __restrict__ gamma, const float* __restrict__ mean,
                                                      const float* __restrict__ rstd, uint16_t* __restrict__ DX,
                                                      float* __restrict__ part, int64_t rows,
-                                                     const uint16_t* __restrict__ DRES) {
+                                                     const uint16_t* __restrict__ DRES, DropT... drop_args) {
+  static_assert(!DROP || DXS, "the dropout variant always reduces DXM's column sums");
+  static_assert(sizeof...(DropT) == (DROP ? 1 : 0), "one LnBwdDrop exactly when DROP");
   constexpr int D = VPL * 256, E = VPL * 4;
   constexpr int NS = DXS ? 3 : 2;
   __shared__ float red[4][NS * D];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  float dg[E], db[E], g[E], dxs[DXS ? E : 1];
+  float dg[E], db[E], g[E], dxs[DXS ? E : 1], dms[DROP ? E : 1];
 #pragma unroll
   for (int i = 0; i < E; ++i) {
     dg[i] = 0.f;
     db[i] = 0.f;
     if constexpr (DXS) dxs[i] = 0.f;
+    if constexpr (DROP) dms[i] = 0.f;
   }
 #pragma unroll
   for (int v = 0; v < VPL; ++v) {
@@ -157,6 +216,34 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const uint16_t* __restrict_
       u.z = f32_to_bf16(o[2]);
       u.w = f32_to_bf16(o[3]);
       reinterpret_cast<ushort4*>(DX + row * D)[lane + 64 * v] = u;
+      if constexpr (DROP) {
+        const LnBwdDrop& drop = ln_bwd_drop_arg(drop_args...);
+        // DX has to be bitwise the DX of the instantiations without dropout. Its fp32 rounding is
+        // the compiler's choice of which products above it fuses and packs, and that choice follows
+        // what hangs off these values. So this variant keeps what the DXS instantiation hangs off
+        // them: the DX column sums stay (dxs below, unused in the end) and the dropout tail reads
+        // the stored DX through an empty asm, out of the optimiser's sight. With both, the fp32
+        // instructions up to the DX store are those of ln_bwd_kernel<VPL, true>; the price is E
+        // accumulators and E adds per row.
+        uint32_t ulo = (uint32_t)u.x | ((uint32_t)u.y << 16), uhi = (uint32_t)u.z | ((uint32_t)u.w << 16);
+        asm volatile("" : "+v"(ulo), "+v"(uhi));
+        ushort4 ub;
+        ub.x = (uint16_t)ulo, ub.y = (uint16_t)(ulo >> 16), ub.z = (uint16_t)uhi, ub.w = (uint16_t)(uhi >> 16);
+        // the mask of the global row (not the pipeline's clamped fetch row), as in the forward
+        const Philox4 w = drop_words((uint64_t)row * (D / 4) + lane + 64 * v, drop.dr);
+        const uint32_t thr = drop.dr.thr;
+        const float sc = drop.dr.scale;
+        ushort4 m;
+        m.x = w.x >= thr ? f32_to_bf16(bf16_to_f32(ub.x) * sc) : (uint16_t)0;
+        m.y = w.y >= thr ? f32_to_bf16(bf16_to_f32(ub.y) * sc) : (uint16_t)0;
+        m.z = w.z >= thr ? f32_to_bf16(bf16_to_f32(ub.z) * sc) : (uint16_t)0;
+        m.w = w.w >= thr ? f32_to_bf16(bf16_to_f32(ub.w) * sc) : (uint16_t)0;
+        reinterpret_cast<ushort4*>(drop.DXM + row * D)[lane + 64 * v] = m;
+        dms[4 * v + 0] += bf16_to_f32(m.x);
+        dms[4 * v + 1] += bf16_to_f32(m.y);
+        dms[4 * v + 2] += bf16_to_f32(m.z);
+        dms[4 * v + 3] += bf16_to_f32(m.w);
+      }
       if constexpr (DXS) {
         dxs[4 * v + 0] += bf16_to_f32(u.x);
         dxs[4 * v + 1] += bf16_to_f32(u.y);
@@ -172,7 +259,12 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const uint16_t* __restrict_
       const int c = 4 * (lane + 64 * v) + q;
       red[wid][c] = dg[4 * v + q];
       red[wid][D + c] = db[4 * v + q];
-      if constexpr (DXS) red[wid][2 * D + c] = dxs[4 * v + q];
+      if constexpr (DROP) {
+        asm volatile("" ::"v"(dxs[4 * v + q]));  // kept alive for DX's rounding only (see above)
+        red[wid][2 * D + c] = dms[4 * v + q];    // the column sums of DXM
+      } else if constexpr (DXS) {
+        red[wid][2 * D + c] = dxs[4 * v + q];
+      }
     }
   __syncthreads();
   for (int c = threadIdx.x; c < NS * D; c += 256)
@@ -364,6 +456,24 @@ void launch_ln_fwd(const uint16_t* X, const float* gamma, const float* beta, uin
   }
 }
 
+void launch_dropout_add_ln_fwd(const uint16_t* Y0, const uint16_t* RES, const float* gamma, const float* beta,
+                               uint16_t* Z, uint16_t* Y, float* mean, float* rstd, int64_t rows, int D, float eps,
+                               DropArgs dr, hipStream_t st) {
+  if (rows <= 0) return;
+  const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+#define MLT_DROP_LN_FWD(V)                                                                                         \
+  hipLaunchKernelGGL(dropout_add_ln_fwd_kernel<V>, grid, block, 0, st, Y0, RES, gamma, beta, Z, Y, mean, rstd, rows, \
+                     eps, dr)
+  switch (ln_vpl(D)) {
+    case 1: MLT_DROP_LN_FWD(1); break;
+    case 2: MLT_DROP_LN_FWD(2); break;
+    case 3: MLT_DROP_LN_FWD(3); break;
+    case 4: MLT_DROP_LN_FWD(4); break;
+    default: break;
+  }
+#undef MLT_DROP_LN_FWD
+}
+
 // the fp8 variant's grid: 32-row chunks, up to 3 blocks per CU (48 KB of LDS each) -- its chunk
 // barriers leave 2 blocks per CU short of latency hiding
 int ln_bwd_q8_partial_blocks(int64_t rows) { return (int)std::min<int64_t>(std::max<int64_t>(rows / 32, 1), 768); }
@@ -394,6 +504,31 @@ void launch_ln_bwd(const uint16_t* DY, const uint16_t* X, const float* gamma, co
 #undef MLT_LN_BWD
   SegOut o{{dgamma, dbeta, dxsum}};
   launch_reduce_rows(part, nb, (dxsum ? 3 : 2) * D, (dxsum ? 3 : 2) * D, D, o, (accumulate ? 3 : 0) | (dxsum_acc ? 4 : 0), st);
+}
+
+// the dropout variant: DX as above, DXM = mask * scale * DX, dxsum = column sums of DXM (required)
+void launch_ln_bwd_dropout(const uint16_t* DY, const uint16_t* X, const float* gamma, const float* mean,
+                           const float* rstd, uint16_t* DX, uint16_t* DXM, float* part, float* dgamma, float* dbeta,
+                           int64_t rows, int D, int accumulate, float* dxsum, int dxsum_acc, DropArgs dr,
+                           hipStream_t st) {
+  if (rows <= 0) return;
+  const int nb = ln_bwd_partial_blocks(rows);
+  const dim3 grid(nb), block(256);
+  const LnBwdDrop d{DXM, dr};
+  const uint16_t* no_res = nullptr;
+#define MLT_LN_BWD(V)                                                                                             \
+  hipLaunchKernelGGL((ln_bwd_kernel<V, true, true, LnBwdDrop>), grid, block, 0, st, DY, X, gamma, mean, rstd, DX, \
+                     part, rows, no_res, d);
+  switch (ln_vpl(D)) {
+    case 1: MLT_LN_BWD(1) break;
+    case 2: MLT_LN_BWD(2) break;
+    case 3: MLT_LN_BWD(3) break;
+    case 4: MLT_LN_BWD(4) break;
+    default: return;
+  }
+#undef MLT_LN_BWD
+  SegOut o{{dgamma, dbeta, dxsum}};
+  launch_reduce_rows(part, nb, 3 * D, 3 * D, D, o, (accumulate ? 3 : 0) | (dxsum_acc ? 4 : 0), st);
 }
 
 bool launch_ln_bwd_q8(const uint16_t* DY, const uint16_t* X, const float* gamma, const float* mean, const float* rstd,

@@ -15,7 +15,17 @@ flash attention, LayerNorm, embedding gather/scatter, and the classifier head: p
 GEMM with a tanh epilogue + the num_labels-wide classifier layer of head.hip) with fp32
 master weights and bf16 activations. On CPU the
 same math runs in plain torch (and serves as the numerics oracle in tests).
-Dropout is 0 (deterministic training; the benchmark measures the compute path).
+
+Hidden dropout (``BertConfig.hidden_dropout``, default 0: the benchmark measures the compute
+path) is BERT's standard one: on the embedding output after its LayerNorm, and on the output of
+the attention out-projection and of FFN2 before the residual add. It is active in ``train()``
+mode only. On the GPU it runs inside the LayerNorm kernels (plus one small kernel for the
+embedding site); the mask is a counter-based Philox stream recomputed in the backward, so nothing
+is stored. One 62-bit seed per forward comes from torch's default CPU generator (no device sync,
+reproducible under ``torch.manual_seed``, saved and restored with the trainer's RNG state) or from
+``dropout_seed=``; ``ops/dropout.py`` defines the mask and the site numbering, and the torch paths
+here apply the same masks. Not covered: attention-probability dropout (there is no
+``attention_dropout`` field) and the LeNet models (the reference model has no dropout).
 """
 from __future__ import annotations
 
@@ -41,6 +51,7 @@ class BertConfig:
     ln_eps: float = 1e-12
     init_std: float = 0.02
     fp8: bool = False
+    hidden_dropout: float = 0.0  # embedding / attention-output / FFN-output dropout (train() only)
     pad_id: Optional[int] = None  # when set, key lengths are derived from trailing pad tokens
 
 
@@ -71,19 +82,24 @@ class BertLayer(nn.Module):
         self.ffn2 = nn.Linear(c.intermediate, h)
         self.ln2 = nn.LayerNorm(h, eps=c.ln_eps)
 
-    def forward_native(self, x, lens, B, S):
+    def forward_native(self, x, lens, B, S, drop=None):
+        """``drop`` = (p, seed, site of the attention sub-layer, rank); the FFN takes the next site."""
         from ml_trainer_amd.ops import transformer as T
         if self.c.fp8:
             from ml_trainer_amd.ops.fp8 import FP8 as impl
         else:
             impl = T.BF16
         x = T.attention_ln_block(x, self.qkv.weight, self.qkv.bias, self.out.weight, self.out.bias, self.ln1.weight,
-                                 self.ln1.bias, lens, B, S, self.c.heads, self.c.ln_eps, impl)
+                                 self.ln1.bias, lens, B, S, self.c.heads, self.c.ln_eps, impl, drop)
+        if drop is not None:
+            drop = (drop[0], drop[1], drop[2] + 1, drop[3])
         return T.ffn_ln_block(x, self.ffn1.weight, self.ffn1.bias, self.ffn2.weight, self.ffn2.bias, self.ln2.weight,
-                              self.ln2.bias, self.c.ln_eps, impl)
+                              self.ln2.bias, self.c.ln_eps, impl, drop)
 
-    def forward_reference(self, x, mask, B, S):
-        """fp32 torch reference. x [B*S, h]; mask [B, S] bool (True = valid key)."""
+    def forward_reference(self, x, mask, B, S, drop=None):
+        """fp32 torch reference. x [B*S, h]; mask [B, S] bool (True = valid key); drop as in
+        forward_native (the same masks, through ops.dropout)."""
+        from ml_trainer_amd.ops import dropout as D
         c = self.c
         H, dh = c.heads, c.hidden // c.heads
         qkv = self.qkv(x).view(B, S, 3, H, dh).permute(2, 0, 3, 1, 4)
@@ -92,8 +108,13 @@ class BertLayer(nn.Module):
         if mask is not None:
             s = s.masked_fill(~mask[:, None, None, :], float("-inf"))
         ctx = (s.softmax(-1) @ v).permute(0, 2, 1, 3).reshape(B * S, c.hidden)
-        x = self.ln1(self.out(ctx) + x)
+        a = self.out(ctx)
+        if drop is not None:
+            a = D.apply(a, *drop)
+        x = self.ln1(a + x)
         f = self.ffn2(F.gelu(self.ffn1(x)))
+        if drop is not None:
+            f = D.apply(f, drop[0], drop[1], drop[2] + 1, drop[3])
         return self.ln2(f + x)
 
 
@@ -103,7 +124,10 @@ class BertClassifier(nn.Module):
         c = c or BertConfig()
         if c.hidden % c.heads or c.hidden // c.heads != 64:
             raise ValueError("the native attention kernel needs head dim 64")
+        if not 0.0 <= c.hidden_dropout < 1.0:
+            raise ValueError(f"hidden_dropout must satisfy 0 <= p < 1, got {c.hidden_dropout}")
         self.config = c
+        self.last_dropout_seed = None  # the seed of the last forward that dropped
         self.word_embeddings = nn.Embedding(c.vocab_size, c.hidden)
         self.position_embeddings = nn.Embedding(c.max_position, c.hidden)
         self.token_type_embeddings = nn.Embedding(c.type_vocab, c.hidden)
@@ -132,11 +156,29 @@ class BertClassifier(nn.Module):
             return (input_ids != self.config.pad_id).to(torch.int32).sum(1).clamp(min=1).to(torch.int32)
         return None
 
-    def forward(self, input_ids, attention_mask=None, token_type_ids=None):
+    def _dropout(self, dropout_seed=None):
+        """(p, seed, rank) of this forward when hidden dropout is active (train() mode and p > 0),
+        else None. Without ``dropout_seed`` one 62-bit seed is drawn from torch's default CPU
+        generator: no device sync, reproducible under torch.manual_seed / set_rng_state."""
+        p = self.config.hidden_dropout
+        if not (self.training and p > 0):
+            return None
+        if dropout_seed is None:
+            dropout_seed = torch.randint(0, 2 ** 62, (), dtype=torch.int64)
+        from ml_trainer_amd.ops.dropout import data_parallel_rank
+        self.last_dropout_seed = int(dropout_seed)
+        return p, self.last_dropout_seed, data_parallel_rank()
+
+    @staticmethod
+    def _site(drop, site):
+        return None if drop is None else (drop[0], drop[1], site, drop[2])
+
+    def forward(self, input_ids, attention_mask=None, token_type_ids=None, dropout_seed=None):
         if isinstance(input_ids, (tuple, list)):
             input_ids, attention_mask = input_ids[0], input_ids[1] if len(input_ids) > 1 else None
         B, S = input_ids.shape
         lens = self._lengths(input_ids, attention_mask)
+        drop = self._dropout(dropout_seed)
         if input_ids.is_cuda:
             from ml_trainer_amd.ops import transformer as T
             if self.config.fp8 and torch.is_grad_enabled():
@@ -145,40 +187,53 @@ class BertClassifier(nn.Module):
             x = T.embeddings(input_ids, token_type_ids, self.word_embeddings.weight, self.position_embeddings.weight,
                              self.token_type_embeddings.weight, S)
             x = T.layer_norm(x, self.emb_ln.weight, self.emb_ln.bias, self.config.ln_eps)
-            for layer in self.layers:
-                x = layer.forward_native(x, lens, B, S)
+            if drop is not None:
+                x = T.dropout(x, *self._site(drop, 0))
+            for l, layer in enumerate(self.layers):
+                x = layer.forward_native(x, lens, B, S, self._site(drop, 1 + 2 * l))
             cls = x.view(B, S, -1)[:, 0]  # strided row view: the pooler GEMM reads it in place
             if cls.shape[1] % 8 == 0 and self.pooler.weight.shape[0] % 8 == 0:
                 return T.classifier_head(cls, self.pooler.weight, self.pooler.bias, self.classifier.weight,
                                          self.classifier.bias)
             cls = cls.float()
         else:
-            cls = self.forward_reference_hidden(input_ids, lens, token_type_ids)
+            cls = self.forward_reference_hidden(input_ids, lens, token_type_ids, drop)
         pooled = torch.tanh(self.pooler(cls))
         return self.classifier(pooled)
 
-    def forward_reference_hidden(self, input_ids, lens=None, token_type_ids=None):
+    def forward_reference_hidden(self, input_ids, lens=None, token_type_ids=None, drop=None):
         B, S = input_ids.shape
         pos = torch.arange(S, device=input_ids.device)
         tt = token_type_ids if token_type_ids is not None else torch.zeros_like(input_ids)
         x = self.word_embeddings(input_ids) + self.position_embeddings(pos)[None] + self.token_type_embeddings(tt)
         x = self.emb_ln(x).view(B * S, -1)
+        if drop is not None:
+            from ml_trainer_amd.ops import dropout as D
+            x = D.apply(x, *self._site(drop, 0))
         mask = None
         if lens is not None:
             mask = torch.arange(S, device=input_ids.device)[None, :] < lens.to(input_ids.device)[:, None]
-        for layer in self.layers:
-            x = layer.forward_reference(x, mask, B, S)
+        for l, layer in enumerate(self.layers):
+            x = layer.forward_reference(x, mask, B, S, self._site(drop, 1 + 2 * l))
         return x.view(B, S, -1)[:, 0]
 
-    def forward_reference(self, input_ids, attention_mask=None, token_type_ids=None):
+    def forward_reference(self, input_ids, attention_mask=None, token_type_ids=None, dropout_seed=None):
         lens = self._lengths(input_ids, attention_mask)
-        cls = self.forward_reference_hidden(input_ids, lens, token_type_ids)
+        cls = self.forward_reference_hidden(input_ids, lens, token_type_ids, self._dropout(dropout_seed))
         return self.classifier(torch.tanh(self.pooler(cls)))
 
-    def forward_torch_bf16(self, input_ids, attention_mask=None, token_type_ids=None):
+    def forward_torch_bf16(self, input_ids, attention_mask=None, token_type_ids=None, dropout_seed=None):
         """PyTorch-eager bf16 path on the same weights (torch.autocast + SDPA + hipBLASLt): the
-        baseline the native kernels are benchmarked and error-budgeted against."""
+        baseline the native kernels are benchmarked and error-budgeted against. Hidden dropout
+        uses the native path's masks (ops.dropout), each applied in the dtype autocast gives the
+        tensor it drops."""
+        from ml_trainer_amd.ops import dropout as D
         c = self.config
+        drop = self._dropout(dropout_seed)
+
+        def dropped(t, site):  # t [B, S, h]
+            return t if drop is None else D.apply(t.reshape(B * S, -1), *self._site(drop, site)).view(B, S, -1)
+
         B, S = input_ids.shape
         lens = self._lengths(input_ids, attention_mask)
         mask = None
@@ -188,12 +243,12 @@ class BertClassifier(nn.Module):
             pos = torch.arange(S, device=input_ids.device)
             tt = token_type_ids if token_type_ids is not None else torch.zeros_like(input_ids)
             x = self.word_embeddings(input_ids) + self.position_embeddings(pos)[None] + self.token_type_embeddings(tt)
-            x = self.emb_ln(x)
-            for L in self.layers:
+            x = dropped(self.emb_ln(x), 0)
+            for l, L in enumerate(self.layers):
                 qkv = L.qkv(x).view(B, S, 3, c.heads, 64).permute(2, 0, 3, 1, 4)
                 ctx = F.scaled_dot_product_attention(qkv[0], qkv[1], qkv[2], attn_mask=mask)
-                x = L.ln1(L.out(ctx.transpose(1, 2).reshape(B, S, -1)) + x)
-                x = L.ln2(L.ffn2(F.gelu(L.ffn1(x))) + x)
+                x = L.ln1(dropped(L.out(ctx.transpose(1, 2).reshape(B, S, -1)), 1 + 2 * l) + x)
+                x = L.ln2(dropped(L.ffn2(F.gelu(L.ffn1(x))), 2 + 2 * l) + x)
             return self.classifier(torch.tanh(self.pooler(x[:, 0].float())))
 
     def num_parameters(self) -> int:

@@ -16,8 +16,11 @@ Blocks (one autograd node each, so the backward can fuse across ops):
   applies gelu'(pre) in its epilogue (no separate elementwise pass).
 * ``attention_ln_block`` / ``ffn_ln_block``: the block followed by its post-LayerNorm as one
   node; the LayerNorm backward kernel also produces the column sums of its dx, which are the
-  bias gradient of the block's last linear layer (no separate pass over dy).
-* ``layer_norm``, ``embeddings``.
+  bias gradient of the block's last linear layer (no separate pass over dy). With ``drop`` they
+  apply hidden dropout to that linear's output: the LayerNorm forward kernel drops, adds the
+  residual and normalises; the backward kernel also writes the masked, scaled dx (the linear's dY)
+  and reduces the bias gradient from it. The mask is recomputed, never stored (ops/dropout.py).
+* ``layer_norm``, ``embeddings``, ``dropout`` (the embedding site).
 
 The linear-layer arithmetic is pluggable (``impl``): ``BF16`` (bf16 operands) or
 ``ops.fp8.FP8`` (OCP fp8 forward / dgrad GEMMs with delayed per-tensor scaling; wgrad bf16).
@@ -192,22 +195,26 @@ class _Grads:
         self.ready = []
 
 
-def _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl=BF16):
+def _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl=BF16, residual=True):
     C = require_native()
     qkv = impl.fwd(x, wqkv, bqkv)
     attn = torch.empty(B * S, H * 64, dtype=torch.bfloat16, device=x.device)
     lse = torch.empty(B * H * S, dtype=torch.float32, device=x.device)
     C.attn_fwd(qkv, attn, lse, lens, B, S, H, _ATTN_SCALE)
-    y = impl.fwd(attn, wo, bo, res=x)  # out-proj + bias + residual
+    # out-proj + bias + residual (under dropout the residual joins in the LayerNorm kernel instead)
+    y = impl.fwd(attn, wo, bo, res=x if residual else None)
     return y, (x, qkv, attn, lse)
 
 
-def _attn_bwd(saved, params, lens, B, S, H, dy, G, dbo="colsum", impl=BF16):
+def _attn_bwd(saved, params, lens, B, S, H, dy, G, dbo="colsum", impl=BF16, dres=None):
     """Backward of the attention block. ``dbo``: "colsum" to reduce dy here, otherwise the
-    out-proj bias gradient already produced by the LayerNorm backward (tensor or None)."""
+    out-proj bias gradient already produced by the LayerNorm backward (tensor or None).
+    ``dres``: the gradient of the residual branch when it differs from the out-proj's ``dy``
+    (hidden dropout sits between them); defaults to ``dy``."""
     C = require_native()
     x, qkv, attn, lse = saved
     wqkv, bqkv, wo, bo = params
+    dres = dy if dres is None else dres
     dwo = G.wgrad(wo, dy, attn, impl)
     if isinstance(dbo, str):
         dbo = G.colsum(bo, dy)
@@ -229,7 +236,7 @@ def _attn_bwd(saved, params, lens, B, S, H, dy, G, dbo="colsum", impl=BF16):
         impl.attn_dy_q_done(wqkv, d8, d8t)
         dwqkv = G.wgrad(wqkv, d8, x, impl)
         dbqkv = None if (bqkv is None or gb is not None) else db
-        dx = impl.dgrad(d8, wqkv, torch.empty_like(x), res=dy)  # dx = dqkv . Wqkv + dy (residual)
+        dx = impl.dgrad(d8, wqkv, torch.empty_like(x), res=dres)  # dx = dqkv . Wqkv + dres (residual)
         return dx, dwqkv, dbqkv, dwo, dbo
     if impl is BF16 and bqkv is not None and _ATTN_COLSUM:
         # the QKV bias gradient (column sums of dQKV) from the backward kernels themselves
@@ -242,23 +249,25 @@ def _attn_bwd(saved, params, lens, B, S, H, dy, G, dbo="colsum", impl=BF16):
     else:
         C.attn_bwd(qkv, attn, dattn, lse, delta, lens, dqkv, B, S, H, _ATTN_SCALE)
         dwqkv, dbqkv = G.wgrad_bias(wqkv, bqkv, dqkv, x, impl)
-    dx = impl.dgrad(dqkv, wqkv, torch.empty_like(x), res=dy)  # dx = dqkv . Wqkv + dy (residual)
+    dx = impl.dgrad(dqkv, wqkv, torch.empty_like(x), res=dres)  # dx = dqkv . Wqkv + dres (residual)
     return dx, dwqkv, dbqkv, dwo, dbo
 
 
-def _ffn_fwd(x, w1, b1, w2, b2, impl=BF16):
+def _ffn_fwd(x, w1, b1, w2, b2, impl=BF16, residual=True):
     pre = torch.empty(x.shape[0], w1.shape[0], dtype=torch.bfloat16, device=x.device)
     # fp8: FFN1's epilogue may emit FFN2's quantised input directly (Fp8Linear.fwd_gelu_q)
     a = impl.fwd_gelu_q(x, w1, b1, pre, w2) if hasattr(impl, "fwd_gelu_q") else None
     if a is None:
         a = impl.fwd(x, w1, b1, gelu_aux=pre)  # a = gelu(pre), pre saved
-    y = impl.fwd(a, w2, b2, res=x)
+    y = impl.fwd(a, w2, b2, res=x if residual else None)
     return y, (x, pre, a)
 
 
-def _ffn_bwd(saved, params, dy, G, db2="colsum", impl=BF16):
+def _ffn_bwd(saved, params, dy, G, db2="colsum", impl=BF16, dres=None):
+    """``dres``: the residual branch's gradient when hidden dropout separates it from FFN2's ``dy``."""
     x, pre, a = saved
     w1, b1, w2, b2 = params
+    dres = dy if dres is None else dres
     dw2 = G.wgrad(w2, dy, a, impl)
     if isinstance(db2, str):
         db2 = G.colsum(b2, dy)
@@ -268,7 +277,7 @@ def _ffn_bwd(saved, params, dy, G, db2="colsum", impl=BF16):
         db1 = gb if gb is not None else torch.empty(w1.shape[0], dtype=torch.float32, device=dy.device)
         d8 = impl.dgrad_gelu_q(dy, w2, pre, w1, db1, gb is not None)
         dw1 = G.wgrad(w1, d8, x, impl)
-        dx = impl.dgrad(d8, w1, torch.empty_like(x), res=dy)
+        dx = impl.dgrad(d8, w1, torch.empty_like(x), res=dres)
         return dx, dw1, (None if gb is not None else db1), dw2, db2
     if impl is BF16 and impl.dgelu_colsum_ok(dy, w2):
         # FFN1's bias gradient from the dGELU epilogue (no separate pass over dpre)
@@ -276,11 +285,11 @@ def _ffn_bwd(saved, params, dy, G, db2="colsum", impl=BF16):
         db1 = gb if gb is not None else torch.empty(w1.shape[0], dtype=torch.float32, device=dy.device)
         dpre = impl.dgrad(dy, w2, torch.empty_like(pre), aux=pre, colsum_out=db1, colsum_acc=gb is not None)
         dw1 = G.wgrad(w1, dpre, x, impl)
-        dx = impl.dgrad(dpre, w1, torch.empty_like(x), res=dy)
+        dx = impl.dgrad(dpre, w1, torch.empty_like(x), res=dres)
         return dx, dw1, (None if gb is not None else db1), dw2, db2
     dpre = impl.dgrad(dy, w2, torch.empty_like(pre), aux=pre)  # (dy . W2) * gelu'(pre)
     dw1, db1 = G.wgrad_bias(w1, b1, dpre, x, impl)
-    dx = impl.dgrad(dpre, w1, torch.empty_like(x), res=dy)
+    dx = impl.dgrad(dpre, w1, torch.empty_like(x), res=dres)
     return dx, dw1, db1, dw2, db2
 
 
@@ -294,11 +303,27 @@ def _ln_fwd(x, gamma, beta, eps):
     return y, (x, gamma, mean, rstd)
 
 
-def _ln_bwd(saved, beta, dy, G, dxsum_param=None, q8=None):
+def _dropout_add_ln_fwd(y0, res, gamma, beta, eps, drop):
+    """LN(dropout(y0) + res) in one kernel; ``drop`` = (p, seed, site, rank). The bf16 sum z takes
+    the saved slot the GEMM output (linear + residual) has without dropout."""
+    C = require_native()
+    rows = y0.shape[0]
+    z = torch.empty_like(y0)
+    y = torch.empty_like(y0)
+    mean = torch.empty(rows, dtype=torch.float32, device=y0.device)
+    rstd = torch.empty(rows, dtype=torch.float32, device=y0.device)
+    C.dropout_add_ln_fwd(y0, res, gamma, beta, z, y, mean, rstd, eps, *drop)
+    return y, (z, gamma, mean, rstd)
+
+
+def _ln_bwd(saved, beta, dy, G, dxsum_param=None, q8=None, drop=None):
     """LayerNorm backward; with ``dxsum_param`` also the column sums of dx (= that bias's grad).
     ``q8`` = (impl, w, x): dx is the dY of linear ``w`` (input ``x``); an fp8 ``impl`` that can take
     it pre-quantised gets dx's e5m2 copy and transpose from this same kernel (C.ln_bwd_q8).
-    Returns (dx, dgamma|None, dbeta|None, dbias|None)."""
+    Returns (dx, dgamma|None, dbeta|None, dbias|None).
+    ``drop`` = (p, seed, site, rank) (needs ``dxsum_param``): the input was dropout(linear) +
+    residual. dx is then the residual's gradient, a fifth result dxm = mask * scale * dx is the
+    linear's dY, and dbias holds dxm's column sums. The quantising variant is not used."""
     C = require_native()
     x, gamma, mean, rstd = saved
     D = gamma.numel()
@@ -326,6 +351,12 @@ def _ln_bwd(saved, beta, dy, G, dxsum_param=None, q8=None):
             dxs_t, dxs_acc = so, True
         else:
             dxs = dxs_t = torch.empty(D, dtype=torch.float32, device=dev)
+    if drop is not None:
+        dxm = torch.empty_like(x)
+        p, seed, site, rank = drop
+        C.ln_bwd(dy, x, gamma, mean, rstd, dx, part, dg_t, db_t, acc, None, dxsum=dxs_t, dxsum_acc=dxs_acc,
+                 dxm=dxm, p=p, seed=seed, site=site, rank=rank)
+        return dx, dg, db, dxs, dxm
     if want and q8 is not None and hasattr(q8[0], "ln_bwd_q_state"):
         r = q8[0].ln_bwd_q_state(q8[1], q8[2])
         if r is not None:
@@ -404,46 +435,66 @@ class _AttentionLNBlock(torch.autograd.Function):
     gradient (column sums of its dx), so no separate pass over dy."""
 
     @staticmethod
-    def forward(ctx, x, wqkv, bqkv, wo, bo, gamma, beta, lens, B, S, H, eps, impl):
-        a, s1 = _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl)
-        y, s2 = _ln_fwd(a, gamma, beta, eps)
+    def forward(ctx, x, wqkv, bqkv, wo, bo, gamma, beta, lens, B, S, H, eps, impl, drop=None):
+        if drop is None:
+            a, s1 = _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl)
+            y, s2 = _ln_fwd(a, gamma, beta, eps)
+        else:  # LN(dropout(out-proj) + x): dropout and the residual add inside the LayerNorm kernel
+            a, s1 = _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl, residual=False)
+            y, s2 = _dropout_add_ln_fwd(a, x, gamma, beta, eps, drop)
         ctx.save_for_backward(*s1, *s2)
         ctx.params, ctx.beta, ctx.impl = (wqkv, bqkv, wo, bo), beta, impl
-        ctx.lens, ctx.dims = lens, (B, S, H)
+        ctx.lens, ctx.dims, ctx.drop = lens, (B, S, H), drop
         return y
 
     @staticmethod
     def backward(ctx, dy):
         t = ctx.saved_tensors
         G = _Grads()
-        da, dg, db, dbo = _ln_bwd(t[4:], ctx.beta, dy.contiguous().to(torch.bfloat16), G, dxsum_param=ctx.params[3],
-                                  q8=(ctx.impl, ctx.params[2], t[2]))  # da = out-proj dY (input attn)
+        if ctx.drop is None:
+            da, dg, db, dbo = _ln_bwd(t[4:], ctx.beta, dy.contiguous().to(torch.bfloat16), G,
+                                      dxsum_param=ctx.params[3],
+                                      q8=(ctx.impl, ctx.params[2], t[2]))  # da = out-proj dY (input attn)
+            dres = None
+        else:  # dres: gradient of the residual x; da = its masked, scaled copy, the out-proj dY
+            dres, dg, db, dbo, da = _ln_bwd(t[4:], ctx.beta, dy.contiguous().to(torch.bfloat16), G,
+                                            dxsum_param=ctx.params[3], drop=ctx.drop)
         dx, dwqkv, dbqkv, dwo, dbo = _attn_bwd(t[:4], ctx.params, ctx.lens, *ctx.dims, da, G, dbo=dbo,
-                                               impl=ctx.impl)
+                                               impl=ctx.impl, dres=dres)
         G.done()
-        return dx, dwqkv, dbqkv, dwo, dbo, dg, db, None, None, None, None, None, None
+        return dx, dwqkv, dbqkv, dwo, dbo, dg, db, None, None, None, None, None, None, None
 
 
 class _FFNLNBlock(torch.autograd.Function):
     """LN(ffn_block(x)) as one node (FFN2 bias gradient fused into the LayerNorm backward)."""
 
     @staticmethod
-    def forward(ctx, x, w1, b1, w2, b2, gamma, beta, eps, impl):
-        f, s1 = _ffn_fwd(x, w1, b1, w2, b2, impl)
-        y, s2 = _ln_fwd(f, gamma, beta, eps)
+    def forward(ctx, x, w1, b1, w2, b2, gamma, beta, eps, impl, drop=None):
+        if drop is None:
+            f, s1 = _ffn_fwd(x, w1, b1, w2, b2, impl)
+            y, s2 = _ln_fwd(f, gamma, beta, eps)
+        else:  # LN(dropout(FFN2) + x)
+            f, s1 = _ffn_fwd(x, w1, b1, w2, b2, impl, residual=False)
+            y, s2 = _dropout_add_ln_fwd(f, x, gamma, beta, eps, drop)
         ctx.save_for_backward(*s1, *s2)
-        ctx.params, ctx.beta, ctx.impl = (w1, b1, w2, b2), beta, impl
+        ctx.params, ctx.beta, ctx.impl, ctx.drop = (w1, b1, w2, b2), beta, impl, drop
         return y
 
     @staticmethod
     def backward(ctx, dy):
         t = ctx.saved_tensors
         G = _Grads()
-        df, dg, db, db2 = _ln_bwd(t[3:], ctx.beta, dy.contiguous().to(torch.bfloat16), G, dxsum_param=ctx.params[3],
-                                  q8=(ctx.impl, ctx.params[2], t[2]))  # df = FFN2 dY (input a)
-        dx, dw1, db1, dw2, db2 = _ffn_bwd(t[:3], ctx.params, df, G, db2=db2, impl=ctx.impl)
+        if ctx.drop is None:
+            df, dg, db, db2 = _ln_bwd(t[3:], ctx.beta, dy.contiguous().to(torch.bfloat16), G,
+                                      dxsum_param=ctx.params[3],
+                                      q8=(ctx.impl, ctx.params[2], t[2]))  # df = FFN2 dY (input a)
+            dres = None
+        else:
+            dres, dg, db, db2, df = _ln_bwd(t[3:], ctx.beta, dy.contiguous().to(torch.bfloat16), G,
+                                            dxsum_param=ctx.params[3], drop=ctx.drop)
+        dx, dw1, db1, dw2, db2 = _ffn_bwd(t[:3], ctx.params, df, G, db2=db2, impl=ctx.impl, dres=dres)
         G.done()
-        return dx, dw1, db1, dw2, db2, dg, db, None, None
+        return dx, dw1, db1, dw2, db2, dg, db, None, None, None
 
 
 class _Embeddings(torch.autograd.Function):
@@ -552,18 +603,46 @@ def ffn_block(x, w1, b1, w2, b2, impl=BF16):
 
 
 def attention_ln_block(x, wqkv, bqkv, wo, bo, gamma, beta, lens: Optional[torch.Tensor], B: int, S: int, H: int,
-                       eps: float, impl=BF16):
+                       eps: float, impl=BF16, drop=None):
+    """``drop`` = (p, seed, site, rank): hidden dropout on the out-projection's output, before the
+    residual add, fused into the LayerNorm kernels (mask: ops/dropout.py). None: no dropout."""
     _mark_training(impl)
-    return _AttentionLNBlock.apply(x, wqkv, bqkv, wo, bo, gamma, beta, lens, B, S, H, eps, impl)
+    return _AttentionLNBlock.apply(x, wqkv, bqkv, wo, bo, gamma, beta, lens, B, S, H, eps, impl, drop)
 
 
-def ffn_ln_block(x, w1, b1, w2, b2, gamma, beta, eps: float, impl=BF16):
+def ffn_ln_block(x, w1, b1, w2, b2, gamma, beta, eps: float, impl=BF16, drop=None):
+    """``drop`` = (p, seed, site, rank): hidden dropout on FFN2's output (see attention_ln_block)."""
     _mark_training(impl)
-    return _FFNLNBlock.apply(x, w1, b1, w2, b2, gamma, beta, eps, impl)
+    return _FFNLNBlock.apply(x, w1, b1, w2, b2, gamma, beta, eps, impl, drop)
 
 
 def layer_norm(x, gamma, beta, eps: float):
     return _LayerNorm.apply(x, gamma, beta, eps)
+
+
+class _Dropout(torch.autograd.Function):
+    """Stand-alone dropout of a bf16 [rows, D] tensor (the embedding site); the backward runs the
+    same kernel on dy with the recomputed mask."""
+
+    @staticmethod
+    def forward(ctx, x, p, seed, site, rank):
+        x = x.contiguous()
+        out = torch.empty_like(x)
+        require_native().dropout(x, out, p, seed, site, rank)
+        ctx.drop = (p, seed, site, rank)
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        dy = dy.contiguous().to(torch.bfloat16)
+        dx = torch.empty_like(dy)
+        require_native().dropout(dy, dx, *ctx.drop)
+        return dx, None, None, None, None
+
+
+def dropout(x, p: float, seed: int, site: int, rank: int):
+    """keep ? bf16(x * 1/(1-p)) : 0 with the mask of ops/dropout.py at (seed, site, rank)."""
+    return _Dropout.apply(x, p, seed, site, rank)
 
 
 def embeddings(ids, tt, ww, wp, wt, S: int):
