@@ -23,7 +23,9 @@
 // Global->LDS staging of the next tile is register-staged (loads issued before the MFMA work
 // of the current tile, LDS writes after it), so HBM latency overlaps the math.
 #include <cstdlib>
+#include <cstring>
 #include <stdexcept>
+#include <string>
 #include <type_traits>
 
 #include "mlt_common.h"
@@ -36,7 +38,6 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 typedef __attribute__((address_space(3))) void lds_void;
 
@@ -46,24 +47,6 @@ constexpr int AB = 64;  // query / key block
 // raw v_exp_f32 (2^x): exp2f wraps it in a denormal-range fix-up (compare, select, two
 // ldexp) that the probabilities here never need; exp2(-inf) = 0 doubles as the mask
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-
-// Backward softmax-gradient math on score PAIRS (build A/B switch, -DMLT_ATTN_PKF32=1): the
-// scale-and-shift and dS = P * dP' of two adjacent accumulator rows as one v_pk_fma_f32 / one
-// v_pk_mul_f32 instead of two scalar ops each; the exp2 stays scalar. Off by default: measured at
-// B512 (profiles/r5/gemm_gelu_tab_attn_pkf32_ab.jsonl, profiles/pmc/attn_bf16_b512_r5*.jsonl) it
-// cuts VALU instructions 5 % (dK/dV) / 9 % (dQ), VALU per MFMA 4.30 -> 4.07 / 4.89 -> 4.44, but the
-// backward pair is not faster (1.946-1.958 vs 1.937-1.945 ms): dQ -2.7 % busy cycles, dK/dV +1.6 %
-// (packed f32 ops between MFMAs cost more issue than the two scalar ops, MI355X_MICROARCH.md).
-#ifndef MLT_ATTN_PKF32
-#define MLT_ATTN_PKF32 0
-#endif
-// p = exp2(s * sl2 - lr) and ds = p * dp for rows (r0, r0 + 1) of one f32x4 accumulator
-__device__ __forceinline__ void pk_prob_ds(const f32x4& s, const f32x4& dp, float sl2, f32x2 nlr, int r0, f32x2& p,
-                                           f32x2& d) {
-  const f32x2 x = __builtin_elementwise_fma(f32x2{s[r0], s[r0 + 1]}, f32x2{sl2, sl2}, nlr);
-  p = f32x2{fast_exp2(x.x), fast_exp2(x.y)};
-  d = p * f32x2{dp[r0], dp[r0 + 1]};
-}
 
 __device__ __forceinline__ f32x4 mfma(bf16x8 a, bf16x8 b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
@@ -651,7 +634,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const uint16_t* __rest
 }
 
 // ---------------------------------------------------------------------------
-// Ring-staged backward (MLT_ATTN_RING, default on). The register-staged kernels above hold
+// Ring-staged backward (the shipped path). The register-staged kernels above hold
 // ~180 VGPRs, i.e. 2 waves per SIMD, and wait at the end of every 64-row step for tile loads
 // issued at its start: one HBM/L2 round trip exposed per step. Here the streamed tiles (Q, dO
 // and the LSE / delta rows for dK/dV; K, V for dQ) go HBM -> LDS by global_load_lds into a
@@ -661,6 +644,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const uint16_t* __rest
 // The math and its order are those of the kernels above: bit-identical gradients.
 // ---------------------------------------------------------------------------
 constexpr int kTile = AB * 128;  // one 64 x 64 bf16 tile
+constexpr int kRing = 4;         // ring depth (3 tied: 1.921 vs 1.923 ms for the backward pair)
 
 // glds of a 64x64 bf16 tile into the (row & 7)-swizzled image tile_off() reads: lane-linear
 // LDS destination, swizzle on the per-lane source; rows past nrows_valid re-read the last valid
@@ -853,7 +837,7 @@ __device__ __forceinline__ void attn_q8_epilogue(const AttnQ8& q8, const float (
 
 // FULLT: S % 64 == 0 (every ring stage a whole tile: the clamped-row copy path is compiled out, which
 // keeps the 2-group kernel within 256 VGPRs)
-template <int NK, int kRing, bool FULLT>
+template <int NK, bool FULLT>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_ring_kernel(const uint16_t* __restrict__ qkv,
                                                                  const uint16_t* __restrict__ dout,
                                                                  const float* __restrict__ lse,
@@ -994,17 +978,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_ring_kernel(const uint16
         const float4 l4 = *reinterpret_cast<const float4*>(lse_s + qt * 16 + 4 * g);
         const float lr[4] = {l4.x, l4.y, l4.z, l4.w};
         f32x4 pc[NK], dsc[NK];
-        if constexpr (PATH == 0 && MLT_ATTN_PKF32) {
-          const f32x2 nl01 = {-lr[0], -lr[1]}, nl23 = {-lr[2], -lr[3]};
-#pragma unroll
-          for (int n = 0; n < NK; ++n) {
-            f32x2 pa, pb, da, db;
-            pk_prob_ds(sv[n], dp[n], sl2, nl01, 0, pa, da);
-            pk_prob_ds(sv[n], dp[n], sl2, nl23, 2, pb, db);
-            pc[n] = f32x4{pa.x, pa.y, pb.x, pb.y};
-            dsc[n] = f32x4{da.x, da.y, db.x, db.y};
-          }
-        } else {
 #pragma unroll
         for (int n = 0; n < NK; ++n)
 #pragma unroll
@@ -1022,7 +995,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_ring_kernel(const uint16
             pc[n][r] = pv;
             dsc[n][r] = pv * dp[n][r];
           }
-        }
 #pragma unroll
         for (int n = 0; n < NK; ++n) {
           if (qt & 1) {
@@ -1127,7 +1099,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_ring_kernel(const uint16
 // The dQ ring kernel runs FIRST and computes delta = rowsum(dO * O) for its own queries in its
 // prologue (dO is in its registers anyway; O is one more 16-byte load per fragment), publishing it
 // for the dK/dV kernel that follows -- no separate delta pass over dO and O.
-template <int NQ, int kRing, bool FULLT>
+template <int NQ, bool FULLT>
 __global__ __launch_bounds__(256) void attn_bwd_dq_ring_kernel(const uint16_t* __restrict__ qkv,
                                                                const uint16_t* __restrict__ dout,
                                                                const uint16_t* __restrict__ out,
@@ -1241,16 +1213,6 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_ring_kernel(const uint16_t* _
             dp[n] = mfma(va, of[n][kh], dp[n]);
           }
         }
-        if constexpr (FULL && MLT_ATTN_PKF32) {
-#pragma unroll
-          for (int n = 0; n < NQ; ++n) {
-            const f32x2 nl = {-lq[n], -lq[n]};
-            f32x2 pa, pb, da, db;
-            pk_prob_ds(sv[n], dp[n], sl2, nl, 0, pa, da);
-            pk_prob_ds(sv[n], dp[n], sl2, nl, 2, pb, db);
-            ds[n][kt] = f32x4{da.x, da.y, db.x, db.y};
-          }
-        } else
 #pragma unroll
         for (int n = 0; n < NQ; ++n)
 #pragma unroll
@@ -1354,42 +1316,43 @@ void launch_attn_fwd(const uint16_t* qkv, uint16_t* out, float* lse, const int* 
 bool launch_attn_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse, float* delta,
                      const int* lens, uint16_t* dqkv, int B, int S, int H, float scale, hipStream_t st,
                      float* colpart_q, float* colpart_kv, int* rows_q, int* rows_kv, const AttnQ8& q8) {
+  // MLT_ATTN_RING: unset or 4 = the ring kernels, 0 = the register-staged kernels. Those stay in the
+  // tree as the bit-for-bit oracle of the ring kernels' test; any other value is an error.
+  const char* rv = getenv("MLT_ATTN_RING");
+  const bool ring = !rv || !strcmp(rv, "4");
+  if (!ring && strcmp(rv, "0"))
+    throw std::runtime_error(std::string("attn_bwd: MLT_ATTN_RING=") + rv + " (accepted: unset or 4 = ring kernels, " +
+                             "0 = register-staged kernels)");
   if (B <= 0 || S <= 0) return false;
   const int64_t pairs = (int64_t)B * S * H;
   const dim3 g2((S + 127) / 128 * H * B), g1((S + 63) / 64 * H * B);
-  // MLT_ATTN_RING: 0 = register-staged kernels, 3 / 4 = ring depth (default 4)
-  const char* rv = getenv("MLT_ATTN_RING");
-  const int ring = rv ? atoi(rv) : 4;
-  if (ring == 3 || ring == 4) {
+  if (ring) {
     const bool k2 = attn_groups("MLT_ATTN_DKDV_GROUPS", S, 2) == 2, q2 = attn_groups("MLT_ATTN_DQ_GROUPS", S) == 2;
-#define MLT_RING_LAUNCH(RD, FL)                                                                                       \
-  {                                                                                                                   \
-    if (q2)                                                                                                           \
-      hipLaunchKernelGGL((attn_bwd_dq_ring_kernel<2, RD, FL>), g2, dim3(256), 0, st, qkv, dout, out, lse, delta, lens, \
-                         dqkv, S, H, scale, colpart_q, q8);                                                           \
-    else                                                                                                              \
-      hipLaunchKernelGGL((attn_bwd_dq_ring_kernel<1, RD, FL>), g1, dim3(256), 0, st, qkv, dout, out, lse, delta, lens, \
-                         dqkv, S, H, scale, colpart_q, q8);                                                           \
-    if (k2)                                                                                                           \
-      hipLaunchKernelGGL((attn_bwd_dkdv_ring_kernel<2, RD, FL>), g2, dim3(256), 0, st, qkv, dout, lse, delta, lens,   \
-                         dqkv, S, H, scale, colpart_kv, q8);                                                          \
-    else                                                                                                              \
-      hipLaunchKernelGGL((attn_bwd_dkdv_ring_kernel<1, RD, FL>), g1, dim3(256), 0, st, qkv, dout, lse, delta, lens,   \
-                         dqkv, S, H, scale, colpart_kv, q8);                                                          \
-  }
-    const bool full = S % AB == 0;
-    if (ring == 3) {
-      if (full) MLT_RING_LAUNCH(3, true) else MLT_RING_LAUNCH(3, false)
-    } else {
-      if (full) MLT_RING_LAUNCH(4, true) else MLT_RING_LAUNCH(4, false)
-    }
-#undef MLT_RING_LAUNCH
+    auto launch = [&](auto fullt) {
+      constexpr bool FL = decltype(fullt)::value;
+      if (q2)
+        hipLaunchKernelGGL((attn_bwd_dq_ring_kernel<2, FL>), g2, dim3(256), 0, st, qkv, dout, out, lse, delta, lens,
+                           dqkv, S, H, scale, colpart_q, q8);
+      else
+        hipLaunchKernelGGL((attn_bwd_dq_ring_kernel<1, FL>), g1, dim3(256), 0, st, qkv, dout, out, lse, delta, lens,
+                           dqkv, S, H, scale, colpart_q, q8);
+      if (k2)
+        hipLaunchKernelGGL((attn_bwd_dkdv_ring_kernel<2, FL>), g2, dim3(256), 0, st, qkv, dout, lse, delta, lens,
+                           dqkv, S, H, scale, colpart_kv, q8);
+      else
+        hipLaunchKernelGGL((attn_bwd_dkdv_ring_kernel<1, FL>), g1, dim3(256), 0, st, qkv, dout, lse, delta, lens,
+                           dqkv, S, H, scale, colpart_kv, q8);
+    };
+    if (S % AB == 0)
+      launch(std::true_type{});
+    else
+      launch(std::false_type{});
     // partial rows actually written: B x (row blocks of the chosen group count)
     if (rows_kv) *rows_kv = B * ((S + (k2 ? 127 : 63)) / (k2 ? 128 : 64));
     if (rows_q) *rows_q = B * ((S + (q2 ? 127 : 63)) / (q2 ? 128 : 64));
     return colpart_q != nullptr && colpart_kv != nullptr;
   }
-  if (q8.y) throw std::runtime_error("attn_bwd: the fp8 (q8) outputs need the ring kernels (MLT_ATTN_RING=3|4)");
+  if (q8.y) throw std::runtime_error("attn_bwd: the fp8 (q8) outputs need the ring kernels (MLT_ATTN_RING unset or 4)");
   hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((pairs + 15) / 16)), dim3(256), 0, st, dout, out, delta,
                      (int64_t)B * S, H);
   if (attn_groups("MLT_ATTN_DKDV_GROUPS", S, 1) == 2)

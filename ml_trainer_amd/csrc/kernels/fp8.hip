@@ -271,12 +271,8 @@ void launch_cast_transpose_fp8(const float* w, uint8_t* y, uint8_t* yt, int R, i
 }
 
 bool cast_transpose_fp8_wide_ok(const void* x, const void* y, const void* yt, int R, int C) {
-  // MLT_FP8_CT_WIDE=0 keeps the 64x64 kernel (A/B knob)
-  static const bool enabled = [] {
-    const char* e = getenv("MLT_FP8_CT_WIDE");
-    return !(e && e[0] == '0');
-  }();
-  return enabled && R > 0 && C > 0 && R % 128 == 0 && C % 128 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 &&
+  // (unaligned shapes and fp32 weights keep the 64x64 kernel)
+  return R > 0 && C > 0 && R % 128 == 0 && C % 128 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 &&
          (reinterpret_cast<uintptr_t>(y) & 7) == 0 && (reinterpret_cast<uintptr_t>(yt) & 7) == 0;
 }
 

@@ -19,7 +19,6 @@ Everything else in the block (bias, GELU, residual, LayerNorm, attention) is unc
 """
 from __future__ import annotations
 
-import os
 from typing import Dict, Optional
 
 import torch
@@ -119,7 +118,9 @@ class _WeightState:
         self.key = None
         self.xt = None   # (x.data_ptr(), X^T in e4m3) of the last forward, for the fp8 weight gradient
         self.dy8 = None  # (dy.data_ptr(), dY in e5m2) cast by wgrad, reused by the dgrad that follows
-        self.dyt = None  # dY^T in e5m2 written by the producing GEMM's quantising epilogue (FFN1)
+        # dY^T in e5m2 from the kernel that produced dY already quantised: FFN2's dgrad epilogue
+        # (for FFN1, dgrad_gelu_q) or the attention backward (for the QKV projection, attn_dy_q_done)
+        self.dyt = None
 
 
 def _state(w: torch.Tensor, ctx: Fp8Context) -> _WeightState:
@@ -201,15 +202,9 @@ class Fp8Linear:
         C = require_native()
         ctx = context(dy.device)
         if dy.dtype == _DT[E5M2]:
-            # dY (+ dY^T, + bias gradient) from the producer's quantising epilogue (dgrad_gelu_q)
+            # dY (+ dY^T, + bias gradient) quantised by its producer (dgrad_gelu_q, attn_dy_q_done)
             if st.dyt is None or st.dy8 is None or st.dy8[0] != dy.data_ptr():
                 raise RuntimeError("fp8 wgrad: pre-quantised dY without its transpose")
-            dy8t, st.dyt = st.dyt, None
-        elif st.dyt is not None and st.dy8 is not None and st.dy8[0] == dy.data_ptr():
-            # bf16 dY whose e5m2 copy and transpose the producing LayerNorm backward already wrote
-            # (ln_bwd_q8, which also reduced the bias gradient)
-            if db_out is not None:
-                raise RuntimeError("fp8 wgrad: LayerNorm-quantised dY carries its bias gradient already")
             dy8t, st.dyt = st.dyt, None
         else:
             dy8, dy8t = ctx.cast_t(dy, st.mdy, E5M2, colsum_out=db_out, colsum_accumulate=db_acc)
@@ -242,7 +237,7 @@ class Fp8Linear:
     # The dQ and dK/dV kernels write dQKV as e5m2 with its transpose and amax (attn_bwd q8_*), from
     # the bf16-rounded values, bitwise what fp8_cast_transpose of the bf16 dQKV gives: the widest
     # cast of the layer (3 x hidden columns) and the bf16 dQKV itself disappear.
-    fuse_attn = os.environ.get("MLT_FP8_ATTN_Q", "1") != "0"
+    fuse_attn = True
 
     @staticmethod
     def attn_dy_q(wqkv, x, rows: int):
@@ -268,36 +263,12 @@ class Fp8Linear:
         st.dy8 = (d8.data_ptr(), d8)
         st.dyt = d8t
 
-    # ---- LayerNorm backward quantises the out-proj / FFN2 dY ------------------------------------
-    # In the post-LN blocks the LayerNorm backward's dx is the dY of the out-projection (attention
-    # block) and of FFN2: C.ln_bwd_q8 writes its e5m2 copy and transpose with that weight's dY scale
-    # (plus amax, plus the bias gradient it already reduced), so the separate cast-transpose pass
-    # over dx disappears. Opt-in (MLT_FP8_LN_Q=1): measured slower -- 508 us per call against 308 us
-    # of ln_bwd + 184 us of cast-transpose at 262144 x 1024, fp8 `large` 1,250 vs 1,254 samples/s
-    # (profiles/r5/fp8_ln_bwd_q8_ab.jsonl). Its 32-row chunk barriers and the transposed pass leave
-    # the loads idle; the two streaming kernels it replaces each run near 5.2-5.8 TB/s.
-    fuse_ln = os.environ.get("MLT_FP8_LN_Q", "0") == "1"
-
-    @staticmethod
-    def ln_bwd_q_state(w, x):
-        """(state, context) when a LayerNorm backward may quantise ``w``'s dY: its e5m2 scale exists
-        and the forward left X^T (of ``x``) for w's fp8 weight gradient; else None."""
-        if not Fp8Linear.fuse_ln:
-            return None
-        st = getattr(w, "_mlt_f8", None)
-        if st is None or st.xt is None or st.xt[0] != x.data_ptr() or not _fp8_wgrad_ok(x, w):
-            return None
-        ctx = context(x.device)
-        if not ctx._ready[st.mdy]:
-            return None
-        return st, ctx
-
     # ---- FFN fusion: the GEMM epilogues quantise for the next GEMM ------------------------------
     # FFN1's forward epilogue writes GELU(.) as FFN2's e4m3 input and its transpose (FFN2's wgrad
     # operand); FFN2's dgrad epilogue writes dGELU(.) as FFN1's e5m2 dY, its transpose and FFN1's
     # bias gradient. The bf16 intermediate [tokens, 4H] and its cast-transpose pass (one read +
     # two writes of the widest activation of the layer, twice per step) disappear.
-    fuse_q = os.environ.get("MLT_FP8_FUSE", "1") != "0"
+    fuse_q = True
 
     @staticmethod
     def _q_shape_ok(x, w1) -> bool:

@@ -78,8 +78,6 @@ class Bf16Linear:
     def fwd(x, w, bias=None, gelu_aux=None, res=None):
         return linear_fwd(x, bf16_weight(w), bias, gelu_aux=gelu_aux, res=res)
 
-    fuse_colsum = os.environ.get("MLT_DGELU_COLSUM", "1") != "0"
-
     @staticmethod
     def dgrad(dy, w, out, aux=None, res=None, colsum_out=None, colsum_acc=False):
         """out = dy . W  (* gelu'(aux) when aux is given) (+ res). Large token counts take W^T as
@@ -101,7 +99,7 @@ class Bf16Linear:
     def dgelu_colsum_ok(dy, w) -> bool:
         """Whether dgrad(dy, w, aux=..., colsum_out=...) can fuse the column sums (ping-pong tiles
         over the whole output: tokens and W's input width multiples of 256)."""
-        return Bf16Linear.fuse_colsum and dy.shape[0] % 256 == 0 and w.shape[1] % 256 == 0 and dy.shape[1] % 64 == 0
+        return dy.shape[0] % 256 == 0 and w.shape[1] % 256 == 0 and dy.shape[1] % 64 == 0
 
 
 BF16 = Bf16Linear()
@@ -148,6 +146,16 @@ class _Grads:
             self.ready.append(p)
         return g
 
+    def out(self, p, n, device):
+        """Where a kernel reduces the ``n``-float gradient of ``p``: (target, accumulate, result) --
+        the flat-gradient sink, accumulated into (the autograd result is then None), or a fresh
+        fp32 vector that is also the result."""
+        g = self.sink(p)
+        if g is not None:
+            return g, True, None
+        t = torch.empty(n, dtype=torch.float32, device=device)
+        return t, False, t
+
     def wgrad(self, p, dy, x, impl=None):
         g = self.sink(p)
         if impl is not None and hasattr(impl, "wgrad"):  # fp8 weight gradient
@@ -165,22 +173,19 @@ class _Grads:
         if pb is None or impl is None or not getattr(impl, "wgrad_fuses_bias", False):
             return self.wgrad(pw, dy, x, impl), self.colsum(pb, dy)
         C = require_native()
-        g, gb = self.sink(pw), self.sink(pb)
-        db = gb if gb is not None else torch.empty(dy.shape[1], dtype=torch.float32, device=dy.device)
-        r = impl.wgrad(pw, dy, x, g, db_out=db, db_acc=gb is not None)
+        g = self.sink(pw)
+        db, db_acc, db_ret = self.out(pb, dy.shape[1], dy.device)
+        r = impl.wgrad(pw, dy, x, g, db_out=db, db_acc=db_acc)
         if r is not None:
-            return (None if g is not None else r), (None if gb is not None else db)
+            return (None if g is not None else r), db_ret
         # fp8 weight gradient not applicable here: separate kernels into the same sinks
         if g is None:
             dw = linear_wgrad(dy, x)
         else:
             C.gemm(dy, x, g, True, True, accumulate=True)
             dw = None
-        if gb is None:
-            C.colsum(dy, db, False)
-            return dw, db
-        C.colsum(dy, gb, accumulate=True)
-        return dw, None
+        C.colsum(dy, db, db_acc)
+        return dw, db_ret
 
     def colsum(self, p, dy):
         g = self.sink(p)
@@ -222,30 +227,20 @@ def _attn_bwd(saved, params, lens, B, S, H, dy, G, dbo="colsum", impl=BF16, dres
     dqkv = torch.empty_like(qkv)
     delta = torch.empty(B * S * H, dtype=torch.float32, device=dy.device)
     q8 = impl.attn_dy_q(wqkv, x, qkv.shape[0]) if (impl is not BF16 and hasattr(impl, "attn_dy_q")) else None
-    if q8 is not None:
-        # fp8: the backward kernels write dQKV as e5m2 + transpose + amax (no bf16 dQKV, no cast
-        # pass) and the QKV bias gradient as their column sums
-        d8, d8t, qs, qa = q8
-        db = None
-        if bqkv is not None:
-            gb = G.sink(bqkv)
-            db = gb if gb is not None else torch.empty(qkv.shape[1], dtype=torch.float32, device=dy.device)
-        C.attn_bwd(qkv, attn, dattn, lse, delta, lens, dqkv, B, S, H, _ATTN_SCALE, colsum_out=db,
-                   colsum_accumulate=bqkv is not None and gb is not None, q8_y=d8, q8_yt=d8t, q8_scale=qs,
-                   q8_amax=qa)
-        impl.attn_dy_q_done(wqkv, d8, d8t)
-        dwqkv = G.wgrad(wqkv, d8, x, impl)
-        dbqkv = None if (bqkv is None or gb is not None) else db
-        dx = impl.dgrad(d8, wqkv, torch.empty_like(x), res=dres)  # dx = dqkv . Wqkv + dres (residual)
-        return dx, dwqkv, dbqkv, dwo, dbo
-    if impl is BF16 and bqkv is not None and _ATTN_COLSUM:
+    if q8 is not None or (impl is BF16 and bqkv is not None):
         # the QKV bias gradient (column sums of dQKV) from the backward kernels themselves
-        gb = G.sink(bqkv)
-        dbqkv = gb if gb is not None else torch.empty(qkv.shape[1], dtype=torch.float32, device=dy.device)
-        C.attn_bwd(qkv, attn, dattn, lse, delta, lens, dqkv, B, S, H, _ATTN_SCALE, colsum_out=dbqkv,
-                   colsum_accumulate=gb is not None)
+        db, db_acc, dbqkv = G.out(bqkv, qkv.shape[1], dy.device) if bqkv is not None else (None, False, None)
+        if q8 is not None:
+            # fp8: the kernels write dQKV as e5m2 + transpose + amax (no bf16 dQKV, no cast pass)
+            d8, d8t, qs, qa = q8
+            C.attn_bwd(qkv, attn, dattn, lse, delta, lens, dqkv, B, S, H, _ATTN_SCALE, colsum_out=db,
+                       colsum_accumulate=db_acc, q8_y=d8, q8_yt=d8t, q8_scale=qs, q8_amax=qa)
+            impl.attn_dy_q_done(wqkv, d8, d8t)
+            dqkv = d8
+        else:
+            C.attn_bwd(qkv, attn, dattn, lse, delta, lens, dqkv, B, S, H, _ATTN_SCALE, colsum_out=db,
+                       colsum_accumulate=db_acc)
         dwqkv = G.wgrad(wqkv, dqkv, x, impl)
-        dbqkv = None if gb is not None else dbqkv
     else:
         C.attn_bwd(qkv, attn, dattn, lse, delta, lens, dqkv, B, S, H, _ATTN_SCALE)
         dwqkv, dbqkv = G.wgrad_bias(wqkv, bqkv, dqkv, x, impl)
@@ -273,20 +268,18 @@ def _ffn_bwd(saved, params, dy, G, db2="colsum", impl=BF16, dres=None):
         db2 = G.colsum(b2, dy)
     if a.dtype == torch.float8_e4m3fn and impl.dgrad_gelu_q_ready(w1, x):
         # fp8 FFN fusion: FFN2's dgrad epilogue emits FFN1's e5m2 dY, dY^T and bias gradient
-        gb = G.sink(b1)
-        db1 = gb if gb is not None else torch.empty(w1.shape[0], dtype=torch.float32, device=dy.device)
-        d8 = impl.dgrad_gelu_q(dy, w2, pre, w1, db1, gb is not None)
+        db, db_acc, db1 = G.out(b1, w1.shape[0], dy.device)
+        d8 = impl.dgrad_gelu_q(dy, w2, pre, w1, db, db_acc)
         dw1 = G.wgrad(w1, d8, x, impl)
         dx = impl.dgrad(d8, w1, torch.empty_like(x), res=dres)
-        return dx, dw1, (None if gb is not None else db1), dw2, db2
+        return dx, dw1, db1, dw2, db2
     if impl is BF16 and impl.dgelu_colsum_ok(dy, w2):
         # FFN1's bias gradient from the dGELU epilogue (no separate pass over dpre)
-        gb = G.sink(b1)
-        db1 = gb if gb is not None else torch.empty(w1.shape[0], dtype=torch.float32, device=dy.device)
-        dpre = impl.dgrad(dy, w2, torch.empty_like(pre), aux=pre, colsum_out=db1, colsum_acc=gb is not None)
+        db, db_acc, db1 = G.out(b1, w1.shape[0], dy.device)
+        dpre = impl.dgrad(dy, w2, torch.empty_like(pre), aux=pre, colsum_out=db, colsum_acc=db_acc)
         dw1 = G.wgrad(w1, dpre, x, impl)
         dx = impl.dgrad(dpre, w1, torch.empty_like(x), res=dres)
-        return dx, dw1, (None if gb is not None else db1), dw2, db2
+        return dx, dw1, db1, dw2, db2
     dpre = impl.dgrad(dy, w2, torch.empty_like(pre), aux=pre)  # (dy . W2) * gelu'(pre)
     dw1, db1 = G.wgrad_bias(w1, b1, dpre, x, impl)
     dx = impl.dgrad(dpre, w1, torch.empty_like(x), res=dres)
@@ -316,14 +309,12 @@ def _dropout_add_ln_fwd(y0, res, gamma, beta, eps, drop):
     return y, (z, gamma, mean, rstd)
 
 
-def _ln_bwd(saved, beta, dy, G, dxsum_param=None, q8=None, drop=None):
+def _ln_bwd(saved, beta, dy, G, dxsum_param=None, drop=None):
     """LayerNorm backward; with ``dxsum_param`` also the column sums of dx (= that bias's grad).
-    ``q8`` = (impl, w, x): dx is the dY of linear ``w`` (input ``x``); an fp8 ``impl`` that can take
-    it pre-quantised gets dx's e5m2 copy and transpose from this same kernel (C.ln_bwd_q8).
     Returns (dx, dgamma|None, dbeta|None, dbias|None).
     ``drop`` = (p, seed, site, rank) (needs ``dxsum_param``): the input was dropout(linear) +
     residual. dx is then the residual's gradient, a fifth result dxm = mask * scale * dx is the
-    linear's dY, and dbias holds dxm's column sums. The quantising variant is not used."""
+    linear's dY, and dbias holds dxm's column sums."""
     C = require_native()
     x, gamma, mean, rstd = saved
     D = gamma.numel()
@@ -343,41 +334,18 @@ def _ln_bwd(saved, beta, dy, G, dxsum_param=None, q8=None, drop=None):
     else:
         dg = dg_t = torch.empty(D, dtype=torch.float32, device=dev)
         db = db_t = torch.empty(D, dtype=torch.float32, device=dev)
-    dxs = dxs_t = None
-    dxs_acc = False
-    if want:
-        so = G.sink(dxsum_param)
-        if so is not None:
-            dxs_t, dxs_acc = so, True
-        else:
-            dxs = dxs_t = torch.empty(D, dtype=torch.float32, device=dev)
+    dxs_t, dxs_acc, dxs = G.out(dxsum_param, D, dev) if want else (None, False, None)
     if drop is not None:
         dxm = torch.empty_like(x)
         p, seed, site, rank = drop
         C.ln_bwd(dy, x, gamma, mean, rstd, dx, part, dg_t, db_t, acc, None, dxsum=dxs_t, dxsum_acc=dxs_acc,
                  dxm=dxm, p=p, seed=seed, site=site, rank=rank)
         return dx, dg, db, dxs, dxm
-    if want and q8 is not None and hasattr(q8[0], "ln_bwd_q_state"):
-        r = q8[0].ln_bwd_q_state(q8[1], q8[2])
-        if r is not None:
-            st, fctx = r
-            rows = x.shape[0]
-            nq = C.ln_q8_partial_blocks(rows) * 3 * D
-            if part.numel() < nq:
-                part = torch.empty(nq, dtype=torch.float32, device=dev)
-            y8 = torch.empty(rows, D, dtype=torch.float8_e5m2, device=dev)
-            yt8 = torch.empty(D, rows, dtype=torch.float8_e5m2, device=dev)
-            if C.ln_bwd_q8(dy, x, gamma, mean, rstd, dx, part, dg_t, db_t, acc, dxs_t, dxs_acc, y8, yt8,
-                           fctx.scale[st.mdy:st.mdy + 1], fctx.amax[st.mdy]):
-                st.dy8 = (dx.data_ptr(), y8)
-                st.dyt = yt8
-                return dx, dg, db, dxs
     C.ln_bwd(dy, x, gamma, mean, rstd, dx, part, dg_t, db_t, acc, None, dxsum=dxs_t, dxsum_acc=dxs_acc)
     return dx, dg, db, dxs
 
 
 _ATTN_SCALE = 1.0 / 8.0  # 1/sqrt(head_dim = 64)
-_ATTN_COLSUM = os.environ.get("MLT_ATTN_COLSUM", "1") != "0"  # QKV bias grad from the attention backward
 
 
 class _AttentionBlock(torch.autograd.Function):
@@ -453,8 +421,7 @@ class _AttentionLNBlock(torch.autograd.Function):
         G = _Grads()
         if ctx.drop is None:
             da, dg, db, dbo = _ln_bwd(t[4:], ctx.beta, dy.contiguous().to(torch.bfloat16), G,
-                                      dxsum_param=ctx.params[3],
-                                      q8=(ctx.impl, ctx.params[2], t[2]))  # da = out-proj dY (input attn)
+                                      dxsum_param=ctx.params[3])  # da = out-proj dY
             dres = None
         else:  # dres: gradient of the residual x; da = its masked, scaled copy, the out-proj dY
             dres, dg, db, dbo, da = _ln_bwd(t[4:], ctx.beta, dy.contiguous().to(torch.bfloat16), G,
@@ -486,8 +453,7 @@ class _FFNLNBlock(torch.autograd.Function):
         G = _Grads()
         if ctx.drop is None:
             df, dg, db, db2 = _ln_bwd(t[3:], ctx.beta, dy.contiguous().to(torch.bfloat16), G,
-                                      dxsum_param=ctx.params[3],
-                                      q8=(ctx.impl, ctx.params[2], t[2]))  # df = FFN2 dY (input a)
+                                      dxsum_param=ctx.params[3])  # df = FFN2 dY
             dres = None
         else:
             dres, dg, db, db2, df = _ln_bwd(t[3:], ctx.beta, dy.contiguous().to(torch.bfloat16), G,

@@ -38,3 +38,19 @@ def test_no_retired_gemm_paths_left():
                  "MLT_GEMM_SPLIT_EXT", "gelu_grad2", "launch_gemm_persist"):
         assert not [p for p, s in text.items() if name in s], name
     assert sum(s.count('getenv("MLT_GEMM_GROUP_M")') for s in text.values()) == 1
+
+
+def test_no_retired_bert_paths_left():
+    """The quantising LayerNorm backward, the packed-f32 attention fork and the switches of settled
+    BERT / fp8 A/Bs are gone from the package (native sources and Python); the attention backward's
+    one remaining switch is read in one place."""
+    text = {}
+    for d, _, files in os.walk(os.path.join(REPO, "ml_trainer_amd")):
+        for f in files:
+            if f.endswith((".py", ".hip", ".cpp", ".h", ".inc")):
+                text[os.path.join(d, f)] = open(os.path.join(d, f), errors="replace").read()
+    assert any(p.endswith("attention.hip") for p in text) and any(p.endswith("transformer.py") for p in text)
+    for name in ("ln_bwd_q8", "ln_q8_partial_blocks", "MLT_FP8_LN_Q", "fuse_ln", "MLT_ATTN_PKF32", "pk_prob_ds",
+                 "MLT_FP8_CT_WIDE", "MLT_ATTN_COLSUM", "MLT_DGELU_COLSUM", "MLT_FP8_ATTN_Q", "MLT_FP8_FUSE"):
+        assert not [p for p, s in text.items() if name in s], name
+    assert sum(s.count('getenv("MLT_ATTN_RING")') for s in text.values()) == 1

@@ -275,23 +275,6 @@ def test_fp8_bert_dropout_close_to_bf16(dev):
         assert r < 0.25, (n, float(r))
 
 
-def test_fp8_dropout_skips_quantising_ln_bwd(dev, monkeypatch):
-    """MLT_FP8_LN_Q=1 (the opt-in quantising LayerNorm backward) changes nothing under dropout:
-    the blocks never ask for it, and the results equal the run without it."""
-    from ml_trainer_amd.ops.fp8 import Fp8Linear
-    base, _, _, o_base = _fp8_dropout_run(dev, 2)  # second step: the dY scales exist by then
-    monkeypatch.setenv("MLT_FP8_LN_Q", "1")
-    monkeypatch.setattr(Fp8Linear, "fuse_ln", True)  # the switch is read at import
-    asked = []
-    orig = Fp8Linear.ln_bwd_q_state
-    monkeypatch.setattr(Fp8Linear, "ln_bwd_q_state", staticmethod(lambda w, x: asked.append(1) or orig(w, x)))
-    q, _, _, o_q = _fp8_dropout_run(dev, 2)
-    assert not asked
-    assert torch.equal(o_q, o_base)
-    for (n, a), b in zip(q.named_parameters(), base.parameters()):
-        assert torch.equal(a.grad, b.grad), n
-
-
 def test_dropout_flat_gradients_match_returned(dev):
     """As test_direct_flat_gradients_match_returned, under dropout: with a FusedAdamW owning the
     parameters the out-projection / FFN2 bias gradients (the DXM column sums) and every other

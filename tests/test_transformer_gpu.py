@@ -339,7 +339,7 @@ def test_attention_bwd_ring_matches_register_staged(dev, B, S, H, use_lens, monk
     C.attn_fwd(qkv, out, lse, lens, B, S, H, scale)
     dout = _bf((B * S, D), g)
     res = {}
-    for ring in ("0", "3", "4"):
+    for ring in ("0", "4"):
         monkeypatch.setenv("MLT_ATTN_RING", ring)
         for grp in ("1", "2"):
             monkeypatch.setenv("MLT_ATTN_DKDV_GROUPS", grp)
@@ -349,7 +349,28 @@ def test_attention_bwd_ring_matches_register_staged(dev, B, S, H, use_lens, monk
             C.attn_bwd(qkv, out, dout, lse, delta, lens, dqkv, B, S, H, scale)
             res[ring, grp] = dqkv
     for grp in ("1", "2"):
-        assert torch.equal(res["0", grp], res["3", grp]) and torch.equal(res["0", grp], res["4", grp])
+        assert torch.equal(res["0", grp], res["4", grp])
+
+
+def test_attention_bwd_rejects_unknown_ring_value(dev, monkeypatch):
+    """MLT_ATTN_RING takes 4 (or unset: the ring kernels) and 0 (the register-staged oracle). Any
+    other value, the retired depth 3 included, is an error raised before any launch: the
+    NaN-prefilled dQKV is untouched."""
+    C = require_native()
+    B, S, H = 1, 64, 1
+    g = torch.Generator().manual_seed(5)
+    qkv = _bf((B * S, 3 * H * 64), g, 1.0)
+    out = torch.empty(B * S, H * 64, dtype=torch.bfloat16, device=dev)
+    lse = torch.empty(B * H * S, device=dev)
+    C.attn_fwd(qkv, out, lse, None, B, S, H, 0.125)
+    dout = _bf((B * S, H * 64), g)
+    dqkv = torch.full_like(qkv, float("nan"))
+    delta = torch.empty(B * S * H, device=dev)
+    monkeypatch.setenv("MLT_ATTN_RING", "3")
+    with pytest.raises(RuntimeError, match="MLT_ATTN_RING"):
+        C.attn_bwd(qkv, out, dout, lse, delta, None, dqkv, B, S, H, 0.125)
+    torch.cuda.synchronize()
+    assert torch.isnan(dqkv).all().item()
 
 
 @pytest.mark.parametrize("B,S,H,use_lens", [(2, 512, 3, False), (3, 200, 2, True), (2, 512, 2, True)])
