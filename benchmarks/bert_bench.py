@@ -5,6 +5,7 @@ baseline of the same model (torch.autocast + SDPA + hipBLASLt) for comparison.
     python benchmarks/bert_bench.py --model bert-base --batch 16 --seq 512 --steps 10
     python benchmarks/bert_bench.py --impl torch      # eager PyTorch baseline
     python benchmarks/bert_bench.py --impl native --dropout 0.1   # hidden dropout in the LayerNorm kernels
+    python benchmarks/bert_bench.py --impl native --attention-dropout 0.1   # ... in the flash attention kernels
 
 Prints one JSON line per run (samples/s, tokens/s, ms/step, model TFLOP/s).
 Synthetic token ids, random-init weights (no network).
@@ -32,6 +33,8 @@ def run(args):
     over = {"layers": args.layers} if args.layers else {}
     if args.dropout:
         over["hidden_dropout"] = args.dropout
+    if args.attention_dropout:
+        over["attention_dropout"] = args.attention_dropout
     cfg = bert_config(args.model, **over)
     m = BertClassifier(cfg).to(dev)
     if args.impl == "native":
@@ -61,7 +64,8 @@ def run(args):
     tokens = args.batch * args.seq
     flops = m.flops_per_token(args.seq) * tokens
     rec = {"bench": "bert_train_step", "impl": args.impl, "model": args.model, "layers": cfg.layers,
-           "batch": args.batch, "seq": args.seq, "dropout": args.dropout, "ms_per_step": dt * 1e3, "samples_per_s": args.batch / dt,
+           "batch": args.batch, "seq": args.seq, "dropout": args.dropout,
+           "attention_dropout": args.attention_dropout, "ms_per_step": dt * 1e3, "samples_per_s": args.batch / dt,
            "tokens_per_s": tokens / dt, "model_tflops": flops / dt / 1e12, "loss": float(loss.detach()),
            "peak_mem_gb": torch.cuda.max_memory_allocated() / 2 ** 30}
     print(json.dumps(rec), flush=True)
@@ -78,6 +82,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--impl", choices=["native", "torch", "both"], default="both")
     ap.add_argument("--dropout", type=float, default=0.0, help="hidden dropout probability (default 0.0)")
+    ap.add_argument("--attention-dropout", type=float, default=0.0,
+                    help="attention-probability dropout, applied as round(p * 256) / 256 (default 0.0)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     recs = []

@@ -15,7 +15,8 @@ CIFAR-shaped dataset and says so in the log.
 Extension flags (not in the reference): ``--model`` (default/tiny/bert-base/
 large), ``--synthetic``, ``--per_device_batch``, ``--no_engine``,
 ``--no_parallel``, ``--resume``, ``--amp bf16``, ``--precision bf16``, ``--metrics_jsonl``, ``--log_jsonl``, ``--zero_stage``, ``--async_checkpoint``,
-``--dropout`` (BERT hidden dropout).
+``--dropout`` (BERT hidden dropout), ``--attention_dropout`` (BERT attention-probability dropout,
+inside the flash attention kernels; applied as round(p * 256) / 256).
 """
 from __future__ import annotations
 
@@ -66,7 +67,12 @@ def main(args):
     lenet = args.model in ("default", "tiny", "lenet")
     if lenet and args.dropout:
         raise ValueError("--dropout applies to the BERT models; the LeNet models have no dropout")
-    model = build_model(args.model, **({"hidden_dropout": args.dropout} if args.dropout else {}))
+    if lenet and args.attention_dropout:
+        raise ValueError("--attention_dropout applies to the BERT models; the LeNet models have no attention")
+    over = {"hidden_dropout": args.dropout} if args.dropout else {}
+    if args.attention_dropout:
+        over["attention_dropout"] = args.attention_dropout
+    model = build_model(args.model, **over)
     if lenet:
         datasets = build_datasets(args)
     else:  # BERT configs: synthetic token classification (no network for GLUE downloads)
@@ -136,6 +142,11 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--dropout", type=float, default=0.0,
                         help="BERT hidden dropout probability (embedding, attention-output and FFN-output "
                              "sites; default: 0.0). An error for the LeNet models")
+    parser.add_argument("--attention_dropout", type=float, default=0.0,
+                        help="BERT attention-probability dropout, inside the flash attention kernels (default: "
+                             "0.0). One random byte per probability: p is applied as p_eff = round(p * 256) / 256 "
+                             "(0.1 -> 26/256 = 0.1015625), kept probabilities scaled by 1 / (1 - p_eff). An error "
+                             "for the LeNet models")
     parser.add_argument("--synthetic", action="store_true", help="use the seeded synthetic dataset")
     parser.add_argument("--synthetic_size", type=int, default=0)
     parser.add_argument("--seq_len", type=int, default=512)

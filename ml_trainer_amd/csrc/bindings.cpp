@@ -10,6 +10,7 @@
 #include <pybind11/stl.h>
 #include <torch/extension.h>
 
+#include <cmath>
 #include <map>
 #include <memory>
 
@@ -673,6 +674,27 @@ static DropArgs make_drop_args(double p, int64_t seed, int64_t site, int64_t ran
   return d;
 }
 
+// The attention-probability site's kernel arguments (one byte per element, mlt_philox.h): thr8 =
+// round(p * 256), scale = 1 / (1 - thr8 / 256) in double rounded once to fp32, T = ceil(S / 4) -- the
+// values ops/dropout.py computes. p == 0 gives thr8 == 0: the plain kernels run.
+static AttnDropArgs make_attn_drop_args(double p, int64_t seed, int64_t site, int64_t rank, int64_t S) {
+  TORCH_CHECK_VALUE(p >= 0.0 && p < 1.0, "attention dropout probability must satisfy 0 <= p < 1, got ", p);
+  TORCH_CHECK(site >= 0 && site <= 0xFFFFFFFFLL && rank >= 0 && rank <= 0xFFFFFFFFLL,
+              "dropout site / rank must fit 32 bits");
+  AttnDropArgs d;
+  d.thr8 = (uint32_t)std::floor(p * 256.0 + 0.5);
+  TORCH_CHECK_VALUE(p == 0.0 || d.thr8 > 0, "attention dropout probability ", p,
+                    " rounds to 0/256: no element would be dropped (the smallest effective p is 1/256)");
+  TORCH_CHECK_VALUE(d.thr8 < 256, "attention dropout probability ", p, " rounds to 256/256: every element dropped");
+  d.scale = (float)(1.0 / (1.0 - (double)d.thr8 / 256.0));
+  d.seed_lo = (uint32_t)((uint64_t)seed & 0xFFFFFFFFull);
+  d.seed_hi = (uint32_t)((uint64_t)seed >> 32);
+  d.site = (uint32_t)site;
+  d.rank = (uint32_t)rank;
+  d.T = (uint32_t)((S + 3) / 4);
+  return d;
+}
+
 // out = keep ? bf16(x * scale) : 0 over a contiguous bf16 tensor (flat element index = mask index)
 void dropout(Tensor x, Tensor out, double p, int64_t seed, int64_t site, int64_t rank) {
   TORCH_CHECK(x.numel() % 8 == 0, "dropout needs numel % 8 == 0, got ", x.numel());
@@ -794,22 +816,26 @@ static const int* lens_ptr(const c10::optional<Tensor>& lens, int64_t B) {
   return lens->data_ptr<int>();
 }
 
+// p, seed, site, rank: attention-probability dropout inside the kernel (p == 0: none)
 void attn_fwd(Tensor qkv, Tensor out, Tensor lse, c10::optional<Tensor> lens, int64_t B, int64_t S, int64_t H,
-              double scale) {
+              double scale, double p, int64_t seed, int64_t site, int64_t rank) {
   const int64_t D = H * 64;
   check_bf16_2d(qkv, "qkv", B * S, 3 * D);
   check_bf16_2d(out, "out", B * S, D);
   check_dev(lse, "lse", at::kFloat, B * H * S, 4);
   TORCH_CHECK(B > 0 && S > 0 && H > 0 && B <= 65535 && H <= 65535, "attention dims");
+  const AttnDropArgs ad = make_attn_drop_args(p, seed, site, rank, S);
   launch_attn_fwd(bf16_ptr(qkv), (uint16_t*)out.data_ptr(), lse.data_ptr<float>(), lens_ptr(lens, B), (int)B, (int)S,
-                  (int)H, (float)scale, cur_stream());
+                  (int)H, (float)scale, cur_stream(), ad);
 }
 
 void attn_bwd(Tensor qkv, Tensor out, Tensor dout, Tensor lse, Tensor delta, c10::optional<Tensor> lens, Tensor dqkv,
               int64_t B, int64_t S, int64_t H, double scale, c10::optional<Tensor> colsum_out,
               bool colsum_accumulate, c10::optional<Tensor> q8_y, c10::optional<Tensor> q8_yt,
-              c10::optional<Tensor> q8_scale, c10::optional<Tensor> q8_amax) {
+              c10::optional<Tensor> q8_scale, c10::optional<Tensor> q8_amax, double p, int64_t seed, int64_t site,
+              int64_t rank) {
   const int64_t D = H * 64;
+  const AttnDropArgs ad = make_attn_drop_args(p, seed, site, rank, S);  // the forward's (p, seed, site, rank)
   check_bf16_2d(qkv, "qkv", B * S, 3 * D);
   check_bf16_2d(out, "out", B * S, D);
   check_bf16_2d(dout, "dout", B * S, D);
@@ -848,7 +874,7 @@ void attn_bwd(Tensor qkv, Tensor out, Tensor dout, Tensor lse, Tensor delta, c10
                                      delta.data_ptr<float>(), lens_ptr(lens, B), (uint16_t*)dqkv.data_ptr(), (int)B,
                                      (int)S, (int)H, (float)scale, cur_stream(),
                                      pq.defined() ? pq.data_ptr<float>() : nullptr,
-                                     pkv.defined() ? pkv.data_ptr<float>() : nullptr, &rq, &rkv, q8);
+                                     pkv.defined() ? pkv.data_ptr<float>() : nullptr, &rq, &rkv, q8, ad);
   TORCH_CHECK(!q8.y || !colsum_out.has_value() || fused, "attn_bwd q8: column sums need the ring kernels");
   if (!colsum_out.has_value()) return;
   float* cs = colsum_out->data_ptr<float>();
@@ -1465,11 +1491,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ln_partial_blocks", &ln_partial_blocks);
   m.def("embed_fwd", &embed_fwd);
   m.def("embed_bwd", &embed_bwd);
-  m.def("attn_fwd", &attn_fwd);
+  m.def("attn_fwd", &attn_fwd, py::arg("qkv"), py::arg("out"), py::arg("lse"), py::arg("lens"), py::arg("B"),
+        py::arg("S"), py::arg("H"), py::arg("scale"), py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("site") = 0,
+        py::arg("rank") = 0);
   m.def("attn_bwd", &attn_bwd, py::arg("qkv"), py::arg("out"), py::arg("dout"), py::arg("lse"), py::arg("delta"),
         py::arg("lens"), py::arg("dqkv"), py::arg("B"), py::arg("S"), py::arg("H"), py::arg("scale"),
         py::arg("colsum_out") = py::none(), py::arg("colsum_accumulate") = false, py::arg("q8_y") = py::none(),
-        py::arg("q8_yt") = py::none(), py::arg("q8_scale") = py::none(), py::arg("q8_amax") = py::none());
+        py::arg("q8_yt") = py::none(), py::arg("q8_scale") = py::none(), py::arg("q8_amax") = py::none(),
+        py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("site") = 0, py::arg("rank") = 0);
   py::class_<PyComm>(m, "Communicator")
       .def(py::init<py::bytes, int, int, int>(), py::arg("unique_id"), py::arg("nranks"), py::arg("rank"),
            py::arg("device"))

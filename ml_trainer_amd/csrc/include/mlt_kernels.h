@@ -306,8 +306,10 @@ void launch_embed_fwd(const int64_t* ids, const int64_t* tt, const uint16_t* Ww,
 void launch_embed_bwd(const int64_t* sid, const int64_t* perm, const int64_t* tt, const uint16_t* DX, float* gw,
                       float* gp, float* gt, float* part, int64_t rows, int S, int D, int64_t vocab, int ntype,
                       hipStream_t st);
+// ad (attention-probability dropout, mlt_philox.h): thr8 > 0 launches the dropout instantiations of
+// the forward and the two ring backward kernels; thr8 == 0 the plain ones
 void launch_attn_fwd(const uint16_t* qkv, uint16_t* out, float* lse, const int* lens, int B, int S, int H,
-                     float scale, hipStream_t st);
+                     float scale, hipStream_t st, const AttnDropArgs& ad = AttnDropArgs{});
 // colpart_q [B * ceil(S/64)][D] and colpart_kv [B * ceil(S/64)][2D] (or nullptr): bias-gradient
 // column partials of dQ and dK|dV; returns whether they were written (ring kernels) and the
 // number of partial rows in rows_q / rows_kv
@@ -325,6 +327,6 @@ struct AttnQ8 {
 bool launch_attn_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse, float* delta,
                      const int* lens, uint16_t* dqkv, int B, int S, int H, float scale, hipStream_t st,
                      float* colpart_q = nullptr, float* colpart_kv = nullptr, int* rows_q = nullptr,
-                     int* rows_kv = nullptr, const AttnQ8& q8 = AttnQ8{});
+                     int* rows_kv = nullptr, const AttnQ8& q8 = AttnQ8{}, const AttnDropArgs& ad = AttnDropArgs{});
 
 }  // namespace mlt

@@ -52,4 +52,35 @@ MLT_HD Philox4 drop_words(uint64_t vec, const DropArgs& d) {
   return philox4x32_10((uint32_t)vec, (uint32_t)(vec >> 32), d.site, d.rank, d.seed_lo, d.seed_hi);
 }
 
+// Attention-probability dropout (the flash attention kernels): one BYTE per element, one call per
+// 4 x 4 tile of (query, key). With T = ceil(S / 4) and
+//   vec = ((b * H + h) * T + (q >> 2)) * T + (k >> 2),
+// element (b, h, q, k) takes byte (k & 3) (little-endian) of word (q & 3) of drop_words(vec) at
+// site 0x40000000 + layer, and is kept iff byte >= thr8, thr8 = round(p * 256). The probability
+// applied is p_eff = thr8 / 256 and kept probabilities are scaled by 1 / (1 - p_eff).
+struct AttnDropArgs {
+  uint32_t thr8 = 0;  // keep iff byte >= thr8; 0 = no dropout (the plain kernels are launched)
+  float scale = 1.f;  // 1 / (1 - thr8 / 256), rounded once from double
+  uint32_t seed_lo = 0, seed_hi = 0;
+  uint32_t site = 0, rank = 0;
+  uint32_t T = 0;     // ceil(S / 4): tiles per row of the S x S matrix
+};
+
+// index of the first tile (key tile 0) of tile row qt = q >> 2 of (batch * H + head) bh
+MLT_HD uint64_t attn_drop_row(const AttnDropArgs& a, uint32_t bh, uint32_t qt) {
+  return ((uint64_t)bh * a.T + qt) * a.T;
+}
+
+// the four words of tile `vec`: word j = query 4 qt + j, its byte c = key 4 kt + c
+MLT_HD Philox4 attn_drop_words(uint64_t vec, const AttnDropArgs& a) {
+  return philox4x32_10((uint32_t)vec, (uint32_t)(vec >> 32), a.site, a.rank, a.seed_lo, a.seed_hi);
+}
+
+// the element rule
+MLT_HD bool attn_drop_keep(const AttnDropArgs& a, uint32_t bh, uint32_t q, uint32_t k) {
+  const Philox4 w = attn_drop_words(attn_drop_row(a, bh, q >> 2) + (k >> 2), a);
+  const uint32_t word = (q & 3) == 0 ? w.x : (q & 3) == 1 ? w.y : (q & 3) == 2 ? w.z : w.w;
+  return ((word >> (8 * (k & 3))) & 0xFFu) >= a.thr8;
+}
+
 }  // namespace mlt

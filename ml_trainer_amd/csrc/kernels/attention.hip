@@ -20,6 +20,8 @@
 //     accumulators in registers across the whole query loop;
 //   dQ: block = 64 queries, swapped like the forward (queries on lanes): S^T = K Q^T,
 //     dP^T = V dO^T, dS^T lane-local, dQ^T += K^T dS^T with dS^T fed from registers.
+// Attention-probability dropout runs inside the forward and the two ring backward kernels (their
+// DROP instantiations; the mask is recomputed from a Philox counter, never stored: see below).
 // Global->LDS staging of the next tile is register-staged (loads issued before the MFMA work
 // of the current tile, LDS writes after it), so HBM latency overlaps the math.
 #include <cstdlib>
@@ -161,6 +163,68 @@ __device__ __forceinline__ void store_tile_v(uint8_t* lds, const u32x4 (&t)[2]) 
 }
 
 // ---------------------------------------------------------------------------
+// Attention-probability dropout (DROP = true instantiations; the element rule is mlt_philox.h's
+// attn_drop_keep). One Philox call serves a 4 x 4 tile of (query, key). In every kernel here a lane
+// holds, per 16-row MFMA tile t of a 64 x 64 block pair, one column c = 16 * wave + i and the rows
+// 16 t + 4 g + r, r = 0..3, so the four lanes of a quad (same g, same i >> 2, i & 3 = 0..3) need
+// the same four mask tiles t = 0..3: lane j of the quad computes tile t = j and a 4 x 4 transpose
+// across the quad (DPP quad_perm, no LDS) hands every lane its share -- one call per 16 scores.
+// Both functions return m[t] with byte r = the random byte of (row 16 t + 4 g + r, this lane's column).
+// (Every lane evaluating its four tiles itself, 4x the Philox work, measured 0.94 -> 1.46 ms forward
+// and 2.72 -> 3.34 ms backward at B512 S512 H12: profiles/attn_dropout/attn_bench_b512_s512.jsonl.)
+// ---------------------------------------------------------------------------
+
+// w[c] of quad lane j <- w[j] of quad lane c (two butterfly stages: lane ^ 1, lane ^ 2)
+__device__ __forceinline__ void quad_transpose4(uint32_t (&w)[4]) {
+  const bool b0 = threadIdx.x & 1, b1 = threadIdx.x & 2;
+#pragma unroll
+  for (int c = 0; c < 4; c += 2) {  // pairs (0, 1), (2, 3) with lane ^ 1
+    const uint32_t a = w[c], b = w[c + 1];
+    const uint32_t recv = (uint32_t)__builtin_amdgcn_mov_dpp((int)(b0 ? a : b), 0xB1, 0xF, 0xF, false);
+    w[c] = b0 ? recv : a;
+    w[c + 1] = b0 ? b : recv;
+  }
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {  // pairs (0, 2), (1, 3) with lane ^ 2
+    const uint32_t a = w[c], b = w[c + 2];
+    const uint32_t recv = (uint32_t)__builtin_amdgcn_mov_dpp((int)(b1 ? a : b), 0x4E, 0xF, 0xF, false);
+    w[c] = b1 ? recv : a;
+    w[c + 2] = b1 ? b : recv;
+  }
+}
+
+// queries on lanes (forward, dQ): rows = keys. `row` = attn_drop_row of this lane's query tile,
+// kt0 = first key tile of the 64-key block; tile t is key tile kt0 + 4 t + g, and the lane wants
+// word (i & 3) of it (its query), whose bytes are the keys 4 g + r.
+__device__ __forceinline__ void attn_drop_bytes_q(const AttnDropArgs& ad, uint64_t row, uint32_t kt0,
+                                                  uint32_t (&m)[4]) {
+  const uint32_t lane = threadIdx.x & 63, g = lane >> 4, j = lane & 3;
+  const Philox4 w = attn_drop_words(row + kt0 + 4 * j + g, ad);
+  m[0] = w.x, m[1] = w.y, m[2] = w.z, m[3] = w.w;
+  quad_transpose4(m);
+}
+
+// keys on lanes (dK/dV): rows = queries. `col` = bh * T * T + this lane's key tile, qt0 = first
+// query tile of the 64-query block; tile t is query tile qt0 + 4 t + g, and the lane wants byte
+// (i & 3) (its key) of each of the four words (the queries 4 g + r).
+__device__ __forceinline__ uint32_t attn_drop_byte_of_words(const Philox4& w, uint32_t j) {
+  const uint32_t sh = 8 * j;
+  return ((w.x >> sh) & 0xFFu) | (((w.y >> sh) & 0xFFu) << 8) | (((w.z >> sh) & 0xFFu) << 16) |
+         (((w.w >> sh) & 0xFFu) << 24);
+}
+__device__ __forceinline__ void attn_drop_bytes_k(const AttnDropArgs& ad, uint64_t col, uint32_t qt0,
+                                                  uint32_t (&m)[4]) {
+  const uint32_t lane = threadIdx.x & 63, g = lane >> 4, j = lane & 3;
+  const Philox4 w = attn_drop_words(col + (uint64_t)(qt0 + 4 * j + g) * ad.T, ad);
+#pragma unroll
+  for (uint32_t c = 0; c < 4; ++c) m[c] = attn_drop_byte_of_words(w, c);
+  quad_transpose4(m);
+}
+__device__ __forceinline__ bool attn_drop_kept(uint32_t m, int r, uint32_t thr8) {
+  return ((m >> (8 * r)) & 0xFFu) >= thr8;
+}
+
+// ---------------------------------------------------------------------------
 // forward: NQ 16-query groups per wave (the K / V^T fragments read from LDS feed NQ MFMAs).
 // The softmax side bounded the first version of this kernel (per 64-key block a wave issued 16
 // MFMAs = 256 MFMA cycles against ~150 VALU instructions = ~600 issue cycles); it is cut to ~3.5
@@ -178,11 +242,14 @@ __device__ __forceinline__ void store_tile_v(uint8_t* lds, const u32x4 (&t)[2]) 
 // ---------------------------------------------------------------------------
 constexpr float kFwdDeferThr = 8.f;
 
-template <int NQ>
+// DROP: attention-probability dropout. l, the running max and the saved LSE come from the undropped
+// P (the all-ones MFMA takes the undropped pack); the P.V product takes a second pack with the
+// dropped entries zeroed, and 1 / (1 - p_eff) folds into the final 1 / l.
+template <int NQ, bool DROP>
 __global__ __launch_bounds__(256) void attn_fwd_lean_kernel(const uint16_t* __restrict__ qkv,
                                                             uint16_t* __restrict__ out, float* __restrict__ lse,
                                                             const int* __restrict__ lens, int S, int H,
-                                                            float scale) {
+                                                            float scale, AttnDropArgs ad) {
   __shared__ __attribute__((aligned(16))) uint8_t Ks[2][AB * 128];
   __shared__ __attribute__((aligned(16))) uint8_t Vs[2][AB * 128];
   int qb, h, b;
@@ -202,6 +269,11 @@ __global__ __launch_bounds__(256) void attn_fwd_lean_kernel(const uint16_t* __re
     for (int kh = 0; kh < 2; ++kh)
       qf[n][kh] = q[n] < S ? *reinterpret_cast<const bf16x8*>(qkv + (base + q[n]) * ld + h * AH + kh * 32 + 8 * g)
                            : bf16x8{};
+  }
+  uint64_t drow[NQ];  // DROP: first mask tile of each query's tile row
+  if constexpr (DROP) {
+#pragma unroll
+    for (int n = 0; n < NQ; ++n) drow[n] = attn_drop_row(ad, (uint32_t)(b * H + h), (uint32_t)q[n] >> 2);
   }
   f32x4 o[NQ][4], lacc[NQ];
   float m[NQ];
@@ -291,6 +363,11 @@ __global__ __launch_bounds__(256) void attn_fwd_lean_kernel(const uint16_t* __re
 #pragma unroll
         for (int r = 0; r < 4; ++r) s[n][kt][r] = fast_exp2(fmaf(s[n][kt][r], sl2, nm));
     }
+    uint32_t dm[NQ][4];  // DROP: random bytes of this block's scores, dm[n][kt] byte r
+    if constexpr (DROP) {
+#pragma unroll
+      for (int n = 0; n < NQ; ++n) attn_drop_bytes_q(ad, drow[n], (uint32_t)kb * (AB / 4), dm[n]);
+    }
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
       bf16x8 pb[NQ];
@@ -298,6 +375,13 @@ __global__ __launch_bounds__(256) void attn_fwd_lean_kernel(const uint16_t* __re
       for (int n = 0; n < NQ; ++n) {
         pb[n] = pack_acc(s[n][2 * ks], s[n][2 * ks + 1]);
         lacc[n] = mfma(ones, pb[n], lacc[n]);  // row sums of P on the MFMA pipe
+        if constexpr (DROP) {  // the P.V operand: dropped entries zeroed
+#pragma unroll
+          for (int t = 2 * ks; t < 2 * ks + 2; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) s[n][t][r] = attn_drop_kept(dm[n][t], r, ad.thr8) ? s[n][t][r] : 0.f;
+          pb[n] = pack_acc(s[n][2 * ks], s[n][2 * ks + 1]);
+        }
       }
 #pragma unroll
       for (int d = 0; d < 4; ++d) {
@@ -317,7 +401,8 @@ __global__ __launch_bounds__(256) void attn_fwd_lean_kernel(const uint16_t* __re
   for (int n = 0; n < NQ; ++n) {
     if (q[n] < S) {
       const float l = lacc[n][0];
-      const float inv = l > 0.f ? 1.f / l : 0.f;
+      float inv = l > 0.f ? 1.f / l : 0.f;
+      if constexpr (DROP) inv *= ad.scale;
       uint16_t* op = out + (base + q[n]) * (int64_t)D + h * AH;
 #pragma unroll
       for (int d = 0; d < 4; ++d) {
@@ -837,14 +922,20 @@ __device__ __forceinline__ void attn_q8_epilogue(const AttnQ8& q8, const float (
 
 // FULLT: S % 64 == 0 (every ring stage a whole tile: the clamped-row copy path is compiled out, which
 // keeps the 2-group kernel within 256 VGPRs)
-template <int NK, bool FULLT>
+// DROP (attention-probability dropout, mask M, s = 1 / (1 - p_eff)): dV^T += dO^T (P o M) with s
+// applied once to the finished dV, and dS = P * (M s dP - delta) as in the dQ kernel. DROP is
+// instantiated for NK = 1 only: with 2 key groups the mask bytes, the separate delta operand and P
+// next to P o M do not fit the 256 VGPRs of __launch_bounds__(256, 2) (60 - 104 bytes of scratch per
+// lane whether the mask is held as bytes or as packed keep bits), so dropout runs 1 group per wave.
+template <int NK, bool FULLT, bool DROP>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_ring_kernel(const uint16_t* __restrict__ qkv,
                                                                  const uint16_t* __restrict__ dout,
                                                                  const float* __restrict__ lse,
                                                                  const float* __restrict__ delta,
                                                                  const int* __restrict__ lens,
                                                                  uint16_t* __restrict__ dqkv, int S, int H,
-                                                                 float scale, float* __restrict__ colpart, AttnQ8 q8) {
+                                                                 float scale, float* __restrict__ colpart, AttnQ8 q8,
+                                                                 AttnDropArgs ad) {
   constexpr int STAGE = 2 * kTile + 2 * AB * 4;  // Q tile, dO tile, lse[64], delta[64]
   __shared__ __attribute__((aligned(16))) uint8_t smem[kRing * STAGE];
   int kbk, h, b;
@@ -924,6 +1015,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_ring_kernel(const uint16
     sl2k[n] = key[n] < len ? sl2 : 0.f;
     kinf[n] = key[n] < len ? 0.f : INFINITY;
   }
+  // DROP: first mask tile of this (batch, head) (block-uniform; the lane adds its key tile key >> 2)
+  const uint64_t dbh = DROP ? (uint64_t)(uint32_t)(b * H + h) * ad.T * ad.T : 0;
   // the ring prologue goes out after the register loads above, so waiting for those is a
   // counted vmcnt that leaves the DMAs in flight
 #pragma unroll
@@ -952,6 +1045,12 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_ring_kernel(const uint16
     // choice is taken once outside the qt loop, so each path's qt iterations are ONE basic block in
     // which one tile's MFMAs interleave with the previous tile's exp / dS VALU work
     bf16x8 pbk[NK][2], sbk[NK][2];
+    uint32_t dm[NK][4];  // DROP: random bytes of this block's scores, dm[n][qt] byte r
+    if constexpr (DROP) {
+#pragma unroll
+      for (int n = 0; n < NK; ++n)
+        attn_drop_bytes_k(ad, dbh + ((uint32_t)key[n] >> 2), (uint32_t)qb * (AB / 4), dm[n]);
+    }
     auto qtiles = [&](auto pathc) __attribute__((always_inline)) {
       constexpr int PATH = decltype(pathc)::value;  // 0 all valid, 1 key mask, 2 key + query mask
       f32x4 pe[NK], dse[NK];  // the even qt of the current pair
@@ -964,7 +1063,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_ring_kernel(const uint16
 #pragma unroll
         for (int n = 0; n < NK; ++n) {
           sv[n] = f32x4{0.f, 0.f, 0.f, 0.f};
-          dp[n] = ndr;
+          if constexpr (DROP)
+            dp[n] = f32x4{0.f, 0.f, 0.f, 0.f};
+          else
+            dp[n] = ndr;
         }
 #pragma unroll
         for (int kh = 0; kh < 2; ++kh) {
@@ -992,8 +1094,14 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_ring_kernel(const uint16
               const bool ok = key[n] < len && q0 + ql < S;
               pv = fast_exp2(ok ? sv[n][r] * sl2 - lr[r] : -INFINITY);
             }
-            pc[n][r] = pv;
-            dsc[n][r] = pv * dp[n][r];
+            if constexpr (DROP) {
+              const bool keep = attn_drop_kept(dm[n][qt], r, ad.thr8);
+              pc[n][r] = keep ? pv : 0.f;
+              dsc[n][r] = pv * fmaf(keep ? ad.scale : 0.f, dp[n][r], ndr[r]);
+            } else {
+              pc[n][r] = pv;
+              dsc[n][r] = pv * dp[n][r];
+            }
           }
 #pragma unroll
         for (int n = 0; n < NK; ++n) {
@@ -1038,6 +1146,12 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_ring_kernel(const uint16
         }
       }
     }
+  }
+  if constexpr (DROP) {  // the kept probabilities' 1 / (1 - p_eff), once on the finished dV
+#pragma unroll
+    for (int n = 0; n < NK; ++n)
+#pragma unroll
+      for (int d = 0; d < 4; ++d) dv[n][d] *= ad.scale;
   }
   if (q8.y) {  // fp8 training: e5m2 dK | dV and their transposes instead of the bf16 dQKV
     float v[2][NK][4][4];
@@ -1099,7 +1213,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_ring_kernel(const uint16
 // The dQ ring kernel runs FIRST and computes delta = rowsum(dO * O) for its own queries in its
 // prologue (dO is in its registers anyway; O is one more 16-byte load per fragment), publishing it
 // for the dK/dV kernel that follows -- no separate delta pass over dO and O.
-template <int NQ, bool FULLT>
+// DROP (attention-probability dropout, mask M, s = 1 / (1 - p_eff)): delta = rowsum(dO * O) is still
+// right (O is the dropped output) and dS = P * (M s dP - delta), so dP starts at 0 instead of
+// -delta and one fma per score applies the mask, the scale and delta.
+template <int NQ, bool FULLT, bool DROP>
 __global__ __launch_bounds__(256) void attn_bwd_dq_ring_kernel(const uint16_t* __restrict__ qkv,
                                                                const uint16_t* __restrict__ dout,
                                                                const uint16_t* __restrict__ out,
@@ -1107,7 +1224,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_ring_kernel(const uint16_t* _
                                                                float* __restrict__ delta,
                                                                const int* __restrict__ lens,
                                                                uint16_t* __restrict__ dqkv, int S, int H, float scale,
-                                                               float* __restrict__ colpart, AttnQ8 q8) {
+                                                               float* __restrict__ colpart, AttnQ8 q8,
+                                                               AttnDropArgs ad) {
   constexpr int STAGE = 2 * kTile;  // K tile, V tile
   __shared__ __attribute__((aligned(16))) uint8_t smem[kRing * STAGE];
   int qb, h, b;
@@ -1181,6 +1299,11 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_ring_kernel(const uint16_t* _
 #pragma unroll
     for (int d = 0; d < 4; ++d) acc[n][d] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
+  uint64_t drow[NQ];  // DROP: first mask tile of each query's tile row
+  if constexpr (DROP) {
+#pragma unroll
+    for (int n = 0; n < NQ; ++n) drow[n] = attn_drop_row(ad, (uint32_t)(b * H + h), (uint32_t)q[n] >> 2);
+  }
 #pragma unroll
   for (int s0 = 0; s0 < kRing - 1; ++s0)
     if (s0 < nkb) issue(s0, s0);
@@ -1192,6 +1315,11 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_ring_kernel(const uint16_t* _
     const uint8_t* Vs = Ks + kTile;
     const bool kfull = (kb + 1) * AB <= len;
     f32x4 ds[NQ][4];
+    uint32_t dm[NQ][4];  // DROP: random bytes of this block's scores, dm[n][kt] byte r
+    if constexpr (DROP) {
+#pragma unroll
+      for (int n = 0; n < NQ; ++n) attn_drop_bytes_q(ad, drow[n], (uint32_t)kb * (AB / 4), dm[n]);
+    }
     // mask-path choice hoisted out of the kt loop (block-uniform): one basic block per path, so
     // MFMAs and the exp / dS VALU work of neighbouring kt tiles interleave (see the dK/dV kernel)
     auto ktiles = [&](auto fullc) __attribute__((always_inline)) {
@@ -1202,7 +1330,10 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_ring_kernel(const uint16_t* _
 #pragma unroll
         for (int n = 0; n < NQ; ++n) {  // dP accumulates onto -delta: dS = P * dP'
           sv[n] = f32x4{0.f, 0.f, 0.f, 0.f};
-          dp[n] = f32x4{-dl[n], -dl[n], -dl[n], -dl[n]};
+          if constexpr (DROP)
+            dp[n] = f32x4{0.f, 0.f, 0.f, 0.f};
+          else
+            dp[n] = f32x4{-dl[n], -dl[n], -dl[n], -dl[n]};
         }
 #pragma unroll
         for (int kh = 0; kh < 2; ++kh) {
@@ -1224,7 +1355,10 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_ring_kernel(const uint16_t* _
               const int key = kb * AB + kt * 16 + 4 * g + r;
               pv = fast_exp2(key < len ? sv[n][r] * sl2 - lq[n] : -INFINITY);
             }
-            ds[n][kt][r] = pv * dp[n][r];
+            if constexpr (DROP)
+              ds[n][kt][r] = pv * fmaf(attn_drop_kept(dm[n][kt], r, ad.thr8) ? ad.scale : 0.f, dp[n][r], -dl[n]);
+            else
+              ds[n][kt][r] = pv * dp[n][r];
           }
       }
     };
@@ -1304,18 +1438,29 @@ static int attn_groups(const char* env, int S, int dflt = 2) {
 }
 
 void launch_attn_fwd(const uint16_t* qkv, uint16_t* out, float* lse, const int* lens, int B, int S, int H,
-                     float scale, hipStream_t st) {
+                     float scale, hipStream_t st, const AttnDropArgs& ad) {
   if (B <= 0 || S <= 0) return;
   const unsigned g2 = (unsigned)((S + 127) / 128 * H * B), g1 = (unsigned)((S + 63) / 64 * H * B);
-  if (attn_groups("MLT_ATTN_FWD_GROUPS", S, 2) == 2)
-    hipLaunchKernelGGL(attn_fwd_lean_kernel<2>, dim3(g2), dim3(256), 0, st, qkv, out, lse, lens, S, H, scale);
+  const bool two = attn_groups("MLT_ATTN_FWD_GROUPS", S, 2) == 2;
+  auto launch = [&](auto dropc) {  // the dropout instantiations only when something is dropped
+    constexpr bool DR = decltype(dropc)::value;
+    if (two)
+      hipLaunchKernelGGL((attn_fwd_lean_kernel<2, DR>), dim3(g2), dim3(256), 0, st, qkv, out, lse, lens, S, H, scale,
+                         ad);
+    else
+      hipLaunchKernelGGL((attn_fwd_lean_kernel<1, DR>), dim3(g1), dim3(256), 0, st, qkv, out, lse, lens, S, H, scale,
+                         ad);
+  };
+  if (ad.thr8 > 0)
+    launch(std::true_type{});
   else
-    hipLaunchKernelGGL(attn_fwd_lean_kernel<1>, dim3(g1), dim3(256), 0, st, qkv, out, lse, lens, S, H, scale);
+    launch(std::false_type{});
 }
 
 bool launch_attn_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse, float* delta,
                      const int* lens, uint16_t* dqkv, int B, int S, int H, float scale, hipStream_t st,
-                     float* colpart_q, float* colpart_kv, int* rows_q, int* rows_kv, const AttnQ8& q8) {
+                     float* colpart_q, float* colpart_kv, int* rows_q, int* rows_kv, const AttnQ8& q8,
+                     const AttnDropArgs& ad) {
   // MLT_ATTN_RING: unset or 4 = the ring kernels, 0 = the register-staged kernels. Those stay in the
   // tree as the bit-for-bit oracle of the ring kernels' test; any other value is an error.
   const char* rv = getenv("MLT_ATTN_RING");
@@ -1327,32 +1472,48 @@ bool launch_attn_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* d
   const int64_t pairs = (int64_t)B * S * H;
   const dim3 g2((S + 127) / 128 * H * B), g1((S + 63) / 64 * H * B);
   if (ring) {
-    const bool k2 = attn_groups("MLT_ATTN_DKDV_GROUPS", S, 2) == 2, q2 = attn_groups("MLT_ATTN_DQ_GROUPS", S) == 2;
-    auto launch = [&](auto fullt) {
-      constexpr bool FL = decltype(fullt)::value;
+    const bool drop = ad.thr8 > 0;  // the dropout instantiations only when something is dropped
+    // (dK/dV under dropout: 1 key group per wave, the 2-group instantiation would spill)
+    const bool k2 = !drop && attn_groups("MLT_ATTN_DKDV_GROUPS", S, 2) == 2;
+    const bool q2 = attn_groups("MLT_ATTN_DQ_GROUPS", S) == 2;
+    auto launch = [&](auto fullt, auto dropc) {
+      constexpr bool FL = decltype(fullt)::value, DR = decltype(dropc)::value;
       if (q2)
-        hipLaunchKernelGGL((attn_bwd_dq_ring_kernel<2, FL>), g2, dim3(256), 0, st, qkv, dout, out, lse, delta, lens,
-                           dqkv, S, H, scale, colpart_q, q8);
+        hipLaunchKernelGGL((attn_bwd_dq_ring_kernel<2, FL, DR>), g2, dim3(256), 0, st, qkv, dout, out, lse, delta, lens,
+                           dqkv, S, H, scale, colpart_q, q8, ad);
       else
-        hipLaunchKernelGGL((attn_bwd_dq_ring_kernel<1, FL>), g1, dim3(256), 0, st, qkv, dout, out, lse, delta, lens,
-                           dqkv, S, H, scale, colpart_q, q8);
-      if (k2)
-        hipLaunchKernelGGL((attn_bwd_dkdv_ring_kernel<2, FL>), g2, dim3(256), 0, st, qkv, dout, lse, delta, lens,
-                           dqkv, S, H, scale, colpart_kv, q8);
-      else
-        hipLaunchKernelGGL((attn_bwd_dkdv_ring_kernel<1, FL>), g1, dim3(256), 0, st, qkv, dout, lse, delta, lens,
-                           dqkv, S, H, scale, colpart_kv, q8);
+        hipLaunchKernelGGL((attn_bwd_dq_ring_kernel<1, FL, DR>), g1, dim3(256), 0, st, qkv, dout, out, lse, delta, lens,
+                           dqkv, S, H, scale, colpart_q, q8, ad);
+      if constexpr (!DR) {
+        if (k2) {
+          hipLaunchKernelGGL((attn_bwd_dkdv_ring_kernel<2, FL, false>), g2, dim3(256), 0, st, qkv, dout, lse, delta,
+                             lens, dqkv, S, H, scale, colpart_kv, q8, ad);
+          return;
+        }
+      }
+      hipLaunchKernelGGL((attn_bwd_dkdv_ring_kernel<1, FL, DR>), g1, dim3(256), 0, st, qkv, dout, lse, delta, lens,
+                         dqkv, S, H, scale, colpart_kv, q8, ad);
     };
-    if (S % AB == 0)
-      launch(std::true_type{});
-    else
-      launch(std::false_type{});
+    if (S % AB == 0) {
+      if (drop)
+        launch(std::true_type{}, std::true_type{});
+      else
+        launch(std::true_type{}, std::false_type{});
+    } else {
+      if (drop)
+        launch(std::false_type{}, std::true_type{});
+      else
+        launch(std::false_type{}, std::false_type{});
+    }
     // partial rows actually written: B x (row blocks of the chosen group count)
     if (rows_kv) *rows_kv = B * ((S + (k2 ? 127 : 63)) / (k2 ? 128 : 64));
     if (rows_q) *rows_q = B * ((S + (q2 ? 127 : 63)) / (q2 ? 128 : 64));
     return colpart_q != nullptr && colpart_kv != nullptr;
   }
   if (q8.y) throw std::runtime_error("attn_bwd: the fp8 (q8) outputs need the ring kernels (MLT_ATTN_RING unset or 4)");
+  if (ad.thr8 > 0)
+    throw std::runtime_error("attn_bwd: attention dropout needs the ring kernels (MLT_ATTN_RING unset or 4); the "
+                             "register-staged kernels are dropout-free");
   hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((pairs + 15) / 16)), dim3(256), 0, st, dout, out, delta,
                      (int64_t)B * S, H);
   if (attn_groups("MLT_ATTN_DKDV_GROUPS", S, 1) == 2)

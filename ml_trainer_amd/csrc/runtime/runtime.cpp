@@ -43,7 +43,14 @@ PinnedPrefetcher::PinnedPrefetcher(size_t slot_bytes, int depth, int device)
     : slot_bytes_(slot_bytes), depth_(depth), device_(device) {
   if (depth < 1 || depth > 64) throw std::invalid_argument("PinnedPrefetcher depth must be in [1, 64]");
   hip_check(hipSetDevice(device), "hipSetDevice");
-  hip_check(hipStreamCreateWithFlags(&copy_stream_, hipStreamNonBlocking), "hipStreamCreate(copy)");
+  // The copy stream is made at the device's highest stream priority. The runtime keeps one pool of
+  // hardware queues per priority and, once a pool is full, puts a new stream on a queue that other
+  // streams already use. At the default priority that can be the compute stream's queue, depending on
+  // how many streams the process has made before (RCCL, graph capture, engines): the copy's
+  // wait-for-release then sits behind the compute kernels and nothing overlaps.
+  int prio_least = 0, prio_greatest = 0;
+  hip_check(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest), "hipDeviceGetStreamPriorityRange");
+  hip_check(hipStreamCreateWithPriority(&copy_stream_, hipStreamNonBlocking, prio_greatest), "hipStreamCreate(copy)");
   slots_.resize(depth, nullptr);
   events_.resize(depth, nullptr);
   released_.resize(depth, nullptr);

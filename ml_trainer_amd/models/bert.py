@@ -24,8 +24,15 @@ embedding site); the mask is a counter-based Philox stream recomputed in the bac
 is stored. One 62-bit seed per forward comes from torch's default CPU generator (no device sync,
 reproducible under ``torch.manual_seed``, saved and restored with the trainer's RNG state) or from
 ``dropout_seed=``; ``ops/dropout.py`` defines the mask and the site numbering, and the torch paths
-here apply the same masks. Not covered: attention-probability dropout (there is no
-``attention_dropout`` field) and the LeNet models (the reference model has no dropout).
+here apply the same masks.
+
+Attention-probability dropout (``BertConfig.attention_dropout``, default 0) drops softmax
+probabilities inside the flash attention kernels (forward, dQ, dK/dV): the S x S matrix is still
+never materialised and the mask is recomputed, never stored. It spends one random byte per
+probability, so the probability applied is ``p_eff = round(p * 256) / 256`` (0.1 -> 26/256 =
+0.1015625) and kept probabilities are scaled by ``1 / (1 - p_eff)``. It shares the forward's one
+seed with hidden dropout (sites ``0x40000000 + layer``) and is active in ``train()`` mode only.
+Not covered: the LeNet models (the reference model has no dropout).
 """
 from __future__ import annotations
 
@@ -52,6 +59,7 @@ class BertConfig:
     init_std: float = 0.02
     fp8: bool = False
     hidden_dropout: float = 0.0  # embedding / attention-output / FFN-output dropout (train() only)
+    attention_dropout: float = 0.0  # attention-probability dropout, applied as round(p * 256) / 256
     pad_id: Optional[int] = None  # when set, key lengths are derived from trailing pad tokens
 
 
@@ -82,23 +90,24 @@ class BertLayer(nn.Module):
         self.ffn2 = nn.Linear(c.intermediate, h)
         self.ln2 = nn.LayerNorm(h, eps=c.ln_eps)
 
-    def forward_native(self, x, lens, B, S, drop=None):
-        """``drop`` = (p, seed, site of the attention sub-layer, rank); the FFN takes the next site."""
+    def forward_native(self, x, lens, B, S, drop=None, attn_drop=None):
+        """``drop`` = (p, seed, site of the attention sub-layer, rank); the FFN takes the next site.
+        ``attn_drop`` = (p, seed, attention site of this layer, rank): attention-probability dropout."""
         from ml_trainer_amd.ops import transformer as T
         if self.c.fp8:
             from ml_trainer_amd.ops.fp8 import FP8 as impl
         else:
             impl = T.BF16
         x = T.attention_ln_block(x, self.qkv.weight, self.qkv.bias, self.out.weight, self.out.bias, self.ln1.weight,
-                                 self.ln1.bias, lens, B, S, self.c.heads, self.c.ln_eps, impl, drop)
+                                 self.ln1.bias, lens, B, S, self.c.heads, self.c.ln_eps, impl, drop, attn_drop)
         if drop is not None:
             drop = (drop[0], drop[1], drop[2] + 1, drop[3])
         return T.ffn_ln_block(x, self.ffn1.weight, self.ffn1.bias, self.ffn2.weight, self.ffn2.bias, self.ln2.weight,
                               self.ln2.bias, self.c.ln_eps, impl, drop)
 
-    def forward_reference(self, x, mask, B, S, drop=None):
-        """fp32 torch reference. x [B*S, h]; mask [B, S] bool (True = valid key); drop as in
-        forward_native (the same masks, through ops.dropout)."""
+    def forward_reference(self, x, mask, B, S, drop=None, attn_drop=None):
+        """fp32 torch reference. x [B*S, h]; mask [B, S] bool (True = valid key); drop and attn_drop
+        as in forward_native (the same masks, through ops.dropout)."""
         from ml_trainer_amd.ops import dropout as D
         c = self.c
         H, dh = c.heads, c.hidden // c.heads
@@ -107,7 +116,12 @@ class BertLayer(nn.Module):
         s = (q @ k.transpose(-1, -2)) / math.sqrt(dh)
         if mask is not None:
             s = s.masked_fill(~mask[:, None, None, :], float("-inf"))
-        ctx = (s.softmax(-1) @ v).permute(0, 2, 1, 3).reshape(B * S, c.hidden)
+        pr = s.softmax(-1)
+        if attn_drop is not None:
+            p, seed, site, rank = attn_drop
+            keep = D.attention_keep_mask(seed, site, rank, B, H, S, p, x.device)
+            pr = pr * keep * D.attention_scale(p)
+        ctx = (pr @ v).permute(0, 2, 1, 3).reshape(B * S, c.hidden)
         a = self.out(ctx)
         if drop is not None:
             a = D.apply(a, *drop)
@@ -126,6 +140,11 @@ class BertClassifier(nn.Module):
             raise ValueError("the native attention kernel needs head dim 64")
         if not 0.0 <= c.hidden_dropout < 1.0:
             raise ValueError(f"hidden_dropout must satisfy 0 <= p < 1, got {c.hidden_dropout}")
+        if not 0.0 <= c.attention_dropout < 1.0:
+            raise ValueError(f"attention_dropout must satisfy 0 <= p < 1, got {c.attention_dropout}")
+        if c.attention_dropout > 0:
+            from ml_trainer_amd.ops.dropout import attention_threshold
+            attention_threshold(c.attention_dropout)  # a p that rounds to 0/256 (or 256/256) is an error
         self.config = c
         self.last_dropout_seed = None  # the seed of the last forward that dropped
         self.word_embeddings = nn.Embedding(c.vocab_size, c.hidden)
@@ -157,28 +176,36 @@ class BertClassifier(nn.Module):
         return None
 
     def _dropout(self, dropout_seed=None):
-        """(p, seed, rank) of this forward when hidden dropout is active (train() mode and p > 0),
-        else None. Without ``dropout_seed`` one 62-bit seed is drawn from torch's default CPU
-        generator: no device sync, reproducible under torch.manual_seed / set_rng_state."""
-        p = self.config.hidden_dropout
-        if not (self.training and p > 0):
-            return None
+        """(hidden, attention) of this forward: each (p, seed, rank) when that dropout is active
+        (train() mode and its p > 0), else None. One seed serves both. Without ``dropout_seed`` one
+        62-bit seed is drawn from torch's default CPU generator when either is active: no device
+        sync, reproducible under torch.manual_seed / set_rng_state."""
+        ph, pa = self.config.hidden_dropout, self.config.attention_dropout
+        if not (self.training and (ph > 0 or pa > 0)):
+            return None, None
         if dropout_seed is None:
             dropout_seed = torch.randint(0, 2 ** 62, (), dtype=torch.int64)
         from ml_trainer_amd.ops.dropout import data_parallel_rank
         self.last_dropout_seed = int(dropout_seed)
-        return p, self.last_dropout_seed, data_parallel_rank()
+        rank = data_parallel_rank()
+        return ((ph, self.last_dropout_seed, rank) if ph > 0 else None,
+                (pa, self.last_dropout_seed, rank) if pa > 0 else None)
 
     @staticmethod
     def _site(drop, site):
         return None if drop is None else (drop[0], drop[1], site, drop[2])
+
+    @classmethod
+    def _attn_site(cls, adrop, l):
+        from ml_trainer_amd.ops.dropout import attention_site
+        return cls._site(adrop, attention_site(l))
 
     def forward(self, input_ids, attention_mask=None, token_type_ids=None, dropout_seed=None):
         if isinstance(input_ids, (tuple, list)):
             input_ids, attention_mask = input_ids[0], input_ids[1] if len(input_ids) > 1 else None
         B, S = input_ids.shape
         lens = self._lengths(input_ids, attention_mask)
-        drop = self._dropout(dropout_seed)
+        drop, adrop = self._dropout(dropout_seed)
         if input_ids.is_cuda:
             from ml_trainer_amd.ops import transformer as T
             if self.config.fp8 and torch.is_grad_enabled():
@@ -190,18 +217,18 @@ class BertClassifier(nn.Module):
             if drop is not None:
                 x = T.dropout(x, *self._site(drop, 0))
             for l, layer in enumerate(self.layers):
-                x = layer.forward_native(x, lens, B, S, self._site(drop, 1 + 2 * l))
+                x = layer.forward_native(x, lens, B, S, self._site(drop, 1 + 2 * l), self._attn_site(adrop, l))
             cls = x.view(B, S, -1)[:, 0]  # strided row view: the pooler GEMM reads it in place
             if cls.shape[1] % 8 == 0 and self.pooler.weight.shape[0] % 8 == 0:
                 return T.classifier_head(cls, self.pooler.weight, self.pooler.bias, self.classifier.weight,
                                          self.classifier.bias)
             cls = cls.float()
         else:
-            cls = self.forward_reference_hidden(input_ids, lens, token_type_ids, drop)
+            cls = self.forward_reference_hidden(input_ids, lens, token_type_ids, drop, adrop)
         pooled = torch.tanh(self.pooler(cls))
         return self.classifier(pooled)
 
-    def forward_reference_hidden(self, input_ids, lens=None, token_type_ids=None, drop=None):
+    def forward_reference_hidden(self, input_ids, lens=None, token_type_ids=None, drop=None, adrop=None):
         B, S = input_ids.shape
         pos = torch.arange(S, device=input_ids.device)
         tt = token_type_ids if token_type_ids is not None else torch.zeros_like(input_ids)
@@ -214,22 +241,23 @@ class BertClassifier(nn.Module):
         if lens is not None:
             mask = torch.arange(S, device=input_ids.device)[None, :] < lens.to(input_ids.device)[:, None]
         for l, layer in enumerate(self.layers):
-            x = layer.forward_reference(x, mask, B, S, self._site(drop, 1 + 2 * l))
+            x = layer.forward_reference(x, mask, B, S, self._site(drop, 1 + 2 * l), self._attn_site(adrop, l))
         return x.view(B, S, -1)[:, 0]
 
     def forward_reference(self, input_ids, attention_mask=None, token_type_ids=None, dropout_seed=None):
         lens = self._lengths(input_ids, attention_mask)
-        cls = self.forward_reference_hidden(input_ids, lens, token_type_ids, self._dropout(dropout_seed))
+        cls = self.forward_reference_hidden(input_ids, lens, token_type_ids, *self._dropout(dropout_seed))
         return self.classifier(torch.tanh(self.pooler(cls)))
 
     def forward_torch_bf16(self, input_ids, attention_mask=None, token_type_ids=None, dropout_seed=None):
         """PyTorch-eager bf16 path on the same weights (torch.autocast + SDPA + hipBLASLt): the
         baseline the native kernels are benchmarked and error-budgeted against. Hidden dropout
         uses the native path's masks (ops.dropout), each applied in the dtype autocast gives the
-        tensor it drops."""
+        tensor it drops. With attention dropout active the attention is computed explicitly under
+        autocast (softmax -> * keep * scale -> @ v) instead of through SDPA, which cannot take our mask."""
         from ml_trainer_amd.ops import dropout as D
         c = self.config
-        drop = self._dropout(dropout_seed)
+        drop, adrop = self._dropout(dropout_seed)
 
         def dropped(t, site):  # t [B, S, h]
             return t if drop is None else D.apply(t.reshape(B * S, -1), *self._site(drop, site)).view(B, S, -1)
@@ -246,7 +274,16 @@ class BertClassifier(nn.Module):
             x = dropped(self.emb_ln(x), 0)
             for l, L in enumerate(self.layers):
                 qkv = L.qkv(x).view(B, S, 3, c.heads, 64).permute(2, 0, 3, 1, 4)
-                ctx = F.scaled_dot_product_attention(qkv[0], qkv[1], qkv[2], attn_mask=mask)
+                if adrop is None:
+                    ctx = F.scaled_dot_product_attention(qkv[0], qkv[1], qkv[2], attn_mask=mask)
+                else:
+                    pa, seed, site, rank = self._attn_site(adrop, l)
+                    sc = (qkv[0] @ qkv[1].transpose(-1, -2)) / 8.0
+                    if mask is not None:
+                        sc = sc.masked_fill(~mask, float("-inf"))
+                    keep = D.attention_keep_mask(seed, site, rank, B, c.heads, S, pa, x.device)
+                    pr = sc.softmax(-1)
+                    ctx = (pr * keep * D.attention_scale(pa)).to(qkv[2].dtype) @ qkv[2]
                 x = L.ln1(dropped(L.out(ctx.transpose(1, 2).reshape(B, S, -1)), 1 + 2 * l) + x)
                 x = L.ln2(dropped(L.ffn2(F.gelu(L.ffn1(x))), 2 + 2 * l) + x)
             return self.classifier(torch.tanh(self.pooler(x[:, 0].float())))

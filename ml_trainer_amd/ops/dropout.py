@@ -11,6 +11,20 @@ scaled by ``1 / (1 - p)`` (computed in double, rounded once to fp32). Sites: 0 =
 (after its LayerNorm), ``1 + 2 l`` = attention sub-layer of layer ``l``, ``2 + 2 l`` = its FFN
 sub-layer. ``rank`` is the data-parallel rank, so ranks draw different masks from one seed.
 
+Attention-probability dropout (inside the flash attention kernels, attention.hip) has ``B*H*S*S``
+elements per layer, recomputed by three kernels, so it spends one BYTE per element and one Philox
+call per 4 x 4 tile of (query, key). With ``T = ceil(S / 4)`` and
+
+    vec = ((b * H + h) * T + (q >> 2)) * T + (k >> 2)
+
+element ``(b, h, q, k)`` takes byte ``k & 3`` (little-endian: ``>> 8 * (k & 3)``) of word ``q & 3`` of
+the same ``philox4x32-10(counter = (lo32(vec), hi32(vec), site, rank), key = seed words)`` and is kept
+iff ``byte >= thr8`` with ``thr8 = round(p * 256)``. The probability actually applied is ``p_eff =
+thr8 / 256`` (``p = 0.1`` -> ``26 / 256 = 0.1015625``) and kept probabilities are scaled by
+``1 / (1 - p_eff)`` (double, rounded once to fp32), so the expectation is exact for ``p_eff``. A ``p > 0``
+that rounds to ``thr8 == 0`` is an error, not a silent no-op. ``S`` need not be a multiple of 4 (edge
+tiles are partly used). Sites: ``attention_site(l) = 0x40000000 + l``, disjoint from the hidden sites.
+
 Everything here is int64 tensor arithmetic that runs on CPU and GPU tensors alike: the CPU model
 path trains with the same masks, and the GPU tests compare the kernels against it bit for bit.
 """
@@ -70,6 +84,53 @@ def keep_mask(seed: int, site: int, rank: int, rows: int, D: int, p: float, devi
     key = torch.tensor([seed & _MASK32, (seed >> 32) & _MASK32], dtype=torch.int64, device=device)
     words = philox4x32(counter, key).reshape(-1)[:n]
     return (words >= thr).view(rows, D)
+
+
+ATTENTION_SITE0 = 0x40000000  # attention-probability sites: ATTENTION_SITE0 + layer
+
+
+def attention_threshold(p: float) -> int:
+    """thr8 = round(p * 256) (halves up): an attention probability is kept iff its byte >= thr8."""
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"attention dropout probability must satisfy 0 <= p < 1, got {p}")
+    thr8 = int(p * 256.0 + 0.5)
+    if p > 0.0 and thr8 == 0:
+        raise ValueError(f"attention dropout probability {p} rounds to 0/256: no element would be dropped "
+                         "(the smallest effective p is 1/256)")
+    if thr8 >= 256:
+        raise ValueError(f"attention dropout probability {p} rounds to 256/256: every element dropped")
+    return thr8
+
+
+def attention_p(p: float) -> float:
+    """p_eff = thr8 / 256: the probability the byte rule actually applies for a requested ``p``."""
+    return attention_threshold(p) / 256.0
+
+
+def attention_scale(p: float) -> float:
+    """1 / (1 - p_eff) as the kernels apply it: computed in double, rounded once to fp32."""
+    return torch.tensor(1.0 / (1.0 - attention_p(p)), dtype=torch.float64).to(torch.float32).item()
+
+
+def attention_site(l: int) -> int:
+    """Dropout site of layer ``l``'s attention probabilities."""
+    return ATTENTION_SITE0 + l
+
+
+def attention_keep_mask(seed: int, site: int, rank: int, B: int, H: int, S: int, p: float,
+                        device=None) -> torch.Tensor:
+    """bool [B, H, S, S]: True where attention probability (b, h, q, k) survives dropout ``p``."""
+    thr8 = attention_threshold(p)
+    T = (S + 3) // 4
+    vec = torch.arange(B * H * T * T, dtype=torch.int64, device=device)
+    counter = torch.stack((vec & _MASK32, vec >> 32, torch.full_like(vec, site & _MASK32),
+                           torch.full_like(vec, rank & _MASK32)), dim=-1)
+    key = torch.tensor([seed & _MASK32, (seed >> 32) & _MASK32], dtype=torch.int64, device=device)
+    words = philox4x32(counter, key)  # [tiles, 4 queries]
+    shifts = torch.arange(4, dtype=torch.int64, device=device) * 8
+    byts = (words[..., None] >> shifts) & 0xFF  # [tiles, 4 queries, 4 keys]
+    keep = (byts >= thr8).view(B, H, T, T, 4, 4).permute(0, 1, 2, 4, 3, 5).reshape(B, H, 4 * T, 4 * T)
+    return keep[:, :, :S, :S]
 
 
 def apply(x: torch.Tensor, p: float, seed: int, site: int, rank: int) -> torch.Tensor:

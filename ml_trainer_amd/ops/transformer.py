@@ -20,6 +20,8 @@ Blocks (one autograd node each, so the backward can fuse across ops):
   apply hidden dropout to that linear's output: the LayerNorm forward kernel drops, adds the
   residual and normalises; the backward kernel also writes the masked, scaled dx (the linear's dY)
   and reduces the bias gradient from it. The mask is recomputed, never stored (ops/dropout.py).
+  With ``attn_drop`` the attention blocks drop attention probabilities inside the flash kernels
+  (forward, dQ, dK/dV), from a byte-per-element mask that is recomputed as well.
 * ``layer_norm``, ``embeddings``, ``dropout`` (the embedding site).
 
 The linear-layer arithmetic is pluggable (``impl``): ``BF16`` (bf16 operands) or
@@ -200,23 +202,34 @@ class _Grads:
         self.ready = []
 
 
-def _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl=BF16, residual=True):
+def _attn_drop_kw(attn_drop):
+    """Keyword arguments of C.attn_fwd / C.attn_bwd for ``attn_drop`` = (p, seed, site, rank) or None."""
+    if attn_drop is None:
+        return {}
+    p, seed, site, rank = attn_drop
+    return dict(p=p, seed=seed, site=site, rank=rank)
+
+
+def _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl=BF16, residual=True, attn_drop=None):
+    """``attn_drop`` = (p, seed, site, rank): attention-probability dropout inside the flash kernels
+    (the byte mask of ops/dropout.py, recomputed in the backward); None: no dropout."""
     C = require_native()
     qkv = impl.fwd(x, wqkv, bqkv)
     attn = torch.empty(B * S, H * 64, dtype=torch.bfloat16, device=x.device)
     lse = torch.empty(B * H * S, dtype=torch.float32, device=x.device)
-    C.attn_fwd(qkv, attn, lse, lens, B, S, H, _ATTN_SCALE)
+    C.attn_fwd(qkv, attn, lse, lens, B, S, H, _ATTN_SCALE, **_attn_drop_kw(attn_drop))
     # out-proj + bias + residual (under dropout the residual joins in the LayerNorm kernel instead)
     y = impl.fwd(attn, wo, bo, res=x if residual else None)
     return y, (x, qkv, attn, lse)
 
 
-def _attn_bwd(saved, params, lens, B, S, H, dy, G, dbo="colsum", impl=BF16, dres=None):
+def _attn_bwd(saved, params, lens, B, S, H, dy, G, dbo="colsum", impl=BF16, dres=None, attn_drop=None):
     """Backward of the attention block. ``dbo``: "colsum" to reduce dy here, otherwise the
     out-proj bias gradient already produced by the LayerNorm backward (tensor or None).
     ``dres``: the gradient of the residual branch when it differs from the out-proj's ``dy``
-    (hidden dropout sits between them); defaults to ``dy``."""
+    (hidden dropout sits between them); defaults to ``dy``. ``attn_drop``: the forward's."""
     C = require_native()
+    akw = _attn_drop_kw(attn_drop)
     x, qkv, attn, lse = saved
     wqkv, bqkv, wo, bo = params
     dres = dy if dres is None else dres
@@ -234,15 +247,15 @@ def _attn_bwd(saved, params, lens, B, S, H, dy, G, dbo="colsum", impl=BF16, dres
             # fp8: the kernels write dQKV as e5m2 + transpose + amax (no bf16 dQKV, no cast pass)
             d8, d8t, qs, qa = q8
             C.attn_bwd(qkv, attn, dattn, lse, delta, lens, dqkv, B, S, H, _ATTN_SCALE, colsum_out=db,
-                       colsum_accumulate=db_acc, q8_y=d8, q8_yt=d8t, q8_scale=qs, q8_amax=qa)
+                       colsum_accumulate=db_acc, q8_y=d8, q8_yt=d8t, q8_scale=qs, q8_amax=qa, **akw)
             impl.attn_dy_q_done(wqkv, d8, d8t)
             dqkv = d8
         else:
             C.attn_bwd(qkv, attn, dattn, lse, delta, lens, dqkv, B, S, H, _ATTN_SCALE, colsum_out=db,
-                       colsum_accumulate=db_acc)
+                       colsum_accumulate=db_acc, **akw)
         dwqkv = G.wgrad(wqkv, dqkv, x, impl)
     else:
-        C.attn_bwd(qkv, attn, dattn, lse, delta, lens, dqkv, B, S, H, _ATTN_SCALE)
+        C.attn_bwd(qkv, attn, dattn, lse, delta, lens, dqkv, B, S, H, _ATTN_SCALE, **akw)
         dwqkv, dbqkv = G.wgrad_bias(wqkv, bqkv, dqkv, x, impl)
     dx = impl.dgrad(dqkv, wqkv, torch.empty_like(x), res=dres)  # dx = dqkv . Wqkv + dres (residual)
     return dx, dwqkv, dbqkv, dwo, dbo
@@ -350,20 +363,20 @@ _ATTN_SCALE = 1.0 / 8.0  # 1/sqrt(head_dim = 64)
 
 class _AttentionBlock(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, wqkv, bqkv, wo, bo, lens, B, S, H, impl):
-        y, saved = _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl)
+    def forward(ctx, x, wqkv, bqkv, wo, bo, lens, B, S, H, impl, attn_drop=None):
+        y, saved = _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl, attn_drop=attn_drop)
         ctx.save_for_backward(*saved)
         ctx.params, ctx.impl = (wqkv, bqkv, wo, bo), impl
-        ctx.lens, ctx.dims = lens, (B, S, H)
+        ctx.lens, ctx.dims, ctx.attn_drop = lens, (B, S, H), attn_drop
         return y
 
     @staticmethod
     def backward(ctx, dy):
         G = _Grads()
         grads = _attn_bwd(ctx.saved_tensors, ctx.params, ctx.lens, *ctx.dims, dy.contiguous().to(torch.bfloat16), G,
-                          impl=ctx.impl)
+                          impl=ctx.impl, attn_drop=ctx.attn_drop)
         G.done()
-        return grads + (None, None, None, None, None)
+        return grads + (None, None, None, None, None, None)
 
 
 class _FFNBlock(torch.autograd.Function):
@@ -403,16 +416,16 @@ class _AttentionLNBlock(torch.autograd.Function):
     gradient (column sums of its dx), so no separate pass over dy."""
 
     @staticmethod
-    def forward(ctx, x, wqkv, bqkv, wo, bo, gamma, beta, lens, B, S, H, eps, impl, drop=None):
+    def forward(ctx, x, wqkv, bqkv, wo, bo, gamma, beta, lens, B, S, H, eps, impl, drop=None, attn_drop=None):
         if drop is None:
-            a, s1 = _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl)
+            a, s1 = _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl, attn_drop=attn_drop)
             y, s2 = _ln_fwd(a, gamma, beta, eps)
         else:  # LN(dropout(out-proj) + x): dropout and the residual add inside the LayerNorm kernel
-            a, s1 = _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl, residual=False)
+            a, s1 = _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl, residual=False, attn_drop=attn_drop)
             y, s2 = _dropout_add_ln_fwd(a, x, gamma, beta, eps, drop)
         ctx.save_for_backward(*s1, *s2)
         ctx.params, ctx.beta, ctx.impl = (wqkv, bqkv, wo, bo), beta, impl
-        ctx.lens, ctx.dims, ctx.drop = lens, (B, S, H), drop
+        ctx.lens, ctx.dims, ctx.drop, ctx.attn_drop = lens, (B, S, H), drop, attn_drop
         return y
 
     @staticmethod
@@ -427,9 +440,9 @@ class _AttentionLNBlock(torch.autograd.Function):
             dres, dg, db, dbo, da = _ln_bwd(t[4:], ctx.beta, dy.contiguous().to(torch.bfloat16), G,
                                             dxsum_param=ctx.params[3], drop=ctx.drop)
         dx, dwqkv, dbqkv, dwo, dbo = _attn_bwd(t[:4], ctx.params, ctx.lens, *ctx.dims, da, G, dbo=dbo,
-                                               impl=ctx.impl, dres=dres)
+                                               impl=ctx.impl, dres=dres, attn_drop=ctx.attn_drop)
         G.done()
-        return dx, dwqkv, dbqkv, dwo, dbo, dg, db, None, None, None, None, None, None, None
+        return dx, dwqkv, dbqkv, dwo, dbo, dg, db, None, None, None, None, None, None, None, None
 
 
 class _FFNLNBlock(torch.autograd.Function):
@@ -558,9 +571,12 @@ def _mark_training(impl) -> None:
         type(impl).training = torch.is_grad_enabled()
 
 
-def attention_block(x, wqkv, bqkv, wo, bo, lens: Optional[torch.Tensor], B: int, S: int, H: int, impl=BF16):
+def attention_block(x, wqkv, bqkv, wo, bo, lens: Optional[torch.Tensor], B: int, S: int, H: int, impl=BF16,
+                    attn_drop=None):
+    """``attn_drop`` = (p, seed, site, rank): attention-probability dropout inside the flash attention
+    kernels (the byte mask of ops/dropout.py: ``p`` is applied as round(p * 256) / 256). None: none."""
     _mark_training(impl)
-    return _AttentionBlock.apply(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl)
+    return _AttentionBlock.apply(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl, attn_drop)
 
 
 def ffn_block(x, w1, b1, w2, b2, impl=BF16):
@@ -569,11 +585,12 @@ def ffn_block(x, w1, b1, w2, b2, impl=BF16):
 
 
 def attention_ln_block(x, wqkv, bqkv, wo, bo, gamma, beta, lens: Optional[torch.Tensor], B: int, S: int, H: int,
-                       eps: float, impl=BF16, drop=None):
+                       eps: float, impl=BF16, drop=None, attn_drop=None):
     """``drop`` = (p, seed, site, rank): hidden dropout on the out-projection's output, before the
-    residual add, fused into the LayerNorm kernels (mask: ops/dropout.py). None: no dropout."""
+    residual add, fused into the LayerNorm kernels (mask: ops/dropout.py). None: no dropout.
+    ``attn_drop`` = (p, seed, site, rank): attention-probability dropout (see attention_block)."""
     _mark_training(impl)
-    return _AttentionLNBlock.apply(x, wqkv, bqkv, wo, bo, gamma, beta, lens, B, S, H, eps, impl, drop)
+    return _AttentionLNBlock.apply(x, wqkv, bqkv, wo, bo, gamma, beta, lens, B, S, H, eps, impl, drop, attn_drop)
 
 
 def ffn_ln_block(x, w1, b1, w2, b2, gamma, beta, eps: float, impl=BF16, drop=None):
