@@ -1,6 +1,9 @@
 """Fused attention throughput (fwd / bwd) vs torch SDPA on BERT shapes; one JSON line per case.
 ``--dropout P``: attention-probability dropout in the native kernels (applied as round(P * 256) / 256)
-next to ``F.scaled_dot_product_attention(dropout_p=P)``."""
+next to ``F.scaled_dot_product_attention(dropout_p=P)``.
+``--min-len L``: variable-length sequences (lengths uniform in [L, S], seeded) through the native kernels,
+as padded ``lens`` or, with ``--packed``, as one [T, 3D] matrix with ``cu_seqlens``; the SDPA columns stay
+the full-length run and the TFLOP/s count the full B x S x S work, so padded and packed compare by time."""
 import argparse
 import json
 import os
@@ -14,7 +17,10 @@ from ml_trainer_amd.ops._ext import require_native  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--dropout", type=float, default=0.0, help="attention-probability dropout (default 0.0)")
-P = ap.parse_args().dropout
+ap.add_argument("--min-len", type=int, default=0, help="variable-length sequences, lengths in [min-len, S]")
+ap.add_argument("--packed", action="store_true", help="packed rows + cu_seqlens instead of padded rows + lens")
+ARGS = ap.parse_args()
+P = ARGS.dropout
 DROP = dict(p=P, seed=0x123456789ABCDEF, site=0x40000000, rank=0) if P > 0 else {}
 C = require_native()
 dev = torch.device("cuda", 0)
@@ -36,12 +42,28 @@ def timeit(fn, iters=20):
 
 
 qkv = torch.randn(B * S, 3 * D, device=dev).to(torch.bfloat16)
-out = torch.empty(B * S, D, dtype=torch.bfloat16, device=dev)
-lse = torch.empty(B * H * S, device=dev)
 dout = torch.randn(B * S, D, device=dev).to(torch.bfloat16)
-dqkv = torch.empty_like(qkv)
-delta = torch.empty(B * S * H, device=dev)
-C.attn_fwd(qkv, out, lse, None, B, S, H, 0.125, **DROP)
+LENS, KW, TOK = None, dict(DROP), B * S
+if ARGS.packed and not ARGS.min_len:
+    ap.error("--packed needs --min-len")
+if ARGS.min_len:
+    ln = torch.randint(ARGS.min_len, S + 1, (B,), generator=torch.Generator().manual_seed(1))
+    TOK = int(ln.sum())
+    if ARGS.packed:
+        cu = torch.zeros(B + 1, dtype=torch.int32)
+        cu[1:] = ln.cumsum(0)
+        KW["cu_seqlens"] = cu.to(dev)
+        nq, nd = qkv[:TOK].contiguous(), dout[:TOK].contiguous()
+    else:
+        LENS = ln.to(torch.int32).to(dev)
+        nq, nd = qkv, dout
+else:
+    nq, nd = qkv, dout
+out = torch.empty(nq.shape[0], D, dtype=torch.bfloat16, device=dev)
+lse = torch.empty(B * H * S, device=dev)
+dqkv = torch.empty_like(nq)
+delta = torch.empty(nq.shape[0] * H, device=dev)
+C.attn_fwd(nq, out, lse, LENS, B, S, H, 0.125, **KW)
 q, k, v = qkv.view(B, S, 3, H, 64).permute(2, 0, 3, 1, 4)
 q, k, v = [t.contiguous().requires_grad_() for t in (q, k, v)]
 o = F.scaled_dot_product_attention(q, k, v, dropout_p=P)
@@ -49,12 +71,13 @@ go = dout.view(B, S, H, 64).transpose(1, 2).contiguous()
 fl_f = 4.0 * B * H * S * S * 64
 
 t = {
-    "native_fwd": timeit(lambda: C.attn_fwd(qkv, out, lse, None, B, S, H, 0.125, **DROP)),
-    "native_bwd": timeit(lambda: C.attn_bwd(qkv, out, dout, lse, delta, None, dqkv, B, S, H, 0.125, **DROP)),
+    "native_fwd": timeit(lambda: C.attn_fwd(nq, out, lse, LENS, B, S, H, 0.125, **KW)),
+    "native_bwd": timeit(lambda: C.attn_bwd(nq, out, nd, lse, delta, LENS, dqkv, B, S, H, 0.125, **KW)),
     "sdpa_fwd": timeit(lambda: F.scaled_dot_product_attention(q, k, v, dropout_p=P)),
     "sdpa_bwd": timeit(lambda: torch.autograd.grad(o, (q, k, v), go, retain_graph=True)),
 }
-rec = {"B": B, "S": S, "H": H, "dropout": P, **{k_: round(v_, 4) for k_, v_ in t.items()},
+rec = {"B": B, "S": S, "H": H, "dropout": P, "min_len": ARGS.min_len, "packed": ARGS.packed, "tokens": TOK,
+       "fill": round(TOK / (B * S), 4), **{k_: round(v_, 4) for k_, v_ in t.items()},
        "native_fwd_tflops": round(fl_f / t["native_fwd"] / 1e9, 1),
        "native_bwd_tflops": round(2.5 * fl_f / t["native_bwd"] / 1e9, 1),
        "sdpa_fwd_tflops": round(fl_f / t["sdpa_fwd"] / 1e9, 1),

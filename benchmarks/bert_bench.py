@@ -6,8 +6,11 @@ baseline of the same model (torch.autocast + SDPA + hipBLASLt) for comparison.
     python benchmarks/bert_bench.py --impl torch      # eager PyTorch baseline
     python benchmarks/bert_bench.py --impl native --dropout 0.1   # hidden dropout in the LayerNorm kernels
     python benchmarks/bert_bench.py --impl native --attention-dropout 0.1   # ... in the flash attention kernels
+    python benchmarks/bert_bench.py --impl native --min-len 64            # variable-length rows, right-padded
+    python benchmarks/bert_bench.py --impl native --min-len 64 --unpad    # ... run on the real tokens only
 
-Prints one JSON line per run (samples/s, tokens/s, ms/step, model TFLOP/s).
+Prints one JSON line per run (samples/s, tokens/s, ms/step, model TFLOP/s; ``tokens`` = the real
+tokens T of the batch, ``fill`` = T / (batch * seq), ``unpad``; tokens/s and TFLOP/s count batch * seq).
 Synthetic token ids, random-init weights (no network).
 """
 from __future__ import annotations
@@ -35,6 +38,10 @@ def run(args):
         over["hidden_dropout"] = args.dropout
     if args.attention_dropout:
         over["attention_dropout"] = args.attention_dropout
+    if args.unpad:
+        over["unpad"] = True
+    if args.min_len:
+        over["pad_id"] = 0
     cfg = bert_config(args.model, **over)
     m = BertClassifier(cfg).to(dev)
     if args.impl == "native":
@@ -44,6 +51,12 @@ def run(args):
         opt = torch.optim.AdamW(m.parameters(), lr=1e-4, weight_decay=0.01, fused=True)
         fwd = m.forward_torch_bf16
     ids = torch.randint(5, cfg.vocab_size, (args.batch, args.seq), device=dev)
+    real = args.batch * args.seq
+    if args.min_len:  # lengths uniform in [min_len, seq] from a seeded generator, right-padded with id 0
+        g = torch.Generator().manual_seed(1)
+        lens = torch.randint(args.min_len, args.seq + 1, (args.batch,), generator=g).to(dev)
+        ids[torch.arange(args.seq, device=dev)[None, :] >= lens[:, None]] = 0
+        real = int(lens.sum())
     y = torch.randint(0, cfg.num_labels, (args.batch,), device=dev)
 
     def step():
@@ -67,7 +80,8 @@ def run(args):
            "batch": args.batch, "seq": args.seq, "dropout": args.dropout,
            "attention_dropout": args.attention_dropout, "ms_per_step": dt * 1e3, "samples_per_s": args.batch / dt,
            "tokens_per_s": tokens / dt, "model_tflops": flops / dt / 1e12, "loss": float(loss.detach()),
-           "peak_mem_gb": torch.cuda.max_memory_allocated() / 2 ** 30}
+           "peak_mem_gb": torch.cuda.max_memory_allocated() / 2 ** 30,
+           "min_len": args.min_len, "tokens": real, "fill": real / tokens, "unpad": bool(args.unpad)}
     print(json.dumps(rec), flush=True)
     return rec
 
@@ -84,6 +98,9 @@ def main():
     ap.add_argument("--dropout", type=float, default=0.0, help="hidden dropout probability (default 0.0)")
     ap.add_argument("--attention-dropout", type=float, default=0.0,
                     help="attention-probability dropout, applied as round(p * 256) / 256 (default 0.0)")
+    ap.add_argument("--min-len", type=int, default=0,
+                    help="variable-length rows: lengths uniform in [min-len, seq], right-padded (default: full rows)")
+    ap.add_argument("--unpad", action="store_true", help="BertConfig.unpad: run the encoder on the real tokens only")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     recs = []

@@ -16,7 +16,9 @@ Extension flags (not in the reference): ``--model`` (default/tiny/bert-base/
 large), ``--synthetic``, ``--per_device_batch``, ``--no_engine``,
 ``--no_parallel``, ``--resume``, ``--amp bf16``, ``--precision bf16``, ``--metrics_jsonl``, ``--log_jsonl``, ``--zero_stage``, ``--async_checkpoint``,
 ``--dropout`` (BERT hidden dropout), ``--attention_dropout`` (BERT attention-probability dropout,
-inside the flash attention kernels; applied as round(p * 256) / 256).
+inside the flash attention kernels; applied as round(p * 256) / 256), ``--unpad`` (BERT: drop the pad
+tokens before the embeddings and run the encoder on the real tokens only), ``--min_seq_len L``
+(variable-length synthetic text, lengths uniform in [L, seq_len], right-padded with ``--pad_id``).
 """
 from __future__ import annotations
 
@@ -59,19 +61,28 @@ def build_datasets(args):
             SyntheticCIFAR10(max(n_train // 5, 1), train=False, transform=tf, seed=args.seed))
 
 
-def main(args):
+def build_model_and_datasets(args):
+    """(model, (train set, validation set)) of the parsed flags; flag combinations that make no sense raise."""
     import torch
     from ml_trainer_amd.models import build_model
-    from ml_trainer_amd.trainer import Trainer
     torch.manual_seed(args.seed)
     lenet = args.model in ("default", "tiny", "lenet")
     if lenet and args.dropout:
         raise ValueError("--dropout applies to the BERT models; the LeNet models have no dropout")
     if lenet and args.attention_dropout:
         raise ValueError("--attention_dropout applies to the BERT models; the LeNet models have no attention")
+    if lenet and args.unpad:
+        raise ValueError("--unpad applies to the BERT models; the LeNet models have no sequences to unpad")
+    if lenet and args.min_seq_len is not None:
+        raise ValueError("--min_seq_len applies to the synthetic text data of the BERT models")
     over = {"hidden_dropout": args.dropout} if args.dropout else {}
     if args.attention_dropout:
         over["attention_dropout"] = args.attention_dropout
+    if args.unpad:
+        over["unpad"] = True
+    pad_id = args.pad_id if args.pad_id is not None else (0 if args.min_seq_len is not None else None)
+    if pad_id is not None and not lenet:
+        over["pad_id"] = pad_id
     model = build_model(args.model, **over)
     if lenet:
         datasets = build_datasets(args)
@@ -80,10 +91,17 @@ def main(args):
         c = model.config
         seq = min(args.seq_len, c.max_position)
         n = args.synthetic_size or 4096
+        var = {} if args.min_seq_len is None else {"min_len": min(args.min_seq_len, seq), "pad_id": pad_id}
         datasets = (SyntheticTextClassification(n, seq_len=seq, vocab_size=c.vocab_size, num_labels=c.num_labels,
-                                                seed=args.seed, learnable=True),
+                                                seed=args.seed, learnable=True, **var),
                     SyntheticTextClassification(max(n // 8, 1), seq_len=seq, vocab_size=c.vocab_size,
-                                                num_labels=c.num_labels, seed=args.seed + 1, learnable=True))
+                                                num_labels=c.num_labels, seed=args.seed + 1, learnable=True, **var))
+    return model, datasets
+
+
+def main(args):
+    from ml_trainer_amd.trainer import Trainer
+    model, datasets = build_model_and_datasets(args)
     config = {
         "seed": args.seed,
         "scheduler": args.scheduler,
@@ -147,6 +165,16 @@ def build_parser() -> argparse.ArgumentParser:
                              "0.0). One random byte per probability: p is applied as p_eff = round(p * 256) / 256 "
                              "(0.1 -> 26/256 = 0.1015625), kept probabilities scaled by 1 / (1 - p_eff). An error "
                              "for the LeNet models")
+    parser.add_argument("--unpad", action="store_true",
+                        help="BERT: drop the pad tokens once, before the embeddings, and run the encoder on the real "
+                             "tokens only (needs lengths: --pad_id / --min_seq_len; one small device-to-host read "
+                             "per forward; not with the fp8 `large` model). An error for the LeNet models")
+    parser.add_argument("--min_seq_len", type=int, default=None,
+                        help="BERT synthetic data: variable-length rows, lengths uniform in [min_seq_len, seq_len], "
+                             "right-padded with --pad_id (default: fixed length)")
+    parser.add_argument("--pad_id", type=int, default=None,
+                        help="BERT: token id of the right padding (key lengths are derived from it); defaults to 0 "
+                             "when --min_seq_len is given")
     parser.add_argument("--synthetic", action="store_true", help="use the seeded synthetic dataset")
     parser.add_argument("--synthetic_size", type=int, default=0)
     parser.add_argument("--seq_len", type=int, default=512)

@@ -768,10 +768,21 @@ void ln_bwd(Tensor DY, Tensor X, Tensor gamma, Tensor mean, Tensor rstd, Tensor 
                 rows, (int)D, accumulate ? 1 : 0, dr, dxs, dxsum_acc ? 1 : 0, cur_stream());
 }
 
-void embed_fwd(Tensor ids, c10::optional<Tensor> tt, Tensor Ww, Tensor Wp, Tensor Wt, Tensor out, int64_t S) {
+// pos (packed batches): int32 [rows], the position of every token inside its own sequence (< S);
+// without it the batch is padded [B, S] and pos = row % S
+void embed_fwd(Tensor ids, c10::optional<Tensor> tt, Tensor Ww, Tensor Wp, Tensor Wt, Tensor out, int64_t S,
+               c10::optional<Tensor> pos) {
   const int64_t rows = ids.numel(), D = Ww.size(1);
   TORCH_CHECK(D % 256 == 0 && D <= 1024, "embedding width must be a multiple of 256 (<= 1024)");
-  TORCH_CHECK(S > 0 && rows % S == 0 && S <= Wp.size(0), "sequence length vs position table");
+  TORCH_CHECK(S > 0 && S <= Wp.size(0), "sequence length vs position table");
+  const int* pp = nullptr;
+  if (pos.has_value()) {
+    check_dev(*pos, "pos", at::kInt, rows, 4);
+    TORCH_CHECK(pos->numel() == rows, "embed_fwd: pos must have one entry per token");
+    pp = pos->data_ptr<int>();
+  } else {
+    TORCH_CHECK(rows % S == 0, "sequence length vs token count (padded batches are [B, S])");
+  }
   check_dev(ids, "ids", at::kLong, rows, 8);
   const int64_t* tp = nullptr;
   if (tt.has_value()) {
@@ -784,14 +795,26 @@ void embed_fwd(Tensor ids, c10::optional<Tensor> tt, Tensor Ww, Tensor Wp, Tenso
   TORCH_CHECK(Wt.size(0) <= 2, "at most 2 token types");
   check_bf16_2d(out, "out", rows, D);
   launch_embed_fwd(ids.data_ptr<int64_t>(), tp, bf16_ptr(Ww), bf16_ptr(Wp), bf16_ptr(Wt), (uint16_t*)out.data_ptr(),
-                   rows, (int)S, (int)D, Ww.size(0), (int)Wt.size(0), cur_stream());
+                   rows, (int)S, (int)D, Ww.size(0), (int)Wt.size(0), cur_stream(), pp);
 }
 
+// cu_seqlens (packed batches): int32 [B + 1] on the device, sequence b = rows cu[b] .. cu[b + 1] (each at
+// most S long, cu[B] <= rows); without it the batch is padded [B, S]
 void embed_bwd(Tensor sid, Tensor perm, c10::optional<Tensor> tt, Tensor DX, Tensor gw, Tensor gp, Tensor gt,
-               Tensor part, int64_t S) {
+               Tensor part, int64_t S, c10::optional<Tensor> cu_seqlens) {
   const int64_t rows = sid.numel(), D = gw.size(1);
   TORCH_CHECK(D % 256 == 0 && D <= 1024, "embedding width");
-  TORCH_CHECK(S > 0 && rows % S == 0 && S <= gp.size(0), "sequence length vs position table");
+  TORCH_CHECK(S > 0 && S <= gp.size(0), "sequence length vs position table");
+  const int* cu = nullptr;
+  int64_t Bc = 0;
+  if (cu_seqlens.has_value()) {
+    check_dev(*cu_seqlens, "cu_seqlens", at::kInt, 2, 4);
+    Bc = cu_seqlens->numel() - 1;
+    TORCH_CHECK(rows <= Bc * S && Bc <= 0x7fffffff, "embed_bwd: ", rows, " packed rows exceed B * S = ", Bc * S);
+    cu = cu_seqlens->data_ptr<int>();
+  } else {
+    TORCH_CHECK(rows % S == 0, "sequence length vs token count (padded batches are [B, S])");
+  }
   check_dev(sid, "sorted ids", at::kLong, rows, 8);
   check_dev(perm, "perm", at::kLong, rows, 8);
   const int64_t* tp = nullptr;
@@ -807,7 +830,7 @@ void embed_bwd(Tensor sid, Tensor perm, c10::optional<Tensor> tt, Tensor DX, Ten
   check_dev(part, "part", at::kFloat, S * 2 * D, 16);
   launch_embed_bwd(sid.data_ptr<int64_t>(), perm.data_ptr<int64_t>(), tp, bf16_ptr(DX), gw.data_ptr<float>(),
                    gp.data_ptr<float>(), gt.data_ptr<float>(), part.data_ptr<float>(), rows, (int)S, (int)D,
-                   gw.size(0), (int)gt.size(0), cur_stream());
+                   gw.size(0), (int)gt.size(0), cur_stream(), cu, (int)Bc);
 }
 
 static const int* lens_ptr(const c10::optional<Tensor>& lens, int64_t B) {
@@ -816,33 +839,56 @@ static const int* lens_ptr(const c10::optional<Tensor>& lens, int64_t B) {
   return lens->data_ptr<int>();
 }
 
+// Packed batches: cu_seqlens int32 [B + 1] on the device; returns the token-row count T the tensors must
+// agree on (qkv.numel() / 3D, at most B * S), or B * S for a padded batch. cu[B] <= T (rows past cu[B]
+// belong to no sequence and stay untouched) cannot be checked here without a device read: debug builds
+// check it in the kernels (MLT_DCHECK).
+static int64_t attn_rows(const c10::optional<Tensor>& cu, const Tensor& qkv, int64_t B, int64_t S, int64_t D,
+                         const int** cup) {
+  *cup = nullptr;
+  if (!cu.has_value()) return B * S;
+  check_dev(*cu, "cu_seqlens", at::kInt, B + 1, 4);
+  TORCH_CHECK(cu->numel() == B + 1, "cu_seqlens has ", cu->numel(), " elements, expected B + 1 = ", B + 1);
+  TORCH_CHECK(D > 0 && qkv.numel() % (3 * D) == 0, "qkv must be [T, 3 * H * 64]");
+  const int64_t T = qkv.numel() / (3 * D);
+  TORCH_CHECK(T <= B * S && T <= 0x7fffffff, "packed attention: ", T, " token rows exceed B * S = ", B * S);
+  *cup = cu->data_ptr<int>();
+  return T;
+}
+
 // p, seed, site, rank: attention-probability dropout inside the kernel (p == 0: none)
+// cu_seqlens: packed (unpadded) batch, see attn_rows; S is then max_seqlen and lens is unused
 void attn_fwd(Tensor qkv, Tensor out, Tensor lse, c10::optional<Tensor> lens, int64_t B, int64_t S, int64_t H,
-              double scale, double p, int64_t seed, int64_t site, int64_t rank) {
+              double scale, double p, int64_t seed, int64_t site, int64_t rank, c10::optional<Tensor> cu_seqlens) {
   const int64_t D = H * 64;
-  check_bf16_2d(qkv, "qkv", B * S, 3 * D);
-  check_bf16_2d(out, "out", B * S, D);
-  check_dev(lse, "lse", at::kFloat, B * H * S, 4);
   TORCH_CHECK(B > 0 && S > 0 && H > 0 && B <= 65535 && H <= 65535, "attention dims");
+  const int* cu = nullptr;
+  const int64_t T = attn_rows(cu_seqlens, qkv, B, S, D, &cu);
+  check_bf16_2d(qkv, "qkv", T, 3 * D);
+  check_bf16_2d(out, "out", T, D);
+  check_dev(lse, "lse", at::kFloat, B * H * S, 4);
   const AttnDropArgs ad = make_attn_drop_args(p, seed, site, rank, S);
-  launch_attn_fwd(bf16_ptr(qkv), (uint16_t*)out.data_ptr(), lse.data_ptr<float>(), lens_ptr(lens, B), (int)B, (int)S,
-                  (int)H, (float)scale, cur_stream(), ad);
+  launch_attn_fwd(bf16_ptr(qkv), (uint16_t*)out.data_ptr(), lse.data_ptr<float>(), cu ? nullptr : lens_ptr(lens, B),
+                  (int)B, (int)S, (int)H, (float)scale, cur_stream(), ad, cu, (int)T);
 }
 
 void attn_bwd(Tensor qkv, Tensor out, Tensor dout, Tensor lse, Tensor delta, c10::optional<Tensor> lens, Tensor dqkv,
               int64_t B, int64_t S, int64_t H, double scale, c10::optional<Tensor> colsum_out,
               bool colsum_accumulate, c10::optional<Tensor> q8_y, c10::optional<Tensor> q8_yt,
               c10::optional<Tensor> q8_scale, c10::optional<Tensor> q8_amax, double p, int64_t seed, int64_t site,
-              int64_t rank) {
+              int64_t rank, c10::optional<Tensor> cu_seqlens) {
   const int64_t D = H * 64;
-  const AttnDropArgs ad = make_attn_drop_args(p, seed, site, rank, S);  // the forward's (p, seed, site, rank)
-  check_bf16_2d(qkv, "qkv", B * S, 3 * D);
-  check_bf16_2d(out, "out", B * S, D);
-  check_bf16_2d(dout, "dout", B * S, D);
-  check_bf16_2d(dqkv, "dqkv", B * S, 3 * D);
-  check_dev(lse, "lse", at::kFloat, B * H * S, 4);
-  check_dev(delta, "delta", at::kFloat, B * H * S, 4);
   TORCH_CHECK(B > 0 && S > 0 && H > 0 && B <= 65535 && H <= 65535, "attention dims");
+  const AttnDropArgs ad = make_attn_drop_args(p, seed, site, rank, S);  // the forward's (p, seed, site, rank)
+  const int* cu = nullptr;
+  const int64_t T = attn_rows(cu_seqlens, qkv, B, S, D, &cu);
+  TORCH_CHECK(!cu || !q8_y.has_value(), "attn_bwd: the fp8 (q8) outputs take padded batches only, not cu_seqlens");
+  check_bf16_2d(qkv, "qkv", T, 3 * D);
+  check_bf16_2d(out, "out", T, D);
+  check_bf16_2d(dout, "dout", T, D);
+  check_bf16_2d(dqkv, "dqkv", T, 3 * D);
+  check_dev(lse, "lse", at::kFloat, B * H * S, 4);
+  check_dev(delta, "delta", at::kFloat, T * H, 4);
   Tensor pq, pkv;
   if (colsum_out.has_value()) {  // QKV bias gradient = column sums of dQKV, from the backward kernels
     check_dev(*colsum_out, "colsum_out", at::kFloat, 3 * D, 16);
@@ -871,10 +917,10 @@ void attn_bwd(Tensor qkv, Tensor out, Tensor dout, Tensor lse, Tensor delta, c10
   }
   int rq = 0, rkv = 0;
   const bool fused = launch_attn_bwd(bf16_ptr(qkv), bf16_ptr(out), bf16_ptr(dout), lse.data_ptr<float>(),
-                                     delta.data_ptr<float>(), lens_ptr(lens, B), (uint16_t*)dqkv.data_ptr(), (int)B,
-                                     (int)S, (int)H, (float)scale, cur_stream(),
+                                     delta.data_ptr<float>(), cu ? nullptr : lens_ptr(lens, B),
+                                     (uint16_t*)dqkv.data_ptr(), (int)B, (int)S, (int)H, (float)scale, cur_stream(),
                                      pq.defined() ? pq.data_ptr<float>() : nullptr,
-                                     pkv.defined() ? pkv.data_ptr<float>() : nullptr, &rq, &rkv, q8, ad);
+                                     pkv.defined() ? pkv.data_ptr<float>() : nullptr, &rq, &rkv, q8, ad, cu, (int)T);
   TORCH_CHECK(!q8.y || !colsum_out.has_value() || fused, "attn_bwd q8: column sums need the ring kernels");
   if (!colsum_out.has_value()) return;
   float* cs = colsum_out->data_ptr<float>();
@@ -885,9 +931,9 @@ void attn_bwd(Tensor qkv, Tensor out, Tensor dout, Tensor lse, Tensor delta, c10
     SegOut okv{{cs + D, cs + 2 * D, nullptr}};
     launch_reduce_rows(pkv.data_ptr<float>(), rkv, 2 * D, (int)(2 * D), (int)D, okv, acc ? 3 : 0, cur_stream());
   } else {
-    Tensor ws = at::empty({std::max<int64_t>(colsum_ws_floats((int)(B * S), (int)(3 * D)), 4)},
+    Tensor ws = at::empty({std::max<int64_t>(colsum_ws_floats((int)T, (int)(3 * D)), 4)},
                           qkv.options().dtype(at::kFloat));
-    launch_colsum_bf16((const uint16_t*)dqkv.data_ptr(), (int)(B * S), (int)(3 * D), dqkv.stride(0), cs, acc,
+    launch_colsum_bf16((const uint16_t*)dqkv.data_ptr(), (int)T, (int)(3 * D), dqkv.stride(0), cs, acc,
                        ws.data_ptr<float>(), cur_stream());
   }
 }
@@ -1489,16 +1535,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("Z"), py::arg("Y"), py::arg("mean"), py::arg("rstd"), py::arg("eps"), py::arg("p"), py::arg("seed"),
         py::arg("site"), py::arg("rank"));
   m.def("ln_partial_blocks", &ln_partial_blocks);
-  m.def("embed_fwd", &embed_fwd);
-  m.def("embed_bwd", &embed_bwd);
+  m.def("embed_fwd", &embed_fwd, py::arg("ids"), py::arg("tt"), py::arg("Ww"), py::arg("Wp"), py::arg("Wt"),
+        py::arg("out"), py::arg("S"), py::arg("pos") = py::none());
+  m.def("embed_bwd", &embed_bwd, py::arg("sid"), py::arg("perm"), py::arg("tt"), py::arg("DX"), py::arg("gw"),
+        py::arg("gp"), py::arg("gt"), py::arg("part"), py::arg("S"), py::arg("cu_seqlens") = py::none());
   m.def("attn_fwd", &attn_fwd, py::arg("qkv"), py::arg("out"), py::arg("lse"), py::arg("lens"), py::arg("B"),
         py::arg("S"), py::arg("H"), py::arg("scale"), py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("site") = 0,
-        py::arg("rank") = 0);
+        py::arg("rank") = 0, py::arg("cu_seqlens") = py::none());
   m.def("attn_bwd", &attn_bwd, py::arg("qkv"), py::arg("out"), py::arg("dout"), py::arg("lse"), py::arg("delta"),
         py::arg("lens"), py::arg("dqkv"), py::arg("B"), py::arg("S"), py::arg("H"), py::arg("scale"),
         py::arg("colsum_out") = py::none(), py::arg("colsum_accumulate") = false, py::arg("q8_y") = py::none(),
         py::arg("q8_yt") = py::none(), py::arg("q8_scale") = py::none(), py::arg("q8_amax") = py::none(),
-        py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("site") = 0, py::arg("rank") = 0);
+        py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("site") = 0, py::arg("rank") = 0,
+        py::arg("cu_seqlens") = py::none());
   py::class_<PyComm>(m, "Communicator")
       .def(py::init<py::bytes, int, int, int>(), py::arg("unique_id"), py::arg("nranks"), py::arg("rank"),
            py::arg("device"))

@@ -298,18 +298,25 @@ void launch_ln_bwd_dropout(const uint16_t* DY, const uint16_t* X, const float* g
                            hipStream_t st);
 // out = keep ? bf16(x * scale) : 0 over numel (% 8 == 0) contiguous bf16 elements (dropout.hip)
 void launch_dropout(const uint16_t* x, uint16_t* out, int64_t numel, DropArgs dr, hipStream_t st);
+// pos (packed batches, or nullptr): the position of every row, each < S; nullptr: row % S
 void launch_embed_fwd(const int64_t* ids, const int64_t* tt, const uint16_t* Ww, const uint16_t* Wp,
                       const uint16_t* Wt, uint16_t* out, int64_t rows, int S, int D, int64_t vocab, int ntype,
-                      hipStream_t st);
+                      hipStream_t st, const int* pos = nullptr);
 // sid / perm: the token ids sorted stably and the sorting permutation (deterministic, atomic-free
-// word-table scatter); part: S x 2D floats of per-position token-type partial sums
+// word-table scatter); part: S x 2D floats of per-position token-type partial sums. cu (packed
+// batches, or nullptr): cu_seqlens [B + 1], sequence b = rows cu[b] .. cu[b + 1], each at most S long
 void launch_embed_bwd(const int64_t* sid, const int64_t* perm, const int64_t* tt, const uint16_t* DX, float* gw,
                       float* gp, float* gt, float* part, int64_t rows, int S, int D, int64_t vocab, int ntype,
-                      hipStream_t st);
+                      hipStream_t st, const int* cu = nullptr, int B = 0);
+// cu (packed / unpadded mode, or nullptr): cu_seqlens [B + 1] on the device. qkv / out / dout / dqkv then
+// hold rows >= cu[B] token rows (sequence b at rows cu[b] .. cu[b + 1]; rows past cu[B] are untouched).
+// S is max_seqlen: it still sizes the grid, lse [B, H, S], the dropout tile stride and the column
+// partials. lens is unused. Ring kernels and bf16 outputs only.
 // ad (attention-probability dropout, mlt_philox.h): thr8 > 0 launches the dropout instantiations of
 // the forward and the two ring backward kernels; thr8 == 0 the plain ones
 void launch_attn_fwd(const uint16_t* qkv, uint16_t* out, float* lse, const int* lens, int B, int S, int H,
-                     float scale, hipStream_t st, const AttnDropArgs& ad = AttnDropArgs{});
+                     float scale, hipStream_t st, const AttnDropArgs& ad = AttnDropArgs{}, const int* cu = nullptr,
+                     int rows = 0);
 // colpart_q [B * ceil(S/64)][D] and colpart_kv [B * ceil(S/64)][2D] (or nullptr): bias-gradient
 // column partials of dQ and dK|dV; returns whether they were written (ring kernels) and the
 // number of partial rows in rows_q / rows_kv
@@ -327,6 +334,7 @@ struct AttnQ8 {
 bool launch_attn_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse, float* delta,
                      const int* lens, uint16_t* dqkv, int B, int S, int H, float scale, hipStream_t st,
                      float* colpart_q = nullptr, float* colpart_kv = nullptr, int* rows_q = nullptr,
-                     int* rows_kv = nullptr, const AttnQ8& q8 = AttnQ8{}, const AttnDropArgs& ad = AttnDropArgs{});
+                     int* rows_kv = nullptr, const AttnQ8& q8 = AttnQ8{}, const AttnDropArgs& ad = AttnDropArgs{},
+                     const int* cu = nullptr, int rows = 0);
 
 }  // namespace mlt

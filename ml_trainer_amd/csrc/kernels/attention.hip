@@ -128,6 +128,20 @@ __device__ __forceinline__ void block_coords(int S, int rows_per_block, int H, i
   MLT_DCHECK((int)gridDim.x % (nrb * H) == 0 && rb * rows_per_block < S);  // grid = B * H * row blocks
 }
 
+// Packed ("unpadded") instantiations (PACKED = true): the batch is one [T, 3D] matrix of the real tokens
+// and the `lens` argument carries cu_seqlens [B + 1] instead: sequence b is rows cu[b] .. cu[b + 1].
+// Everything that is a property of the sequence (loop bounds, key mask, row guards, clamped ring stages,
+// buffer-resource sizes) uses its own length Ss; the rows after it belong to the next sequence (or to
+// nobody), so no guard may use the launch-wide S. S (= max_seqlen, the width of the padded input) still
+// defines the grid, the dropout tile stride and the row-block numbering of the column partials, so a
+// packed run draws the mask bytes of the padded run. A block that starts at or past Ss returns before
+// its first load or barrier (block-uniform). Debug builds check cu against the row count (`rows` >=
+// cu[B]: the matrix may end in tail rows that belong to no sequence and are neither read nor written).
+__device__ __forceinline__ void packed_dcheck(const int* cu, int b, int S, int rows) {
+  (void)cu, (void)b, (void)S, (void)rows;
+  MLT_DCHECK(cu[b] >= 0 && cu[b + 1] >= cu[b] && cu[b + 1] - cu[b] <= S && cu[b + 1] <= rows);
+}
+
 // Register staging with buffer loads issued as inline asm. Through the builtins, hipcc's waitcnt
 // pass puts an s_waitcnt vmcnt(0) at the top of the K/V loop (in front of the first QK^T MFMA),
 // i.e. it waits for the next block's loads right after issuing them and the staging hides no
@@ -245,11 +259,11 @@ constexpr float kFwdDeferThr = 8.f;
 // DROP: attention-probability dropout. l, the running max and the saved LSE come from the undropped
 // P (the all-ones MFMA takes the undropped pack); the P.V product takes a second pack with the
 // dropped entries zeroed, and 1 / (1 - p_eff) folds into the final 1 / l.
-template <int NQ, bool DROP>
+template <int NQ, bool DROP, bool PACKED = false>
 __global__ __launch_bounds__(256) void attn_fwd_lean_kernel(const uint16_t* __restrict__ qkv,
                                                             uint16_t* __restrict__ out, float* __restrict__ lse,
                                                             const int* __restrict__ lens, int S, int H,
-                                                            float scale, AttnDropArgs ad) {
+                                                            float scale, AttnDropArgs ad, int rows) {
   __shared__ __attribute__((aligned(16))) uint8_t Ks[2][AB * 128];
   __shared__ __attribute__((aligned(16))) uint8_t Vs[2][AB * 128];
   int qb, h, b;
@@ -257,9 +271,14 @@ __global__ __launch_bounds__(256) void attn_fwd_lean_kernel(const uint16_t* __re
   const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, i = lane & 15;
   const int D = H * AH;
   const int64_t ld = 3 * (int64_t)D;
-  const int64_t base = (int64_t)b * S;
-  const int len = lens ? lens[b] : S;
+  const int64_t base = PACKED ? (int64_t)lens[b] : (int64_t)b * S;
+  const int Ss = PACKED ? lens[b + 1] - lens[b] : S;  // rows of this sequence (S: the launch-wide maximum)
+  const int len = PACKED ? Ss : (lens ? lens[b] : S);
+  if constexpr (PACKED) packed_dcheck(lens, b, S, rows);
   MLT_DCHECK(len >= 0 && len <= S);
+  if constexpr (PACKED) {
+    if (qb * (64 * NQ) >= Ss) return;  // no query of this sequence here (block-uniform)
+  }
   int q[NQ];
   bf16x8 qf[NQ][2];
 #pragma unroll
@@ -267,7 +286,7 @@ __global__ __launch_bounds__(256) void attn_fwd_lean_kernel(const uint16_t* __re
     q[n] = qb * (64 * NQ) + n * 64 + wid * 16 + i;
 #pragma unroll
     for (int kh = 0; kh < 2; ++kh)
-      qf[n][kh] = q[n] < S ? *reinterpret_cast<const bf16x8*>(qkv + (base + q[n]) * ld + h * AH + kh * 32 + 8 * g)
+      qf[n][kh] = q[n] < Ss ? *reinterpret_cast<const bf16x8*>(qkv + (base + q[n]) * ld + h * AH + kh * 32 + 8 * g)
                            : bf16x8{};
   }
   uint64_t drow[NQ];  // DROP: first mask tile of each query's tile row
@@ -298,8 +317,8 @@ __global__ __launch_bounds__(256) void attn_fwd_lean_kernel(const uint16_t* __re
     voff[t] = (int)(((int64_t)(e >> 3) * ld + D + h * AH + (e & 7) * 8) * 2);
   }
   if (nkb > 0) {
-    stage_tile(Ks[0], qkv, ld, base, min(AB, S), D + h * AH);
-    stage_tile(Vs[0], qkv, ld, base, min(AB, S), 2 * D + h * AH);
+    stage_tile(Ks[0], qkv, ld, base, min(AB, Ss), D + h * AH);
+    stage_tile(Vs[0], qkv, ld, base, min(AB, Ss), 2 * D + h * AH);
   }
   __syncthreads();
   // retire the Q fragment loads here, on every path into the loop: the waitcnt pass merges paths
@@ -309,9 +328,9 @@ __global__ __launch_bounds__(256) void attn_fwd_lean_kernel(const uint16_t* __re
   for (int kb = 0; kb < nkb; ++kb) {
     const int cur = kb & 1;
     const bool more = kb + 1 < nkb;
-    if (more) {  // next K / V block -> registers (rows >= S read as 0), LDS after the math
+    if (more) {  // next K / V block -> registers (rows >= Ss read as 0: num_records ends at the sequence), LDS after the math
       const int k1 = (kb + 1) * AB;
-      const i32x4 rs = buffer_rsrc(qkv + (base + k1) * ld, (int64_t)(S - k1) * ld * 2);
+      const i32x4 rs = buffer_rsrc(qkv + (base + k1) * ld, (int64_t)(Ss - k1) * ld * 2);
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         kr[t] = buffer_load_x4_asm(rs, voff[t]);
@@ -399,7 +418,7 @@ __global__ __launch_bounds__(256) void attn_fwd_lean_kernel(const uint16_t* __re
   }
 #pragma unroll
   for (int n = 0; n < NQ; ++n) {
-    if (q[n] < S) {
+    if (q[n] < Ss) {
       const float l = lacc[n][0];
       float inv = l > 0.f ? 1.f / l : 0.f;
       if constexpr (DROP) inv *= ad.scale;
@@ -927,7 +946,7 @@ __device__ __forceinline__ void attn_q8_epilogue(const AttnQ8& q8, const float (
 // instantiated for NK = 1 only: with 2 key groups the mask bytes, the separate delta operand and P
 // next to P o M do not fit the 256 VGPRs of __launch_bounds__(256, 2) (60 - 104 bytes of scratch per
 // lane whether the mask is held as bytes or as packed keep bits), so dropout runs 1 group per wave.
-template <int NK, bool FULLT, bool DROP>
+template <int NK, bool FULLT, bool DROP, bool PACKED = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_ring_kernel(const uint16_t* __restrict__ qkv,
                                                                  const uint16_t* __restrict__ dout,
                                                                  const float* __restrict__ lse,
@@ -935,7 +954,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_ring_kernel(const uint16
                                                                  const int* __restrict__ lens,
                                                                  uint16_t* __restrict__ dqkv, int S, int H,
                                                                  float scale, float* __restrict__ colpart, AttnQ8 q8,
-                                                                 AttnDropArgs ad) {
+                                                                 AttnDropArgs ad, int rows) {
+  static_assert(!(FULLT && PACKED), "packed sequences end anywhere: the clamped-row stages are needed");
   constexpr int STAGE = 2 * kTile + 2 * AB * 4;  // Q tile, dO tile, lse[64], delta[64]
   __shared__ __attribute__((aligned(16))) uint8_t smem[kRing * STAGE];
   int kbk, h, b;
@@ -943,15 +963,17 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_ring_kernel(const uint16
   const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, i = lane & 15;
   const int D = H * AH;
   const int64_t ld = 3 * (int64_t)D;
-  const int64_t base = (int64_t)b * S;
-  const int len = lens ? lens[b] : S;
+  const int64_t base = PACKED ? (int64_t)lens[b] : (int64_t)b * S;
+  const int Ss = PACKED ? lens[b + 1] - lens[b] : S;  // rows of this sequence (S: the launch-wide maximum)
+  const int len = PACKED ? Ss : (lens ? lens[b] : S);
+  if constexpr (PACKED) packed_dcheck(lens, b, S, rows);
   const int k0b = kbk * (64 * NK);
   // column partials [B * key blocks][2 D] (dK | dV) of the bias gradient, or nullptr
   float* cp = colpart ? colpart + ((int64_t)b * ((S + 64 * NK - 1) / (64 * NK)) + kbk) * 2 * D + h * AH : nullptr;
-  if (k0b >= len) {  // fully masked key block: zero gradients
+  if (k0b >= len) {  // fully masked key block: zero gradients (PACKED: past the sequence, no rows to zero)
     for (int e = threadIdx.x; e < 64 * NK * AH; e += 256) {
       const int kk = k0b + e / AH, d = e % AH;
-      if (kk < S) {
+      if (kk < Ss) {
         if (q8.y) {
           q8.y[(base + kk) * ld + D + h * AH + d] = 0;
           q8.y[(base + kk) * ld + 2 * D + h * AH + d] = 0;
@@ -970,7 +992,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_ring_kernel(const uint16
     return;
   }
   const float sl2 = scale * 1.4426950408889634f;
-  const int nqb = (S + AB - 1) / AB;
+  const int nqb = (Ss + AB - 1) / AB;
   // stage = 5 glds per thread: 2 (Q) + 2 (dO) + 1 (waves 0/2: LSE row, waves 1/3: delta row);
   // full stages from sources computed once (advance q0 rows per stage), the partial last one clamped
   const int wu = __builtin_amdgcn_readfirstlane(wid);
@@ -979,7 +1001,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_ring_kernel(const uint16
   const uint32_t ol = (uint32_t)lane * ((wu & 1) ? (uint32_t)H * 4u : 4u);  // this lane's LSE / delta entry
   auto issue = [&](int slot, int qb) {
     uint8_t* st = smem + slot * STAGE;
-    const int q0 = qb * AB, nv = min(AB, S - q0);
+    const int q0 = qb * AB, nv = min(AB, Ss - q0);
     if constexpr (FULLT) {
       glds_tile2(st, qkv + (base + q0) * ld + h * AH, oq0, oq1, wu);
       glds_tile2(st + kTile, dout + (base + q0) * (int64_t)D + h * AH, oo0, oo1, wu);
@@ -1001,9 +1023,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_ring_kernel(const uint16
     key[n] = k0b + n * 64 + wid * 16 + i;
 #pragma unroll
     for (int kh = 0; kh < 2; ++kh) {
-      kf[n][kh] = key[n] < S ? *reinterpret_cast<const bf16x8*>(qkv + (base + key[n]) * ld + D + h * AH + kh * 32 + 8 * g)
+      kf[n][kh] = key[n] < Ss ? *reinterpret_cast<const bf16x8*>(qkv + (base + key[n]) * ld + D + h * AH + kh * 32 + 8 * g)
                              : bf16x8{};
-      vf[n][kh] = key[n] < S
+      vf[n][kh] = key[n] < Ss
                       ? *reinterpret_cast<const bf16x8*>(qkv + (base + key[n]) * ld + 2 * D + h * AH + kh * 32 + 8 * g)
                       : bf16x8{};
     }
@@ -1039,7 +1061,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_ring_kernel(const uint16
     const float* lse_s = reinterpret_cast<const float*>(Qs + 2 * kTile);
     const float* del_s = lse_s + AB;
     const int q0 = qb * AB;
-    const bool qfull = q0 + AB <= S;
+    const bool qfull = q0 + AB <= Ss;
     // P and dS leave the fp32 accumulators as bf16 MFMA operands as soon as a qt pair is done
     // (half the registers of keeping all four qt tiles in fp32), and the block-uniform score-path
     // choice is taken once outside the qt loop, so each path's qt iterations are ONE basic block in
@@ -1091,7 +1113,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_ring_kernel(const uint16
               pv = fast_exp2(sv[n][r] * sl2k[n] - (lr[r] + kinf[n]));
             } else {
               const int ql = qt * 16 + 4 * g + r;
-              const bool ok = key[n] < len && q0 + ql < S;
+              const bool ok = key[n] < len && q0 + ql < Ss;
               pv = fast_exp2(ok ? sv[n][r] * sl2 - lr[r] : -INFINITY);
             }
             if constexpr (DROP) {
@@ -1165,11 +1187,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_ring_kernel(const uint16
           v[1][n][d][r] = dv[n][d][r];
         }
     const int col0[2] = {D + h * AH, 2 * D + h * AH};
-    attn_q8_epilogue<2, NK>(q8, v, smem, base, k0b, S, D, col0);
+    attn_q8_epilogue<2, NK>(q8, v, smem, base, k0b, Ss, D, col0);
   } else {
 #pragma unroll
   for (int n = 0; n < NK; ++n) {
-    if (key[n] < S) {
+    if (key[n] < Ss) {
 #pragma unroll
       for (int d = 0; d < 4; ++d) {
         uint16_t* kp = dqkv + (base + key[n]) * ld + D + h * AH + d * 16 + 4 * g;
@@ -1199,8 +1221,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_ring_kernel(const uint16
         vv[d][r] = 0.f;
 #pragma unroll
         for (int n = 0; n < NK; ++n) {
-          vk[d][r] += key[n] < S ? dk[n][d][r] * scale : 0.f;
-          vv[d][r] += key[n] < S ? dv[n][d][r] : 0.f;
+          vk[d][r] += key[n] < Ss ? dk[n][d][r] * scale : 0.f;
+          vv[d][r] += key[n] < Ss ? dv[n][d][r] : 0.f;
         }
       }
     float* red = reinterpret_cast<float*>(smem);
@@ -1216,7 +1238,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_ring_kernel(const uint16
 // DROP (attention-probability dropout, mask M, s = 1 / (1 - p_eff)): delta = rowsum(dO * O) is still
 // right (O is the dropped output) and dS = P * (M s dP - delta), so dP starts at 0 instead of
 // -delta and one fma per score applies the mask, the scale and delta.
-template <int NQ, bool FULLT, bool DROP>
+template <int NQ, bool FULLT, bool DROP, bool PACKED = false>
 __global__ __launch_bounds__(256) void attn_bwd_dq_ring_kernel(const uint16_t* __restrict__ qkv,
                                                                const uint16_t* __restrict__ dout,
                                                                const uint16_t* __restrict__ out,
@@ -1225,7 +1247,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_ring_kernel(const uint16_t* _
                                                                const int* __restrict__ lens,
                                                                uint16_t* __restrict__ dqkv, int S, int H, float scale,
                                                                float* __restrict__ colpart, AttnQ8 q8,
-                                                               AttnDropArgs ad) {
+                                                               AttnDropArgs ad, int rows) {
+  static_assert(!(FULLT && PACKED), "packed sequences end anywhere: the clamped-row stages are needed");
   constexpr int STAGE = 2 * kTile;  // K tile, V tile
   __shared__ __attribute__((aligned(16))) uint8_t smem[kRing * STAGE];
   int qb, h, b;
@@ -1234,15 +1257,24 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_ring_kernel(const uint16_t* _
   (void)lane;
   const int D = H * AH;
   const int64_t ld = 3 * (int64_t)D;
-  const int64_t base = (int64_t)b * S;
-  const int len = lens ? lens[b] : S;
+  const int64_t base = PACKED ? (int64_t)lens[b] : (int64_t)b * S;
+  const int Ss = PACKED ? lens[b + 1] - lens[b] : S;  // rows of this sequence (S: the launch-wide maximum)
+  const int len = PACKED ? Ss : (lens ? lens[b] : S);
+  if constexpr (PACKED) packed_dcheck(lens, b, S, rows);
+  if constexpr (PACKED) {
+    if (qb * (64 * NQ) >= Ss) {  // no query of this sequence here (block-uniform): zero column partials
+      if (colpart && threadIdx.x < 64)
+        (colpart + ((int64_t)b * ((S + 64 * NQ - 1) / (64 * NQ)) + qb) * D + h * AH)[threadIdx.x] = 0.f;
+      return;
+    }
+  }
   const float sl2 = scale * 1.4426950408889634f;
   const int nkb = (len + AB - 1) / AB;
   const int wu = __builtin_amdgcn_readfirstlane(wid);
   const uint32_t ok0 = glds_off_row(ld, 0), ok1 = glds_off_row(ld, 1);
   auto issue = [&](int slot, int kb) {  // (K and V: the same rows, D columns apart)
     uint8_t* st = smem + slot * STAGE;
-    const int k0 = kb * AB, nv = min(AB, S - k0);
+    const int k0 = kb * AB, nv = min(AB, Ss - k0);
     if constexpr (FULLT) {
       const uint16_t* kr = qkv + (base + k0) * ld + D + h * AH;
       glds_tile2(st, kr, ok0, ok1, wu);
@@ -1261,20 +1293,20 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_ring_kernel(const uint16_t* _
     q[n] = qb * (64 * NQ) + n * 64 + wid * 16 + i;
 #pragma unroll
     for (int kh = 0; kh < 2; ++kh) {
-      qf[n][kh] = q[n] < S ? *reinterpret_cast<const bf16x8*>(qkv + (base + q[n]) * ld + h * AH + kh * 32 + 8 * g)
+      qf[n][kh] = q[n] < Ss ? *reinterpret_cast<const bf16x8*>(qkv + (base + q[n]) * ld + h * AH + kh * 32 + 8 * g)
                            : bf16x8{};
-      of[n][kh] = q[n] < S
+      of[n][kh] = q[n] < Ss
                       ? *reinterpret_cast<const bf16x8*>(dout + (base + q[n]) * (int64_t)D + h * AH + kh * 32 + 8 * g)
                       : bf16x8{};
     }
-    lq[n] = q[n] < S ? lse[((int64_t)b * H + h) * S + q[n]] : 0.f;
+    lq[n] = q[n] < Ss ? lse[((int64_t)b * H + h) * S + q[n]] : 0.f;
     {  // delta of query q[n], bit-identical to attn_delta_kernel: its 16 four-dim partials (dims 4 sub ..)
        // are this lane's (kh, half) quads, sub = 8 kh + 2 g + half, summed in group_sum<16>'s
        // butterfly order (xor 8 = kh in-lane, xor 4 = lane ^ 32, xor 2 = lane ^ 16, xor 1 = half)
       float s4[2][2];
 #pragma unroll
       for (int kh = 0; kh < 2; ++kh) {
-        const bf16x8 o8 = q[n] < S ? *reinterpret_cast<const bf16x8*>(out + (base + q[n]) * (int64_t)D + h * AH +
+        const bf16x8 o8 = q[n] < Ss ? *reinterpret_cast<const bf16x8*>(out + (base + q[n]) * (int64_t)D + h * AH +
                                                                         kh * 32 + 8 * g)
                                    : bf16x8{};
 #pragma unroll
@@ -1293,8 +1325,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_ring_kernel(const uint16_t* _
         w[hf] = v;
       }
       const float sacc = w[0] + w[1];
-      dl[n] = q[n] < S ? sacc : 0.f;
-      if (g == 0 && q[n] < S) delta[(base + q[n]) * H + h] = sacc;
+      dl[n] = q[n] < Ss ? sacc : 0.f;
+      if (g == 0 && q[n] < Ss) delta[(base + q[n]) * H + h] = sacc;
     }
 #pragma unroll
     for (int d = 0; d < 4; ++d) acc[n][d] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -1391,11 +1423,11 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_ring_kernel(const uint16_t* _
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[0][n][d][r] = acc[n][d][r] * scale;
     const int col0[1] = {h * AH};
-    attn_q8_epilogue<1, NQ>(q8, v, smem, base, qb * (64 * NQ), S, D, col0);
+    attn_q8_epilogue<1, NQ>(q8, v, smem, base, qb * (64 * NQ), Ss, D, col0);
   } else {
 #pragma unroll
   for (int n = 0; n < NQ; ++n) {
-    if (q[n] < S) {
+    if (q[n] < Ss) {
       uint16_t* qp = dqkv + (base + q[n]) * ld + h * AH;
 #pragma unroll
       for (int d = 0; d < 4; ++d) {
@@ -1417,7 +1449,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_ring_kernel(const uint16_t* _
       for (int r = 0; r < 4; ++r) {
         vq[d][r] = 0.f;
 #pragma unroll
-        for (int n = 0; n < NQ; ++n) vq[d][r] += q[n] < S ? acc[n][d][r] * scale : 0.f;
+        for (int n = 0; n < NQ; ++n) vq[d][r] += q[n] < Ss ? acc[n][d][r] * scale : 0.f;
       }
     __syncthreads();  // every wave is past its last ring-stage read
     block_colsum64(vq, reinterpret_cast<float*>(smem),
@@ -1437,30 +1469,42 @@ static int attn_groups(const char* env, int S, int dflt = 2) {
   return S >= 128 ? dflt : 1;
 }
 
+// cu (packed mode, see packed_dcheck): cu_seqlens [B + 1] on the device; qkv / out then hold `rows`
+// (cu[B] <= rows <= B * S) token rows, S is max_seqlen and `lens` is unused. The packed instantiations keep the
+// group counts of the padded ones (forward and dQ 2 groups, dK/dV 2 groups without dropout and 1 with):
+// they are the non-FULLT kernels plus two scalar loads, and build with the same VGPR counts and no scratch.
 void launch_attn_fwd(const uint16_t* qkv, uint16_t* out, float* lse, const int* lens, int B, int S, int H,
-                     float scale, hipStream_t st, const AttnDropArgs& ad) {
+                     float scale, hipStream_t st, const AttnDropArgs& ad, const int* cu, int rows) {
   if (B <= 0 || S <= 0) return;
   const unsigned g2 = (unsigned)((S + 127) / 128 * H * B), g1 = (unsigned)((S + 63) / 64 * H * B);
   const bool two = attn_groups("MLT_ATTN_FWD_GROUPS", S, 2) == 2;
-  auto launch = [&](auto dropc) {  // the dropout instantiations only when something is dropped
-    constexpr bool DR = decltype(dropc)::value;
+  const int* sl = cu ? cu : lens;
+  auto launch = [&](auto dropc, auto packc) {  // the dropout instantiations only when something is dropped
+    constexpr bool DR = decltype(dropc)::value, PK = decltype(packc)::value;
     if (two)
-      hipLaunchKernelGGL((attn_fwd_lean_kernel<2, DR>), dim3(g2), dim3(256), 0, st, qkv, out, lse, lens, S, H, scale,
-                         ad);
+      hipLaunchKernelGGL((attn_fwd_lean_kernel<2, DR, PK>), dim3(g2), dim3(256), 0, st, qkv, out, lse, sl, S, H, scale,
+                         ad, rows);
     else
-      hipLaunchKernelGGL((attn_fwd_lean_kernel<1, DR>), dim3(g1), dim3(256), 0, st, qkv, out, lse, lens, S, H, scale,
-                         ad);
+      hipLaunchKernelGGL((attn_fwd_lean_kernel<1, DR, PK>), dim3(g1), dim3(256), 0, st, qkv, out, lse, sl, S, H, scale,
+                         ad, rows);
   };
-  if (ad.thr8 > 0)
-    launch(std::true_type{});
-  else
-    launch(std::false_type{});
+  if (cu) {
+    if (ad.thr8 > 0)
+      launch(std::true_type{}, std::true_type{});
+    else
+      launch(std::false_type{}, std::true_type{});
+  } else {
+    if (ad.thr8 > 0)
+      launch(std::true_type{}, std::false_type{});
+    else
+      launch(std::false_type{}, std::false_type{});
+  }
 }
 
 bool launch_attn_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse, float* delta,
                      const int* lens, uint16_t* dqkv, int B, int S, int H, float scale, hipStream_t st,
                      float* colpart_q, float* colpart_kv, int* rows_q, int* rows_kv, const AttnQ8& q8,
-                     const AttnDropArgs& ad) {
+                     const AttnDropArgs& ad, const int* cu, int rows) {
   // MLT_ATTN_RING: unset or 4 = the ring kernels, 0 = the register-staged kernels. Those stay in the
   // tree as the bit-for-bit oracle of the ring kernels' test; any other value is an error.
   const char* rv = getenv("MLT_ATTN_RING");
@@ -1468,6 +1512,12 @@ bool launch_attn_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* d
   if (!ring && strcmp(rv, "0"))
     throw std::runtime_error(std::string("attn_bwd: MLT_ATTN_RING=") + rv + " (accepted: unset or 4 = ring kernels, " +
                              "0 = register-staged kernels)");
+  if (cu && !ring)
+    throw std::runtime_error("attn_bwd: packed sequences (cu_seqlens) need the ring kernels (MLT_ATTN_RING unset or "
+                             "4); the register-staged kernels take padded batches only");
+  if (cu && q8.y)
+    throw std::runtime_error("attn_bwd: the fp8 (q8) outputs take padded batches only (their transposed 16-row runs "
+                             "sit at b * S offsets), not cu_seqlens");
   if (B <= 0 || S <= 0) return false;
   const int64_t pairs = (int64_t)B * S * H;
   const dim3 g2((S + 127) / 128 * H * B), g1((S + 63) / 64 * H * B);
@@ -1476,34 +1526,40 @@ bool launch_attn_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* d
     // (dK/dV under dropout: 1 key group per wave, the 2-group instantiation would spill)
     const bool k2 = !drop && attn_groups("MLT_ATTN_DKDV_GROUPS", S, 2) == 2;
     const bool q2 = attn_groups("MLT_ATTN_DQ_GROUPS", S) == 2;
-    auto launch = [&](auto fullt, auto dropc) {
-      constexpr bool FL = decltype(fullt)::value, DR = decltype(dropc)::value;
+    const int* sl = cu ? cu : lens;
+    auto launch = [&](auto fullt, auto dropc, auto packc) {
+      constexpr bool FL = decltype(fullt)::value, DR = decltype(dropc)::value, PK = decltype(packc)::value;
       if (q2)
-        hipLaunchKernelGGL((attn_bwd_dq_ring_kernel<2, FL, DR>), g2, dim3(256), 0, st, qkv, dout, out, lse, delta, lens,
-                           dqkv, S, H, scale, colpart_q, q8, ad);
+        hipLaunchKernelGGL((attn_bwd_dq_ring_kernel<2, FL, DR, PK>), g2, dim3(256), 0, st, qkv, dout, out, lse, delta,
+                           sl, dqkv, S, H, scale, colpart_q, q8, ad, rows);
       else
-        hipLaunchKernelGGL((attn_bwd_dq_ring_kernel<1, FL, DR>), g1, dim3(256), 0, st, qkv, dout, out, lse, delta, lens,
-                           dqkv, S, H, scale, colpart_q, q8, ad);
+        hipLaunchKernelGGL((attn_bwd_dq_ring_kernel<1, FL, DR, PK>), g1, dim3(256), 0, st, qkv, dout, out, lse, delta,
+                           sl, dqkv, S, H, scale, colpart_q, q8, ad, rows);
       if constexpr (!DR) {
         if (k2) {
-          hipLaunchKernelGGL((attn_bwd_dkdv_ring_kernel<2, FL, false>), g2, dim3(256), 0, st, qkv, dout, lse, delta,
-                             lens, dqkv, S, H, scale, colpart_kv, q8, ad);
+          hipLaunchKernelGGL((attn_bwd_dkdv_ring_kernel<2, FL, false, PK>), g2, dim3(256), 0, st, qkv, dout, lse, delta,
+                             sl, dqkv, S, H, scale, colpart_kv, q8, ad, rows);
           return;
         }
       }
-      hipLaunchKernelGGL((attn_bwd_dkdv_ring_kernel<1, FL, DR>), g1, dim3(256), 0, st, qkv, dout, lse, delta, lens,
-                         dqkv, S, H, scale, colpart_kv, q8, ad);
+      hipLaunchKernelGGL((attn_bwd_dkdv_ring_kernel<1, FL, DR, PK>), g1, dim3(256), 0, st, qkv, dout, lse, delta, sl,
+                         dqkv, S, H, scale, colpart_kv, q8, ad, rows);
     };
-    if (S % AB == 0) {
+    if (cu) {  // packed: a sequence ends anywhere, so always the clamped-row (non-FULLT) stages
       if (drop)
-        launch(std::true_type{}, std::true_type{});
+        launch(std::false_type{}, std::true_type{}, std::true_type{});
       else
-        launch(std::true_type{}, std::false_type{});
+        launch(std::false_type{}, std::false_type{}, std::true_type{});
+    } else if (S % AB == 0) {
+      if (drop)
+        launch(std::true_type{}, std::true_type{}, std::false_type{});
+      else
+        launch(std::true_type{}, std::false_type{}, std::false_type{});
     } else {
       if (drop)
-        launch(std::false_type{}, std::true_type{});
+        launch(std::false_type{}, std::true_type{}, std::false_type{});
       else
-        launch(std::false_type{}, std::false_type{});
+        launch(std::false_type{}, std::false_type{}, std::false_type{});
     }
     // partial rows actually written: B x (row blocks of the chosen group count)
     if (rows_kv) *rows_kv = B * ((S + (k2 ? 127 : 63)) / (k2 ? 128 : 64));

@@ -397,12 +397,15 @@ void launch_ln_bwd_dropout(const uint16_t* DY, const uint16_t* X, const float* g
 
 // ---------------------------------------------------------------------------
 // BERT embeddings: out[t] = Wword[ids[t]] + Wpos[pos[t]] + Wtype[tt[t]]  (bf16 tables, bf16 out)
+// pos[t] = t % S for a padded [B, S] batch; a packed batch (T real tokens, no pads) passes the
+// positions explicitly (posv [T], each the index inside the token's own sequence, < S).
 // ---------------------------------------------------------------------------
 template <int VPL>
 __global__ __launch_bounds__(256) void embed_fwd_kernel(const int64_t* __restrict__ ids, const int64_t* __restrict__ tt,
                                                         const uint16_t* __restrict__ Ww, const uint16_t* __restrict__ Wp,
                                                         const uint16_t* __restrict__ Wt, uint16_t* __restrict__ out,
-                                                        int64_t rows, int S, int64_t vocab, int ntype) {
+                                                        int64_t rows, int S, int64_t vocab, int ntype,
+                                                        const int* __restrict__ posv) {
   constexpr int D = VPL * 256, E = VPL * 4;
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -411,7 +414,11 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(const int64_t* __restric
   id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
   int64_t ty = tt ? tt[row] : 0;
   ty = ty < 0 ? 0 : (ty >= ntype ? ntype - 1 : ty);
-  const int pos = (int)(row % S);
+  int pos = posv ? posv[row] : (int)(row % S);
+  if (posv) {
+    MLT_DCHECK(pos >= 0 && pos < S);
+    pos = pos < 0 ? 0 : (pos >= S ? S - 1 : pos);  // (S <= position-table rows, checked by the caller)
+  }
   float a[E], b[E], c[E];
   load_row<VPL>(Ww + id * D, a);
   load_row<VPL>(Wp + (int64_t)pos * D, b);
@@ -434,7 +441,9 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(const int64_t* __restric
 //    one wave per sorted entry, and the wave that starts a run of equal ids sums that run's
 //    gradient rows in token order and adds the sum to its table row (one writer per row);
 //  * positions / token types: one wave per position sums the B rows of that position in batch
-//    order into gp, and leaves the per-type sums as a partial row for reduce_rows.
+//    order into gp, and leaves the per-type sums as a partial row for reduce_rows. PACKED: the batch
+//    is T token rows with sequence b at rows cu[b] .. cu[b + 1]; the wave of position p sums rows
+//    cu[b] + p over the sequences longer than p, still in batch order.
 template <int VPL>
 __global__ __launch_bounds__(256) void embed_bwd_word_kernel(const int64_t* __restrict__ sid,
                                                              const int64_t* __restrict__ perm,
@@ -468,10 +477,11 @@ __global__ __launch_bounds__(256) void embed_bwd_word_kernel(const int64_t* __re
   }
 }
 
-template <int VPL>
+template <int VPL, bool PACKED>
 __global__ __launch_bounds__(256) void embed_bwd_pos_kernel(const int64_t* __restrict__ tt,
                                                             const uint16_t* __restrict__ DX, float* __restrict__ gp,
-                                                            float* __restrict__ part_t, int64_t rows, int S) {
+                                                            float* __restrict__ part_t, int64_t rows, int S,
+                                                            const int* __restrict__ cu, int B) {
   constexpr int D = VPL * 256, E = VPL * 4;
   const int lane = threadIdx.x & 63;
   const int pos = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -479,7 +489,7 @@ __global__ __launch_bounds__(256) void embed_bwd_pos_kernel(const int64_t* __res
   float a[E], t0[E], t1[E];
 #pragma unroll
   for (int e = 0; e < E; ++e) a[e] = t0[e] = t1[e] = 0.f;
-  for (int64_t r = pos; r < rows; r += S) {
+  auto add_row = [&](int64_t r) {
     float d[E];
     load_row<VPL>(DX + r * D, d);
     const bool one = tt && tt[r] != 0;
@@ -489,6 +499,15 @@ __global__ __launch_bounds__(256) void embed_bwd_pos_kernel(const int64_t* __res
       t0[e] += one ? 0.f : d[e];
       t1[e] += one ? d[e] : 0.f;
     }
+  };
+  if constexpr (PACKED) {
+    for (int b = 0; b < B; ++b) {
+      const int c0 = cu[b], c1 = cu[b + 1];
+      MLT_DCHECK(c0 >= 0 && c1 >= c0 && c1 - c0 <= S && c1 <= rows);
+      if (pos < c1 - c0 && (int64_t)c0 + pos < rows) add_row((int64_t)c0 + pos);
+    }
+  } else {
+    for (int64_t r = pos; r < rows; r += S) add_row(r);
   }
 #pragma unroll
   for (int v = 0; v < VPL; ++v) {
@@ -509,26 +528,29 @@ __global__ __launch_bounds__(256) void embed_bwd_pos_kernel(const int64_t* __res
 
 void launch_embed_fwd(const int64_t* ids, const int64_t* tt, const uint16_t* Ww, const uint16_t* Wp,
                       const uint16_t* Wt, uint16_t* out, int64_t rows, int S, int D, int64_t vocab, int ntype,
-                      hipStream_t st) {
+                      hipStream_t st, const int* pos) {
   if (rows <= 0) return;
   const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
   switch (D / 256) {
-    case 3: hipLaunchKernelGGL(embed_fwd_kernel<3>, grid, block, 0, st, ids, tt, Ww, Wp, Wt, out, rows, S, vocab, ntype); break;
-    case 4: hipLaunchKernelGGL(embed_fwd_kernel<4>, grid, block, 0, st, ids, tt, Ww, Wp, Wt, out, rows, S, vocab, ntype); break;
-    case 1: hipLaunchKernelGGL(embed_fwd_kernel<1>, grid, block, 0, st, ids, tt, Ww, Wp, Wt, out, rows, S, vocab, ntype); break;
-    case 2: hipLaunchKernelGGL(embed_fwd_kernel<2>, grid, block, 0, st, ids, tt, Ww, Wp, Wt, out, rows, S, vocab, ntype); break;
+    case 3: hipLaunchKernelGGL(embed_fwd_kernel<3>, grid, block, 0, st, ids, tt, Ww, Wp, Wt, out, rows, S, vocab, ntype, pos); break;
+    case 4: hipLaunchKernelGGL(embed_fwd_kernel<4>, grid, block, 0, st, ids, tt, Ww, Wp, Wt, out, rows, S, vocab, ntype, pos); break;
+    case 1: hipLaunchKernelGGL(embed_fwd_kernel<1>, grid, block, 0, st, ids, tt, Ww, Wp, Wt, out, rows, S, vocab, ntype, pos); break;
+    case 2: hipLaunchKernelGGL(embed_fwd_kernel<2>, grid, block, 0, st, ids, tt, Ww, Wp, Wt, out, rows, S, vocab, ntype, pos); break;
     default: break;
   }
 }
 
 void launch_embed_bwd(const int64_t* sid, const int64_t* perm, const int64_t* tt, const uint16_t* DX, float* gw,
                       float* gp, float* gt, float* part, int64_t rows, int S, int D, int64_t vocab, int ntype,
-                      hipStream_t st) {
+                      hipStream_t st, const int* cu, int B) {
   if (rows <= 0) return;
   const dim3 gw_grid((unsigned)((rows + 3) / 4)), gp_grid((unsigned)((S + 3) / 4)), block(256);
 #define MLT_EMB_BWD(V)                                                                                          \
   hipLaunchKernelGGL(embed_bwd_word_kernel<V>, gw_grid, block, 0, st, sid, perm, DX, gw, rows, vocab);         \
-  hipLaunchKernelGGL(embed_bwd_pos_kernel<V>, gp_grid, block, 0, st, tt, DX, gp, part, rows, S);
+  if (cu)                                                                                                       \
+    hipLaunchKernelGGL((embed_bwd_pos_kernel<V, true>), gp_grid, block, 0, st, tt, DX, gp, part, rows, S, cu, B); \
+  else                                                                                                          \
+    hipLaunchKernelGGL((embed_bwd_pos_kernel<V, false>), gp_grid, block, 0, st, tt, DX, gp, part, rows, S, cu, B);
   switch (D / 256) {
     case 1: MLT_EMB_BWD(1) break;
     case 2: MLT_EMB_BWD(2) break;

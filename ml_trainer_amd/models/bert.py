@@ -33,6 +33,22 @@ probability, so the probability applied is ``p_eff = round(p * 256) / 256`` (0.1
 0.1015625) and kept probabilities are scaled by ``1 / (1 - p_eff)``. It shares the forward's one
 seed with hidden dropout (sites ``0x40000000 + layer``) and is active in ``train()`` mode only.
 Not covered: the LeNet models (the reference model has no dropout).
+
+Unpadded execution (``BertConfig.unpad``, default False) drops the pad tokens of a right-padded
+``[B, S]`` batch once, before the embeddings, and runs the whole encoder on the ``T = sum(len_b)`` real
+tokens as one ``[T, hidden]`` matrix (``ops.transformer.pack_batch``). GEMMs, LayerNorm, GELU and
+hidden dropout are row-count agnostic. The native path rounds the row count up to the GEMMs' 256-row
+tile with inert tail rows that belong to no sequence and get zero gradients. The flash attention
+kernels find sequence ``b`` at rows ``cu_seqlens[b] .. cu_seqlens[b + 1]`` (their packed
+instantiations) and the embedding kernels take
+explicit positions (the index inside the token's own sequence). The CLS rows are ``cu_seqlens[:-1]``,
+so the logits equal the padded model's: pads never reach the CLS loss. It needs lengths
+(``attention_mask`` or ``pad_id``; without them the padded path runs unchanged) and assumes right
+padding, as ``_lengths`` does. Packing needs ``T`` on the host to size the packed tensors: one small
+device-to-host read per forward. Attention-probability dropout draws the bytes of the padded run
+(element ``(b, h, q, k)`` is indexed with the padded width ``S``); hidden dropout is indexed by packed
+row, so its masks differ from a padded run's with the same seed. ``unpad`` with ``fp8`` is rejected: the
+fp8 attention epilogue writes 16-row transposed runs at ``b * S`` offsets.
 """
 from __future__ import annotations
 
@@ -61,6 +77,7 @@ class BertConfig:
     hidden_dropout: float = 0.0  # embedding / attention-output / FFN-output dropout (train() only)
     attention_dropout: float = 0.0  # attention-probability dropout, applied as round(p * 256) / 256
     pad_id: Optional[int] = None  # when set, key lengths are derived from trailing pad tokens
+    unpad: bool = False  # run the encoder on the real tokens only (needs lengths; not with fp8)
 
 
 _PRESETS = {
@@ -90,28 +107,36 @@ class BertLayer(nn.Module):
         self.ffn2 = nn.Linear(c.intermediate, h)
         self.ln2 = nn.LayerNorm(h, eps=c.ln_eps)
 
-    def forward_native(self, x, lens, B, S, drop=None, attn_drop=None):
+    def forward_native(self, x, lens, B, S, drop=None, attn_drop=None, cu_seqlens=None):
         """``drop`` = (p, seed, site of the attention sub-layer, rank); the FFN takes the next site.
-        ``attn_drop`` = (p, seed, attention site of this layer, rank): attention-probability dropout."""
+        ``attn_drop`` = (p, seed, attention site of this layer, rank): attention-probability dropout.
+        ``cu_seqlens``: x is a packed [T, h] batch (S = max_seqlen, lens unused)."""
         from ml_trainer_amd.ops import transformer as T
         if self.c.fp8:
             from ml_trainer_amd.ops.fp8 import FP8 as impl
         else:
             impl = T.BF16
         x = T.attention_ln_block(x, self.qkv.weight, self.qkv.bias, self.out.weight, self.out.bias, self.ln1.weight,
-                                 self.ln1.bias, lens, B, S, self.c.heads, self.c.ln_eps, impl, drop, attn_drop)
+                                 self.ln1.bias, lens, B, S, self.c.heads, self.c.ln_eps, impl, drop, attn_drop,
+                                 cu_seqlens)
         if drop is not None:
             drop = (drop[0], drop[1], drop[2] + 1, drop[3])
         return T.ffn_ln_block(x, self.ffn1.weight, self.ffn1.bias, self.ffn2.weight, self.ffn2.bias, self.ln2.weight,
                               self.ln2.bias, self.c.ln_eps, impl, drop)
 
-    def forward_reference(self, x, mask, B, S, drop=None, attn_drop=None):
+    def forward_reference(self, x, mask, B, S, drop=None, attn_drop=None, packed=None):
         """fp32 torch reference. x [B*S, h]; mask [B, S] bool (True = valid key); drop and attn_drop
-        as in forward_native (the same masks, through ops.dropout)."""
+        as in forward_native (the same masks, through ops.dropout). ``packed`` (a PackedBatch): x is
+        [T, h]; the linears, LayerNorms and hidden dropout run on the packed rows, attention on a
+        padded scratch of the QKV rows (so its dropout mask is the padded run's)."""
         from ml_trainer_amd.ops import dropout as D
         c = self.c
         H, dh = c.heads, c.hidden // c.heads
-        qkv = self.qkv(x).view(B, S, 3, H, dh).permute(2, 0, 3, 1, 4)
+        qkv = self.qkv(x)
+        if packed is not None:
+            from ml_trainer_amd.ops.transformer import unpack_rows
+            qkv = unpack_rows(qkv, packed)
+        qkv = qkv.view(B, S, 3, H, dh).permute(2, 0, 3, 1, 4)
         q, k, v = qkv[0], qkv[1], qkv[2]
         s = (q @ k.transpose(-1, -2)) / math.sqrt(dh)
         if mask is not None:
@@ -122,6 +147,8 @@ class BertLayer(nn.Module):
             keep = D.attention_keep_mask(seed, site, rank, B, H, S, p, x.device)
             pr = pr * keep * D.attention_scale(p)
         ctx = (pr @ v).permute(0, 2, 1, 3).reshape(B * S, c.hidden)
+        if packed is not None:
+            ctx = ctx.index_select(0, packed.index)
         a = self.out(ctx)
         if drop is not None:
             a = D.apply(a, *drop)
@@ -145,6 +172,9 @@ class BertClassifier(nn.Module):
         if c.attention_dropout > 0:
             from ml_trainer_amd.ops.dropout import attention_threshold
             attention_threshold(c.attention_dropout)  # a p that rounds to 0/256 (or 256/256) is an error
+        if c.unpad and c.fp8:
+            raise ValueError("unpad=True with fp8=True is not supported: the fp8 attention epilogue writes 16-row "
+                             "transposed runs at b * S offsets and cannot take packed row offsets")
         self.config = c
         self.last_dropout_seed = None  # the seed of the last forward that dropped
         self.word_embeddings = nn.Embedding(c.vocab_size, c.hidden)
@@ -200,7 +230,18 @@ class BertClassifier(nn.Module):
         from ml_trainer_amd.ops.dropout import attention_site
         return cls._site(adrop, attention_site(l))
 
+    def _pack(self, input_ids, lens, token_type_ids, row_multiple=1):
+        """The PackedBatch of this forward when ``unpad`` is on and lengths are known, else None."""
+        if not self.config.unpad or lens is None:
+            return None
+        from ml_trainer_amd.ops.transformer import pack_batch
+        return pack_batch(input_ids, lens, token_type_ids, row_multiple)
+
     def forward(self, input_ids, attention_mask=None, token_type_ids=None, dropout_seed=None):
+        """Logits [B, num_labels]. With ``config.unpad`` and lengths known (``attention_mask`` or
+        ``pad_id``; right padding assumed) the batch is packed on the device and the encoder runs on
+        the real tokens only; sizing the packed tensors costs one small device-to-host read (the
+        token count) per forward. Without lengths the padded path runs."""
         if isinstance(input_ids, (tuple, list)):
             input_ids, attention_mask = input_ids[0], input_ids[1] if len(input_ids) > 1 else None
         B, S = input_ids.shape
@@ -211,6 +252,9 @@ class BertClassifier(nn.Module):
             if self.config.fp8 and torch.is_grad_enabled():
                 from ml_trainer_amd.ops.fp8 import context
                 context(input_ids.device).update()  # delayed scaling: fold last step's amaxes
+            pk = self._pack(input_ids, lens, token_type_ids, T.PACK_ROW_MULTIPLE)
+            if pk is not None:
+                return self._forward_native_packed(pk, drop, adrop)
             x = T.embeddings(input_ids, token_type_ids, self.word_embeddings.weight, self.position_embeddings.weight,
                              self.token_type_embeddings.weight, S)
             x = T.layer_norm(x, self.emb_ln.weight, self.emb_ln.bias, self.config.ln_eps)
@@ -228,8 +272,42 @@ class BertClassifier(nn.Module):
         pooled = torch.tanh(self.pooler(cls))
         return self.classifier(pooled)
 
+    def _forward_native_packed(self, pk, drop, adrop):
+        """The native path on a PackedBatch: [rows, h] throughout (the T tokens, then the inert tail rows
+        that round the count up to the GEMMs' 256-row tile), CLS rows at cu_seqlens[:-1]."""
+        from ml_trainer_amd.ops import transformer as T
+        B, S, cu = pk.batch, pk.max_seqlen, pk.cu_seqlens
+        x = T.embeddings(pk.ids, pk.tt, self.word_embeddings.weight, self.position_embeddings.weight,
+                         self.token_type_embeddings.weight, S, pos=pk.pos, cu_seqlens=cu)
+        x = T.layer_norm(x, self.emb_ln.weight, self.emb_ln.bias, self.config.ln_eps)
+        if drop is not None:
+            x = T.dropout(x, *self._site(drop, 0))
+        for l, layer in enumerate(self.layers):
+            x = layer.forward_native(x, None, B, S, self._site(drop, 1 + 2 * l), self._attn_site(adrop, l), cu)
+        cls = x.index_select(0, pk.cls_rows)  # contiguous [B, h]
+        if cls.shape[1] % 8 == 0 and self.pooler.weight.shape[0] % 8 == 0:
+            return T.classifier_head(cls, self.pooler.weight, self.pooler.bias, self.classifier.weight,
+                                     self.classifier.bias)
+        return self.classifier(torch.tanh(self.pooler(cls.float())))
+
+    def _reference_hidden_packed(self, pk, lens, drop, adrop):
+        B, S = pk.batch, pk.max_seqlen
+        tt = pk.tt if pk.tt is not None else torch.zeros_like(pk.ids)
+        x = self.word_embeddings(pk.ids) + self.position_embeddings(pk.pos.long()) + self.token_type_embeddings(tt)
+        x = self.emb_ln(x)
+        if drop is not None:
+            from ml_trainer_amd.ops import dropout as D
+            x = D.apply(x, *self._site(drop, 0))
+        mask = torch.arange(S, device=x.device)[None, :] < lens.to(x.device).clamp(1, S)[:, None]
+        for l, layer in enumerate(self.layers):
+            x = layer.forward_reference(x, mask, B, S, self._site(drop, 1 + 2 * l), self._attn_site(adrop, l), pk)
+        return x.index_select(0, pk.cls_rows)
+
     def forward_reference_hidden(self, input_ids, lens=None, token_type_ids=None, drop=None, adrop=None):
         B, S = input_ids.shape
+        pk = self._pack(input_ids, lens, token_type_ids)
+        if pk is not None:
+            return self._reference_hidden_packed(pk, lens, drop, adrop)
         pos = torch.arange(S, device=input_ids.device)
         tt = token_type_ids if token_type_ids is not None else torch.zeros_like(input_ids)
         x = self.word_embeddings(input_ids) + self.position_embeddings(pos)[None] + self.token_type_embeddings(tt)
@@ -259,21 +337,33 @@ class BertClassifier(nn.Module):
         c = self.config
         drop, adrop = self._dropout(dropout_seed)
 
-        def dropped(t, site):  # t [B, S, h]
-            return t if drop is None else D.apply(t.reshape(B * S, -1), *self._site(drop, site)).view(B, S, -1)
+        def dropped(t, site):  # t [B, S, h] (unpad: [1, T, h]), masks indexed by row
+            return t if drop is None else D.apply(t.reshape(-1, t.shape[-1]), *self._site(drop, site)).view(t.shape)
 
         B, S = input_ids.shape
         lens = self._lengths(input_ids, attention_mask)
+        pk = self._pack(input_ids, lens, token_type_ids)
+        if pk is not None:
+            from ml_trainer_amd.ops.transformer import unpack_rows
         mask = None
         if lens is not None:
             mask = (torch.arange(S, device=input_ids.device)[None, :] < lens[:, None])[:, None, None, :]
         with torch.autocast(input_ids.device.type, dtype=torch.bfloat16):
-            pos = torch.arange(S, device=input_ids.device)
-            tt = token_type_ids if token_type_ids is not None else torch.zeros_like(input_ids)
-            x = self.word_embeddings(input_ids) + self.position_embeddings(pos)[None] + self.token_type_embeddings(tt)
+            if pk is None:
+                pos = torch.arange(S, device=input_ids.device)
+                tt = token_type_ids if token_type_ids is not None else torch.zeros_like(input_ids)
+                x = (self.word_embeddings(input_ids) + self.position_embeddings(pos)[None] +
+                     self.token_type_embeddings(tt))
+            else:  # the packed rows as a batch of one: x [1, T, h]; attention on a padded scratch of the QKV rows
+                tt = pk.tt if pk.tt is not None else torch.zeros_like(pk.ids)
+                x = (self.word_embeddings(pk.ids) + self.position_embeddings(pk.pos.long()) +
+                     self.token_type_embeddings(tt))[None]
             x = dropped(self.emb_ln(x), 0)
             for l, L in enumerate(self.layers):
-                qkv = L.qkv(x).view(B, S, 3, c.heads, 64).permute(2, 0, 3, 1, 4)
+                qkv = L.qkv(x)
+                if pk is not None:
+                    qkv = unpack_rows(qkv[0], pk)
+                qkv = qkv.view(B, S, 3, c.heads, 64).permute(2, 0, 3, 1, 4)
                 if adrop is None:
                     ctx = F.scaled_dot_product_attention(qkv[0], qkv[1], qkv[2], attn_mask=mask)
                 else:
@@ -284,9 +374,13 @@ class BertClassifier(nn.Module):
                     keep = D.attention_keep_mask(seed, site, rank, B, c.heads, S, pa, x.device)
                     pr = sc.softmax(-1)
                     ctx = (pr * keep * D.attention_scale(pa)).to(qkv[2].dtype) @ qkv[2]
-                x = L.ln1(dropped(L.out(ctx.transpose(1, 2).reshape(B, S, -1)), 1 + 2 * l) + x)
+                ctx = ctx.transpose(1, 2).reshape(B, S, -1)
+                if pk is not None:
+                    ctx = ctx.reshape(B * S, -1).index_select(0, pk.index)[None]
+                x = L.ln1(dropped(L.out(ctx), 1 + 2 * l) + x)
                 x = L.ln2(dropped(L.ffn2(F.gelu(L.ffn1(x))), 2 + 2 * l) + x)
-            return self.classifier(torch.tanh(self.pooler(x[:, 0].float())))
+            cls = x[:, 0] if pk is None else x[0].index_select(0, pk.cls_rows)
+            return self.classifier(torch.tanh(self.pooler(cls.float())))
 
     def num_parameters(self) -> int:
         return sum(p.numel() for p in self.parameters())

@@ -24,6 +24,12 @@ Blocks (one autograd node each, so the backward can fuse across ops):
   (forward, dQ, dK/dV), from a byte-per-element mask that is recomputed as well.
 * ``layer_norm``, ``embeddings``, ``dropout`` (the embedding site).
 
+Packed ("unpadded") batches: ``pack_batch`` drops the pad tokens of a right-padded [B, S] batch once
+and the blocks then run on the T = sum(lens) real tokens as one [T, D] matrix. The attention blocks
+take ``cu_seqlens`` (sequence b = rows cu[b] .. cu[b + 1]; ``S`` is then max_seqlen, the width of the
+padded input, and ``lens`` is unused), ``embeddings`` takes explicit positions; everything else is
+row-count agnostic.
+
 The linear-layer arithmetic is pluggable (``impl``): ``BF16`` (bf16 operands) or
 ``ops.fp8.FP8`` (OCP fp8 forward / dgrad GEMMs with delayed per-tensor scaling; wgrad bf16).
 
@@ -210,26 +216,44 @@ def _attn_drop_kw(attn_drop):
     return dict(p=p, seed=seed, site=site, rank=rank)
 
 
-def _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl=BF16, residual=True, attn_drop=None):
+def _zero_packed_tail(t, cu_seqlens):
+    """Packed batches may end in inert tail rows (``pack_batch``) that the attention kernels never write:
+    zero the last rows before the launch, which then overwrites the real ones among them. T is not known
+    on the host here, so the attention blocks support FEWER THAN PACK_ROW_MULTIPLE tail rows, which is
+    what ``pack_batch`` produces; rows of a longer tail would keep uninitialised memory."""
+    if cu_seqlens is not None:
+        t[-min(PACK_ROW_MULTIPLE - 1, t.shape[0]):].zero_()
+
+
+def _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl=BF16, residual=True, attn_drop=None, cu_seqlens=None):
     """``attn_drop`` = (p, seed, site, rank): attention-probability dropout inside the flash kernels
-    (the byte mask of ops/dropout.py, recomputed in the backward); None: no dropout."""
+    (the byte mask of ops/dropout.py, recomputed in the backward); None: no dropout.
+    ``cu_seqlens`` (int32 [B + 1], device): packed batch, x is [T, D] with sequence b at rows
+    cu[b] .. cu[b + 1]; S is max_seqlen and ``lens`` is unused."""
     C = require_native()
+    if cu_seqlens is not None and impl is not BF16:
+        raise ValueError("packed (cu_seqlens) attention runs the bf16 linears only: the fp8 attention epilogue "
+                         "writes at b * S offsets")
     qkv = impl.fwd(x, wqkv, bqkv)
-    attn = torch.empty(B * S, H * 64, dtype=torch.bfloat16, device=x.device)
+    attn = torch.empty(x.shape[0], H * 64, dtype=torch.bfloat16, device=x.device)
     lse = torch.empty(B * H * S, dtype=torch.float32, device=x.device)
-    C.attn_fwd(qkv, attn, lse, lens, B, S, H, _ATTN_SCALE, **_attn_drop_kw(attn_drop))
+    _zero_packed_tail(attn, cu_seqlens)
+    C.attn_fwd(qkv, attn, lse, lens, B, S, H, _ATTN_SCALE, cu_seqlens=cu_seqlens, **_attn_drop_kw(attn_drop))
     # out-proj + bias + residual (under dropout the residual joins in the LayerNorm kernel instead)
     y = impl.fwd(attn, wo, bo, res=x if residual else None)
     return y, (x, qkv, attn, lse)
 
 
-def _attn_bwd(saved, params, lens, B, S, H, dy, G, dbo="colsum", impl=BF16, dres=None, attn_drop=None):
+def _attn_bwd(saved, params, lens, B, S, H, dy, G, dbo="colsum", impl=BF16, dres=None, attn_drop=None,
+              cu_seqlens=None):
     """Backward of the attention block. ``dbo``: "colsum" to reduce dy here, otherwise the
     out-proj bias gradient already produced by the LayerNorm backward (tensor or None).
     ``dres``: the gradient of the residual branch when it differs from the out-proj's ``dy``
-    (hidden dropout sits between them); defaults to ``dy``. ``attn_drop``: the forward's."""
+    (hidden dropout sits between them); defaults to ``dy``. ``attn_drop``, ``cu_seqlens``: the forward's."""
     C = require_native()
     akw = _attn_drop_kw(attn_drop)
+    if cu_seqlens is not None:
+        akw["cu_seqlens"] = cu_seqlens
     x, qkv, attn, lse = saved
     wqkv, bqkv, wo, bo = params
     dres = dy if dres is None else dres
@@ -238,7 +262,8 @@ def _attn_bwd(saved, params, lens, B, S, H, dy, G, dbo="colsum", impl=BF16, dres
         dbo = G.colsum(bo, dy)
     dattn = impl.dgrad(dy, wo, torch.empty_like(attn))
     dqkv = torch.empty_like(qkv)
-    delta = torch.empty(B * S * H, dtype=torch.float32, device=dy.device)
+    _zero_packed_tail(dqkv, cu_seqlens)
+    delta = torch.empty(qkv.shape[0] * H, dtype=torch.float32, device=dy.device)
     q8 = impl.attn_dy_q(wqkv, x, qkv.shape[0]) if (impl is not BF16 and hasattr(impl, "attn_dy_q")) else None
     if q8 is not None or (impl is BF16 and bqkv is not None):
         # the QKV bias gradient (column sums of dQKV) from the backward kernels themselves
@@ -363,20 +388,20 @@ _ATTN_SCALE = 1.0 / 8.0  # 1/sqrt(head_dim = 64)
 
 class _AttentionBlock(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, wqkv, bqkv, wo, bo, lens, B, S, H, impl, attn_drop=None):
-        y, saved = _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl, attn_drop=attn_drop)
+    def forward(ctx, x, wqkv, bqkv, wo, bo, lens, B, S, H, impl, attn_drop=None, cu_seqlens=None):
+        y, saved = _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl, attn_drop=attn_drop, cu_seqlens=cu_seqlens)
         ctx.save_for_backward(*saved)
         ctx.params, ctx.impl = (wqkv, bqkv, wo, bo), impl
-        ctx.lens, ctx.dims, ctx.attn_drop = lens, (B, S, H), attn_drop
+        ctx.lens, ctx.dims, ctx.attn_drop, ctx.cu = lens, (B, S, H), attn_drop, cu_seqlens
         return y
 
     @staticmethod
     def backward(ctx, dy):
         G = _Grads()
         grads = _attn_bwd(ctx.saved_tensors, ctx.params, ctx.lens, *ctx.dims, dy.contiguous().to(torch.bfloat16), G,
-                          impl=ctx.impl, attn_drop=ctx.attn_drop)
+                          impl=ctx.impl, attn_drop=ctx.attn_drop, cu_seqlens=ctx.cu)
         G.done()
-        return grads + (None, None, None, None, None, None)
+        return grads + (None, None, None, None, None, None, None)
 
 
 class _FFNBlock(torch.autograd.Function):
@@ -416,16 +441,18 @@ class _AttentionLNBlock(torch.autograd.Function):
     gradient (column sums of its dx), so no separate pass over dy."""
 
     @staticmethod
-    def forward(ctx, x, wqkv, bqkv, wo, bo, gamma, beta, lens, B, S, H, eps, impl, drop=None, attn_drop=None):
+    def forward(ctx, x, wqkv, bqkv, wo, bo, gamma, beta, lens, B, S, H, eps, impl, drop=None, attn_drop=None,
+                cu_seqlens=None):
         if drop is None:
-            a, s1 = _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl, attn_drop=attn_drop)
+            a, s1 = _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl, attn_drop=attn_drop, cu_seqlens=cu_seqlens)
             y, s2 = _ln_fwd(a, gamma, beta, eps)
         else:  # LN(dropout(out-proj) + x): dropout and the residual add inside the LayerNorm kernel
-            a, s1 = _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl, residual=False, attn_drop=attn_drop)
+            a, s1 = _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl, residual=False, attn_drop=attn_drop,
+                              cu_seqlens=cu_seqlens)
             y, s2 = _dropout_add_ln_fwd(a, x, gamma, beta, eps, drop)
         ctx.save_for_backward(*s1, *s2)
         ctx.params, ctx.beta, ctx.impl = (wqkv, bqkv, wo, bo), beta, impl
-        ctx.lens, ctx.dims, ctx.drop, ctx.attn_drop = lens, (B, S, H), drop, attn_drop
+        ctx.lens, ctx.dims, ctx.drop, ctx.attn_drop, ctx.cu = lens, (B, S, H), drop, attn_drop, cu_seqlens
         return y
 
     @staticmethod
@@ -440,9 +467,9 @@ class _AttentionLNBlock(torch.autograd.Function):
             dres, dg, db, dbo, da = _ln_bwd(t[4:], ctx.beta, dy.contiguous().to(torch.bfloat16), G,
                                             dxsum_param=ctx.params[3], drop=ctx.drop)
         dx, dwqkv, dbqkv, dwo, dbo = _attn_bwd(t[:4], ctx.params, ctx.lens, *ctx.dims, da, G, dbo=dbo,
-                                               impl=ctx.impl, dres=dres, attn_drop=ctx.attn_drop)
+                                               impl=ctx.impl, dres=dres, attn_drop=ctx.attn_drop, cu_seqlens=ctx.cu)
         G.done()
-        return dx, dwqkv, dbqkv, dwo, dbo, dg, db, None, None, None, None, None, None, None, None
+        return dx, dwqkv, dbqkv, dwo, dbo, dg, db, None, None, None, None, None, None, None, None, None
 
 
 class _FFNLNBlock(torch.autograd.Function):
@@ -478,14 +505,17 @@ class _FFNLNBlock(torch.autograd.Function):
 
 class _Embeddings(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, ids, tt, ww, wp, wt, S):
+    def forward(ctx, ids, tt, ww, wp, wt, S, pos=None, cu_seqlens=None):
         C = require_native()
         ids = ids.contiguous().view(-1).to(torch.int64)
         ttf = tt.contiguous().view(-1).to(torch.int64) if tt is not None else None
         D = ww.shape[1]
         out = torch.empty(ids.numel(), D, dtype=torch.bfloat16, device=ids.device)
-        C.embed_fwd(ids, ttf, bf16_weight(ww), bf16_weight(wp), bf16_weight(wt), out, S)
+        if (pos is None) != (cu_seqlens is None):
+            raise ValueError("packed embeddings take both pos and cu_seqlens")
+        C.embed_fwd(ids, ttf, bf16_weight(ww), bf16_weight(wp), bf16_weight(wt), out, S, pos=pos)
         ctx.save_for_backward(ids, ttf if ttf is not None else torch.empty(0, dtype=torch.int64))
+        ctx.cu = cu_seqlens
         ctx.meta = (tt is not None, S, ww.shape, wp.shape, wt.shape)
         ctx.tables = (ww, wp, wt)
         return out
@@ -513,9 +543,9 @@ class _Embeddings(torch.autograd.Function):
         # tokens in order (no atomics, bitwise reproducible)
         sid, perm = torch.sort(ids.view(-1).clamp(0, sw[0] - 1), stable=True)
         part = torch.empty(S * 2 * D, dtype=torch.float32, device=dout.device)
-        C.embed_bwd(sid, perm, ttf if has_tt else None, dout, gw, gp, gt, part, S)
+        C.embed_bwd(sid, perm, ttf if has_tt else None, dout, gw, gp, gt, part, S, cu_seqlens=ctx.cu)
         G.done()
-        return (None, None) + ret + (None,)
+        return (None, None) + ret + (None, None, None)
 
 
 class _ClassifierHead(torch.autograd.Function):
@@ -572,11 +602,16 @@ def _mark_training(impl) -> None:
 
 
 def attention_block(x, wqkv, bqkv, wo, bo, lens: Optional[torch.Tensor], B: int, S: int, H: int, impl=BF16,
-                    attn_drop=None):
+                    attn_drop=None, cu_seqlens: Optional[torch.Tensor] = None):
     """``attn_drop`` = (p, seed, site, rank): attention-probability dropout inside the flash attention
-    kernels (the byte mask of ops/dropout.py: ``p`` is applied as round(p * 256) / 256). None: none."""
+    kernels (the byte mask of ops/dropout.py: ``p`` is applied as round(p * 256) / 256). None: none.
+    ``cu_seqlens`` (int32 [B + 1], device): x is a packed [T, D] batch (``pack_batch``), ``S`` is
+    max_seqlen and ``lens`` is unused. The dropout mask of element (b, h, q, k) is the padded run's.
+    x may end in tail rows past cu_seqlens[B] that belong to no sequence: fewer than PACK_ROW_MULTIPLE
+    of them (``pack_batch`` keeps to that), since only that many trailing rows of the attention output
+    and of dQKV are zeroed (``_zero_packed_tail``)."""
     _mark_training(impl)
-    return _AttentionBlock.apply(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl, attn_drop)
+    return _AttentionBlock.apply(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl, attn_drop, cu_seqlens)
 
 
 def ffn_block(x, w1, b1, w2, b2, impl=BF16):
@@ -585,12 +620,15 @@ def ffn_block(x, w1, b1, w2, b2, impl=BF16):
 
 
 def attention_ln_block(x, wqkv, bqkv, wo, bo, gamma, beta, lens: Optional[torch.Tensor], B: int, S: int, H: int,
-                       eps: float, impl=BF16, drop=None, attn_drop=None):
+                       eps: float, impl=BF16, drop=None, attn_drop=None, cu_seqlens: Optional[torch.Tensor] = None):
     """``drop`` = (p, seed, site, rank): hidden dropout on the out-projection's output, before the
     residual add, fused into the LayerNorm kernels (mask: ops/dropout.py). None: no dropout.
-    ``attn_drop`` = (p, seed, site, rank): attention-probability dropout (see attention_block)."""
+    ``attn_drop`` = (p, seed, site, rank): attention-probability dropout (see attention_block).
+    ``cu_seqlens``: packed batch, with fewer than PACK_ROW_MULTIPLE tail rows (see attention_block);
+    hidden-dropout masks are indexed by packed row."""
     _mark_training(impl)
-    return _AttentionLNBlock.apply(x, wqkv, bqkv, wo, bo, gamma, beta, lens, B, S, H, eps, impl, drop, attn_drop)
+    return _AttentionLNBlock.apply(x, wqkv, bqkv, wo, bo, gamma, beta, lens, B, S, H, eps, impl, drop, attn_drop,
+                                   cu_seqlens)
 
 
 def ffn_ln_block(x, w1, b1, w2, b2, gamma, beta, eps: float, impl=BF16, drop=None):
@@ -628,5 +666,67 @@ def dropout(x, p: float, seed: int, site: int, rank: int):
     return _Dropout.apply(x, p, seed, site, rank)
 
 
-def embeddings(ids, tt, ww, wp, wt, S: int):
-    return _Embeddings.apply(ids, tt, ww, wp, wt, S)
+def embeddings(ids, tt, ww, wp, wt, S: int, pos=None, cu_seqlens=None):
+    """Padded form: ids / tt [B, S], position = column. Packed form (``pack_batch``): ids / tt [T],
+    ``pos`` int32 [T] (index inside the token's own sequence), ``cu_seqlens`` int32 [B + 1], S = max_seqlen."""
+    return _Embeddings.apply(ids, tt, ww, wp, wt, S, pos, cu_seqlens)
+
+
+class PackedBatch:
+    """A right-padded [B, S] batch without its pads: ``ids`` / ``tt`` (or None) [T], ``pos`` int32 [T]
+    (index inside the token's own sequence), ``cu_seqlens`` int32 [B + 1] (sequence b = rows cu[b] ..
+    cu[b + 1]; ``cu_seqlens[:-1]`` are the CLS rows), ``index`` int64 [T] (the flat b * S + pos of every
+    kept token), ``max_seqlen`` = S and ``tokens`` = T as a host int. ``rows`` >= T is the row count of
+    ``ids`` / ``tt`` / ``pos``: with ``row_multiple`` the packed matrix ends in ``rows - T`` inert tail
+    rows (token 0 at position 0) that belong to no sequence, see ``pack_batch``."""
+
+    __slots__ = ("ids", "tt", "pos", "cu_seqlens", "index", "max_seqlen", "tokens", "batch", "rows")
+
+    def __init__(self, ids, tt, pos, cu_seqlens, index, max_seqlen, tokens, batch, rows):
+        self.ids, self.tt, self.pos, self.cu_seqlens, self.index = ids, tt, pos, cu_seqlens, index
+        self.max_seqlen, self.tokens, self.batch, self.rows = max_seqlen, tokens, batch, rows
+
+    @property
+    def cls_rows(self):
+        return self.cu_seqlens[:-1].to(torch.int64)
+
+
+PACK_ROW_MULTIPLE = 256  # the row tile of the fast GEMM kernels (M of forward / dgrad, K of wgrad)
+
+
+def pack_batch(ids, lens, token_type_ids=None, row_multiple: int = 1) -> PackedBatch:
+    """Drop the pads of ``ids`` [B, S] given ``lens`` [B] (right padding: row b holds its tokens at
+    columns 0 .. lens[b] - 1; lengths are clamped to 1 .. S). Runs on the device of ``ids`` with torch
+    index ops; reading T = sum(lens) back to size the packed tensors is the one device-to-host read.
+
+    ``row_multiple`` > 1 rounds the row count up to that multiple (when that still fits B * S) with
+    inert tail rows: the 256-row GEMM tiles need it, an odd T sends every linear layer to the slow
+    general kernels. The tail rows belong to no sequence (cu_seqlens[B] = T): attention neither reads
+    nor writes them (the attention blocks zero them), they never reach a CLS row, and their gradients
+    are exactly zero, so they add nothing to any weight gradient."""
+    B, S = ids.shape
+    lens = lens.to(device=ids.device, dtype=torch.int64).clamp(1, S)
+    cu = torch.zeros(B + 1, dtype=torch.int32, device=ids.device)
+    cu[1:] = torch.cumsum(lens, 0)
+    keep = torch.arange(S, device=ids.device)[None, :] < lens[:, None]
+    index = keep.view(-1).nonzero().view(-1)  # (the host read of T happens here)
+    T = int(index.numel())
+    pos = (index % S).to(torch.int32)
+    pids = ids.reshape(-1).index_select(0, index)
+    ptt = token_type_ids.reshape(-1).index_select(0, index) if token_type_ids is not None else None
+    rows = -(-T // row_multiple) * row_multiple
+    if rows > T and rows <= B * S:
+        tail = rows - T
+        pids = torch.cat((pids, pids.new_zeros(tail)))
+        pos = torch.cat((pos, pos.new_zeros(tail)))
+        ptt = torch.cat((ptt, ptt.new_zeros(tail))) if ptt is not None else None
+    else:
+        rows = T
+    return PackedBatch(pids, ptt, pos, cu, index, S, T, B, rows)
+
+
+def unpack_rows(x, packed: PackedBatch, fill=0):
+    """The packed rows ``x`` [T, ...] back at their padded places: [B * S, ...] with ``fill`` at the pads."""
+    out = x.new_full((packed.batch * packed.max_seqlen,) + tuple(x.shape[1:]), fill)
+    out.index_copy_(0, packed.index, x[:packed.tokens])
+    return out
