@@ -8,6 +8,7 @@ baseline of the same model (torch.autocast + SDPA + hipBLASLt) for comparison.
     python benchmarks/bert_bench.py --impl native --attention-dropout 0.1   # ... in the flash attention kernels
     python benchmarks/bert_bench.py --impl native --min-len 64            # variable-length rows, right-padded
     python benchmarks/bert_bench.py --impl native --min-len 64 --unpad    # ... run on the real tokens only
+    python benchmarks/bert_bench.py --impl native --optimizer lamb --no-decay-1d   # LAMB, biases / LayerNorm excluded
 
 Prints one JSON line per run (samples/s, tokens/s, ms/step, model TFLOP/s; ``tokens`` = the real
 tokens T of the batch, ``fill`` = T / (batch * seq), ``unpad``; tokens/s and TFLOP/s count batch * seq).
@@ -30,7 +31,7 @@ import torch.nn.functional as F  # noqa: E402
 
 def run(args):
     from ml_trainer_amd.models.bert import BertClassifier, bert_config
-    from ml_trainer_amd.ops.optim import FusedAdamW
+    from ml_trainer_amd.ops.optim import build_optimizer
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
     over = {"layers": args.layers} if args.layers else {}
@@ -45,9 +46,13 @@ def run(args):
     cfg = bert_config(args.model, **over)
     m = BertClassifier(cfg).to(dev)
     if args.impl == "native":
-        opt = FusedAdamW(m.parameters(), lr=1e-4, weight_decay=0.01)
+        # adamw without --no-decay-1d is FusedAdamW's plain flat launch, as this benchmark always ran it
+        opt = build_optimizer(args.optimizer, m.parameters(), lr=1e-4, weight_decay=0.01,
+                              no_decay_1d=args.no_decay_1d)
         fwd = m
     else:
+        if args.optimizer != "adamw" or args.no_decay_1d:
+            raise SystemExit("--optimizer / --no-decay-1d apply to --impl native")
         opt = torch.optim.AdamW(m.parameters(), lr=1e-4, weight_decay=0.01, fused=True)
         fwd = m.forward_torch_bf16
     ids = torch.randint(5, cfg.vocab_size, (args.batch, args.seq), device=dev)
@@ -81,7 +86,8 @@ def run(args):
            "attention_dropout": args.attention_dropout, "ms_per_step": dt * 1e3, "samples_per_s": args.batch / dt,
            "tokens_per_s": tokens / dt, "model_tflops": flops / dt / 1e12, "loss": float(loss.detach()),
            "peak_mem_gb": torch.cuda.max_memory_allocated() / 2 ** 30,
-           "min_len": args.min_len, "tokens": real, "fill": real / tokens, "unpad": bool(args.unpad)}
+           "min_len": args.min_len, "tokens": real, "fill": real / tokens, "unpad": bool(args.unpad),
+           "optimizer": args.optimizer, "no_decay_1d": bool(args.no_decay_1d)}
     print(json.dumps(rec), flush=True)
     return rec
 
@@ -101,6 +107,10 @@ def main():
     ap.add_argument("--min-len", type=int, default=0,
                     help="variable-length rows: lengths uniform in [min-len, seq], right-padded (default: full rows)")
     ap.add_argument("--unpad", action="store_true", help="BertConfig.unpad: run the encoder on the real tokens only")
+    ap.add_argument("--optimizer", choices=["adamw", "lamb"], default="adamw",
+                    help="native optimizer: adamw (one flat launch) or lamb (three launches, layer-wise trust ratio)")
+    ap.add_argument("--no-decay-1d", action="store_true",
+                    help="no weight decay (lamb: no trust ratio) on biases and LayerNorm parameters (ndim <= 1)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     recs = []

@@ -18,7 +18,8 @@ large), ``--synthetic``, ``--per_device_batch``, ``--no_engine``,
 ``--dropout`` (BERT hidden dropout), ``--attention_dropout`` (BERT attention-probability dropout,
 inside the flash attention kernels; applied as round(p * 256) / 256), ``--unpad`` (BERT: drop the pad
 tokens before the embeddings and run the encoder on the real tokens only), ``--min_seq_len L``
-(variable-length synthetic text, lengths uniform in [L, seq_len], right-padded with ``--pad_id``).
+(variable-length synthetic text, lengths uniform in [L, seq_len], right-padded with ``--pad_id``), ``--optimizer lamb`` (layer-wise trust ratios on the flat buffer) and
+``--no_decay_1d`` (adamw / lamb: biases and LayerNorm parameters take no weight decay).
 """
 from __future__ import annotations
 
@@ -118,7 +119,8 @@ def main(args):
     options = {"per_device_batch": args.per_device_batch, "resume": args.resume,
                "metrics_jsonl": args.metrics_jsonl, "amp": args.amp, "progress": not args.no_progress,
                "precision": getattr(args, "precision", "fp32"),
-               "zero_stage": args.zero_stage, "async_checkpoint": args.async_checkpoint}
+               "zero_stage": args.zero_stage, "async_checkpoint": args.async_checkpoint,
+               "no_decay_1d": getattr(args, "no_decay_1d", False)}
     if args.no_engine:
         options["use_engine"] = False
     if args.log_jsonl:  # every structured log record, one JSON object per line
@@ -134,7 +136,8 @@ def build_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser()
     parser.add_argument("--batch_size", type=int, default=32, help="input batch size for training (default: 32)")
     parser.add_argument("--epochs", type=int, default=10, help="number of epochs to train (default: 10)")
-    parser.add_argument("--optimizer", type=str, default="sgd", help="optimizer for backward pass (default: sgd)")
+    parser.add_argument("--optimizer", type=str, default="sgd",
+                        help="optimizer for backward pass: sgd|adam|adagrad|adamax|adamw|lamb (default: sgd)")
     parser.add_argument("--lr", type=float, default=0.001, help="learning rate (default: 0.001)")
     parser.add_argument("--momentum", type=float, default=0.9, help="Optimizer momentum (default: 0.9)")
     parser.add_argument("--weight_decay", type=float, default=0.0, help="Optimizer weight decay (default: 0.0)")
@@ -175,6 +178,10 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--pad_id", type=int, default=None,
                         help="BERT: token id of the right padding (key lengths are derived from it); defaults to 0 "
                              "when --min_seq_len is given")
+    parser.add_argument("--no_decay_1d", action="store_true",
+                        help="--optimizer adamw|lamb: no weight decay (lamb: and no trust ratio) on parameters with "
+                             "ndim <= 1, i.e. biases and LayerNorm weight / bias. An error for the other optimizers "
+                             "and with --zero_stage 1")
     parser.add_argument("--synthetic", action="store_true", help="use the seeded synthetic dataset")
     parser.add_argument("--synthetic_size", type=int, default=0)
     parser.add_argument("--seq_len", type=int, default=512)

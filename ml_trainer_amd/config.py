@@ -50,6 +50,8 @@ class TrainerOptions:
     precision: str = "fp32"               # fused LeNet engine: "fp32" (reference dtype) | "bf16" (MFMA step,
                                           # fp32 masters; BASELINE.json configs 2/3)
     grad_clip: Optional[float] = None     # clip-by-global-norm (fused kernel)
+    no_decay_1d: bool = False             # adamw | lamb: no weight decay (lamb: no trust ratio either) on
+                                          # parameters with ndim <= 1 (biases, LayerNorm weight and bias)
     grad_accum_steps: int = 1             # micro-batches per optimizer step (DDP no_sync between)
     # --- distributed ----------------------------------------------------------------
     bucket_cap_mb: float = 32.0

@@ -103,6 +103,102 @@ void flat_optim(Tensor p, Tensor g, c10::optional<Tensor> s1, c10::optional<Tens
                     cf, cur_stream());
 }
 
+// Arguments that flat_optim_seg and lamb_step share with flat_optim, checked the same way.
+struct StepPtrs {
+  const float* lr = nullptr;
+  const int64_t* lr_index = nullptr;
+  const int64_t* step = nullptr;
+  uint16_t* shadow = nullptr;
+  const float* coef = nullptr;
+  const unsigned* skip = nullptr;
+};
+
+static StepPtrs step_ptrs(int64_t n, const c10::optional<Tensor>& lr_t, const c10::optional<Tensor>& lr_index,
+                          const c10::optional<Tensor>& step_t, const c10::optional<Tensor>& shadow,
+                          const c10::optional<Tensor>& coef, const c10::optional<Tensor>& skip) {
+  StepPtrs s;
+  if (lr_t.has_value()) {
+    check_dev(*lr_t, "lr", at::kFloat, 1, 4);
+    s.lr = lr_t->data_ptr<float>();
+  }
+  if (lr_index.has_value()) {
+    TORCH_CHECK(lr_t.has_value(), "lr_index needs lr_t");
+    check_dev(*lr_index, "lr_index", at::kLong, 1, 8);
+    s.lr_index = lr_index->data_ptr<int64_t>();
+  }
+  if (step_t.has_value()) {
+    check_dev(*step_t, "step", at::kLong, 1, 8);
+    s.step = step_t->data_ptr<int64_t>();
+  }
+  if (shadow.has_value()) {
+    check_dev(*shadow, "shadow", at::kBFloat16, n);
+    s.shadow = reinterpret_cast<uint16_t*>(shadow->data_ptr());
+  }
+  if (coef.has_value()) {
+    check_dev(*coef, "coef", at::kFloat, 1, 4);
+    s.coef = coef->data_ptr<float>();
+  }
+  if (skip.has_value()) {
+    check_dev(*skip, "skip", at::kInt, 1, 4);
+    s.skip = reinterpret_cast<const unsigned*>(skip->data_ptr<int>());
+  }
+  return s;
+}
+
+// the flat buffers and the segment table; returns {nchunks, nt}
+static std::pair<int, int> check_seg(const Tensor& p, const Tensor& g, const Tensor& s1, const Tensor& s2,
+                                     const Tensor& chunks, const Tensor& wd) {
+  const int64_t n = p.numel();
+  TORCH_CHECK(n % 4 == 0, "flat buffer length must be a multiple of 4");
+  TORCH_CHECK(n / 4 < (int64_t(1) << 31), "flat buffer too long for the 32-bit segment table");
+  check_dev(p, "p", at::kFloat, n);
+  check_dev(g, "g", at::kFloat, n);
+  check_dev(s1, "s1", at::kFloat, n);
+  check_dev(s2, "s2", at::kFloat, n);
+  TORCH_CHECK(g.numel() == n && s1.numel() == n && s2.numel() == n, "p, g, s1, s2 must have one length");
+  TORCH_CHECK(chunks.dim() == 2 && chunks.size(1) == 4, "chunks must be [nchunks, 4]");
+  check_dev(chunks, "chunks", at::kInt, 0);
+  TORCH_CHECK(wd.dim() == 1, "wd must be [tensors]");
+  check_dev(wd, "wd", at::kFloat, 0, 4);
+  TORCH_CHECK(chunks.size(0) < (int64_t(1) << 31) && wd.numel() < (int64_t(1) << 31), "segment table too long");
+  return {(int)chunks.size(0), (int)wd.numel()};
+}
+
+void flat_optim_seg(Tensor p, Tensor g, Tensor s1, Tensor s2, Tensor chunks, Tensor wd, double lr, double beta1,
+                    double beta2, double eps, double grad_scale, bool maximize, c10::optional<Tensor> lr_t,
+                    c10::optional<Tensor> lr_index, c10::optional<Tensor> step_t, double t_host,
+                    c10::optional<Tensor> shadow, c10::optional<Tensor> coef, c10::optional<Tensor> skip,
+                    int max_blocks) {
+  const auto [nchunks, nt] = check_seg(p, g, s1, s2, chunks, wd);
+  const StepPtrs s = step_ptrs(p.numel(), lr_t, lr_index, step_t, shadow, coef, skip);
+  const OptHyper h = make_hyper(OPT_ADAMW, lr, 0.0, 0.0, 0.0, beta1, beta2, eps, 0.0, grad_scale, false, maximize);
+  launch_flat_optim_seg(p.data_ptr<float>(), g.data_ptr<float>(), s1.data_ptr<float>(), s2.data_ptr<float>(),
+                        p.numel(), chunks.data_ptr<int>(), nchunks, wd.data_ptr<float>(), nt, h, s.lr, s.lr_index,
+                        s.step, (float)t_host, s.shadow, s.coef, s.skip, max_blocks, cur_stream());
+}
+
+void lamb_step(Tensor p, Tensor g, Tensor m, Tensor v, Tensor chunks, Tensor tseg, Tensor wd, Tensor adapt,
+               Tensor part, Tensor norms, Tensor trust, double lr, double beta1, double beta2, double eps,
+               double grad_scale, bool maximize, c10::optional<Tensor> lr_t, c10::optional<Tensor> lr_index,
+               c10::optional<Tensor> step_t, double t_host, c10::optional<Tensor> shadow,
+               c10::optional<Tensor> coef, c10::optional<Tensor> skip, int max_blocks, int stages) {
+  const auto [nchunks, nt] = check_seg(p, g, m, v, chunks, wd);
+  TORCH_CHECK(tseg.dim() == 2 && tseg.size(0) == nt && tseg.size(1) == 2, "tseg must be [tensors, 2]");
+  check_dev(tseg, "tseg", at::kInt, 0, 8);
+  check_dev(adapt, "adapt", at::kInt, nt, 4);
+  check_dev(part, "part", at::kFloat, 2 * (int64_t)nchunks, 8);
+  check_dev(norms, "norms", at::kFloat, 2 * (int64_t)nt, 8);
+  check_dev(trust, "trust", at::kFloat, nt, 4);
+  TORCH_CHECK(stages >= 1 && stages <= 7, "stages is a mask of the three launches");
+  const StepPtrs s = step_ptrs(p.numel(), lr_t, lr_index, step_t, shadow, coef, skip);
+  const OptHyper h = make_hyper(OPT_LAMB, lr, 0.0, 0.0, 0.0, beta1, beta2, eps, 0.0, grad_scale, false, maximize);
+  launch_lamb_step(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), p.numel(),
+                   chunks.data_ptr<int>(), nchunks, tseg.data_ptr<int>(), wd.data_ptr<float>(),
+                   adapt.data_ptr<int>(), nt, part.data_ptr<float>(), norms.data_ptr<float>(),
+                   trust.data_ptr<float>(), h, s.lr, s.lr_index, s.step, (float)t_host, s.shadow, s.coef, s.skip,
+                   max_blocks, stages, cur_stream());
+}
+
 void sq_norm(Tensor x, Tensor out) {
   TORCH_CHECK(x.numel() % 4 == 0, "sq_norm needs numel % 4 == 0");
   check_dev(x, "x", at::kFloat, x.numel());
@@ -1462,6 +1558,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("maximize"), py::arg("lr_t") = py::none(), py::arg("lr_index") = py::none(),
         py::arg("step_t") = py::none(), py::arg("t_host") = 1.0, py::arg("shadow") = py::none(),
         py::arg("coef") = py::none());
+  m.def("optim_chunk_elems", &optim_chunk_elems);
+  m.def("flat_optim_seg", &flat_optim_seg, py::arg("p"), py::arg("g"), py::arg("s1"), py::arg("s2"),
+        py::arg("chunks"), py::arg("wd"), py::arg("lr"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"),
+        py::arg("grad_scale"), py::arg("maximize"), py::arg("lr_t") = py::none(), py::arg("lr_index") = py::none(),
+        py::arg("step_t") = py::none(), py::arg("t_host") = 1.0, py::arg("shadow") = py::none(),
+        py::arg("coef") = py::none(), py::arg("skip") = py::none(), py::arg("max_blocks") = 0);
+  m.def("lamb_step", &lamb_step, py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("chunks"),
+        py::arg("tseg"), py::arg("wd"), py::arg("adapt"), py::arg("part"), py::arg("norms"), py::arg("trust"),
+        py::arg("lr"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"), py::arg("grad_scale"),
+        py::arg("maximize"), py::arg("lr_t") = py::none(), py::arg("lr_index") = py::none(),
+        py::arg("step_t") = py::none(), py::arg("t_host") = 1.0, py::arg("shadow") = py::none(),
+        py::arg("coef") = py::none(), py::arg("skip") = py::none(), py::arg("max_blocks") = 0,
+        py::arg("stages") = 7);
   m.def("sq_norm", &sq_norm);
   m.def("clip_coef", &clip_coef);
   m.def("cast_bf16", &cast_bf16);

@@ -18,6 +18,25 @@ void launch_flat_optim(float* p, const float* g, float* s1, float* s2, int64_t n
                        const float* lr_ptr, const int64_t* lr_index_ptr, const int64_t* step_ptr, float t_host,
                        uint16_t* shadow_bf16, const float* coef_ptr, hipStream_t stream,
                        const unsigned* skip = nullptr);  // skip: no update while *skip != 0
+// Per-tensor updates through a segment table over the flat buffer (built by ops/optim.py):
+//   chunks[nchunks][4] = {tensor id, first float4, float4 count (<= optim_chunk_elems() / 4), 0}
+//   tseg[nt][2] = {first chunk, chunk count}; wd[nt]; adapt[nt] (0/1)
+// lr / step / coef / skip as launch_flat_optim. max_blocks > 0 lowers the block cap (results do not
+// depend on it). An entry that points outside the buffer or the tables is skipped by the kernels.
+int optim_chunk_elems();
+// AdamW with weight_decay = wd[tensor], one launch; a tensor's bits equal launch_flat_optim's with that decay
+void launch_flat_optim_seg(float* p, const float* g, float* s1, float* s2, int64_t n, const int* chunks,
+                           int nchunks, const float* wd, int nt, const OptHyper& h, const float* lr_ptr,
+                           const int64_t* lr_index_ptr, const int64_t* step_ptr, float t_host,
+                           uint16_t* shadow_bf16, const float* coef_ptr, const unsigned* skip, int max_blocks,
+                           hipStream_t stream);
+// LAMB: stage 1 (moments, per-chunk sums of w^2 and u^2 -> part[nchunks][2]), finalize (norms[nt][2] = the sums
+// of squares, trust[nt]), stage 2 (apply, shadow). stages: bit 0 / 1 / 2 selects the launches (7 = a step).
+void launch_lamb_step(float* p, const float* g, float* m, float* v, int64_t n, const int* chunks, int nchunks,
+                      const int* tseg, const float* wd, const int* adapt, int nt, float* part, float* norms,
+                      float* trust, const OptHyper& h, const float* lr_ptr, const int64_t* lr_index_ptr,
+                      const int64_t* step_ptr, float t_host, uint16_t* shadow_bf16, const float* coef_ptr,
+                      const unsigned* skip, int max_blocks, int stages, hipStream_t stream);
 // out[0] = sum of squares of x[0..n): per-block partials into `part` (sq_norm_partials_needed() floats,
 // contents irrelevant), then summed in block order -> bitwise reproducible. out is overwritten.
 int sq_norm_partials_needed();

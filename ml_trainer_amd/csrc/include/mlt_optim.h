@@ -6,13 +6,21 @@
 // src/trainer.py:123-138): SGD(momentum, dampening, nesterov, weight_decay as L2),
 // Adam (L2 weight decay), AdamW (decoupled decay), Adagrad (lr_decay,
 // initial_accumulator_value=0), Adamax (infinity norm).
+//
+// LAMB (You et al., layer-wise trust ratio; apex FusedLAMB with use_nvlamb=False) is not a
+// torch.optim rule and not an element-wise one: tensor i moves along
+//   u = (m / bc1) / (sqrtf(v) / sqrtf(bc2) + eps) + wd_i * w
+// by lr * r_i with r_i = |w_i| / |u_i| (1 for an excluded tensor or a zero norm), so it needs two
+// per-tensor norms between the moment update and the weight update. lamb_moments / lamb_direction /
+// lamb_trust / lamb_apply are the pieces; the three launches of optim.hip put them together. The
+// moments are Adam's, bit for bit (the same expressions as opt_update_k<OPT_ADAM> with no decay).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace mlt {
 
-enum OptKind : int { OPT_SGD = 0, OPT_ADAM = 1, OPT_ADAMW = 2, OPT_ADAGRAD = 3, OPT_ADAMAX = 4 };
+enum OptKind : int { OPT_SGD = 0, OPT_ADAM = 1, OPT_ADAMW = 2, OPT_ADAGRAD = 3, OPT_ADAMAX = 4, OPT_LAMB = 5 };
 
 struct OptHyper {
   float lr;            // used when lr_ptr == nullptr
@@ -104,6 +112,30 @@ __device__ __forceinline__ void opt_update_k(const OptHyper& h, float lr, float 
     p = fmaf(-clr, s1 / s2, p);
   }
 }
+
+// ---- LAMB --------------------------------------------------------------------------------
+// Moments of one element: g scaled / negated as in opt_update_k, then Adam's exp_avg / exp_avg_sq.
+__device__ __forceinline__ void lamb_moments(const OptHyper& h, float g, float& m, float& v) {
+  g *= h.grad_scale;
+  if (h.maximize) g = -g;
+  m = fmaf(h.omb1, g - m, m);
+  v = fmaf(1.f - h.omb2, v, h.omb2 * g * g);
+}
+
+// Update direction of one element from the UPDATED moments. Stage 1 (norms) and stage 2 (apply) both
+// call this with the same m, v, w, so both see the same bits; every fused multiply-add is written
+// out, none is left to the compiler's contraction.
+__device__ __forceinline__ float lamb_direction(float wd, float eps, float bc1, float bc2, float w, float m,
+                                                float v) {
+  return fmaf(wd, w, (m / bc1) / (sqrtf(v) / sqrtf(bc2) + eps));
+}
+
+// Trust ratio of a tensor from its sums of squares: |w| / |u|, 1 when not adapted or a norm is 0.
+__device__ __forceinline__ float lamb_trust(int adapt, float w_sq, float u_sq) {
+  return (adapt != 0 && w_sq > 0.f && u_sq > 0.f) ? sqrtf(w_sq) / sqrtf(u_sq) : 1.f;
+}
+
+__device__ __forceinline__ float lamb_apply(float lr, float r, float u, float w) { return fmaf(-lr * r, u, w); }
 
 __device__ __forceinline__ void opt_update(const OptHyper& h, float lr, float t, float& p, float g, float& s1,
                                            float& s2) {

@@ -120,6 +120,10 @@ class Trainer:
         self.lr = cfg["lr"]
         self.criterion_type = cfg["criterion"]
         self.metric = cfg["metric"]
+        per_tensor = self.opts.no_decay_1d or str(self.optimizer_type or "").lower() == "lamb"
+        if self.opts.zero_stage == 1 and per_tensor:
+            raise ValueError("zero_stage=1 cannot be combined with optimizer 'lamb' or no_decay_1d: ZeRO-1 shards "
+                             "cut tensors, and a per-tensor norm or decay over a sharded tensor needs a collective")
         self.pred_function_type = cfg["pred_function"]
         self.model_dir = cfg["model_dir"]
         backend = cfg["backend"]
@@ -230,9 +234,10 @@ class Trainer:
             return None
         opt = build_optimizer(self.optimizer_type, params, lr=self.lr, momentum=self.momentum,
                               weight_decay=self.weight_decay,
-                              flat=self._zero.shard if self._zero is not None else self.flat)
+                              flat=self._zero.shard if self._zero is not None else self.flat,
+                              no_decay_1d=self.opts.no_decay_1d)
         if opt is None:
-            raise ValueError(f"unknown optimizer {self.optimizer_type!r} (sgd|adam|adagrad|adamax|adamw)")
+            raise ValueError(f"unknown optimizer {self.optimizer_type!r} (sgd|adam|adagrad|adamax|adamw|lamb)")
         return self._zero.attach_optimizer(opt) if self._zero is not None else opt
 
     def _get_criterion(self):
@@ -284,6 +289,7 @@ class Trainer:
         ok = (isinstance(self._core, MLModel) and self.criterion_type == "cross_entropy"
               and self.metric in ("accuracy", None) and self.pred_function_type in (None, "softmax", "logsoftmax")
               and isinstance(self.optimizer, FusedOptimizer) and len(self.optimizer.param_groups) == 1
+              and not self.optimizer.per_tensor  # the engine's kernels embed the five element-wise rules
               and self.optimizer.flats[0] is self.flat and o.grad_accum_steps == 1 and o.grad_clip is None
               and o.amp is None)
         if not ok:
