@@ -5,6 +5,8 @@ import pytest
 import torch
 
 from ml_trainer_amd.ops._ext import require_native
+from tests.helpers import (assert_within, dgelu_bound, gelu64, gelu_grad64, gelu_out_bound, gemm_bound,
+                           gemm_expected, gemm_t32)
 
 pytestmark = pytest.mark.gpu
 
@@ -17,6 +19,28 @@ def _ref(A, B, a_mn, b_mn):
     a = A.float().t() if a_mn else A.float()
     b = B.float() if b_mn else B.float().t()
     return a @ b
+
+
+def _ref64(A, B, a_mn, b_mn):
+    """fp64 operands in the mathematical layout (A [M,K], B [K,N]) for the derived bound of helpers.py."""
+    return (A.double().t() if a_mn else A.double()), (B.double() if b_mn else B.double().t())
+
+
+def _assert_bound(out, A64, B64, terms, what):
+    """out against the fp64 value of alpha A.B + bias + res + c_prev, per element, within helpers.gemm_bound."""
+    assert_within(out, gemm_expected(A64, B64, terms), gemm_bound(A64, B64, A64.shape[1], terms, out.dtype), what)
+
+
+def _assert_gelu(out, aux, A64, B64, terms, what):
+    """GELU epilogue: the saved pre-activation within the bf16 bound, the output within one bf16
+    rounding of fp64 GELU at the kernel's own aux."""
+    _assert_bound(aux, A64, B64, terms, what + " aux")
+    assert_within(out, gelu64(aux.double()), gelu_out_bound(aux.double()), what)
+
+
+def _assert_dgelu(out, pre, A64, B64, what):
+    exp, x = gemm_expected(A64, B64), pre.double()
+    assert_within(out, exp * gelu_grad64(x), dgelu_bound(exp, gemm_t32(A64, B64, A64.shape[1]), x, out.dtype), what)
 
 
 @pytest.mark.parametrize("a_mn,b_mn", [(0, 0), (0, 1), (1, 0), (1, 1)])
@@ -52,26 +76,22 @@ def test_epilogues(dev):
     A, B = _mk((M, K), dev, g), _mk((N, K), dev, g)
     bias = torch.randn(N, device=dev)
     res = _mk((M, N), dev, g)
-    ref = A.float() @ B.float().t()
+    A64, B64 = _ref64(A, B, 0, 0)
     # bias + residual + alpha
     out = torch.empty(M, N, dtype=torch.bfloat16, device=dev)
     C.gemm(A, B, out, False, False, bias=bias, res=res, alpha=0.5)
-    torch.testing.assert_close(out.float(), 0.5 * ref + bias + res.float(), rtol=2e-2, atol=3e-2)
+    _assert_bound(out, A64, B64, {"alpha": 0.5, "bias": bias.double(), "res": res.double()}, "bias + res + alpha")
     # GELU: pre-activation saved to aux
     aux = torch.empty(M, N, dtype=torch.bfloat16, device=dev)
     C.gemm(A, B, out, False, False, bias=bias, aux=aux, mode=1)
-    pre = ref + bias
-    torch.testing.assert_close(aux.float(), pre, rtol=2e-2, atol=3e-2)
-    torch.testing.assert_close(out.float(), torch.nn.functional.gelu(aux.float()), rtol=2e-2, atol=3e-2)
+    _assert_gelu(out, aux, A64, B64, {"bias": bias.double()}, "gelu")
     # dGELU: result * gelu'(aux)
-    x = aux.float().requires_grad_(True)
-    torch.nn.functional.gelu(x).backward(torch.ones_like(x))
     C.gemm(A, B, out, False, False, aux=aux, mode=2)
-    torch.testing.assert_close(out.float(), ref * x.grad, rtol=3e-2, atol=5e-2)
+    _assert_dgelu(out, aux, A64, B64, "dgelu")
     # fp32 accumulate
     acc = torch.ones(M, N, device=dev)
     C.gemm(A, B, acc, False, False, accumulate=True)
-    torch.testing.assert_close(acc, ref + 1, rtol=2e-3, atol=2e-3)
+    _assert_bound(acc, A64, B64, {"c_prev": torch.ones(M, N, dtype=torch.float64, device=dev)}, "accumulate")
 
 
 def test_colsum(dev):
@@ -94,32 +114,28 @@ def test_tile_kernels(dev, cfg, splits, a_mn, b_mn):
     A = _mk((K, M + 8) if a_mn else (M, K + 64), dev, g)
     A = A[:, :M] if a_mn else A[:, :K]
     B = _mk((K, N) if b_mn else (N, K), dev, g)
-    ref = _ref(A, B, a_mn, b_mn)
+    A64, B64 = _ref64(A, B, a_mn, b_mn)
     plan = C.gemm_plan(bool(a_mn), bool(b_mn), M, N, K, cfg, splits)
     assert plan[0] == cfg and plan[1] == splits
     for out_dtype in (torch.bfloat16, torch.float32):
         out = torch.empty(M, N, dtype=out_dtype, device=dev)
         C.gemm(A, B, out, bool(a_mn), bool(b_mn), cfg=cfg, splits=splits)
-        tol = 2e-2 if out_dtype == torch.bfloat16 else 2e-3
-        torch.testing.assert_close(out.float(), ref, rtol=tol, atol=tol * 8)
+        _assert_bound(out, A64, B64, None, f"plain {out_dtype}")
     bias = torch.randn(N, device=dev)
     res = _mk((M, N), dev, g)
     out = torch.empty(M, N, dtype=torch.bfloat16, device=dev)
     aux = torch.empty(M, N, dtype=torch.bfloat16, device=dev)
     C.gemm(A, B, out, bool(a_mn), bool(b_mn), bias=bias, aux=aux, mode=1, cfg=cfg, splits=splits)
-    torch.testing.assert_close(aux.float(), ref + bias, rtol=2e-2, atol=0.15)
-    torch.testing.assert_close(out.float(), torch.nn.functional.gelu(aux.float()), rtol=2e-2, atol=0.15)
+    _assert_gelu(out, aux, A64, B64, {"bias": bias.double()}, "gelu")
     C.gemm(A, B, out, bool(a_mn), bool(b_mn), res=res, alpha=0.5, cfg=cfg, splits=splits)
-    torch.testing.assert_close(out.float(), 0.5 * ref + res.float(), rtol=2e-2, atol=0.15)
+    _assert_bound(out, A64, B64, {"alpha": 0.5, "res": res.double()}, "res + alpha")
     acc = torch.ones(M, N, device=dev)
     C.gemm(A, B, acc, bool(a_mn), bool(b_mn), accumulate=True, cfg=cfg, splits=splits)
-    torch.testing.assert_close(acc, ref + 1, rtol=2e-3, atol=2e-2)
+    _assert_bound(acc, A64, B64, {"c_prev": torch.ones(M, N, dtype=torch.float64, device=dev)}, "accumulate")
     # dGELU epilogue (interior tile takes the prefetched side-operand path, tails the general one)
     pre = _mk((M, N), dev, g)
     C.gemm(A, B, out, bool(a_mn), bool(b_mn), aux=pre, mode=2, cfg=cfg, splits=splits)
-    x = pre.float()
-    dg = 0.5 * (1 + torch.erf(x * 0.7071067811865476)) + x * torch.exp(-0.5 * x * x) * 0.3989422804014327
-    torch.testing.assert_close(out.float(), ref * dg, rtol=2e-2, atol=0.15)
+    _assert_dgelu(out, pre, A64, B64, "dgelu")
 
 
 def test_tile_split_k_deterministic(dev):
@@ -370,33 +386,29 @@ def test_w4_asm_kernel(dev, b_mn):
     g = torch.Generator().manual_seed(71 + b_mn)
     A = _mk((M, K + 64), dev, g)[:, :K]
     B = _mk((K, N + 128), dev, g)[:, :N] if b_mn else _mk((N, K), dev, g)
-    ref = _ref(A, B, 0, b_mn)
+    A64, B64 = _ref64(A, B, 0, b_mn)
     assert C.gemm_plan(False, bool(b_mn), 65536, N, K)[0] == 7  # planner: tiles fill the chip
     assert C.gemm_plan(False, bool(b_mn), 1024, 1024, 65536)[0] != 7  # few tiles, long K: split-K
     for out_dtype in (torch.bfloat16, torch.float32):
         out = torch.empty(M, N, dtype=out_dtype, device=dev)
         C.gemm(A, B, out, False, bool(b_mn), cfg=7)
-        tol = 2e-2 if out_dtype == torch.bfloat16 else 2e-3
-        torch.testing.assert_close(out.float(), ref, rtol=tol, atol=tol * 8)
+        _assert_bound(out, A64, B64, None, f"plain {out_dtype}")
     bias = torch.randn(N, device=dev)
     out = torch.empty(M, N, dtype=torch.bfloat16, device=dev)
     aux = torch.empty(M, N, dtype=torch.bfloat16, device=dev)
     C.gemm(A, B, out, False, bool(b_mn), bias=bias, aux=aux, mode=1, cfg=7)
-    torch.testing.assert_close(aux.float(), ref + bias, rtol=2e-2, atol=0.15)
-    torch.testing.assert_close(out.float(), torch.nn.functional.gelu(aux.float()), rtol=2e-2, atol=0.15)
+    _assert_gelu(out, aux, A64, B64, {"bias": bias.double()}, "gelu")
     res = _mk((M, N), dev, g)
     C.gemm(A, B, out, False, bool(b_mn), res=res, alpha=0.5, cfg=7)
-    torch.testing.assert_close(out.float(), 0.5 * ref + res.float(), rtol=2e-2, atol=0.15)
+    _assert_bound(out, A64, B64, {"alpha": 0.5, "res": res.double()}, "res + alpha")
     pre = _mk((M, N), dev, g)
     C.gemm(A, B, out, False, bool(b_mn), aux=pre, mode=2, cfg=7)
-    x = pre.float()
-    dg = 0.5 * (1 + torch.erf(x * 0.7071067811865476)) + x * torch.exp(-0.5 * x * x) * 0.3989422804014327
-    torch.testing.assert_close(out.float(), ref * dg, rtol=2e-2, atol=0.15)
+    _assert_dgelu(out, pre, A64, B64, "dgelu")
     # outside the 256-multiple domain -> the ping-pong fallback, same numbers
     Bt = B[:, : N - 40] if b_mn else B[: N - 40]
     out = torch.empty(M, N - 40, dtype=torch.float32, device=dev)
     C.gemm(A, Bt, out, False, bool(b_mn), cfg=7)
-    torch.testing.assert_close(out, ref[:, : N - 40], rtol=2e-3, atol=2e-2)
+    _assert_bound(out, A64, B64[:, : N - 40], None, "N tail fallback")
 
 
 @pytest.mark.parametrize("b_mn", [0, 1])
