@@ -9,10 +9,13 @@ baseline of the same model (torch.autocast + SDPA + hipBLASLt) for comparison.
     python benchmarks/bert_bench.py --impl native --min-len 64            # variable-length rows, right-padded
     python benchmarks/bert_bench.py --impl native --min-len 64 --unpad    # ... run on the real tokens only
     python benchmarks/bert_bench.py --impl native --optimizer lamb --no-decay-1d   # LAMB, biases / LayerNorm excluded
+    python benchmarks/bert_bench.py --impl native --task mlm   # masked-LM pre-training step (fused vocabulary CE head)
 
 Prints one JSON line per run (samples/s, tokens/s, ms/step, model TFLOP/s; ``tokens`` = the real
 tokens T of the batch, ``fill`` = T / (batch * seq), ``unpad``; tokens/s and TFLOP/s count batch * seq).
-Synthetic token ids, random-init weights (no network).
+Synthetic token ids, random-init weights (no network). ``--task mlm`` trains BertForMaskedLM on
+SyntheticMaskedLM rows and adds ``head_ms`` / ``head_share`` (the MLM head's forward + backward alone on
+the step's hidden states, timed after the steps) and ``max_predictions`` / ``chunk_rows``.
 """
 from __future__ import annotations
 
@@ -30,8 +33,9 @@ import torch.nn.functional as F  # noqa: E402
 
 
 def run(args):
-    from ml_trainer_amd.models.bert import BertClassifier, bert_config
+    from ml_trainer_amd.models.bert import BertClassifier, BertForMaskedLM, bert_config
     from ml_trainer_amd.ops.optim import build_optimizer
+    mlm = args.task == "mlm"
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
     over = {"layers": args.layers} if args.layers else {}
@@ -44,7 +48,9 @@ def run(args):
     if args.min_len:
         over["pad_id"] = 0
     cfg = bert_config(args.model, **over)
-    m = BertClassifier(cfg).to(dev)
+    m = (BertForMaskedLM if mlm else BertClassifier)(cfg).to(dev)
+    if mlm and args.chunk_rows:
+        m.mlm_chunk_rows = args.chunk_rows
     if args.impl == "native":
         # adamw without --no-decay-1d is FusedAdamW's plain flat launch, as this benchmark always ran it
         opt = build_optimizer(args.optimizer, m.parameters(), lr=1e-4, weight_decay=0.01,
@@ -63,10 +69,21 @@ def run(args):
         ids[torch.arange(args.seq, device=dev)[None, :] >= lens[:, None]] = 0
         real = int(lens.sum())
     y = torch.randint(0, cfg.num_labels, (args.batch,), device=dev)
+    if mlm:  # masked rows (80 / 10 / 10) of the learnable synthetic text; lengths as above
+        from ml_trainer_amd.data.text import SyntheticMaskedLM
+        ds = SyntheticMaskedLM(args.batch, seq_len=args.seq, vocab_size=cfg.vocab_size, seed=1,
+                               max_predictions=m.max_predictions(args.seq),
+                               **({"min_len": args.min_len, "pad_id": 0} if args.min_len else {}))
+        ids, y = ds.ids.to(dev), ds.labels.to(dev)
+        real = int(ds.lengths.sum())
+        loss_fn = m.mlm_loss if args.impl == "native" else m.mlm_loss_torch_bf16
+    else:
+        def loss_fn(out, y):
+            return F.cross_entropy(out, y)
 
     def step():
         opt.zero_grad(set_to_none=False)
-        loss = F.cross_entropy(fwd(ids), y)
+        loss = loss_fn(fwd(ids), y)
         loss.backward()
         opt.step()
         return loss
@@ -88,6 +105,26 @@ def run(args):
            "peak_mem_gb": torch.cuda.max_memory_allocated() / 2 ** 30,
            "min_len": args.min_len, "tokens": real, "fill": real / tokens, "unpad": bool(args.unpad),
            "optimizer": args.optimizer, "no_decay_1d": bool(args.no_decay_1d)}
+    if mlm:
+        with torch.no_grad():
+            hidden = fwd(ids)
+        hidden = hidden.detach().requires_grad_()
+
+        def head():
+            hidden.grad = None
+            loss_fn(hidden, y).backward()
+
+        for _ in range(2):
+            head()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            head()
+        torch.cuda.synchronize()
+        hd = (time.perf_counter() - t0) / args.steps
+        rec.update({"task": "mlm", "head_ms": hd * 1e3, "head_share": hd / dt,
+                    "max_predictions": m.max_predictions(args.seq), "chunk_rows": m.mlm_chunk_rows,
+                    "mlm_accuracy": float(m.last_mlm_accuracy) if args.impl == "native" else None})
     print(json.dumps(rec), flush=True)
     return rec
 
@@ -111,6 +148,10 @@ def main():
                     help="native optimizer: adamw (one flat launch) or lamb (three launches, layer-wise trust ratio)")
     ap.add_argument("--no-decay-1d", action="store_true",
                     help="no weight decay (lamb: no trust ratio) on biases and LayerNorm parameters (ndim <= 1)")
+    ap.add_argument("--task", choices=["classify", "mlm"], default="classify",
+                    help="classify: BertClassifier + cross-entropy; mlm: BertForMaskedLM + the fused MLM head")
+    ap.add_argument("--chunk-rows", type=int, default=0, help="--task mlm: rows of logits alive at once (default: "
+                    "ops.mlm.DEFAULT_CHUNK_ROWS)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     recs = []

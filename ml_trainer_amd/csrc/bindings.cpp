@@ -740,6 +740,75 @@ static void check_bf16_2d(const Tensor& t, const char* name, int64_t rows, int64
   TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, name, " must be 16-byte aligned");
 }
 
+// ---------------------------------------------------------------------------- masked-LM head (mlm.hip)
+void vocab_ce(Tensor Z, int64_t V, Tensor labels, Tensor row_loss, Tensor row_lse, Tensor row_hit, bool write_grad,
+              int64_t ignore_index) {
+  TORCH_CHECK(Z.dim() == 2 && Z.is_cuda() && Z.scalar_type() == at::kBFloat16 && Z.stride(1) == 1,
+              "vocab_ce: Z must be a bf16 [R, ldz] device tensor with unit column stride");
+  const int64_t R = Z.size(0), ldz = Z.size(1);
+  TORCH_CHECK(R == 0 || Z.stride(0) == ldz, "vocab_ce: Z rows must be contiguous (the row stride is the padded width)");
+  TORCH_CHECK(ldz % 8 == 0 && reinterpret_cast<uintptr_t>(Z.data_ptr()) % 16 == 0,
+              "vocab_ce needs ldz % 8 == 0 and a 16-byte aligned base");
+  TORCH_CHECK(V >= 1 && V <= ldz && ldz < (1LL << 31), "vocab_ce: 1 <= V <= ldz < 2^31");
+  TORCH_CHECK(R < (1LL << 31), "vocab_ce: too many rows");
+  check_dev(labels, "labels", at::kLong, R, 8);
+  check_dev(row_loss, "row_loss", at::kFloat, R, 4);
+  check_dev(row_lse, "row_lse", at::kFloat, R, 4);
+  check_dev(row_hit, "row_hit", at::kFloat, R, 4);
+  launch_vocab_ce((uint16_t*)Z.data_ptr(), R, ldz, (int)V, labels.data_ptr<int64_t>(), row_loss.data_ptr<float>(),
+                  row_lse.data_ptr<float>(), row_hit.data_ptr<float>(), ignore_index, write_grad, cur_stream());
+}
+
+void mlm_select(Tensor labels, int64_t P, Tensor slot_row, Tensor slot_label, Tensor seq_overflow, Tensor overflow,
+                c10::optional<Tensor> lens, c10::optional<Tensor> cu_seqlens, int64_t ignore_index) {
+  TORCH_CHECK(labels.dim() == 2, "mlm_select: labels must be [B, S]");
+  const int64_t B = labels.size(0), S = labels.size(1), R = slot_row.numel();
+  TORCH_CHECK(P >= 1 && B >= 1 && S >= 1 && B * S < (1LL << 31) && B * P <= R && R < (1LL << 31),
+              "mlm_select: need P >= 1, B * S < 2^31 and B * P <= R slots");
+  check_dev(labels, "labels", at::kLong, B * S, 8);
+  check_dev(slot_row, "slot_row", at::kInt, R, 4);
+  check_dev(slot_label, "slot_label", at::kLong, R, 8);
+  TORCH_CHECK(slot_label.numel() == R, "mlm_select: slot_label must have as many entries as slot_row");
+  check_dev(seq_overflow, "seq_overflow", at::kInt, B, 4);
+  check_dev(overflow, "overflow", at::kInt, 1, 4);
+  TORCH_CHECK(!(lens.has_value() && cu_seqlens.has_value()), "mlm_select takes lens or cu_seqlens, not both");
+  const int* lp = nullptr;
+  const int* cp = nullptr;
+  if (lens.has_value()) {
+    check_dev(*lens, "lens", at::kInt, B, 4);
+    lp = lens->data_ptr<int>();
+  }
+  if (cu_seqlens.has_value()) {
+    check_dev(*cu_seqlens, "cu_seqlens", at::kInt, B + 1, 4);
+    cp = cu_seqlens->data_ptr<int>();
+  }
+  launch_mlm_select(labels.data_ptr<int64_t>(), (int)B, (int)S, (int)P, R, lp, cp, ignore_index,
+                    slot_row.data_ptr<int>(), slot_label.data_ptr<int64_t>(), seq_overflow.data_ptr<int>(),
+                    overflow.data_ptr<int>(), cur_stream());
+}
+
+void gather_rows(Tensor X, Tensor slot_row, Tensor out) {
+  TORCH_CHECK(X.dim() == 2 && out.dim() == 2 && X.size(1) == out.size(1) && X.size(1) % 8 == 0,
+              "gather_rows: X [N, h], out [R, h], h % 8 == 0");
+  const int64_t N = X.size(0), h = X.size(1), R = out.size(0);
+  TORCH_CHECK(N < (1LL << 31) && R < (1LL << 31), "gather_rows: too many rows");
+  check_bf16_2d(X, "X", N, h);
+  check_bf16_2d(out, "out", R, h);
+  check_dev(slot_row, "slot_row", at::kInt, R, 4);
+  launch_gather_rows(bf16_ptr(X), N, (int)h, slot_row.data_ptr<int>(), R, (uint16_t*)out.data_ptr(), cur_stream());
+}
+
+void scatter_rows(Tensor G, Tensor slot_row, Tensor dX) {
+  TORCH_CHECK(G.dim() == 2 && dX.dim() == 2 && G.size(1) == dX.size(1) && G.size(1) % 8 == 0,
+              "scatter_rows: G [R, h], dX [N, h], h % 8 == 0");
+  const int64_t R = G.size(0), h = G.size(1), N = dX.size(0);
+  TORCH_CHECK(N < (1LL << 31) && R < (1LL << 31), "scatter_rows: too many rows");
+  check_bf16_2d(G, "G", R, h);
+  check_bf16_2d(dX, "dX", N, h);
+  check_dev(slot_row, "slot_row", at::kInt, R, 4);
+  launch_scatter_rows(bf16_ptr(G), R, (int)h, slot_row.data_ptr<int>(), N, (uint16_t*)dX.data_ptr(), cur_stream());
+}
+
 void ln_fwd(Tensor X, Tensor gamma, Tensor beta, Tensor Y, Tensor mean, Tensor rstd, double eps) {
   const int64_t D = gamma.numel(), rows = X.numel() / std::max<int64_t>(D, 1);
   TORCH_CHECK(D % 256 == 0 && D >= 256 && D <= 1024, "LayerNorm width must be 256/512/768/1024");
@@ -1632,6 +1701,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_plan", &gemm_plan, py::arg("a_mn"), py::arg("b_mn"), py::arg("M"), py::arg("N"), py::arg("K"),
         py::arg("cfg") = -1, py::arg("splits") = 0, py::arg("accumulate") = false);
   m.def("colsum", &colsum, py::arg("X"), py::arg("out"), py::arg("accumulate") = false);
+  m.def("vocab_ce", &vocab_ce, py::arg("Z"), py::arg("V"), py::arg("labels"), py::arg("row_loss"), py::arg("row_lse"),
+        py::arg("row_hit"), py::arg("write_grad"), py::arg("ignore_index") = -100);
+  m.def("vocab_ce_resident_cols", &vocab_ce_resident_cols);
+  m.def("mlm_select", &mlm_select, py::arg("labels"), py::arg("P"), py::arg("slot_row"), py::arg("slot_label"),
+        py::arg("seq_overflow"), py::arg("overflow"), py::arg("lens") = py::none(),
+        py::arg("cu_seqlens") = py::none(), py::arg("ignore_index") = -100);
+  m.def("gather_rows", &gather_rows, py::arg("X"), py::arg("slot_row"), py::arg("out"));
+  m.def("scatter_rows", &scatter_rows, py::arg("G"), py::arg("slot_row"), py::arg("dX"));
   m.def("ln_fwd", &ln_fwd);
   m.def("ln_bwd", &ln_bwd, py::arg("DY"), py::arg("X"), py::arg("gamma"), py::arg("mean"), py::arg("rstd"),
         py::arg("DX"), py::arg("part"), py::arg("dgamma"), py::arg("dbeta"), py::arg("accumulate") = false,

@@ -356,4 +356,27 @@ bool launch_attn_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* d
                      int* rows_kv = nullptr, const AttnQ8& q8 = AttnQ8{}, const AttnDropArgs& ad = AttnDropArgs{},
                      const int* cu = nullptr, int rows = 0);
 
+// ----------------------------------------------------------------------------
+// Masked-LM head (mlm.hip)
+// ----------------------------------------------------------------------------
+// vocab_ce: softmax cross-entropy over rows of bf16 logits Z[R, ldz] (ldz % 8 == 0, 16-byte aligned base,
+// V <= ldz valid columns), one workgroup per row, the unscaled gradient softmax - onehot written in
+// place when write_grad (padding columns and ignored rows as zeros). row_loss / row_lse / row_hit are
+// fp32 [R], 0 for ignored rows. Rows of up to kVocabCeResidentCols columns stay in LDS between the
+// statistics and the gradient write (one read of the logits); wider rows are read a second time.
+constexpr int kVocabCeResidentCols = 31744;  // 62 KB of bf16: the 64 KB workgroup LDS less the reduction scratch
+int vocab_ce_resident_cols();
+void launch_vocab_ce(uint16_t* Z, int64_t R, int64_t ldz, int V, const int64_t* labels, float* row_loss,
+                     float* row_lse, float* row_hit, int64_t ignore_index, bool write_grad, hipStream_t st);
+// labels [B, S] -> P slots per sequence (slot_row int32 / slot_label int64, [R], R >= B * P; empty and
+// tail slots -1 / ignore_index); lens [B] or cu [B + 1] (int32) or neither; seq_overflow [B], overflow [1].
+void launch_mlm_select(const int64_t* labels, int B, int S, int P, int64_t R, const int* lens, const int* cu,
+                       int64_t ignore_index, int* slot_row, int64_t* slot_label, int* seq_overflow, int* overflow,
+                       hipStream_t st);
+// out[R, h] = X[slot_row] (zeros for empty slots); dX[N, h] = 0 then dX[slot_row] = G. h % 8 == 0.
+void launch_gather_rows(const uint16_t* X, int64_t N, int h, const int* slot_row, int64_t R, uint16_t* out,
+                        hipStream_t st);
+void launch_scatter_rows(const uint16_t* G, int64_t R, int h, const int* slot_row, int64_t N, uint16_t* dX,
+                         hipStream_t st);
+
 }  // namespace mlt

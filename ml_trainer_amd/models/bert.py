@@ -49,6 +49,11 @@ device-to-host read per forward. Attention-probability dropout draws the bytes o
 (element ``(b, h, q, k)`` is indexed with the padded width ``S``); hidden dropout is indexed by packed
 row, so its masks differ from a padded run's with the same seed. ``unpad`` with ``fp8`` is rejected: the
 fp8 attention epilogue writes 16-row transposed runs at ``b * S`` offsets.
+
+Masked-LM pre-training: ``BertForMaskedLM`` is the same encoder (same state-dict keys) without the pooler
+and classifier, under the MLM head of ``ops/mlm.py`` (transform dense + GELU + LayerNorm, vocabulary
+projection tied to the word table, fused chunked softmax cross-entropy). Hidden dropout, attention
+dropout and ``unpad`` work unchanged; fp8 is rejected.
 """
 from __future__ import annotations
 
@@ -78,6 +83,7 @@ class BertConfig:
     attention_dropout: float = 0.0  # attention-probability dropout, applied as round(p * 256) / 256
     pad_id: Optional[int] = None  # when set, key lengths are derived from trailing pad tokens
     unpad: bool = False  # run the encoder on the real tokens only (needs lengths; not with fp8)
+    max_predictions: Optional[int] = None  # MLM slots per sequence; None: ceil(0.15 * S) rounded up to 8
 
 
 _PRESETS = {
@@ -182,9 +188,12 @@ class BertClassifier(nn.Module):
         self.token_type_embeddings = nn.Embedding(c.type_vocab, c.hidden)
         self.emb_ln = nn.LayerNorm(c.hidden, eps=c.ln_eps)
         self.layers = nn.ModuleList([BertLayer(c) for _ in range(c.layers)])
+        self._build_head(c)
+        self.apply(self._init)
+
+    def _build_head(self, c):
         self.pooler = nn.Linear(c.hidden, c.hidden)
         self.classifier = nn.Linear(c.hidden, c.num_labels)
-        self.apply(self._init)
 
     def _init(self, m):
         std = self.config.init_std
@@ -255,13 +264,7 @@ class BertClassifier(nn.Module):
             pk = self._pack(input_ids, lens, token_type_ids, T.PACK_ROW_MULTIPLE)
             if pk is not None:
                 return self._forward_native_packed(pk, drop, adrop)
-            x = T.embeddings(input_ids, token_type_ids, self.word_embeddings.weight, self.position_embeddings.weight,
-                             self.token_type_embeddings.weight, S)
-            x = T.layer_norm(x, self.emb_ln.weight, self.emb_ln.bias, self.config.ln_eps)
-            if drop is not None:
-                x = T.dropout(x, *self._site(drop, 0))
-            for l, layer in enumerate(self.layers):
-                x = layer.forward_native(x, lens, B, S, self._site(drop, 1 + 2 * l), self._attn_site(adrop, l))
+            x = self._encode_native(input_ids, lens, token_type_ids, drop, adrop)
             cls = x.view(B, S, -1)[:, 0]  # strided row view: the pooler GEMM reads it in place
             if cls.shape[1] % 8 == 0 and self.pooler.weight.shape[0] % 8 == 0:
                 return T.classifier_head(cls, self.pooler.weight, self.pooler.bias, self.classifier.weight,
@@ -272,9 +275,22 @@ class BertClassifier(nn.Module):
         pooled = torch.tanh(self.pooler(cls))
         return self.classifier(pooled)
 
-    def _forward_native_packed(self, pk, drop, adrop):
-        """The native path on a PackedBatch: [rows, h] throughout (the T tokens, then the inert tail rows
-        that round the count up to the GEMMs' 256-row tile), CLS rows at cu_seqlens[:-1]."""
+    def _encode_native(self, input_ids, lens, token_type_ids, drop, adrop):
+        """The native encoder on a padded [B, S] batch: the last layer's hidden states [B * S, h] bf16."""
+        from ml_trainer_amd.ops import transformer as T
+        B, S = input_ids.shape
+        x = T.embeddings(input_ids, token_type_ids, self.word_embeddings.weight, self.position_embeddings.weight,
+                         self.token_type_embeddings.weight, S)
+        x = T.layer_norm(x, self.emb_ln.weight, self.emb_ln.bias, self.config.ln_eps)
+        if drop is not None:
+            x = T.dropout(x, *self._site(drop, 0))
+        for l, layer in enumerate(self.layers):
+            x = layer.forward_native(x, lens, B, S, self._site(drop, 1 + 2 * l), self._attn_site(adrop, l))
+        return x
+
+    def _encode_native_packed(self, pk, drop, adrop):
+        """The native encoder on a PackedBatch: [rows, h] throughout (the T tokens, then the inert tail rows
+        that round the count up to the GEMMs' 256-row tile)."""
         from ml_trainer_amd.ops import transformer as T
         B, S, cu = pk.batch, pk.max_seqlen, pk.cu_seqlens
         x = T.embeddings(pk.ids, pk.tt, self.word_embeddings.weight, self.position_embeddings.weight,
@@ -284,13 +300,19 @@ class BertClassifier(nn.Module):
             x = T.dropout(x, *self._site(drop, 0))
         for l, layer in enumerate(self.layers):
             x = layer.forward_native(x, None, B, S, self._site(drop, 1 + 2 * l), self._attn_site(adrop, l), cu)
+        return x
+
+    def _forward_native_packed(self, pk, drop, adrop):
+        """The native path on a PackedBatch, CLS rows at cu_seqlens[:-1]."""
+        from ml_trainer_amd.ops import transformer as T
+        x = self._encode_native_packed(pk, drop, adrop)
         cls = x.index_select(0, pk.cls_rows)  # contiguous [B, h]
         if cls.shape[1] % 8 == 0 and self.pooler.weight.shape[0] % 8 == 0:
             return T.classifier_head(cls, self.pooler.weight, self.pooler.bias, self.classifier.weight,
                                      self.classifier.bias)
         return self.classifier(torch.tanh(self.pooler(cls.float())))
 
-    def _reference_hidden_packed(self, pk, lens, drop, adrop):
+    def _reference_hidden_packed(self, pk, lens, drop, adrop, full=False):
         B, S = pk.batch, pk.max_seqlen
         tt = pk.tt if pk.tt is not None else torch.zeros_like(pk.ids)
         x = self.word_embeddings(pk.ids) + self.position_embeddings(pk.pos.long()) + self.token_type_embeddings(tt)
@@ -301,13 +323,14 @@ class BertClassifier(nn.Module):
         mask = torch.arange(S, device=x.device)[None, :] < lens.to(x.device).clamp(1, S)[:, None]
         for l, layer in enumerate(self.layers):
             x = layer.forward_reference(x, mask, B, S, self._site(drop, 1 + 2 * l), self._attn_site(adrop, l), pk)
-        return x.index_select(0, pk.cls_rows)
+        return x if full else x.index_select(0, pk.cls_rows)
 
-    def forward_reference_hidden(self, input_ids, lens=None, token_type_ids=None, drop=None, adrop=None):
+    def forward_reference_hidden(self, input_ids, lens=None, token_type_ids=None, drop=None, adrop=None, full=False):
+        """The CLS rows [B, h] of the fp32 torch encoder; ``full``: every row, [B * S, h] (packed: [T, h])."""
         B, S = input_ids.shape
         pk = self._pack(input_ids, lens, token_type_ids)
         if pk is not None:
-            return self._reference_hidden_packed(pk, lens, drop, adrop)
+            return self._reference_hidden_packed(pk, lens, drop, adrop, full)
         pos = torch.arange(S, device=input_ids.device)
         tt = token_type_ids if token_type_ids is not None else torch.zeros_like(input_ids)
         x = self.word_embeddings(input_ids) + self.position_embeddings(pos)[None] + self.token_type_embeddings(tt)
@@ -320,7 +343,7 @@ class BertClassifier(nn.Module):
             mask = torch.arange(S, device=input_ids.device)[None, :] < lens.to(input_ids.device)[:, None]
         for l, layer in enumerate(self.layers):
             x = layer.forward_reference(x, mask, B, S, self._site(drop, 1 + 2 * l), self._attn_site(adrop, l))
-        return x.view(B, S, -1)[:, 0]
+        return x if full else x.view(B, S, -1)[:, 0]
 
     def forward_reference(self, input_ids, attention_mask=None, token_type_ids=None, dropout_seed=None):
         lens = self._lengths(input_ids, attention_mask)
@@ -328,11 +351,18 @@ class BertClassifier(nn.Module):
         return self.classifier(torch.tanh(self.pooler(cls)))
 
     def forward_torch_bf16(self, input_ids, attention_mask=None, token_type_ids=None, dropout_seed=None):
+        with torch.autocast(input_ids.device.type, dtype=torch.bfloat16):
+            x, pk = self._hidden_torch_bf16(input_ids, attention_mask, token_type_ids, dropout_seed)
+            cls = x[:, 0] if pk is None else x[0].index_select(0, pk.cls_rows)
+            return self.classifier(torch.tanh(self.pooler(cls.float())))
+
+    def _hidden_torch_bf16(self, input_ids, attention_mask=None, token_type_ids=None, dropout_seed=None):
         """PyTorch-eager bf16 path on the same weights (torch.autocast + SDPA + hipBLASLt): the
         baseline the native kernels are benchmarked and error-budgeted against. Hidden dropout
         uses the native path's masks (ops.dropout), each applied in the dtype autocast gives the
         tensor it drops. With attention dropout active the attention is computed explicitly under
-        autocast (softmax -> * keep * scale -> @ v) instead of through SDPA, which cannot take our mask."""
+        autocast (softmax -> * keep * scale -> @ v) instead of through SDPA, which cannot take our mask.
+        Returns (hidden [B, S, h] -- packed: [1, T, h] --, the PackedBatch or None); the callers add their head."""
         from ml_trainer_amd.ops import dropout as D
         c = self.config
         drop, adrop = self._dropout(dropout_seed)
@@ -379,8 +409,7 @@ class BertClassifier(nn.Module):
                     ctx = ctx.reshape(B * S, -1).index_select(0, pk.index)[None]
                 x = L.ln1(dropped(L.out(ctx), 1 + 2 * l) + x)
                 x = L.ln2(dropped(L.ffn2(F.gelu(L.ffn1(x))), 2 + 2 * l) + x)
-            cls = x[:, 0] if pk is None else x[0].index_select(0, pk.cls_rows)
-            return self.classifier(torch.tanh(self.pooler(cls.float())))
+            return x, pk
 
     def num_parameters(self) -> int:
         return sum(p.numel() for p in self.parameters())
@@ -391,3 +420,131 @@ class BertClassifier(nn.Module):
         h, f = c.hidden, c.intermediate
         per_layer = 2 * (3 * h * h + h * h + 2 * h * f) + 2 * 2 * seq_len * h  # linears + QK^T / PV
         return 3.0 * c.layers * per_layer
+
+
+class BertForMaskedLM(BertClassifier):
+    """The same encoder (same state-dict keys as ``BertClassifier``) under BERT's masked-language-model
+    head instead of the pooler and classifier: transform ``mlm_dense`` + GELU + ``mlm_ln``, then the
+    vocabulary projection with ``word_embeddings.weight`` itself (tied: no second module, no duplicate
+    key) plus the output bias ``mlm_bias`` [V]. An MLM-pretrained state dict loads into a
+    ``BertClassifier`` with ``strict=False`` (the fine-tune flow) and vice versa.
+
+    ``forward`` returns the last layer's hidden states ([B * S, h]; bf16 on the GPU; the packed rows
+    under ``unpad``) and remembers B, S and cu_seqlens of that forward; ``mlm_loss(hidden, labels)``
+    runs ``ops.mlm.mlm_head`` on them (labels [B, S], -100 = not a target) and sets
+    ``last_mlm_accuracy`` / ``last_mlm_overflow`` (device scalars). The vocabulary logits never exist
+    beyond one chunk of ``mlm_chunk_rows`` rows. Every sequence gets ``config.max_predictions`` slots
+    (default ceil(0.15 * S) rounded up to 8); targets past that are dropped and counted in the overflow.
+    On the CPU, and in ``forward_reference``, everything runs in plain fp32 torch."""
+
+    def __init__(self, c: Optional[BertConfig] = None):
+        c = c or BertConfig()
+        if c.fp8:
+            raise ValueError("fp8=True with the masked-LM head is not supported: the fp8 linears are wired for "
+                             "the classifier model only")
+        if c.max_predictions is not None and c.max_predictions < 1:
+            raise ValueError(f"max_predictions must be >= 1, got {c.max_predictions}")
+        super().__init__(c)
+        from ml_trainer_amd.ops.mlm import DEFAULT_CHUNK_ROWS
+        self.mlm_chunk_rows = DEFAULT_CHUNK_ROWS
+        self.last_mlm_accuracy = None
+        self.last_mlm_overflow = None
+        self._last_batch = None  # (B, S, lens, cu_seqlens) of the last forward
+
+    def _build_head(self, c):
+        self.mlm_dense = nn.Linear(c.hidden, c.hidden)
+        self.mlm_ln = nn.LayerNorm(c.hidden, eps=c.ln_eps)
+        self.mlm_bias = nn.Parameter(torch.zeros(c.vocab_size))
+
+    def mlm_params(self):
+        from ml_trainer_amd.ops.mlm import MLMParams
+        return MLMParams(self.mlm_dense.weight, self.mlm_dense.bias, self.mlm_ln.weight, self.mlm_ln.bias,
+                         self.word_embeddings.weight, self.mlm_bias, self.config.ln_eps)
+
+    def max_predictions(self, S: int) -> int:
+        from ml_trainer_amd.ops.mlm import default_max_predictions
+        P = self.config.max_predictions
+        return P if P is not None else default_max_predictions(S)
+
+    def forward(self, input_ids, attention_mask=None, token_type_ids=None, dropout_seed=None):
+        if isinstance(input_ids, (tuple, list)):
+            input_ids, attention_mask = input_ids[0], input_ids[1] if len(input_ids) > 1 else None
+        B, S = input_ids.shape
+        lens = self._lengths(input_ids, attention_mask)
+        drop, adrop = self._dropout(dropout_seed)
+        if not input_ids.is_cuda:
+            return self._hidden_reference(input_ids, lens, token_type_ids, drop, adrop)
+        from ml_trainer_amd.ops import transformer as T
+        pk = self._pack(input_ids, lens, token_type_ids, T.PACK_ROW_MULTIPLE)
+        if pk is not None:
+            self._last_batch = (B, S, None, pk.cu_seqlens)
+            return self._encode_native_packed(pk, drop, adrop)
+        self._last_batch = (B, S, lens, None)
+        return self._encode_native(input_ids, lens, token_type_ids, drop, adrop)
+
+    def _hidden_reference(self, input_ids, lens, token_type_ids, drop, adrop):
+        B, S = input_ids.shape
+        pk = self._pack(input_ids, lens, token_type_ids)
+        self._last_batch = (B, S, lens if pk is None else None, None if pk is None else pk.cu_seqlens)
+        return self.forward_reference_hidden(input_ids, lens, token_type_ids, drop, adrop, full=True)
+
+    def forward_reference(self, input_ids, attention_mask=None, token_type_ids=None, dropout_seed=None):
+        """The hidden states in fp32 torch on any device (the numerics oracle of ``forward``)."""
+        lens = self._lengths(input_ids, attention_mask)
+        return self._hidden_reference(input_ids, lens, token_type_ids, *self._dropout(dropout_seed))
+
+    def forward_torch_bf16(self, input_ids, attention_mask=None, token_type_ids=None, dropout_seed=None):
+        """The hidden states of the PyTorch-eager bf16 baseline, [B * S, h] (packed: [T, h])."""
+        B, S = input_ids.shape
+        with torch.autocast(input_ids.device.type, dtype=torch.bfloat16):
+            x, pk = self._hidden_torch_bf16(input_ids, attention_mask, token_type_ids, dropout_seed)
+        lens = self._lengths(input_ids, attention_mask)
+        self._last_batch = (B, S, lens if pk is None else None, None if pk is None else pk.cu_seqlens)
+        return x.reshape(-1, x.shape[-1])
+
+    def _head(self, fn, hidden, labels, **kw):
+        if self._last_batch is None:
+            raise RuntimeError("mlm_loss needs the hidden states of a forward of this model")
+        B, S, lens, cu = self._last_batch
+        if tuple(labels.shape) != (B, S):
+            raise ValueError(f"labels must be [B, S] = [{B}, {S}] as the last forward's input_ids, got "
+                             f"{tuple(labels.shape)}")
+        out = fn(hidden, labels.to(hidden.device), self.max_predictions(S), self.mlm_params(), cu_seqlens=cu,
+                 lens=lens, **kw)
+        self.last_mlm_accuracy = out.accuracy.detach()
+        self.last_mlm_overflow = out.overflow
+        self.last_mlm_row_loss = out.row_loss
+        return out.loss
+
+    def mlm_loss(self, hidden, labels):
+        """Mean masked-LM loss (device scalar; 0 for a batch without targets) of ``hidden`` = this model's
+        last forward output and ``labels`` [B, S]. Targets at pad positions are dropped."""
+        from ml_trainer_amd.ops import mlm as M
+        if hidden.is_cuda and hidden.dtype == torch.bfloat16:
+            return self._head(M.mlm_head, hidden, labels, chunk_rows=self.mlm_chunk_rows)
+        return self._head(M.mlm_head_reference, hidden, labels)
+
+    def mlm_loss_reference(self, hidden, labels):
+        from ml_trainer_amd.ops import mlm as M
+        return self._head(M.mlm_head_reference, hidden, labels)
+
+    def mlm_loss_torch_bf16(self, hidden, labels):
+        """The eager bf16 head on the same weights (torch.autocast: F.linear + F.cross_entropy over the
+        full [R, V] logits): the baseline next to ``forward_torch_bf16``."""
+        from ml_trainer_amd.ops import mlm as M
+        if self._last_batch is None:
+            raise RuntimeError("mlm_loss_torch_bf16 needs the hidden states of a forward of this model")
+        B, S, lens, cu = self._last_batch
+        p = self.mlm_params()
+        slot_row, slot_label, _ = M.select_reference(labels.to(hidden.device), self.max_predictions(S), lens, cu)
+        with torch.autocast(hidden.device.type, dtype=torch.bfloat16):
+            x = M.gather_reference(hidden, slot_row)
+            t = self.mlm_ln(F.gelu(self.mlm_dense(x)))
+            logits = F.linear(t, p.word_w, p.out_bias)
+            n = (slot_label != M.IGNORE_INDEX).sum().clamp(min=1)
+            return F.cross_entropy(logits.float(), slot_label, ignore_index=M.IGNORE_INDEX, reduction="sum") / n
+
+    def mlm_logits(self, hidden, rows):
+        """fp32 [len(rows), V]: the vocabulary logits of the given rows of ``hidden`` (inspection, tests)."""
+        from ml_trainer_amd.ops import mlm as M
+        return M.mlm_logits(hidden, rows, self.mlm_params())

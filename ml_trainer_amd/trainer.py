@@ -252,9 +252,13 @@ class Trainer:
             return L.MSELoss()
         if c == "custom":
             return _CustomLoss(custom_loss_function)
+        if c == "mlm":  # masked-LM pre-training: the model's own head over its hidden states
+            if not hasattr(self._core, "mlm_loss"):
+                raise ValueError("criterion 'mlm' needs a model with an mlm_loss head (BertForMaskedLM)")
+            return _CustomLoss(self._core.mlm_loss)
         if callable(c):
             return c if isinstance(c, nn.Module) else _CustomLoss(c)
-        raise ValueError(f"unknown criterion {c!r} (cross_entropy|neg-loss|l1|l2|custom or a callable)")
+        raise ValueError(f"unknown criterion {c!r} (cross_entropy|neg-loss|l1|l2|custom|mlm or a callable)")
 
     def _average_gradients(self):
         """Manual gradient averaging (reference src/trainer.py:152-158): one flat all-reduce."""
@@ -276,8 +280,15 @@ class Trainer:
         if self.metric == "mcrmse":
             return L.mcrmse(outputs, targets)
         if self.metric == "accuracy":
+            if self.criterion_type == "mlm":  # masked-token accuracy of the criterion call just made
+                return self._core.last_mlm_accuracy
             return L.accuracy(outputs, targets)
         return None
+
+    def _metric_outputs(self, outputs):
+        """What ``_evaluate`` takes: the fp32 outputs (criterion 'mlm': the hidden states as they are,
+        its metric comes from the head)."""
+        return outputs.detach() if self.criterion_type == "mlm" else outputs.detach().float()
 
     # ------------------------------------------------------------------ engine selection
     def _engine_eligible(self, for_eval: bool = False) -> bool:
@@ -519,7 +530,7 @@ class Trainer:
                     self.scheduler.step(epoch - 1 + i / n)
             running_loss += loss.detach().double()
             if self.metric:
-                running_metric += self._evaluate(outputs.detach().float(), targets).double()
+                running_metric += self._evaluate(self._metric_outputs(outputs), targets).double()
             samples += inputs.shape[0]
             if self.opts.log_interval and (i + 1) % self.opts.log_interval == 0:
                 bar.set_postfix(loss=running_loss.item() / (i + 1))
@@ -562,7 +573,7 @@ class Trainer:
             outputs = model(inputs)
             running_loss += self.criterion(outputs, targets).detach().double()
             if self.metric:
-                running_metric += self._evaluate(outputs.float(), targets).double()
+                running_metric += self._evaluate(self._metric_outputs(outputs), targets).double()
         if was_training:
             model.train()
         loss = running_loss.item() / max(n, 1)
