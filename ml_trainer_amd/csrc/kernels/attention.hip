@@ -3,6 +3,7 @@
 // Layout: the QKV projection's output qkv [B*S, 3*H*64] is read in place (q | k | v
 // blocks of H heads x 64 dims per row); O [B*S, H*64]; the backward writes dQKV in the
 // same packed layout. Head dim 64, key-padding mask by per-sequence valid length.
+// Every length (lens[b], or cu[b + 1] - cu[b] in packed mode) is >= 1: a sequence with no valid key is not supported.
 //
 // Forward, one 256-thread block per (64-query block, head, batch), wave = 16 queries:
 //   S^T (keys x queries) = K . Q^T   -- "swapped" product: each lane owns ONE query

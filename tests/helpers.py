@@ -263,3 +263,170 @@ def assert_within(out, expected, tol, what=""):
                              f"got {float(out[idx]):.9g}, expected {float(expected[idx]):.9g}, "
                              f"|err| {float(err[idx]):.3g} > tol {float(tol[idx]):.3g}")
     return float((err / tol).max())
+
+
+# ---------------------------------------------------------------------------------------------
+# Derived attention bounds (tests/test_attn_bound_cpu.py checks these against a torch emulation of
+# the kernels on the CPU; tests/test_attention_edges_gpu.py uses them on the GPU). Everything is fp64
+# from the bf16 inputs, per (batch, head): q, k, v, do, o are [B, H, S, 64], lse [B, H, S], lens a
+# list of B valid key counts or None, keep a [B, H, S, S] bool mask or None, c = attention_scale(p).
+# Each function returns references together with `t`, the allowance on the kernel's fp32 value before
+# its store; bf16 outputs then go through store_bound.
+# ---------------------------------------------------------------------------------------------
+_UB = 2.0 ** -8                  # unit roundoff of bf16 as the kernels' packs use it (see store_bound on 2^-9)
+_LOG2E = 1.4426950408889634
+_LN2 = 0.6931471805599453
+_EXP2_REL = 2.0 ** -22           # v_exp_f32: 1 ulp (2^-23) in AMD's CDNA ISA reference; the allowance is 2 ulp
+
+
+def attn_sl2(scale):
+    """fp32(scale * log2 e): the factor that takes q.k to a base-2 exponent."""
+    return float(torch.tensor(float(scale) * _LOG2E, dtype=torch.float64).float())
+
+
+def attn_split(qkv, B, S, H):
+    """qkv [B * S, 3 * H * 64] -> q, k, v [B, H, S, 64] in fp64."""
+    q, k, v = qkv.double().view(B, S, 3, H, 64).permute(2, 0, 3, 1, 4)
+    return q, k, v
+
+
+def attn_heads(x, B, S, H):
+    """[B * S, H * 64] -> [B, H, S, 64] in fp64."""
+    return x.double().view(B, S, H, 64).permute(0, 2, 1, 3)
+
+
+def _attn_valid(lens, B, S, dev):
+    n = torch.full((B,), S, dtype=torch.int64) if lens is None else torch.as_tensor(list(lens), dtype=torch.int64)
+    return (torch.arange(S)[None, :] < n[:, None]).to(dev)[:, None, None, :]  # [B, 1, 1, S] over the keys
+
+
+def _attn_eta(q, k, s2, sl2):
+    """Relative error of one fp32 probability 2^(s2 - m), without any bf16 rounding:
+        ln2 (64 2^-24 sl2 sum_d |q_id k_jd| + 2^-22 |s2_ij|) + 2^-22
+    = the fp32 accumulation of the 64-term dot product (the bf16 x bf16 products are exact), the fma that
+    scales it and the rounding of sl2 itself, carried through 2^x (d 2^x = ln2 2^x dx), and v_exp_f32."""
+    return _LN2 * (64 * _U32 * sl2 * (q.abs() @ k.abs().transpose(-1, -2)) + 2.0 ** -22 * s2.abs()) + _EXP2_REL
+
+
+def attn_fwd_bound(q, k, v, lens, scale, keep=None, c=1.0):
+    """(O, t_O, LSE2, t_LSE) of the forward kernel (attn_fwd_lean_kernel).
+
+    Reference: sl2 = fp32(scale log2 e); s2_ij = (q_i . k_j) sl2 for j < len, -inf otherwise; p^ = softmax
+    over j (base 2); w_j = c M_ij v_j with a keep mask M (w_j = v_j without); O_i = sum_j p^_ij w_j; LSE2_i =
+    the base-2 logsumexp of the UNDROPPED scores.
+
+    Per-score relative error of the bf16 probability the kernel multiplies with,
+        eps_ij = u + ln2 (64 2^-24 sl2 sum_d |q_id k_jd| + 2^-22 |s2_ij|) + 2^-22,    u = 2^-8:
+      u ......... pack_acc rounds P to bf16 before it re-enters the MFMA (unit roundoff 2^-8; 2^-9 is broken by
+                  the CPU emulation at S = 17, len = 5: test_half_the_unit_roundoff_rejects_the_emulation)
+      64 2^-24 .. fp32 accumulation of the 64-term q.k product (_attn_eta)
+      2^-22 |s2|  the fma(s, sl2, -m) and the rounding of sl2
+      2^-22 ..... v_exp_f32
+    The row sum l comes from the SAME bf16 P as the P.V product (the all-ones MFMA), so numerator and
+    denominator err together: O' - O = sum_j p^_ij eps_ij (w_j - O_i) / (1 + sum_j p^_ij eps_ij), hence
+        t_O[i,d] = sum_j p^_ij eps_ij |w_jd - O_id| / (1 - 2u)       the tied bf16 / exponent errors
+                 + S 2^-24 sum_j p^_ij |w_jd|                         fp32 accumulation over the keys
+                 + 2^-22 |O_id|                                       1 / l, the multiply by it (and by c)
+        t_LSE[i] = sum_j p^_ij eps_ij / (ln2 (1 - 2u))                l's relative error through log2
+                 + 2^-21 max(1, |LSE2_i|)                             v_log_f32 and m + log2 l
+    The running max m (stale by up to 2^8 under defer-max) cancels between P and the saved m + log2 l."""
+    B, H, S, _ = q.shape
+    sl2 = attn_sl2(scale)
+    valid = _attn_valid(lens, B, S, q.device)
+    s2 = (q @ k.transpose(-1, -2)) * sl2
+    s2m = s2.masked_fill(~valid, float("-inf"))
+    lse2 = torch.logsumexp(s2m * _LN2, -1) / _LN2
+    ph = torch.exp2(s2m - lse2[..., None])
+    pe = ph * (_UB + _attn_eta(q, k, s2, sl2))
+    cm = torch.ones_like(ph) if keep is None else keep.double() * c
+    O = (ph * cm) @ v
+    tO = S * _U32 * ((ph * cm) @ v.abs()) + 2.0 ** -22 * O.abs() + 1e-30
+    for b in range(B):
+        for h in range(H):
+            w = cm[b, h][:, :, None] * v[b, h][None, :, :]  # [S(i), S(j), 64]
+            tO[b, h] += (pe[b, h][:, :, None] * (w - O[b, h][:, None, :]).abs()).sum(1) / (1 - 2 * _UB)
+    tL = pe.sum(-1) / (_LN2 * (1 - 2 * _UB)) + 2.0 ** -21 * lse2.abs().clamp_min(1.0)
+    return O, tO, lse2, tL
+
+
+def attn_bwd_bound(q, k, v, do, o, lse, lens, scale, keep=None, c=1.0):
+    """References and allowances of the backward kernels (attn_bwd_dq_ring_kernel, attn_bwd_dkdv_ring_kernel
+    and the register-staged pair) as a dict: delta, t_delta [B, H, S]; dq, t_dq, dk, t_dk, dv, t_dv [B, H, S, 64].
+
+    attn_bwd is a function of (qkv, out, dout, lse): `o` and `lse` are the forward kernel's OWN bf16 output
+    and fp32 LSE, given inputs here as they are to the kernels.
+        P_ij = 2^(s2_ij - lse_i) for j < len, else 0 (not renormalised);  delta_i = sum_d dO_id O_id
+        dP_ij = sum_d dO_id v_jd;   dV_j = c sum_i (P o M)_ij dO_i;   dS_ij = P_ij (c M_ij dP_ij - delta_i)
+        dQ_i = scale sum_j dS_ij k_j;   dK_j = scale sum_i dS_ij q_i
+    Rounding points, as attention.hip has them:
+      eta_ij = _attn_eta + ln2 2^-24 |lse_i| ... fast_exp2(sv * sl2 - lse): the fp32 score, its scaling, the
+                  subtraction of the given lse (relative to the larger operand), v_exp_f32
+      t_delta[i] = 64 2^-24 sum_d |dO_id O_id| ... 64 exact products summed in fp32 (the dQ prologue)
+      u on P o M and on dS ..................... pack_acc: both leave the accumulators as bf16 MFMA operands
+      t_dV[j,d] = c sum_i (u + eta_ij)(P o M)_ij |dO_id| + (S + 4) 2^-24 c sum_i (P o M)_ij |dO_id|
+                  (fp32 accumulation over the S queries, then `dv *= c` once on the finished sum)
+      e_dS_ij = (u + eta_ij)|dS_ij| + P_ij (64 2^-24 c M_ij sum_d |dO_id v_jd| + 2^-23 (c M_ij |dP_ij| + |delta_i|)
+                  + t_delta[i]) ... dP is an MFMA accumulation started at -delta (or 0, then one
+                  fma(c M, dP, -delta) under dropout): its 64 additions, the fold-in of delta, delta's own error
+      t_dQ[i,d] = scale sum_j e_dS_ij |k_jd| + (S + 4) 2^-24 scale sum_j |dS_ij k_jd|
+      t_dK[j,d] = scale sum_i e_dS_ij |q_id| + (S + 4) 2^-24 scale sum_i |dS_ij q_id|
+                  (`scale` multiplies the finished fp32 accumulator once, AFTER the accumulation: the S additions
+                  plus the rounding of `scale` to fp32 and that multiply, inside the 4 spare operations)."""
+    B, H, S, _ = q.shape
+    sl2 = attn_sl2(scale)
+    valid = _attn_valid(lens, B, S, q.device)
+    T_ = lambda x: x.transpose(-1, -2)
+    s2 = (q @ T_(k)) * sl2
+    P = torch.where(valid, torch.exp2(s2 - lse[..., None]), torch.zeros_like(s2))
+    ueta = _UB + _attn_eta(q, k, s2, sl2) + _LN2 * _U32 * lse.abs()[..., None]
+    delta = (do * o).sum(-1)
+    t_delta = 64 * _U32 * (do * o).abs().sum(-1) + 1e-30
+    cm = torch.ones_like(P) if keep is None else keep.double() * c
+    keepd = torch.ones_like(P) if keep is None else keep.double()
+    dP = do @ T_(v)
+    PM = P * keepd
+    acc = (S + 4) * _U32
+    dV = c * (T_(PM) @ do)
+    t_dV = c * (T_(ueta * PM) @ do.abs()) + acc * c * (T_(PM) @ do.abs()) + 1e-30
+    dS = P * (cm * dP - delta[..., None])
+    e_dS = ueta * dS.abs() + P * (64 * _U32 * cm * (do.abs() @ T_(v.abs()))
+                                  + 2.0 ** -23 * (cm * dP.abs() + delta.abs()[..., None]) + t_delta[..., None])
+    dQ = scale * (dS @ k)
+    t_dQ = scale * (e_dS @ k.abs()) + acc * scale * (dS.abs() @ k.abs()) + 1e-30
+    dK = scale * (T_(dS) @ q)
+    t_dK = scale * (T_(e_dS) @ q.abs()) + acc * scale * (T_(dS.abs()) @ q.abs()) + 1e-30
+    return dict(delta=delta, t_delta=t_delta, dq=dQ, t_dq=t_dQ, dk=dK, t_dk=t_dK, dv=dV, t_dv=t_dV)
+
+
+# (B, S, H, lens, scale) of the attention edge cases, padded mode, and the S at which dropout p = 0.1 runs too
+ATTN_EDGE_SHAPES = [
+    (2, 1, 1, None, 0.125),               # one query, one key
+    (2, 17, 2, [17, 5], 0.125),           # S < 64: min(AB, S) rows already in the prologue tile
+    (2, 63, 1, [63, 1], 0.125),           # one row short of a block; a one-key sequence
+    (3, 65, 1, [65, 64, 1], 0.125),       # a 1-row tail block, which lens = 64 makes a fully masked key block
+    (2, 127, 2, None, 0.125),             # the last S below the 2-group kernels
+    (2, 129, 1, [129, 128], 0.2),         # 2-group kernels with a 1-row tail; a scale that is no power of two
+    (2, 192, 2, [192, 130], 0.125),       # FULLT, the last 2-group block half empty, exactly kRing - 1 stages
+    (2, 320, 1, [320, 257], 0.125),       # FULLT, 5 stages: the first reuse of a ring slot
+]
+ATTN_EDGE_DROPOUT_S = (17, 65, 192, 320)
+
+
+def attn_edge_inputs(B, S, H, lens, scale, seed, sentinel_keys=True):
+    """qkv [B * S, 3 * H * 64] and dout [B * S, H * 64] (bf16, CPU) of one edge case. With `lens`, per (b, h),
+    the construction of test_attention_fwd_defer_max_branches: key len - 1 is a multiple of query 0, so that its
+    base-2 score leads row 0 by about 40 (the last valid key then carries row 0 alone: t_O there is at fp32 level
+    and losing the key is an error of order |v|), and where len < S key len is the same multiple of query 1 (the
+    first masked key would carry row 1 if it leaked)."""
+    g = torch.Generator().manual_seed(seed)
+    qkv = torch.randn(B * S, 3 * H * 64, generator=g) * 0.5
+    dout = torch.randn(B * S, H * 64, generator=g)
+    if lens is not None and sentinel_keys:
+        x = qkv.view(B, S, 3, H, 64)
+        for b in range(B):
+            for h in range(H):
+                for key, qi in ((lens[b] - 1, 0), (lens[b], 1)):
+                    if key < S and qi < S:
+                        qv = x[b, qi, 0, h].to(torch.bfloat16).double()
+                        x[b, key, 1, h] = (qv * (40.0 / (qv.pow(2).sum().item() * scale * _LOG2E))).float()
+    return qkv.to(torch.bfloat16), dout.to(torch.bfloat16)

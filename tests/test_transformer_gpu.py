@@ -322,7 +322,8 @@ def test_direct_flat_gradients_match_returned(dev):
     assert direct <= set(seen)
 
 
-@pytest.mark.parametrize("B,S,H,use_lens", [(2, 512, 3, False), (3, 200, 2, True), (2, 64, 1, False)])
+@pytest.mark.parametrize("B,S,H,use_lens", [(2, 512, 3, False), (3, 200, 2, True), (2, 64, 1, False),
+                                            (2, 17, 1, True), (3, 65, 1, True), (2, 192, 2, True), (2, 320, 1, False)])
 def test_attention_bwd_ring_matches_register_staged(dev, B, S, H, use_lens, monkeypatch):
     """The glds ring-staged backward kernels (MLT_ATTN_RING) compute the same products in the
     same order as the register-staged ones: bit-identical dQKV, including tails and masks."""
