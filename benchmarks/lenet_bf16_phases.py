@@ -1,9 +1,10 @@
 """Per-phase timing of the bf16 per-sample LeNet kernel (lenet_mfma.hip, LENET_TRACE): block 0
 stores s_memtime stamps at every phase boundary (each stamp adds a barrier, so the sum runs a
 little over the untraced kernel). Needs a trace build (-DMLT_LENET_TRACE_BUILD=1: the stamps are
-compiled out of the shipped kernel). With the split tail (two blocks per sample; MLT_LENET_SPLIT=0
-turns it off) block 0 is role D's, whose conv1 wgrad runs on waves 7-13, and the role-W blocks' end
-times are reported against it. Usage: python benchmarks/lenet_bf16_phases.py [batch] [--jsonl F]"""
+compiled out of the shipped kernel). With the split tail (ND + 1 blocks per sample; MLT_LENET_SPLIT=0
+turns it off, MLT_LENET_SPLIT_D picks ND) block 0 is role D's part 0, whose conv1 wgrad runs on waves
+7-13, and the other parts' and the role-W blocks' end times are reported against it.
+Usage: python benchmarks/lenet_bf16_phases.py [batch] [--jsonl F]"""
 import json
 import os
 import sys
@@ -100,11 +101,23 @@ ks_end = max(e for _, e in ks)
 print(f"KS blocks: start spread {(max(a for a, _ in ks) - t0) * 10} ns, block time "
       f"{min(e - a for a, e in ks) * 10}..{max(e - a for a, e in ks) * 10} ns, last end at {(ks_end - t0) * 10} ns")
 rec["ks_block_ns"] = [[(a - t0) * 10, (e - t0) * 10] for a, e in ks]
-# split tail (two blocks per sample): the phases above are role D's block 0; the role-W blocks'
-# wall clock follows role D's in the per-block slots (sample i: slot 600 + 2 (B + i))
+# split tail (ND + 1 blocks per sample): the phases above are block 0's, role D part 0 of sample 0;
+# part d of sample i has the per-block slot 600 + 2 (d B + i), its role-W block 600 + 2 (ND B + i)
 rec["split"] = split = bool(eng.eng.split_active(B))
+rec["split_blocks"] = nblk_s = int(eng.eng.split_blocks(B))
 if split:
-    kwr = [(tr[600 + 2 * (B + i)], tr[601 + 2 * (B + i)]) for i in range(B) if B + i < 200]
+    ND = nblk_s - 1
+    rec["role_d_part_block_ns"] = {}
+    for d in range(ND):
+        pt = [(tr[600 + 2 * (d * B + i)], tr[601 + 2 * (d * B + i)]) for i in range(B) if d * B + i < 200]
+        if not pt or not all(a and e for a, e in pt):
+            continue
+        print(f"split: role D part {d} of sample 0 ends {(pt[0][1] - ks[0][1]) * 10} ns after block 0 ends; its blocks "
+              f"start {(min(a for a, _ in pt) - t0) * 10}..{(max(a for a, _ in pt) - t0) * 10} ns, end "
+              f"{(min(e for _, e in pt) - t0) * 10}..{(max(e for _, e in pt) - t0) * 10} ns after the first start")
+        rec["role_d_part_block_ns"][str(d)] = [[(a - t0) * 10, (e - t0) * 10] for a, e in pt]
+        ks_end = max(ks_end, max(e for _, e in pt))
+    kwr = [(tr[600 + 2 * (ND * B + i)], tr[601 + 2 * (ND * B + i)]) for i in range(B) if ND * B + i < 200]
     if kwr and all(a and e for a, e in kwr):
         print(f"split: role W of sample 0 ends {(kwr[0][1] - ks[0][1]) * 10} ns after role D's block 0 ends "
               f"(negative: before); role W blocks start {(min(a for a, _ in kwr) - t0) * 10}.."

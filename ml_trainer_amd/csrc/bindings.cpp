@@ -1332,6 +1332,14 @@ class LeNetEngine {
     // bf16 per-sample kernel with two blocks per sample where eligible (MLT_LENET_SPLIT=0: off, for A/B)
     const char* se = std::getenv("MLT_LENET_SPLIT");
     split_ = !(se && std::string(se) == "0");
+    // ... and the role-D parts per sample of a split launch (MLT_LENET_SPLIT_D: 0 auto, else that ND)
+    const char* sd = std::getenv("MLT_LENET_SPLIT_D");
+    split_parts_ = 0;
+    if (sd && *sd) {
+      const int n = std::atoi(sd);
+      TORCH_CHECK(lenet_mfma_split_parts_valid(n), "MLT_LENET_SPLIT_D=", sd, ": not a built part count");
+      split_parts_ = n;
+    }
     A_ = LeNetAug{};
     O_ = LeNetOpt{};
   }
@@ -1458,9 +1466,23 @@ class LeNetEngine {
     if (prec_ != 1 || B <= 0 || B > max_b_) return false;
     return lenet_mfma_split_active(split_bits(LENET_FWD | LENET_CE | LENET_BWD), B, P_, A_);
   }
-  // (the switch travels to the bf16 step's launch as an internal mode bit; no other kernel sees it)
+  // role-D parts per sample of a split launch (0: auto; a forced value falls back to the next
+  // smaller one where (ND + 1) B blocks do not fit the CUs: split_blocks)
+  void set_split_parts(int n) {
+    TORCH_CHECK(lenet_mfma_split_parts_valid(n), "set_split_parts: ", n, " is not a built part count");
+    split_parts_ = n;
+    graphs_.clear();
+  }
+  int split_parts() const { return split_parts_; }
+  // blocks per sample of a bf16 training launch at batch B
+  int split_blocks(int B) const {
+    if (prec_ != 1 || B <= 0 || B > max_b_) return 1;
+    return lenet_mfma_split_blocks(split_bits(LENET_FWD | LENET_CE | LENET_BWD), B, P_, A_);
+  }
+  // (the switches travel to the bf16 step's launch as internal mode bits; no other kernel sees them)
   int split_bits(int mode) const {
-    return split_ || prec_ != 1 || !(mode & LENET_BWD) ? mode : mode | LENET_NOSPLIT;
+    if (prec_ != 1 || !(mode & LENET_BWD)) return mode;
+    return split_ ? mode | (split_parts_ << LENET_SPLITD_SHIFT) : mode | LENET_NOSPLIT;
   }
 
   void check_mode(int mode, int B) const {
@@ -1610,6 +1632,7 @@ class LeNetEngine {
   int prec_ = 0;
   bool fused_dp_ = true;
   bool split_ = true;
+  int split_parts_ = 0;
   int64_t shadow_n_ = 0;
   Tensor master_;          // the fp32 masters (version counter: host-side changes)
   int64_t pack_ver_ = -1;  // master_._version() at the last pack
@@ -1778,6 +1801,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("set_split", &LeNetEngine::set_split)
       .def("split", &LeNetEngine::split)
       .def("split_active", &LeNetEngine::split_active, py::arg("B"))
+      .def("set_split_parts", &LeNetEngine::set_split_parts, py::arg("n"))
+      .def("split_parts", &LeNetEngine::split_parts)
+      .def("split_blocks", &LeNetEngine::split_blocks, py::arg("B"))
       .def("clear_aug", &LeNetEngine::clear_aug)
       .def("set_ctrl", &LeNetEngine::set_ctrl)
       .def("set_opt", &LeNetEngine::set_opt)

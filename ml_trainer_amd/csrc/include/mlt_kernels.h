@@ -64,6 +64,9 @@ enum LeNetMode : int {
   LENET_PROBE_NOF1W = 1 << 18,  // role B skips the fc1 forward weight fetch
   LENET_PROBE_NOF2 = 1 << 19,   // fc2 forward + dgrad weight fetches skipped
   LENET_NOSPLIT = 1 << 20,      // internal: the bf16 per-sample kernel runs one block per sample (engine switch off)
+  // internal: role-D parts per sample of the split per-sample kernel, 3 bits (0: auto, else that ND)
+  LENET_SPLITD_SHIFT = 21,
+  LENET_SPLITD_MASK = 7 << 21,
 };
 
 struct LeNetPtrs {
@@ -131,6 +134,10 @@ void launch_lenet_mfma(int cfg, int mode, int B, const LeNetPtrs& P, const LeNet
                        hipStream_t stream);
 // whether that step's per-sample kernel would run two blocks per sample at batch B (split tail)
 bool lenet_mfma_split_active(int mode, int B, const LeNetPtrs& P, const LeNetAug& A);
+// blocks per sample of that launch: 1 unsplit, else ND + 1 (ND role-D parts sharing the conv1 wgrad
+// by kernel column, and the role-W block); whether n is a LENET_SPLITD value the build carries
+int lenet_mfma_split_blocks(int mode, int B, const LeNetPtrs& P, const LeNetAug& A);
+bool lenet_mfma_split_parts_valid(int n);
 int lenet_mfma_slab_floats(int cfg);
 int lenet_mfma_kw_blocks(int cfg);  // grid of the batch-reduction / optimizer kernel
 // data-parallel bf16 step: optimizer update from the all-reduced gradient + bf16 shadow + fragment

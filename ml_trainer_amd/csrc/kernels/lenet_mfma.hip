@@ -12,7 +12,16 @@ void launch_ms(int cfg, int mode, int B, const LeNetPtrs& P, const LeNetAug& A, 
 }  // namespace lm
 
 bool lenet_mfma_split_active(int mode, int B, const LeNetPtrs& P, const LeNetAug& A) {
+  return lm::split_eligible(mode, B, P, A) > 1;
+}
+int lenet_mfma_split_blocks(int mode, int B, const LeNetPtrs& P, const LeNetAug& A) {
   return lm::split_eligible(mode, B, P, A);
+}
+bool lenet_mfma_split_parts_valid(int n) {
+  if (n == 0) return true;
+  for (int nd : lm::kSplitND)
+    if (n == nd) return true;
+  return false;
 }
 
 void launch_lenet_mfma_reduce(int cfg, int B, const LeNetPtrs& P, const LeNetOpt& O, const XgmiFused* X,

@@ -10,9 +10,10 @@
 //       pixels the previous KW's prep blocks made (tag hit: one load); without prep buffers the
 //       NEXT step's raw image is gathered (epoch permutation -> dataset row) and staged by an
 //       otherwise idle wave instead.
-//       lenet_ms<D, true> (grid 2 B, where 2 B fits the CUs): a second CU per sample recomputes the
-//       chain up to the fc1 dgrad and takes the stores, the staging and the conv2 wgrad off the
-//       first one's conv2 dgrad -> conv1 wgrad chain (see the kernel).
+//       lenet_ms<D, ND> (ND > 0: grid (ND + 1) B, where that fits the CUs): a further CU per sample
+//       recomputes the chain up to the fc1 dgrad and takes the stores, the staging and the conv2
+//       wgrad off the first one's conv2 dgrad -> conv1 wgrad chain; with ND > 1 that chain runs on
+//       ND CUs, which share the conv1 wgrad by kernel column (see the kernel).
 //       The ~250 KB of fc weight fragments a CU fetches per step are the other cost besides the
 //       latency chain (a CU's vector memory path moves ~35 B/clk and a wave stalls while its loads
 //       queue), so fetches go to waves without work in that phase: waves 8-15 fetch fc1 while 0-7
@@ -178,6 +179,18 @@ constexpr int D1S = 28 * 32 + 16;  // [oc][Y][X32] unpooled conv1 grad: channel 
 constexpr int kWgT = 256;        // KW threads
 constexpr int kP13W = 7;         // conv1 wgrad waves (28 output rows / 4 each)
 constexpr int kC1W = 8;          // conv1 forward waves (the fc1 forward waves 8-15 fetch weights meanwhile)
+// Role-D parts per sample (ND) the split kernel is built for, ascending, and what a launch picks by
+// itself where it fits. Part d of ND owns the conv1 wgrad's kernel columns kw in [lo, hi): ND 1 all
+// five; ND 3: {0,1} {2,3} {4}; part 0 always owns kw 0 (the bias row).
+// Measured alternatives that lost (batch 32, us per step, medians of 6 alternating runs,
+// profiles/r8/lenet_splitd_ab_summary.txt; ND 1 15.05, ND 3 14.70):
+//   ND 2, {0,1,2} {3,4}: 14.80 -- part 0 still carries three of the five tiles
+//   ND 5, one kw each: 14.78 -- the MFMA phase shrinks further (1200 vs 1488 cycles) but six blocks
+//     per sample stretch the P0 loads (1.55 vs 1.23 us in block 0)
+constexpr int kSplitND[] = {1, 3};
+constexpr int kSplitAuto = 3;
+constexpr int c1w_kw_lo(int nd, int d) { return nd == 3 ? 2 * d : 0; }
+constexpr int c1w_kw_hi(int nd, int d) { return nd == 3 ? (d == 2 ? 5 : 2 * d + 2) : 5; }
 #ifndef MLT_LENET_TRACE_BUILD
 #define MLT_LENET_TRACE_BUILD 0  // 1: the LENET_TRACE stamps are compiled in (benchmarks/lenet_bf16_phases.py)
 #endif
@@ -400,21 +413,28 @@ __device__ __forceinline__ void pool4(f32x4 a, float bias, float& pv, uint8_t& c
 // ---------------------------------------------------------------------------
 // KS: the per-sample chain
 // ---------------------------------------------------------------------------
-// The per-sample kernel of the two-launch step (grid B; SPLIT: grid 2 B).
+// The per-sample kernel of the two-launch step (ND = 0: grid B; SPLIT = ND > 0: grid (ND + 1) B).
 //
-// SPLIT: two workgroups per sample, on two CUs. Blocks [0, B) are role D (dgrad), blocks [B, 2 B)
-// role W (wgrad) of sample blockIdx.x - B. Both run P0 .. P8 on the same inputs with the same
-// arithmetic, so each holds bit for bit what the single block holds; then the tail's two independent
-// halves part ways: role D runs the conv2 dgrad -> conv1 wgrad chain (the critical path), role W
-// everything else (the stores for KW, the next-step staging, the conv2 wgrad) and returns. The two
-// blocks of a sample never synchronise or communicate: no flag, counter or poll.
-// Global memory audit (SPLIT): every location is written by exactly one role, and nothing one role
-// writes is read by the other role in the same launch.
+// SPLIT: ND + 1 workgroups per sample, each on a CU of its own. Blocks [d B, (d + 1) B), d < ND, are
+// role D (dgrad), part d, of sample blockIdx.x - d B; the last B blocks are role W (wgrad). All run
+// P0 .. P8 on the same inputs with the same arithmetic, so each holds bit for bit what the single
+// block holds; then the tail's independent pieces part ways: role D runs the conv2 dgrad -> conv1
+// wgrad chain (the critical path), role W everything else (the stores for KW, the next-step
+// staging, the conv2 wgrad) and returns. With ND > 1 every role-D part runs the whole dgrad (P11)
+// and then the conv1 wgrad of the kernel columns kw it owns (c1w_kw_lo / _hi): the five kw tiles are
+// independent accumulator chains over all 28 rows, their 7 row-range partials are summed per
+// element in the order p0 .. p6 and each sum goes to its own slab element, so every element is
+// produced exactly as in the single block, by the one part that owns its kw. The blocks of a sample
+// never synchronise or communicate: no flag, counter or poll.
+// Global memory audit (SPLIT): every location is written by exactly one block of a sample, and
+// nothing one block writes is read by another block in the same launch.
 //   written by role W only: stage2 / meta2 / metaN rows b (staging wave 7); p2, h1, h2, dh2, logits,
-//     dlogits, cestat rows b (P5); dflat, dh1 rows b, targets[b], stepinfo (block B: b == 0) (P10);
+//     dlogits, cestat rows b (P5); dflat, dh1 rows b, targets[b], stepinfo (block ND B: b == 0) (P10);
 //     slab1 row b, the conv2 part [S2OFF, S2OFF + S2)
-//   written by role D only: slab1 row b, the conv1 part [0, S1); the LENET_TRACE phase stamps (block 0)
-//   written by both, to distinct slots: the LENET_TRACE per-block wall clock (slot by blockIdx.x)
+//   written by role D only: slab1 row b, the conv1 part [0, S1): element oc*76 + (c*5 + kh)*5 + kw by
+//     the part d that owns kw, the bias element oc*76 + 75 by part 0 (the owner of kw 0); the
+//     LENET_TRACE phase stamps (block 0: part 0 of sample 0)
+//   written by all, to distinct slots: the LENET_TRACE per-block wall clock (slot by blockIdx.x)
 //   read by both: ctrl, pmeta / prep rows b (written by KW only), wimg, shadow, the biases, x, perm,
 //     data, dtargets, targets[b] (read only without a dataset, written only with one)
 //   read by role W only: metaN row b (its own staging wave, before that wave rewrites it), lr table
@@ -422,7 +442,7 @@ __device__ __forceinline__ void pool4(f32x4 a, float bias, float& pv, uint8_t& c
 //     the staging wave rewrites later -- ordered inside one block, a race across two. The host never
 //     launches SPLIT there (split_eligible). Without a dataset P0 still loads those rows (unused),
 //     but nothing stages, so nothing writes them.
-template <class D, bool SPLIT>
+template <class D, int ND>
 // The pointers the first loads need lead the argument list as plain scalars: the file is built with
 // kernarg preloading (build.py), so they arrive in SGPRs with the wave instead of behind an s_load
 // of the kernarg segment (aggregates are never preloaded).
@@ -440,10 +460,23 @@ __global__ __launch_bounds__(kT) void lenet_ms(uint8_t* __restrict__ pstage2, in
   // so a role's pending loads never force waits on the other roles' code paths
   // the role is block-uniform (an SGPR); without SPLIT every block does both halves of the tail
   // (doW / doD fold to true)
+  // (part index pd and sample b from compares against multiples of B: no division)
+  constexpr bool SPLIT = ND > 0;
   const int bi = (int)blockIdx.x;
-  const bool roleW = SPLIT && bi >= B;
+  int pd = 0, b = bi;
+  if constexpr (ND > 1) {
+#pragma unroll
+    for (int k = 1; k <= ND; ++k) {
+      if (bi >= k * B) {
+        pd = k;
+        b = bi - k * B;
+      }
+    }
+  }
+  const bool roleW = ND > 1 ? pd == ND : SPLIT && bi >= B;
+  if constexpr (ND == 1) b = roleW ? bi - B : bi;
   const bool doW = !SPLIT || roleW, doD = !SPLIT || !roleW;
-  const int b = roleW ? bi - B : bi, t = threadIdx.x, lane = t & 63, g = lane >> 4, m = lane & 15;
+  const int t = threadIdx.x, lane = t & 63, g = lane >> 4, m = lane & 15;
   const int w = __builtin_amdgcn_readfirstlane(t >> 6);
   // LENET_TRACE: s_memtime stamps of block 0 per phase (P.trace: 32 8-byte slots; 100 MHz wall
   // stamps at 14, 15; sub-phase stamps at 16..)
@@ -1092,7 +1125,8 @@ __global__ __launch_bounds__(kT) void lenet_ms(uint8_t* __restrict__ pstage2, in
     }
   };
   // LENET_TRACE: this block's wall clock (slots 600 + 2 blockIdx (+1); SPLIT: role W's blocks follow
-  // role D's, so slot 600 + 2 B (+1) is when the role-W block of sample 0 started / ended)
+  // role D's parts, so slot 600 + 2 (d B + i) (+1) is when part d of sample i started / ended and
+  // slot 600 + 2 (ND B + i) (+1) its role-W block)
   auto block_clock = [&]() {
     if constexpr (!kTraceBuild) return;
     if (!((mode & LENET_TRACE) && P.trace && bi < 200)) return;
@@ -1121,9 +1155,13 @@ __global__ __launch_bounds__(kT) void lenet_ms(uint8_t* __restrict__ pstage2, in
     lo = *reinterpret_cast<const u32x4*>(xrow + Y * XCS);
     hi = *reinterpret_cast<const u32x4*>(xrow + Y * XCS + 8);
   };
-  // row range `slot` -> partial slot `slot`; PRE: the input rows are already in plo / phi
-  auto c1w = [&](int slot, auto PREc, const u32x4* plo, const u32x4* phi) __attribute__((always_inline)) {
+  // row range `slot` -> partial slot `slot`; PRE: the input rows are already in plo / phi; the kw
+  // tiles [K0, K1) only (compile-time: the shifts, MFMAs and scr writes of the others do not exist)
+  auto c1w = [&](int slot, auto PREc, auto K0c, auto K1c, const u32x4* plo, const u32x4* phi)
+                 __attribute__((always_inline)) {
     constexpr bool PRE = decltype(PREc)::value;
+    constexpr int K0 = decltype(K0c)::value, K1 = decltype(K1c)::value;
+    static_assert(0 <= K0 && K0 < K1 && K1 <= 5, "kw range");
     const bool valid = m < 15;
     const int x0 = 8 * g;
     const uint16_t* drow = L.v.k.d1 + min(m, C1 - 1) * D1S + x0;
@@ -1144,16 +1182,34 @@ __global__ __launch_bounds__(kT) void lenet_ms(uint8_t* __restrict__ pstage2, in
       } else {
         c1w_row(slot, yy, lo, hi);
       }
-      acc[0] = mfma(valid ? fshift<0>(lo, hi) : (m == 15 ? ONES : Z), bq, acc[0]);
-      acc[1] = mfma(valid ? fshift<1>(lo, hi) : Z, bq, acc[1]);
-      acc[2] = mfma(valid ? fshift<2>(lo, hi) : Z, bq, acc[2]);
-      acc[3] = mfma(valid ? fshift<3>(lo, hi) : Z, bq, acc[3]);
-      acc[4] = mfma(valid ? fshift<4>(lo, hi) : Z, bq, acc[4]);
+      if constexpr (K0 <= 0 && 0 < K1) acc[0] = mfma(valid ? fshift<0>(lo, hi) : (m == 15 ? ONES : Z), bq, acc[0]);
+      if constexpr (K0 <= 1 && 1 < K1) acc[1] = mfma(valid ? fshift<1>(lo, hi) : Z, bq, acc[1]);
+      if constexpr (K0 <= 2 && 2 < K1) acc[2] = mfma(valid ? fshift<2>(lo, hi) : Z, bq, acc[2]);
+      if constexpr (K0 <= 3 && 3 < K1) acc[3] = mfma(valid ? fshift<3>(lo, hi) : Z, bq, acc[3]);
+      if constexpr (K0 <= 4 && 4 < K1) acc[4] = mfma(valid ? fshift<4>(lo, hi) : Z, bq, acc[4]);
     }
 #pragma unroll
-    for (int kw = 0; kw < 5; ++kw)
+    for (int kw = K0; kw < K1; ++kw)
 #pragma unroll
       for (int r = 0; r < 4; ++r) L.u.b.scr[((slot * 5 + kw) * 16 + 4 * g + r) * 16 + m] = acc[kw][r];
+  };
+  // role D, part pd: its kw range, one dispatch per block (pd is block-uniform)
+  auto c1w_part = [&](int slot, const u32x4* plo, const u32x4* phi) __attribute__((always_inline)) {
+    auto part = [&](auto Dc) __attribute__((always_inline)) {
+      constexpr int d = decltype(Dc)::value;
+      c1w(slot, std::true_type{}, std::integral_constant<int, c1w_kw_lo(ND, d)>{},
+          std::integral_constant<int, c1w_kw_hi(ND, d)>{}, plo, phi);
+    };
+    if constexpr (ND <= 1) {
+      part(std::integral_constant<int, 0>{});
+    } else {
+      static_assert(ND == 3, "role-D parts: 1 or 3");
+      switch (pd) {
+        case 0: part(std::integral_constant<int, 0>{}); break;
+        case 1: part(std::integral_constant<int, 1>{}); break;
+        default: part(std::integral_constant<int, 2>{}); break;
+      }
+    }
   };
   if constexpr (SPLIT) {
     if (roleW) {  // (its operands, dcc and p1c, were complete at the barrier that closed P8)
@@ -1174,7 +1230,7 @@ __global__ __launch_bounds__(kT) void lenet_ms(uint8_t* __restrict__ pstage2, in
 #pragma unroll
       for (int yy = 0; yy < 28 / kP13W; ++yy) c1w_row(w - 7, yy, xlo[yy], xhi[yy]);
       p11_end();
-      c1w(w - 7, std::true_type{}, xlo, xhi);
+      c1w_part(w - 7, xlo, xhi);
     } else {
       p11_end();
     }
@@ -1189,12 +1245,25 @@ __global__ __launch_bounds__(kT) void lenet_ms(uint8_t* __restrict__ pstage2, in
       for (int tt0 = t0; tt0 < t1; ++tt0) wgrad_tile(w == 7 && tt0 == 1 ? 9 : tt0);
     }
     p11_end();
-    if (w < kP13W) c1w(w, std::false_type{}, nullptr, nullptr);
+    if (w < kP13W)
+      c1w(w, std::false_type{}, std::integral_constant<int, 0>{}, std::integral_constant<int, 5>{}, nullptr, nullptr);
   }
   wstamp(4);
   lbar();
   stamp(23);
-  for (int e = t; e < 5 * 256; e += kT) {
+  // the fixed-order sum p0 .. p6 of the kw tiles this block owns (block-uniform bounds; all five
+  // unless ND > 1)
+  int e0 = 0, e1 = 5 * 256;
+  if constexpr (ND > 1) {
+#pragma unroll
+    for (int k = 0; k < ND; ++k) {
+      if (pd == k) {
+        e0 = c1w_kw_lo(ND, k) * 256;
+        e1 = c1w_kw_hi(ND, k) * 256;
+      }
+    }
+  }
+  for (int e = e0 + t; e < e1; e += kT) {
     const int kw = e >> 8, i = (e >> 4) & 15, oc = e & 15;
     float v = L.u.b.scr[e];
 #pragma unroll
@@ -1206,8 +1275,8 @@ __global__ __launch_bounds__(kT) void lenet_ms(uint8_t* __restrict__ pstage2, in
   }
   stamp(24);
   stamp(13);
-  if (kTraceBuild && (mode & LENET_TRACE) && b == 0 && t < 32 && P.trace) reinterpret_cast<unsigned long long*>(P.trace)[t] = L.tr[t];
-  if (kTraceBuild && (mode & LENET_TRACE) && b == 0 && t < 96 && P.trace)
+  if (kTraceBuild && (mode & LENET_TRACE) && bi == 0 && t < 32 && P.trace) reinterpret_cast<unsigned long long*>(P.trace)[t] = L.tr[t];
+  if (kTraceBuild && (mode & LENET_TRACE) && bi == 0 && t < 96 && P.trace)
     reinterpret_cast<unsigned long long*>(P.trace)[1024 + t] = (&L.wtr[0][0])[t];
   block_clock();
 }
@@ -2008,26 +2077,40 @@ inline int device_cus() {
   return cus[dev] > 0 ? cus[dev] : 0;
 }
 
-// Whether a per-sample launch at batch B runs two blocks per sample (lenet_ms<D, true>): a whole
-// training step, the engine's switch on (LENET_NOSPLIT clear), nothing
-// the kernel reads is written by it (the audit above lenet_ms: with a dataset the inputs must come
-// from the prep buffers), and both blocks of every sample resident at once -- a second round of
-// blocks would cost more than the split saves.
-inline bool split_eligible(int mode, int B, const LeNetPtrs& P, const LeNetAug& A) {
-  if (!(mode & LENET_BWD) || (mode & LENET_NOSPLIT)) return false;
-  if (A.data && !(P.prep && P.pmeta)) return false;
-  return B > 0 && 2 * B <= device_cus();
+// The blocks per sample of a per-sample launch at batch B: 1 (lenet_ms<D, 0>), or ND + 1
+// (lenet_ms<D, ND>) for a whole training step with the engine's switch on (LENET_NOSPLIT clear),
+// where nothing the kernel reads is written by it (the audit above lenet_ms: with a dataset the
+// inputs must come from the prep buffers) and every block of every sample is resident at once -- a
+// second round of blocks would cost more than the split saves. ND is the LENET_SPLITD value (0:
+// kSplitAuto) or, where (ND + 1) B exceeds the CUs, the next smaller built one; unsplit when not
+// even 2 B fits.
+inline int split_eligible(int mode, int B, const LeNetPtrs& P, const LeNetAug& A) {
+  if (!(mode & LENET_BWD) || (mode & LENET_NOSPLIT)) return 1;
+  if (A.data && !(P.prep && P.pmeta)) return 1;
+  if (B <= 0) return 1;
+  int want = (mode & LENET_SPLITD_MASK) >> LENET_SPLITD_SHIFT;
+  if (want == 0) want = kSplitAuto;
+  const int cus = device_cus();
+  int nd = 0;
+  for (int k : kSplitND)  // ascending
+    if (k <= want && (k + 1) * B <= cus) nd = k;
+  return nd + 1;
+}
+
+template <class D, int ND>
+void launch_ms_nd(int mode, int B, const LeNetPtrs& P, const LeNetAug& A, const LeNetOpt& O, hipStream_t st) {
+  hipLaunchKernelGGL((lenet_ms<D, ND>), dim3((ND + 1) * B), dim3(kT), 0, st, P.stage2, P.meta2, A.ctrl, P.wimg,
+                     P.metaN, mode, 1.f / (float)B, P, A, O, B);
 }
 
 template <class D>
 void launch_ms_t(int mode, int B, const LeNetPtrs& P, const LeNetAug& A, const LeNetOpt& O, hipStream_t st) {
-  const float inv_B = 1.f / (float)B;
-  if (split_eligible(mode, B, P, A))
-    hipLaunchKernelGGL((lenet_ms<D, true>), dim3(2 * B), dim3(kT), 0, st, P.stage2, P.meta2, A.ctrl, P.wimg, P.metaN,
-                       mode, inv_B, P, A, O, B);
-  else
-    hipLaunchKernelGGL((lenet_ms<D, false>), dim3(B), dim3(kT), 0, st, P.stage2, P.meta2, A.ctrl, P.wimg, P.metaN,
-                       mode, inv_B, P, A, O, B);
+  switch (split_eligible(mode, B, P, A) - 1) {
+    case 0: launch_ms_nd<D, 0>(mode, B, P, A, O, st); break;
+    case 1: launch_ms_nd<D, 1>(mode, B, P, A, O, st); break;
+    case 3: launch_ms_nd<D, 3>(mode, B, P, A, O, st); break;
+    default: throw std::runtime_error("lenet_ms: role-D part count not built");
+  }
 }
 
 template <class D>

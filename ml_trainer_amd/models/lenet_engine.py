@@ -9,7 +9,9 @@ zero_grad -> H2D -> forward -> CE -> loss.item() -> backward (DDP all-reduce)
   input -- RandomCrop/HFlip/Normalize of the HBM-resident uint8 image, prepared by
   the previous step's second kernel -- conv/fc forward on MFMA, softmax-CE, the
   whole backward of the sample, its weight-gradient slab; a second CU per sample
-  takes half of the backward tail where 2 x batch fits the CUs, ``set_split``).
+  takes half of the backward tail where 2 x batch fits the CUs, ``set_split``, and
+  the other half's conv1 weight gradient is shared by kernel column over three CUs
+  where 4 x batch fits, ``set_split_parts``).
   ``lenet_mw``: the batch
   reductions in sample order, the on-device loss/accuracy sums, the fused optimizer
   update of the fp32 masters + bf16 shadow + fragment images, and (on CUs those
@@ -416,6 +418,20 @@ class LeNetStepEngine:
         """Whether a bf16 training step at batch ``B`` would run split: the switch is on, with a
         dataset attached the prep buffers are in use, and ``2 * B`` fits the device's CUs."""
         return bool(self.eng.split_active(int(B)))
+
+    def set_split_parts(self, n: int) -> None:
+        """bf16 step, split on: the number ND of role-D workgroups per sample, which share the conv1
+        weight gradient by kernel column ``kw`` (each recomputes the chain up to the conv2 dgrad and
+        does the ``kw`` tiles it owns). 0: auto (the measured-best ND that fits the CUs: 3); 1, 3:
+        that ND where ``(ND + 1) * B`` fits, else the next smaller one -- see ``split_blocks``.
+        Default: MLT_LENET_SPLIT_D, else auto. Results are bitwise the same for every value; the
+        captured graphs are dropped."""
+        self.eng.set_split_parts(int(n))
+
+    def split_blocks(self, B: int) -> int:
+        """Workgroups per sample that a bf16 training step at batch ``B`` would launch: 1 unsplit,
+        else ND + 1 (ND role-D parts and the role-W block)."""
+        return int(self.eng.split_blocks(int(B)))
 
     # ------------------------------------------------------------------ steps
     @property
