@@ -3,7 +3,9 @@
 next to ``F.scaled_dot_product_attention(dropout_p=P)``.
 ``--min-len L``: variable-length sequences (lengths uniform in [L, S], seeded) through the native kernels,
 as padded ``lens`` or, with ``--packed``, as one [T, 3D] matrix with ``cu_seqlens``; the SDPA columns stay
-the full-length run and the TFLOP/s count the full B x S x S work, so padded and packed compare by time."""
+the full-length run and the TFLOP/s count the full B x S x S work, so padded and packed compare by time.
+``--causal``: the causal instantiations of the native kernels next to ``F.scaled_dot_product_attention(
+is_causal=True)``; the TFLOP/s still count the full B x S x S work, so causal and non-causal compare by time."""
 import argparse
 import json
 import os
@@ -19,6 +21,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--dropout", type=float, default=0.0, help="attention-probability dropout (default 0.0)")
 ap.add_argument("--min-len", type=int, default=0, help="variable-length sequences, lengths in [min-len, S]")
 ap.add_argument("--packed", action="store_true", help="packed rows + cu_seqlens instead of padded rows + lens")
+ap.add_argument("--causal", action="store_true", help="causal attention (key <= query), SDPA with is_causal=True")
 ARGS = ap.parse_args()
 P = ARGS.dropout
 DROP = dict(p=P, seed=0x123456789ABCDEF, site=0x40000000, rank=0) if P > 0 else {}
@@ -43,7 +46,7 @@ def timeit(fn, iters=20):
 
 qkv = torch.randn(B * S, 3 * D, device=dev).to(torch.bfloat16)
 dout = torch.randn(B * S, D, device=dev).to(torch.bfloat16)
-LENS, KW, TOK = None, dict(DROP), B * S
+LENS, KW, TOK = None, dict(DROP, **({"causal": True} if ARGS.causal else {})), B * S
 if ARGS.packed and not ARGS.min_len:
     ap.error("--packed needs --min-len")
 if ARGS.min_len:
@@ -66,17 +69,17 @@ delta = torch.empty(nq.shape[0] * H, device=dev)
 C.attn_fwd(nq, out, lse, LENS, B, S, H, 0.125, **KW)
 q, k, v = qkv.view(B, S, 3, H, 64).permute(2, 0, 3, 1, 4)
 q, k, v = [t.contiguous().requires_grad_() for t in (q, k, v)]
-o = F.scaled_dot_product_attention(q, k, v, dropout_p=P)
+o = F.scaled_dot_product_attention(q, k, v, dropout_p=P, is_causal=ARGS.causal)
 go = dout.view(B, S, H, 64).transpose(1, 2).contiguous()
 fl_f = 4.0 * B * H * S * S * 64
 
 t = {
     "native_fwd": timeit(lambda: C.attn_fwd(nq, out, lse, LENS, B, S, H, 0.125, **KW)),
     "native_bwd": timeit(lambda: C.attn_bwd(nq, out, nd, lse, delta, LENS, dqkv, B, S, H, 0.125, **KW)),
-    "sdpa_fwd": timeit(lambda: F.scaled_dot_product_attention(q, k, v, dropout_p=P)),
+    "sdpa_fwd": timeit(lambda: F.scaled_dot_product_attention(q, k, v, dropout_p=P, is_causal=ARGS.causal)),
     "sdpa_bwd": timeit(lambda: torch.autograd.grad(o, (q, k, v), go, retain_graph=True)),
 }
-rec = {"B": B, "S": S, "H": H, "dropout": P, "min_len": ARGS.min_len, "packed": ARGS.packed, "tokens": TOK,
+rec = {"B": B, "S": S, "H": H, "dropout": P, "causal": ARGS.causal, "min_len": ARGS.min_len, "packed": ARGS.packed, "tokens": TOK,
        "fill": round(TOK / (B * S), 4), **{k_: round(v_, 4) for k_, v_ in t.items()},
        "native_fwd_tflops": round(fl_f / t["native_fwd"] / 1e9, 1),
        "native_bwd_tflops": round(2.5 * fl_f / t["native_bwd"] / 1e9, 1),

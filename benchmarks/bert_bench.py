@@ -33,9 +33,10 @@ import torch.nn.functional as F  # noqa: E402
 
 
 def run(args):
-    from ml_trainer_amd.models.bert import BertClassifier, BertForMaskedLM, bert_config
+    from ml_trainer_amd.models.bert import BertClassifier, BertForMaskedLM, BertLMHeadModel, bert_config
     from ml_trainer_amd.ops.optim import build_optimizer
-    mlm = args.task == "mlm"
+    clm = args.task == "clm"
+    mlm = args.task == "mlm" or clm  # (clm: the same head, one slot per position)
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
     over = {"layers": args.layers} if args.layers else {}
@@ -48,7 +49,7 @@ def run(args):
     if args.min_len:
         over["pad_id"] = 0
     cfg = bert_config(args.model, **over)
-    m = (BertForMaskedLM if mlm else BertClassifier)(cfg).to(dev)
+    m = (BertLMHeadModel if clm else BertForMaskedLM if mlm else BertClassifier)(cfg).to(dev)
     if mlm and args.chunk_rows:
         m.mlm_chunk_rows = args.chunk_rows
     if args.impl == "native":
@@ -69,11 +70,14 @@ def run(args):
         ids[torch.arange(args.seq, device=dev)[None, :] >= lens[:, None]] = 0
         real = int(lens.sum())
     y = torch.randint(0, cfg.num_labels, (args.batch,), device=dev)
-    if mlm:  # masked rows (80 / 10 / 10) of the learnable synthetic text; lengths as above
-        from ml_trainer_amd.data.text import SyntheticMaskedLM
-        ds = SyntheticMaskedLM(args.batch, seq_len=args.seq, vocab_size=cfg.vocab_size, seed=1,
-                               max_predictions=m.max_predictions(args.seq),
-                               **({"min_len": args.min_len, "pad_id": 0} if args.min_len else {}))
+    if mlm:  # masked rows (80 / 10 / 10) of the learnable synthetic text (clm: unmasked, next-token labels)
+        from ml_trainer_amd.data.text import SyntheticCausalLM, SyntheticMaskedLM
+        var = {"min_len": args.min_len, "pad_id": 0} if args.min_len else {}
+        if clm:
+            ds = SyntheticCausalLM(args.batch, seq_len=args.seq, vocab_size=cfg.vocab_size, seed=1, **var)
+        else:
+            ds = SyntheticMaskedLM(args.batch, seq_len=args.seq, vocab_size=cfg.vocab_size, seed=1,
+                                   max_predictions=m.max_predictions(args.seq), **var)
         ids, y = ds.ids.to(dev), ds.labels.to(dev)
         real = int(ds.lengths.sum())
         loss_fn = m.mlm_loss if args.impl == "native" else m.mlm_loss_torch_bf16
@@ -122,7 +126,7 @@ def run(args):
             head()
         torch.cuda.synchronize()
         hd = (time.perf_counter() - t0) / args.steps
-        rec.update({"task": "mlm", "head_ms": hd * 1e3, "head_share": hd / dt,
+        rec.update({"task": args.task, "head_ms": hd * 1e3, "head_share": hd / dt,
                     "max_predictions": m.max_predictions(args.seq), "chunk_rows": m.mlm_chunk_rows,
                     "mlm_accuracy": float(m.last_mlm_accuracy) if args.impl == "native" else None})
     print(json.dumps(rec), flush=True)
@@ -148,8 +152,9 @@ def main():
                     help="native optimizer: adamw (one flat launch) or lamb (three launches, layer-wise trust ratio)")
     ap.add_argument("--no-decay-1d", action="store_true",
                     help="no weight decay (lamb: no trust ratio) on biases and LayerNorm parameters (ndim <= 1)")
-    ap.add_argument("--task", choices=["classify", "mlm"], default="classify",
-                    help="classify: BertClassifier + cross-entropy; mlm: BertForMaskedLM + the fused MLM head")
+    ap.add_argument("--task", choices=["classify", "mlm", "clm"], default="classify",
+                    help="classify: BertClassifier + cross-entropy; mlm: BertForMaskedLM + the fused MLM head; "
+                         "clm: BertLMHeadModel (causal attention) + that head on every position's next token")
     ap.add_argument("--chunk-rows", type=int, default=0, help="--task mlm: rows of logits alive at once (default: "
                     "ops.mlm.DEFAULT_CHUNK_ROWS)")
     ap.add_argument("--out", default="")

@@ -1024,7 +1024,8 @@ static int64_t attn_rows(const c10::optional<Tensor>& cu, const Tensor& qkv, int
 // p, seed, site, rank: attention-probability dropout inside the kernel (p == 0: none)
 // cu_seqlens: packed (unpadded) batch, see attn_rows; S is then max_seqlen and lens is unused
 void attn_fwd(Tensor qkv, Tensor out, Tensor lse, c10::optional<Tensor> lens, int64_t B, int64_t S, int64_t H,
-              double scale, double p, int64_t seed, int64_t site, int64_t rank, c10::optional<Tensor> cu_seqlens) {
+              double scale, double p, int64_t seed, int64_t site, int64_t rank, c10::optional<Tensor> cu_seqlens,
+              bool causal) {
   const int64_t D = H * 64;
   TORCH_CHECK(B > 0 && S > 0 && H > 0 && B <= 65535 && H <= 65535, "attention dims");
   const int* cu = nullptr;
@@ -1034,16 +1035,18 @@ void attn_fwd(Tensor qkv, Tensor out, Tensor lse, c10::optional<Tensor> lens, in
   check_dev(lse, "lse", at::kFloat, B * H * S, 4);
   const AttnDropArgs ad = make_attn_drop_args(p, seed, site, rank, S);
   launch_attn_fwd(bf16_ptr(qkv), (uint16_t*)out.data_ptr(), lse.data_ptr<float>(), cu ? nullptr : lens_ptr(lens, B),
-                  (int)B, (int)S, (int)H, (float)scale, cur_stream(), ad, cu, (int)T);
+                  (int)B, (int)S, (int)H, (float)scale, cur_stream(), ad, cu, (int)T, causal);
 }
 
 void attn_bwd(Tensor qkv, Tensor out, Tensor dout, Tensor lse, Tensor delta, c10::optional<Tensor> lens, Tensor dqkv,
               int64_t B, int64_t S, int64_t H, double scale, c10::optional<Tensor> colsum_out,
               bool colsum_accumulate, c10::optional<Tensor> q8_y, c10::optional<Tensor> q8_yt,
               c10::optional<Tensor> q8_scale, c10::optional<Tensor> q8_amax, double p, int64_t seed, int64_t site,
-              int64_t rank, c10::optional<Tensor> cu_seqlens) {
+              int64_t rank, c10::optional<Tensor> cu_seqlens, bool causal) {
   const int64_t D = H * 64;
   TORCH_CHECK(B > 0 && S > 0 && H > 0 && B <= 65535 && H <= 65535, "attention dims");
+  TORCH_CHECK(!causal || !q8_y.has_value(), "attn_bwd: causal attention has no fp8 (q8) outputs: the q8 epilogue has "
+              "no causal instantiation");
   const AttnDropArgs ad = make_attn_drop_args(p, seed, site, rank, S);  // the forward's (p, seed, site, rank)
   const int* cu = nullptr;
   const int64_t T = attn_rows(cu_seqlens, qkv, B, S, D, &cu);
@@ -1085,7 +1088,8 @@ void attn_bwd(Tensor qkv, Tensor out, Tensor dout, Tensor lse, Tensor delta, c10
                                      delta.data_ptr<float>(), cu ? nullptr : lens_ptr(lens, B),
                                      (uint16_t*)dqkv.data_ptr(), (int)B, (int)S, (int)H, (float)scale, cur_stream(),
                                      pq.defined() ? pq.data_ptr<float>() : nullptr,
-                                     pkv.defined() ? pkv.data_ptr<float>() : nullptr, &rq, &rkv, q8, ad, cu, (int)T);
+                                     pkv.defined() ? pkv.data_ptr<float>() : nullptr, &rq, &rkv, q8, ad, cu, (int)T,
+                                     causal);
   TORCH_CHECK(!q8.y || !colsum_out.has_value() || fused, "attn_bwd q8: column sums need the ring kernels");
   if (!colsum_out.has_value()) return;
   float* cs = colsum_out->data_ptr<float>();
@@ -1750,13 +1754,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("gp"), py::arg("gt"), py::arg("part"), py::arg("S"), py::arg("cu_seqlens") = py::none());
   m.def("attn_fwd", &attn_fwd, py::arg("qkv"), py::arg("out"), py::arg("lse"), py::arg("lens"), py::arg("B"),
         py::arg("S"), py::arg("H"), py::arg("scale"), py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("site") = 0,
-        py::arg("rank") = 0, py::arg("cu_seqlens") = py::none());
+        py::arg("rank") = 0, py::arg("cu_seqlens") = py::none(), py::arg("causal") = false);
   m.def("attn_bwd", &attn_bwd, py::arg("qkv"), py::arg("out"), py::arg("dout"), py::arg("lse"), py::arg("delta"),
         py::arg("lens"), py::arg("dqkv"), py::arg("B"), py::arg("S"), py::arg("H"), py::arg("scale"),
         py::arg("colsum_out") = py::none(), py::arg("colsum_accumulate") = false, py::arg("q8_y") = py::none(),
         py::arg("q8_yt") = py::none(), py::arg("q8_scale") = py::none(), py::arg("q8_amax") = py::none(),
         py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("site") = 0, py::arg("rank") = 0,
-        py::arg("cu_seqlens") = py::none());
+        py::arg("cu_seqlens") = py::none(), py::arg("causal") = false);
   py::class_<PyComm>(m, "Communicator")
       .def(py::init<py::bytes, int, int, int>(), py::arg("unique_id"), py::arg("nranks"), py::arg("rank"),
            py::arg("device"))

@@ -340,9 +340,12 @@ void launch_embed_bwd(const int64_t* sid, const int64_t* perm, const int64_t* tt
 // partials. lens is unused. Ring kernels and bf16 outputs only.
 // ad (attention-probability dropout, mlt_philox.h): thr8 > 0 launches the dropout instantiations of
 // the forward and the two ring backward kernels; thr8 == 0 the plain ones
+// causal: key j of a sequence is visible to query i of the same sequence iff j <= i and j < len_b (the
+// CAUSAL instantiations: the key / query loops stop at / start from the diagonal). Ring kernels and bf16
+// outputs only; composes with ad and cu.
 void launch_attn_fwd(const uint16_t* qkv, uint16_t* out, float* lse, const int* lens, int B, int S, int H,
                      float scale, hipStream_t st, const AttnDropArgs& ad = AttnDropArgs{}, const int* cu = nullptr,
-                     int rows = 0);
+                     int rows = 0, bool causal = false);
 // colpart_q [B * ceil(S/64)][D] and colpart_kv [B * ceil(S/64)][2D] (or nullptr): bias-gradient
 // column partials of dQ and dK|dV; returns whether they were written (ring kernels) and the
 // number of partial rows in rows_q / rows_kv
@@ -361,7 +364,7 @@ bool launch_attn_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* d
                      const int* lens, uint16_t* dqkv, int B, int S, int H, float scale, hipStream_t st,
                      float* colpart_q = nullptr, float* colpart_kv = nullptr, int* rows_q = nullptr,
                      int* rows_kv = nullptr, const AttnQ8& q8 = AttnQ8{}, const AttnDropArgs& ad = AttnDropArgs{},
-                     const int* cu = nullptr, int rows = 0);
+                     const int* cu = nullptr, int rows = 0, bool causal = false);
 
 // ----------------------------------------------------------------------------
 // Masked-LM head (mlm.hip)

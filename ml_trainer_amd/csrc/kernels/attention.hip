@@ -23,6 +23,12 @@
 //     dP^T = V dO^T, dS^T lane-local, dQ^T += K^T dS^T with dS^T fed from registers.
 // Attention-probability dropout runs inside the forward and the two ring backward kernels (their
 // DROP instantiations; the mask is recomputed from a Philox counter, never stored: see below).
+// Causal mask (the CAUSAL instantiations of the forward and the two ring backward kernels): key j of a
+// sequence is visible to query i of the same sequence iff j <= i and j < len. The forward and dQ end their key
+// loop at the block that holds the block's last query, dK/dV starts its query loop (and its ring) at the key
+// block's own first query block, so the blocks above the diagonal are skipped, not masked; only the blocks on
+// the diagonal compare per element. Composes with dropout (the same byte per (b, h, q, k)) and packed mode;
+// not with the register-staged backward kernels or the fp8 (q8) outputs. CAUSAL = false is the code it was.
 // Global->LDS staging of the next tile is register-staged (loads issued before the MFMA work
 // of the current tile, LDS writes after it), so HBM latency overlaps the math.
 #include <cstdlib>
@@ -260,7 +266,14 @@ constexpr float kFwdDeferThr = 8.f;
 // DROP: attention-probability dropout. l, the running max and the saved LSE come from the undropped
 // P (the all-ones MFMA takes the undropped pack); the P.V product takes a second pack with the
 // dropped entries zeroed, and 1 / (1 - p_eff) folds into the final 1 / l.
-template <int NQ, bool DROP, bool PACKED = false>
+// CAUSAL: key j is visible to query i iff j <= i and j < len. The key loop ends with the block that holds
+// the block's last query (the blocks above the diagonal are never loaded), and a 64-query group n
+// compares key <= q[n] only from its own diagonal block on (block-uniform branch, as the key mask).
+// With NQ = 2 group 0 sees nothing of the last block: its scores are all -inf there, bm = -inf, and
+// since its m is finite by then (its diagonal block came first and holds key <= q for every query)
+// cand - m = -inf never triggers the rescale, the exponent fma gives exp2(-inf) = 0 and l gains 0: no
+// inf - inf anywhere.
+template <int NQ, bool DROP, bool PACKED = false, bool CAUSAL = false>
 __global__ __launch_bounds__(256) void attn_fwd_lean_kernel(const uint16_t* __restrict__ qkv,
                                                             uint16_t* __restrict__ out, float* __restrict__ lse,
                                                             const int* __restrict__ lens, int S, int H,
@@ -306,7 +319,8 @@ __global__ __launch_bounds__(256) void attn_fwd_lean_kernel(const uint16_t* __re
   }
   const s16x8 ones_bits = {0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80};
   const bf16x8 ones = __builtin_bit_cast(bf16x8, ones_bits);
-  const int nkb = (len + AB - 1) / AB;
+  const int nkb = CAUSAL ? min((len + AB - 1) / AB, (min((qb + 1) * (64 * NQ), Ss) + AB - 1) / AB)
+                         : (len + AB - 1) / AB;
   const float sl2 = scale * 1.4426950408889634f;  // exponents in base 2
   u32x4 kr[2], vr[2];
   // loop-invariant byte offsets of this thread's two 16-byte K chunks inside a 64-row block (V:
@@ -358,6 +372,17 @@ __global__ __launch_bounds__(256) void attn_fwd_lean_kernel(const uint16_t* __re
 #pragma unroll
           for (int r = 0; r < 4; ++r)
             if (kb * AB + kt * 16 + 4 * g + r >= len) s[n][kt][r] = -INFINITY;
+    }
+    if constexpr (CAUSAL) {
+#pragma unroll
+      for (int n = 0; n < NQ; ++n)
+        if (kb >= qb * NQ + n) {  // group n's diagonal block, or (NQ = 2, n = 0) the one past it: all -inf
+#pragma unroll
+          for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              if (kb * AB + kt * 16 + 4 * g + r > q[n]) s[n][kt][r] = -INFINITY;
+        }
     }
 #pragma unroll
     for (int n = 0; n < NQ; ++n) {
@@ -947,7 +972,12 @@ __device__ __forceinline__ void attn_q8_epilogue(const AttnQ8& q8, const float (
 // instantiated for NK = 1 only: with 2 key groups the mask bytes, the separate delta operand and P
 // next to P o M do not fit the 256 VGPRs of __launch_bounds__(256, 2) (60 - 104 bytes of scratch per
 // lane whether the mask is held as bytes or as packed keep bits), so dropout runs 1 group per wave.
-template <int NK, bool FULLT, bool DROP, bool PACKED = false>
+// CAUSAL: the query loop starts at the key block's own first query block qb0 = k0b / 64 (the queries before
+// it see none of these keys); ring stage j = qb - qb0 lives in slot j % kRing, so the prologue, the
+// refill and the wait counts are those of a loop from 0 over nqb - qb0 stages. The first NK query blocks
+// intersect the diagonal and take PATH 3 (query >= key per element, exact zeros through exp2(-inf)); with
+// NK = 2 group 1 sees nothing of the first block.
+template <int NK, bool FULLT, bool DROP, bool PACKED = false, bool CAUSAL = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_ring_kernel(const uint16_t* __restrict__ qkv,
                                                                  const uint16_t* __restrict__ dout,
                                                                  const float* __restrict__ lse,
@@ -1042,9 +1072,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_ring_kernel(const uint16
   const uint64_t dbh = DROP ? (uint64_t)(uint32_t)(b * H + h) * ad.T * ad.T : 0;
   // the ring prologue goes out after the register loads above, so waiting for those is a
   // counted vmcnt that leaves the DMAs in flight
+  const int qb0 = CAUSAL ? k0b / AB : 0;  // first query block of the loop (< nqb: k0b < len <= Ss)
 #pragma unroll
   for (int s0 = 0; s0 < kRing - 1; ++s0)
-    if (s0 < nqb) issue(s0, s0);
+    if (qb0 + s0 < nqb) issue(s0, qb0 + s0);
   f32x4 dk[NK][4], dv[NK][4];
 #pragma unroll
   for (int n = 0; n < NK; ++n)
@@ -1053,11 +1084,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_ring_kernel(const uint16
       dk[n][d] = f32x4{0.f, 0.f, 0.f, 0.f};
       dv[n][d] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
-  for (int qb = 0; qb < nqb; ++qb) {
+  for (int qb = qb0; qb < nqb; ++qb) {
     ring_wait(min(kRing - 2, nqb - 1 - qb));
-    raw_barrier();  // stage qb visible to all waves; everyone is done with slot (qb - 1) % kRing
-    if (qb + kRing - 1 < nqb) issue((qb + kRing - 1) % kRing, qb + kRing - 1);
-    const uint8_t* Qs = smem + (qb % kRing) * STAGE;
+    raw_barrier();  // stage qb visible to all waves; everyone is done with slot (qb - qb0 - 1) % kRing
+    if (qb + kRing - 1 < nqb) issue((qb - qb0 + kRing - 1) % kRing, qb + kRing - 1);
+    const uint8_t* Qs = smem + ((qb - qb0) % kRing) * STAGE;
     const uint8_t* Os = Qs + kTile;
     const float* lse_s = reinterpret_cast<const float*>(Qs + 2 * kTile);
     const float* del_s = lse_s + AB;
@@ -1075,7 +1106,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_ring_kernel(const uint16
         attn_drop_bytes_k(ad, dbh + ((uint32_t)key[n] >> 2), (uint32_t)qb * (AB / 4), dm[n]);
     }
     auto qtiles = [&](auto pathc) __attribute__((always_inline)) {
-      constexpr int PATH = decltype(pathc)::value;  // 0 all valid, 1 key mask, 2 key + query mask
+      constexpr int PATH = decltype(pathc)::value;  // 0 all valid, 1 key mask, 2 key + query mask, 3 + diagonal
       f32x4 pe[NK], dse[NK];  // the even qt of the current pair
 #pragma unroll
       for (int qt = 0; qt < 4; ++qt) {
@@ -1112,9 +1143,13 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_ring_kernel(const uint16
               pv = fast_exp2(sv[n][r] * sl2 - lr[r]);
             } else if constexpr (PATH == 1) {  // key mask folded into per-lane constants
               pv = fast_exp2(sv[n][r] * sl2k[n] - (lr[r] + kinf[n]));
-            } else {
+            } else if constexpr (PATH == 2) {
               const int ql = qt * 16 + 4 * g + r;
               const bool ok = key[n] < len && q0 + ql < Ss;
+              pv = fast_exp2(ok ? sv[n][r] * sl2 - lr[r] : -INFINITY);
+            } else {
+              const int ql = qt * 16 + 4 * g + r;
+              const bool ok = key[n] < len && q0 + ql < Ss && q0 + ql >= key[n];
               pv = fast_exp2(ok ? sv[n][r] * sl2 - lr[r] : -INFINITY);
             }
             if constexpr (DROP) {
@@ -1138,7 +1173,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_ring_kernel(const uint16
         }
       }
     };
-    if (qfull && kfull)
+    if (CAUSAL && qb < qb0 + NK)  // the query blocks that intersect this key block's diagonal
+      qtiles(std::integral_constant<int, CAUSAL ? 3 : 0>{});
+    else if (qfull && kfull)
       qtiles(std::integral_constant<int, 0>{});
     else if (qfull)
       qtiles(std::integral_constant<int, 1>{});
@@ -1239,7 +1276,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_ring_kernel(const uint16
 // DROP (attention-probability dropout, mask M, s = 1 / (1 - p_eff)): delta = rowsum(dO * O) is still
 // right (O is the dropped output) and dS = P * (M s dP - delta), so dP starts at 0 instead of
 // -delta and one fma per score applies the mask, the scale and delta.
-template <int NQ, bool FULLT, bool DROP, bool PACKED = false>
+// CAUSAL: the key loop ends with the block that holds this block's last query (as the forward); from the
+// block's first diagonal key block on, the scores take the per-element path key <= q[n] && key < len.
+template <int NQ, bool FULLT, bool DROP, bool PACKED = false, bool CAUSAL = false>
 __global__ __launch_bounds__(256) void attn_bwd_dq_ring_kernel(const uint16_t* __restrict__ qkv,
                                                                const uint16_t* __restrict__ dout,
                                                                const uint16_t* __restrict__ out,
@@ -1270,7 +1309,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_ring_kernel(const uint16_t* _
     }
   }
   const float sl2 = scale * 1.4426950408889634f;
-  const int nkb = (len + AB - 1) / AB;
+  const int nkb = CAUSAL ? min((len + AB - 1) / AB, (min((qb + 1) * (64 * NQ), Ss) + AB - 1) / AB)
+                         : (len + AB - 1) / AB;
   const int wu = __builtin_amdgcn_readfirstlane(wid);
   const uint32_t ok0 = glds_off_row(ld, 0), ok1 = glds_off_row(ld, 1);
   auto issue = [&](int slot, int kb) {  // (K and V: the same rows, D columns apart)
@@ -1355,8 +1395,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_ring_kernel(const uint16_t* _
     }
     // mask-path choice hoisted out of the kt loop (block-uniform): one basic block per path, so
     // MFMAs and the exp / dS VALU work of neighbouring kt tiles interleave (see the dK/dV kernel)
-    auto ktiles = [&](auto fullc) __attribute__((always_inline)) {
-      constexpr bool FULL = decltype(fullc)::value;
+    auto ktiles = [&](auto pathc) __attribute__((always_inline)) {
+      constexpr int PATH = decltype(pathc)::value;  // 0 every key valid, 1 key mask, 2 key mask + diagonal
 #pragma unroll
       for (int kt = 0; kt < 4; ++kt) {
         f32x4 sv[NQ], dp[NQ];
@@ -1382,11 +1422,14 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_ring_kernel(const uint16_t* _
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             float pv;
-            if constexpr (FULL) {  // every key of this block is valid
+            if constexpr (PATH == 0) {  // every key of this block is valid
               pv = fast_exp2(sv[n][r] * sl2 - lq[n]);
-            } else {
+            } else if constexpr (PATH == 1) {
               const int key = kb * AB + kt * 16 + 4 * g + r;
               pv = fast_exp2(key < len ? sv[n][r] * sl2 - lq[n] : -INFINITY);
+            } else {
+              const int key = kb * AB + kt * 16 + 4 * g + r;
+              pv = fast_exp2(key < len && key <= q[n] ? sv[n][r] * sl2 - lq[n] : -INFINITY);
             }
             if constexpr (DROP)
               ds[n][kt][r] = pv * fmaf(attn_drop_kept(dm[n][kt], r, ad.thr8) ? ad.scale : 0.f, dp[n][r], -dl[n]);
@@ -1395,10 +1438,12 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_ring_kernel(const uint16_t* _
           }
       }
     };
-    if (kfull)
-      ktiles(std::true_type{});
+    if (CAUSAL && kb >= qb * NQ)  // a key block on or past the diagonal of the block's first group
+      ktiles(std::integral_constant<int, CAUSAL ? 2 : 0>{});
+    else if (kfull)
+      ktiles(std::integral_constant<int, 0>{});
     else
-      ktiles(std::false_type{});
+      ktiles(std::integral_constant<int, 1>{});
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
       bf16x8 sb[NQ];
@@ -1475,37 +1520,43 @@ static int attn_groups(const char* env, int S, int dflt = 2) {
 // group counts of the padded ones (forward and dQ 2 groups, dK/dV 2 groups without dropout and 1 with):
 // they are the non-FULLT kernels plus two scalar loads, and build with the same VGPR counts and no scratch.
 void launch_attn_fwd(const uint16_t* qkv, uint16_t* out, float* lse, const int* lens, int B, int S, int H,
-                     float scale, hipStream_t st, const AttnDropArgs& ad, const int* cu, int rows) {
+                     float scale, hipStream_t st, const AttnDropArgs& ad, const int* cu, int rows, bool causal) {
   if (B <= 0 || S <= 0) return;
   const unsigned g2 = (unsigned)((S + 127) / 128 * H * B), g1 = (unsigned)((S + 63) / 64 * H * B);
   const bool two = attn_groups("MLT_ATTN_FWD_GROUPS", S, 2) == 2;
   const int* sl = cu ? cu : lens;
-  auto launch = [&](auto dropc, auto packc) {  // the dropout instantiations only when something is dropped
-    constexpr bool DR = decltype(dropc)::value, PK = decltype(packc)::value;
+  auto launch = [&](auto dropc, auto packc, auto causc) {  // the dropout instantiations only when something is dropped
+    constexpr bool DR = decltype(dropc)::value, PK = decltype(packc)::value, CA = decltype(causc)::value;
     if (two)
-      hipLaunchKernelGGL((attn_fwd_lean_kernel<2, DR, PK>), dim3(g2), dim3(256), 0, st, qkv, out, lse, sl, S, H, scale,
-                         ad, rows);
+      hipLaunchKernelGGL((attn_fwd_lean_kernel<2, DR, PK, CA>), dim3(g2), dim3(256), 0, st, qkv, out, lse, sl, S, H,
+                         scale, ad, rows);
     else
-      hipLaunchKernelGGL((attn_fwd_lean_kernel<1, DR, PK>), dim3(g1), dim3(256), 0, st, qkv, out, lse, sl, S, H, scale,
-                         ad, rows);
+      hipLaunchKernelGGL((attn_fwd_lean_kernel<1, DR, PK, CA>), dim3(g1), dim3(256), 0, st, qkv, out, lse, sl, S, H,
+                         scale, ad, rows);
   };
-  if (cu) {
-    if (ad.thr8 > 0)
-      launch(std::true_type{}, std::true_type{});
-    else
-      launch(std::false_type{}, std::true_type{});
-  } else {
-    if (ad.thr8 > 0)
-      launch(std::true_type{}, std::false_type{});
-    else
-      launch(std::false_type{}, std::false_type{});
-  }
+  auto pick = [&](auto causc) {
+    if (cu) {
+      if (ad.thr8 > 0)
+        launch(std::true_type{}, std::true_type{}, causc);
+      else
+        launch(std::false_type{}, std::true_type{}, causc);
+    } else {
+      if (ad.thr8 > 0)
+        launch(std::true_type{}, std::false_type{}, causc);
+      else
+        launch(std::false_type{}, std::false_type{}, causc);
+    }
+  };
+  if (causal)
+    pick(std::true_type{});
+  else
+    pick(std::false_type{});
 }
 
 bool launch_attn_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse, float* delta,
                      const int* lens, uint16_t* dqkv, int B, int S, int H, float scale, hipStream_t st,
                      float* colpart_q, float* colpart_kv, int* rows_q, int* rows_kv, const AttnQ8& q8,
-                     const AttnDropArgs& ad, const int* cu, int rows) {
+                     const AttnDropArgs& ad, const int* cu, int rows, bool causal) {
   // MLT_ATTN_RING: unset or 4 = the ring kernels, 0 = the register-staged kernels. Those stay in the
   // tree as the bit-for-bit oracle of the ring kernels' test; any other value is an error.
   const char* rv = getenv("MLT_ATTN_RING");
@@ -1519,49 +1570,62 @@ bool launch_attn_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* d
   if (cu && q8.y)
     throw std::runtime_error("attn_bwd: the fp8 (q8) outputs take padded batches only (their transposed 16-row runs "
                              "sit at b * S offsets), not cu_seqlens");
+  if (causal && !ring)
+    throw std::runtime_error("attn_bwd: causal attention needs the ring kernels (MLT_ATTN_RING unset or 4); the "
+                             "register-staged kernels have no causal mask");
+  if (causal && q8.y)
+    throw std::runtime_error("attn_bwd: the fp8 (q8) outputs have no causal instantiation");
   if (B <= 0 || S <= 0) return false;
   const int64_t pairs = (int64_t)B * S * H;
   const dim3 g2((S + 127) / 128 * H * B), g1((S + 63) / 64 * H * B);
   if (ring) {
     const bool drop = ad.thr8 > 0;  // the dropout instantiations only when something is dropped
     // (dK/dV under dropout: 1 key group per wave, the 2-group instantiation would spill)
-    const bool k2 = !drop && attn_groups("MLT_ATTN_DKDV_GROUPS", S, 2) == 2;
+    // (packed causal dK/dV as well: its 2-group instantiation needs 24 bytes of scratch per lane)
+    const bool k2 = !drop && !(cu && causal) && attn_groups("MLT_ATTN_DKDV_GROUPS", S, 2) == 2;
     const bool q2 = attn_groups("MLT_ATTN_DQ_GROUPS", S) == 2;
     const int* sl = cu ? cu : lens;
-    auto launch = [&](auto fullt, auto dropc, auto packc) {
+    auto launch = [&](auto fullt, auto dropc, auto packc, auto causc) {
       constexpr bool FL = decltype(fullt)::value, DR = decltype(dropc)::value, PK = decltype(packc)::value;
+      constexpr bool CA = decltype(causc)::value;
       if (q2)
-        hipLaunchKernelGGL((attn_bwd_dq_ring_kernel<2, FL, DR, PK>), g2, dim3(256), 0, st, qkv, dout, out, lse, delta,
-                           sl, dqkv, S, H, scale, colpart_q, q8, ad, rows);
+        hipLaunchKernelGGL((attn_bwd_dq_ring_kernel<2, FL, DR, PK, CA>), g2, dim3(256), 0, st, qkv, dout, out, lse,
+                           delta, sl, dqkv, S, H, scale, colpart_q, q8, ad, rows);
       else
-        hipLaunchKernelGGL((attn_bwd_dq_ring_kernel<1, FL, DR, PK>), g1, dim3(256), 0, st, qkv, dout, out, lse, delta,
-                           sl, dqkv, S, H, scale, colpart_q, q8, ad, rows);
-      if constexpr (!DR) {
+        hipLaunchKernelGGL((attn_bwd_dq_ring_kernel<1, FL, DR, PK, CA>), g1, dim3(256), 0, st, qkv, dout, out, lse,
+                           delta, sl, dqkv, S, H, scale, colpart_q, q8, ad, rows);
+      if constexpr (!DR && !(PK && CA)) {
         if (k2) {
-          hipLaunchKernelGGL((attn_bwd_dkdv_ring_kernel<2, FL, false, PK>), g2, dim3(256), 0, st, qkv, dout, lse, delta,
-                             sl, dqkv, S, H, scale, colpart_kv, q8, ad, rows);
+          hipLaunchKernelGGL((attn_bwd_dkdv_ring_kernel<2, FL, false, PK, CA>), g2, dim3(256), 0, st, qkv, dout, lse,
+                             delta, sl, dqkv, S, H, scale, colpart_kv, q8, ad, rows);
           return;
         }
       }
-      hipLaunchKernelGGL((attn_bwd_dkdv_ring_kernel<1, FL, DR, PK>), g1, dim3(256), 0, st, qkv, dout, lse, delta, sl,
-                         dqkv, S, H, scale, colpart_kv, q8, ad, rows);
+      hipLaunchKernelGGL((attn_bwd_dkdv_ring_kernel<1, FL, DR, PK, CA>), g1, dim3(256), 0, st, qkv, dout, lse, delta,
+                         sl, dqkv, S, H, scale, colpart_kv, q8, ad, rows);
     };
-    if (cu) {  // packed: a sequence ends anywhere, so always the clamped-row (non-FULLT) stages
-      if (drop)
-        launch(std::false_type{}, std::true_type{}, std::true_type{});
-      else
-        launch(std::false_type{}, std::false_type{}, std::true_type{});
-    } else if (S % AB == 0) {
-      if (drop)
-        launch(std::true_type{}, std::true_type{}, std::false_type{});
-      else
-        launch(std::true_type{}, std::false_type{}, std::false_type{});
-    } else {
-      if (drop)
-        launch(std::false_type{}, std::true_type{}, std::false_type{});
-      else
-        launch(std::false_type{}, std::false_type{}, std::false_type{});
-    }
+    auto pick = [&](auto causc) {
+      if (cu) {  // packed: a sequence ends anywhere, so always the clamped-row (non-FULLT) stages
+        if (drop)
+          launch(std::false_type{}, std::true_type{}, std::true_type{}, causc);
+        else
+          launch(std::false_type{}, std::false_type{}, std::true_type{}, causc);
+      } else if (S % AB == 0) {
+        if (drop)
+          launch(std::true_type{}, std::true_type{}, std::false_type{}, causc);
+        else
+          launch(std::true_type{}, std::false_type{}, std::false_type{}, causc);
+      } else {
+        if (drop)
+          launch(std::false_type{}, std::true_type{}, std::false_type{}, causc);
+        else
+          launch(std::false_type{}, std::false_type{}, std::false_type{}, causc);
+      }
+    };
+    if (causal)
+      pick(std::true_type{});
+    else
+      pick(std::false_type{});
     // partial rows actually written: B x (row blocks of the chosen group count)
     if (rows_kv) *rows_kv = B * ((S + (k2 ? 127 : 63)) / (k2 ? 128 : 64));
     if (rows_q) *rows_q = B * ((S + (q2 ? 127 : 63)) / (q2 ? 128 : 64));

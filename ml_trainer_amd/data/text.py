@@ -104,3 +104,44 @@ class SyntheticMaskedLM(torch.utils.data.Dataset):
 
     def __getitem__(self, i):
         return self.ids[i], self.labels[i]
+
+
+class SyntheticCausalLM(torch.utils.data.Dataset):
+    """Synthetic next-token data for the causal language-model task: ``(ids [S], labels [S])`` per row.
+
+    The rows are ``SyntheticMaskedLM``'s arithmetic progressions ``5 + (a_i + t * d_i) mod (vocab_size - 5)``,
+    unmasked. With ``d_i`` in {1, 2, 3} the next token follows from the two before it (their difference is
+    the step), so the task needs attention and is learnable. ``labels`` are already shifted:
+    ``labels[s] = ids[s + 1]`` where ``s + 1 < len_i``, and -100 at each row's last real token and at the
+    pads. With ``min_len`` the rows are variable-length (lengths uniform in ``[min_len, seq_len]``) and
+    right-padded with ``pad_id``. ``lengths`` holds the row lengths."""
+
+    def __init__(self, n: int, seq_len: int = 512, vocab_size: int = 30522, seed: int = 0, min_len=None,
+                 pad_id: int = 0):
+        if vocab_size <= 8:
+            raise ValueError("vocab_size must exceed 8 (ids below 5 are reserved)")
+        rng = np.random.default_rng(seed)
+        a = rng.integers(0, vocab_size - 5, size=(n, 1), dtype=np.int64)
+        d = rng.integers(1, 4, size=(n, 1), dtype=np.int64)
+        t = np.arange(seq_len, dtype=np.int64)[None, :]
+        ids = 5 + (a + t * d) % (vocab_size - 5)
+        lengths = np.full(n, seq_len, dtype=np.int64)
+        if min_len is not None:
+            if not 1 <= min_len <= seq_len:
+                raise ValueError(f"min_len must satisfy 1 <= min_len <= seq_len = {seq_len}, got {min_len}")
+            lengths = rng.integers(min_len, seq_len + 1, size=n, dtype=np.int64)
+        labels = np.full_like(ids, -100)
+        labels[:, :-1] = ids[:, 1:]
+        labels[t + 1 >= lengths[:, None]] = -100
+        ids[t >= lengths[:, None]] = pad_id
+        self.ids = torch.from_numpy(ids)
+        self.labels = torch.from_numpy(labels)
+        self.lengths = torch.from_numpy(lengths)
+        self.seq_len = seq_len
+        self.pad_id = pad_id if min_len is not None else None
+
+    def __len__(self) -> int:
+        return self.ids.shape[0]
+
+    def __getitem__(self, i):
+        return self.ids[i], self.labels[i]

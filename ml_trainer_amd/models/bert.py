@@ -54,6 +54,13 @@ Masked-LM pre-training: ``BertForMaskedLM`` is the same encoder (same state-dict
 and classifier, under the MLM head of ``ops/mlm.py`` (transform dense + GELU + LayerNorm, vocabulary
 projection tied to the word table, fused chunked softmax cross-entropy). Hidden dropout, attention
 dropout and ``unpad`` work unchanged; fp8 is rejected.
+
+Causal attention (``BertConfig.causal``, default False): key ``j`` of a sequence is visible to query ``i``
+of the same sequence iff ``j <= i`` and ``j < len_b``, inside the flash attention kernels (their causal
+instantiations skip the key blocks above the diagonal; no S x S mask exists anywhere). It composes with
+hidden dropout, attention dropout and ``unpad``; with ``fp8`` it is rejected. ``BertLMHeadModel`` is the
+encoder run as a next-token decoder (post-LN, learned positions, tied word table: GPT-1's block) under
+the MLM prediction head with one slot per position.
 """
 from __future__ import annotations
 
@@ -84,6 +91,7 @@ class BertConfig:
     pad_id: Optional[int] = None  # when set, key lengths are derived from trailing pad tokens
     unpad: bool = False  # run the encoder on the real tokens only (needs lengths; not with fp8)
     max_predictions: Optional[int] = None  # MLM slots per sequence; None: ceil(0.15 * S) rounded up to 8
+    causal: bool = False  # key j visible to query i iff j <= i (and j < len_b); not with fp8
 
 
 _PRESETS = {
@@ -124,7 +132,7 @@ class BertLayer(nn.Module):
             impl = T.BF16
         x = T.attention_ln_block(x, self.qkv.weight, self.qkv.bias, self.out.weight, self.out.bias, self.ln1.weight,
                                  self.ln1.bias, lens, B, S, self.c.heads, self.c.ln_eps, impl, drop, attn_drop,
-                                 cu_seqlens)
+                                 cu_seqlens, self.c.causal)
         if drop is not None:
             drop = (drop[0], drop[1], drop[2] + 1, drop[3])
         return T.ffn_ln_block(x, self.ffn1.weight, self.ffn1.bias, self.ffn2.weight, self.ffn2.bias, self.ln2.weight,
@@ -134,7 +142,8 @@ class BertLayer(nn.Module):
         """fp32 torch reference. x [B*S, h]; mask [B, S] bool (True = valid key); drop and attn_drop
         as in forward_native (the same masks, through ops.dropout). ``packed`` (a PackedBatch): x is
         [T, h]; the linears, LayerNorms and hidden dropout run on the packed rows, attention on a
-        padded scratch of the QKV rows (so its dropout mask is the padded run's)."""
+        padded scratch of the QKV rows (so its dropout mask is the padded run's). With ``config.causal``
+        the lower-triangular mask (key <= query) joins the key mask."""
         from ml_trainer_amd.ops import dropout as D
         c = self.c
         H, dh = c.heads, c.hidden // c.heads
@@ -147,6 +156,8 @@ class BertLayer(nn.Module):
         s = (q @ k.transpose(-1, -2)) / math.sqrt(dh)
         if mask is not None:
             s = s.masked_fill(~mask[:, None, None, :], float("-inf"))
+        if c.causal:
+            s = s.masked_fill(~torch.ones(S, S, dtype=torch.bool, device=s.device).tril(), float("-inf"))
         pr = s.softmax(-1)
         if attn_drop is not None:
             p, seed, site, rank = attn_drop
@@ -181,6 +192,9 @@ class BertClassifier(nn.Module):
         if c.unpad and c.fp8:
             raise ValueError("unpad=True with fp8=True is not supported: the fp8 attention epilogue writes 16-row "
                              "transposed runs at b * S offsets and cannot take packed row offsets")
+        if c.causal and c.fp8:
+            raise ValueError("causal=True with fp8=True is not supported: the fp8 (q8) attention epilogue has no "
+                             "causal instantiation")
         self.config = c
         self.last_dropout_seed = None  # the seed of the last forward that dropped
         self.word_embeddings = nn.Embedding(c.vocab_size, c.hidden)
@@ -378,6 +392,11 @@ class BertClassifier(nn.Module):
         mask = None
         if lens is not None:
             mask = (torch.arange(S, device=input_ids.device)[None, :] < lens[:, None])[:, None, None, :]
+        causal = c.causal
+        if causal and (mask is not None or adrop is not None):  # one boolean mask: key < len and key <= query
+            tril = torch.ones(S, S, dtype=torch.bool, device=input_ids.device).tril()[None, None]
+            mask = tril if mask is None else mask & tril
+            causal = False
         with torch.autocast(input_ids.device.type, dtype=torch.bfloat16):
             if pk is None:
                 pos = torch.arange(S, device=input_ids.device)
@@ -395,7 +414,7 @@ class BertClassifier(nn.Module):
                     qkv = unpack_rows(qkv[0], pk)
                 qkv = qkv.view(B, S, 3, c.heads, 64).permute(2, 0, 3, 1, 4)
                 if adrop is None:
-                    ctx = F.scaled_dot_product_attention(qkv[0], qkv[1], qkv[2], attn_mask=mask)
+                    ctx = F.scaled_dot_product_attention(qkv[0], qkv[1], qkv[2], attn_mask=mask, is_causal=causal)
                 else:
                     pa, seed, site, rank = self._attn_site(adrop, l)
                     sc = (qkv[0] @ qkv[1].transpose(-1, -2)) / 8.0
@@ -548,3 +567,38 @@ class BertForMaskedLM(BertClassifier):
         """fp32 [len(rows), V]: the vocabulary logits of the given rows of ``hidden`` (inspection, tests)."""
         from ml_trainer_amd.ops import mlm as M
         return M.mlm_logits(hidden, rows, self.mlm_params())
+
+
+def shift_labels(input_ids, lens=None):
+    """Next-token labels of ``input_ids`` [B, S]: labels[b, s] = input_ids[b, s + 1] where s + 1 < len_b
+    (``lens`` [B], or S without it), else -100. Pads and each sequence's last real token have no target."""
+    B, S = input_ids.shape
+    labels = torch.full_like(input_ids, -100)
+    labels[:, :-1] = input_ids[:, 1:]
+    if lens is not None:
+        pos = torch.arange(S, device=input_ids.device)[None, :]
+        labels = labels.masked_fill(pos + 1 >= lens.to(input_ids.device).long()[:, None], -100)
+    return labels
+
+
+class BertLMHeadModel(BertForMaskedLM):
+    """The encoder run as a next-token decoder: ``causal`` forced on, under the MLM prediction head (the
+    state-dict keys of ``BertForMaskedLM``). Every position has a prediction slot (``max_predictions(S)``
+    is S), so ``ops.mlm.mlm_head`` (select, gather, transform, chunked tied decoder, ``vocab_ce``) is the
+    LM head unchanged and nothing overflows. ``lm_loss(hidden, labels)`` is that head on next-token
+    labels (``shift_labels``); ``last_mlm_accuracy`` is then the next-token accuracy."""
+
+    def __init__(self, c: Optional[BertConfig] = None):
+        c = c or BertConfig()
+        super().__init__(c if c.causal else replace(c, causal=True))
+
+    def max_predictions(self, S: int) -> int:
+        return S
+
+    def lm_loss(self, hidden, labels):
+        """Mean next-token loss of ``hidden`` = this model's last forward output and the already shifted
+        ``labels`` [B, S] (-100 = no target)."""
+        return self.mlm_loss(hidden, labels)
+
+    def lm_loss_reference(self, hidden, labels):
+        return self.mlm_loss_reference(hidden, labels)

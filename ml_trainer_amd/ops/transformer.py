@@ -225,12 +225,25 @@ def _zero_packed_tail(t, cu_seqlens):
         t[-min(PACK_ROW_MULTIPLE - 1, t.shape[0]):].zero_()
 
 
-def _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl=BF16, residual=True, attn_drop=None, cu_seqlens=None):
+def _causal_kw(causal, impl):
+    """Keyword arguments of C.attn_fwd / C.attn_bwd for ``causal``; the keyword goes out only when set."""
+    if not causal:
+        return {}
+    if impl is not BF16:
+        raise ValueError("causal attention runs the bf16 linears only: the fp8 (q8) attention epilogue has no "
+                         "causal instantiation")
+    return dict(causal=True)
+
+
+def _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl=BF16, residual=True, attn_drop=None, cu_seqlens=None,
+              causal: bool = False):
     """``attn_drop`` = (p, seed, site, rank): attention-probability dropout inside the flash kernels
     (the byte mask of ops/dropout.py, recomputed in the backward); None: no dropout.
     ``cu_seqlens`` (int32 [B + 1], device): packed batch, x is [T, D] with sequence b at rows
-    cu[b] .. cu[b + 1]; S is max_seqlen and ``lens`` is unused."""
+    cu[b] .. cu[b + 1]; S is max_seqlen and ``lens`` is unused.
+    ``causal``: key j is visible to query i of its sequence iff j <= i and j < len_b."""
     C = require_native()
+    ckw = _causal_kw(causal, impl)
     if cu_seqlens is not None and impl is not BF16:
         raise ValueError("packed (cu_seqlens) attention runs the bf16 linears only: the fp8 attention epilogue "
                          "writes at b * S offsets")
@@ -238,20 +251,22 @@ def _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl=BF16, residual=True, at
     attn = torch.empty(x.shape[0], H * 64, dtype=torch.bfloat16, device=x.device)
     lse = torch.empty(B * H * S, dtype=torch.float32, device=x.device)
     _zero_packed_tail(attn, cu_seqlens)
-    C.attn_fwd(qkv, attn, lse, lens, B, S, H, _ATTN_SCALE, cu_seqlens=cu_seqlens, **_attn_drop_kw(attn_drop))
+    C.attn_fwd(qkv, attn, lse, lens, B, S, H, _ATTN_SCALE, cu_seqlens=cu_seqlens, **_attn_drop_kw(attn_drop), **ckw)
     # out-proj + bias + residual (under dropout the residual joins in the LayerNorm kernel instead)
     y = impl.fwd(attn, wo, bo, res=x if residual else None)
     return y, (x, qkv, attn, lse)
 
 
 def _attn_bwd(saved, params, lens, B, S, H, dy, G, dbo="colsum", impl=BF16, dres=None, attn_drop=None,
-              cu_seqlens=None):
+              cu_seqlens=None, causal: bool = False):
     """Backward of the attention block. ``dbo``: "colsum" to reduce dy here, otherwise the
     out-proj bias gradient already produced by the LayerNorm backward (tensor or None).
     ``dres``: the gradient of the residual branch when it differs from the out-proj's ``dy``
-    (hidden dropout sits between them); defaults to ``dy``. ``attn_drop``, ``cu_seqlens``: the forward's."""
+    (hidden dropout sits between them); defaults to ``dy``. ``attn_drop``, ``cu_seqlens``, ``causal``: the
+    forward's."""
     C = require_native()
     akw = _attn_drop_kw(attn_drop)
+    akw.update(_causal_kw(causal, impl))
     if cu_seqlens is not None:
         akw["cu_seqlens"] = cu_seqlens
     x, qkv, attn, lse = saved
@@ -388,20 +403,21 @@ _ATTN_SCALE = 1.0 / 8.0  # 1/sqrt(head_dim = 64)
 
 class _AttentionBlock(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, wqkv, bqkv, wo, bo, lens, B, S, H, impl, attn_drop=None, cu_seqlens=None):
-        y, saved = _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl, attn_drop=attn_drop, cu_seqlens=cu_seqlens)
+    def forward(ctx, x, wqkv, bqkv, wo, bo, lens, B, S, H, impl, attn_drop=None, cu_seqlens=None, causal=False):
+        y, saved = _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl, attn_drop=attn_drop, cu_seqlens=cu_seqlens,
+                             causal=causal)
         ctx.save_for_backward(*saved)
         ctx.params, ctx.impl = (wqkv, bqkv, wo, bo), impl
-        ctx.lens, ctx.dims, ctx.attn_drop, ctx.cu = lens, (B, S, H), attn_drop, cu_seqlens
+        ctx.lens, ctx.dims, ctx.attn_drop, ctx.cu, ctx.causal = lens, (B, S, H), attn_drop, cu_seqlens, causal
         return y
 
     @staticmethod
     def backward(ctx, dy):
         G = _Grads()
         grads = _attn_bwd(ctx.saved_tensors, ctx.params, ctx.lens, *ctx.dims, dy.contiguous().to(torch.bfloat16), G,
-                          impl=ctx.impl, attn_drop=ctx.attn_drop, cu_seqlens=ctx.cu)
+                          impl=ctx.impl, attn_drop=ctx.attn_drop, cu_seqlens=ctx.cu, causal=ctx.causal)
         G.done()
-        return grads + (None, None, None, None, None, None, None)
+        return grads + (None, None, None, None, None, None, None, None)
 
 
 class _FFNBlock(torch.autograd.Function):
@@ -442,17 +458,19 @@ class _AttentionLNBlock(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, wqkv, bqkv, wo, bo, gamma, beta, lens, B, S, H, eps, impl, drop=None, attn_drop=None,
-                cu_seqlens=None):
+                cu_seqlens=None, causal=False):
         if drop is None:
-            a, s1 = _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl, attn_drop=attn_drop, cu_seqlens=cu_seqlens)
+            a, s1 = _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl, attn_drop=attn_drop, cu_seqlens=cu_seqlens,
+                              causal=causal)
             y, s2 = _ln_fwd(a, gamma, beta, eps)
         else:  # LN(dropout(out-proj) + x): dropout and the residual add inside the LayerNorm kernel
             a, s1 = _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl, residual=False, attn_drop=attn_drop,
-                              cu_seqlens=cu_seqlens)
+                              cu_seqlens=cu_seqlens, causal=causal)
             y, s2 = _dropout_add_ln_fwd(a, x, gamma, beta, eps, drop)
         ctx.save_for_backward(*s1, *s2)
         ctx.params, ctx.beta, ctx.impl = (wqkv, bqkv, wo, bo), beta, impl
         ctx.lens, ctx.dims, ctx.drop, ctx.attn_drop, ctx.cu = lens, (B, S, H), drop, attn_drop, cu_seqlens
+        ctx.causal = causal
         return y
 
     @staticmethod
@@ -467,9 +485,10 @@ class _AttentionLNBlock(torch.autograd.Function):
             dres, dg, db, dbo, da = _ln_bwd(t[4:], ctx.beta, dy.contiguous().to(torch.bfloat16), G,
                                             dxsum_param=ctx.params[3], drop=ctx.drop)
         dx, dwqkv, dbqkv, dwo, dbo = _attn_bwd(t[:4], ctx.params, ctx.lens, *ctx.dims, da, G, dbo=dbo,
-                                               impl=ctx.impl, dres=dres, attn_drop=ctx.attn_drop, cu_seqlens=ctx.cu)
+                                               impl=ctx.impl, dres=dres, attn_drop=ctx.attn_drop, cu_seqlens=ctx.cu,
+                                               causal=ctx.causal)
         G.done()
-        return dx, dwqkv, dbqkv, dwo, dbo, dg, db, None, None, None, None, None, None, None, None, None
+        return dx, dwqkv, dbqkv, dwo, dbo, dg, db, None, None, None, None, None, None, None, None, None, None
 
 
 class _FFNLNBlock(torch.autograd.Function):
@@ -602,16 +621,19 @@ def _mark_training(impl) -> None:
 
 
 def attention_block(x, wqkv, bqkv, wo, bo, lens: Optional[torch.Tensor], B: int, S: int, H: int, impl=BF16,
-                    attn_drop=None, cu_seqlens: Optional[torch.Tensor] = None):
+                    attn_drop=None, cu_seqlens: Optional[torch.Tensor] = None, causal: bool = False):
     """``attn_drop`` = (p, seed, site, rank): attention-probability dropout inside the flash attention
     kernels (the byte mask of ops/dropout.py: ``p`` is applied as round(p * 256) / 256). None: none.
     ``cu_seqlens`` (int32 [B + 1], device): x is a packed [T, D] batch (``pack_batch``), ``S`` is
     max_seqlen and ``lens`` is unused. The dropout mask of element (b, h, q, k) is the padded run's.
     x may end in tail rows past cu_seqlens[B] that belong to no sequence: fewer than PACK_ROW_MULTIPLE
     of them (``pack_batch`` keeps to that), since only that many trailing rows of the attention output
-    and of dQKV are zeroed (``_zero_packed_tail``)."""
+    and of dQKV are zeroed (``_zero_packed_tail``).
+    ``causal``: key j is visible to query i of the same sequence iff j <= i and j < len_b (the causal
+    instantiations of the three kernels, which skip the blocks above the diagonal); bf16 linears only.
+    Composes with ``attn_drop`` (the non-causal run's keep mask, restricted) and ``cu_seqlens``."""
     _mark_training(impl)
-    return _AttentionBlock.apply(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl, attn_drop, cu_seqlens)
+    return _AttentionBlock.apply(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl, attn_drop, cu_seqlens, causal)
 
 
 def ffn_block(x, w1, b1, w2, b2, impl=BF16):
@@ -620,15 +642,16 @@ def ffn_block(x, w1, b1, w2, b2, impl=BF16):
 
 
 def attention_ln_block(x, wqkv, bqkv, wo, bo, gamma, beta, lens: Optional[torch.Tensor], B: int, S: int, H: int,
-                       eps: float, impl=BF16, drop=None, attn_drop=None, cu_seqlens: Optional[torch.Tensor] = None):
+                       eps: float, impl=BF16, drop=None, attn_drop=None, cu_seqlens: Optional[torch.Tensor] = None,
+                       causal: bool = False):
     """``drop`` = (p, seed, site, rank): hidden dropout on the out-projection's output, before the
     residual add, fused into the LayerNorm kernels (mask: ops/dropout.py). None: no dropout.
     ``attn_drop`` = (p, seed, site, rank): attention-probability dropout (see attention_block).
     ``cu_seqlens``: packed batch, with fewer than PACK_ROW_MULTIPLE tail rows (see attention_block);
-    hidden-dropout masks are indexed by packed row."""
+    hidden-dropout masks are indexed by packed row. ``causal``: see attention_block."""
     _mark_training(impl)
     return _AttentionLNBlock.apply(x, wqkv, bqkv, wo, bo, gamma, beta, lens, B, S, H, eps, impl, drop, attn_drop,
-                                   cu_seqlens)
+                                   cu_seqlens, causal)
 
 
 def ffn_ln_block(x, w1, b1, w2, b2, gamma, beta, eps: float, impl=BF16, drop=None):

@@ -256,9 +256,13 @@ class Trainer:
             if not hasattr(self._core, "mlm_loss"):
                 raise ValueError("criterion 'mlm' needs a model with an mlm_loss head (BertForMaskedLM)")
             return _CustomLoss(self._core.mlm_loss)
+        if c == "clm":  # causal language model: the same head on next-token labels
+            if not hasattr(self._core, "lm_loss"):
+                raise ValueError("criterion 'clm' needs a model with an lm_loss head (BertLMHeadModel)")
+            return _CustomLoss(self._core.lm_loss)
         if callable(c):
             return c if isinstance(c, nn.Module) else _CustomLoss(c)
-        raise ValueError(f"unknown criterion {c!r} (cross_entropy|neg-loss|l1|l2|custom|mlm or a callable)")
+        raise ValueError(f"unknown criterion {c!r} (cross_entropy|neg-loss|l1|l2|custom|mlm|clm or a callable)")
 
     def _average_gradients(self):
         """Manual gradient averaging (reference src/trainer.py:152-158): one flat all-reduce."""
@@ -280,15 +284,15 @@ class Trainer:
         if self.metric == "mcrmse":
             return L.mcrmse(outputs, targets)
         if self.metric == "accuracy":
-            if self.criterion_type == "mlm":  # masked-token accuracy of the criterion call just made
+            if self.criterion_type in ("mlm", "clm"):  # masked- / next-token accuracy of the criterion call just made
                 return self._core.last_mlm_accuracy
             return L.accuracy(outputs, targets)
         return None
 
     def _metric_outputs(self, outputs):
-        """What ``_evaluate`` takes: the fp32 outputs (criterion 'mlm': the hidden states as they are,
+        """What ``_evaluate`` takes: the fp32 outputs (criterion 'mlm' / 'clm': the hidden states as they are,
         its metric comes from the head)."""
-        return outputs.detach() if self.criterion_type == "mlm" else outputs.detach().float()
+        return outputs.detach() if self.criterion_type in ("mlm", "clm") else outputs.detach().float()
 
     # ------------------------------------------------------------------ engine selection
     def _engine_eligible(self, for_eval: bool = False) -> bool:
