@@ -118,6 +118,10 @@ __global__ __launch_bounds__(256) void dropout_add_ln_fwd_kernel(
 // DXM = keep ? bf16(dx_bf16 * scale) : 0 with the forward's mask, and the column sums are DXM's.
 // The dropout arguments are a trailing pack (one LnBwdDrop when DROP, empty otherwise), so the
 // instantiations without dropout keep the argument list, and with it the code, they had before.
+// DX is bitwise the same in every instantiation (DXS or not, DROP or not): the row's fp32 arithmetic is
+// written out below with contraction off and every fused multiply-add an explicit fmaf, so which
+// products fuse is this source's choice and not the compiler's, which used to follow what else hangs
+// off the values (the plain and the DXS instantiation then rounded a few DX per million differently).
 struct LnBwdDrop {
   uint16_t* DXM;
   DropArgs dr;
@@ -130,19 +134,19 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const uint16_t* __restrict_
                                                      const float* __restrict__ rstd, uint16_t* __restrict__ DX,
                                                      float* __restrict__ part, int64_t rows,
                                                      const uint16_t* __restrict__ DRES, DropT... drop_args) {
+#pragma clang fp contract(off)
   static_assert(!DROP || DXS, "the dropout variant always reduces DXM's column sums");
   static_assert(sizeof...(DropT) == (DROP ? 1 : 0), "one LnBwdDrop exactly when DROP");
   constexpr int D = VPL * 256, E = VPL * 4;
   constexpr int NS = DXS ? 3 : 2;
   __shared__ float red[4][NS * D];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  float dg[E], db[E], g[E], dxs[DXS ? E : 1], dms[DROP ? E : 1];
+  float dg[E], db[E], g[E], dxs[DXS ? E : 1];  // dxs: the column sums of DX, or of DXM when DROP
 #pragma unroll
   for (int i = 0; i < E; ++i) {
     dg[i] = 0.f;
     db[i] = 0.f;
     if constexpr (DXS) dxs[i] = 0.f;
-    if constexpr (DROP) dms[i] = 0.f;
   }
 #pragma unroll
   for (int v = 0; v < VPL; ++v) {
@@ -191,8 +195,8 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const uint16_t* __restrict_
       x[i] = xh;
       const float t = dy[i] * g[i];
       s1 += t;
-      s2 += t * xh;
-      dg[i] += dy[i] * xh;
+      s2 = fmaf(t, xh, s2);
+      dg[i] = fmaf(dy[i], xh, dg[i]);
       db[i] += dy[i];
     }
     s1 = wave_sum(s1) * (1.f / D);
@@ -205,7 +209,10 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const uint16_t* __restrict_
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int i = 4 * v + q;
-        o[q] = rs * (dy[i] * g[i] - s1 - x[i] * s2) + (DRES ? dres[i] : 0.f);
+        // rs * (dy * g - s1 - xh * s2) + dres, one rounding per line
+        const float a = fmaf(dy[i], g[i], -s1);
+        const float b = fmaf(-x[i], s2, a);
+        o[q] = DRES ? fmaf(rs, b, dres[i]) : rs * b;
       }
       ushort4 u;
       u.x = f32_to_bf16(o[0]);
@@ -215,33 +222,22 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const uint16_t* __restrict_
       reinterpret_cast<ushort4*>(DX + row * D)[lane + 64 * v] = u;
       if constexpr (DROP) {
         const LnBwdDrop& drop = ln_bwd_drop_arg(drop_args...);
-        // DX has to be bitwise the DX of the instantiations without dropout. Its fp32 rounding is
-        // the compiler's choice of which products above it fuses and packs, and that choice follows
-        // what hangs off these values. So this variant keeps what the DXS instantiation hangs off
-        // them: the DX column sums stay (dxs below, unused in the end) and the dropout tail reads
-        // the stored DX through an empty asm, out of the optimiser's sight. With both, the fp32
-        // instructions up to the DX store are those of ln_bwd_kernel<VPL, true>; the price is E
-        // accumulators and E adds per row.
-        uint32_t ulo = (uint32_t)u.x | ((uint32_t)u.y << 16), uhi = (uint32_t)u.z | ((uint32_t)u.w << 16);
-        asm volatile("" : "+v"(ulo), "+v"(uhi));
-        ushort4 ub;
-        ub.x = (uint16_t)ulo, ub.y = (uint16_t)(ulo >> 16), ub.z = (uint16_t)uhi, ub.w = (uint16_t)(uhi >> 16);
-        // the mask of the global row (not the pipeline's clamped fetch row), as in the forward
+        // DXM from the stored (bf16-rounded) DX; the mask of the global row (not the pipeline's
+        // clamped fetch row), as in the forward
         const Philox4 w = drop_words((uint64_t)row * (D / 4) + lane + 64 * v, drop.dr);
         const uint32_t thr = drop.dr.thr;
         const float sc = drop.dr.scale;
         ushort4 m;
-        m.x = w.x >= thr ? f32_to_bf16(bf16_to_f32(ub.x) * sc) : (uint16_t)0;
-        m.y = w.y >= thr ? f32_to_bf16(bf16_to_f32(ub.y) * sc) : (uint16_t)0;
-        m.z = w.z >= thr ? f32_to_bf16(bf16_to_f32(ub.z) * sc) : (uint16_t)0;
-        m.w = w.w >= thr ? f32_to_bf16(bf16_to_f32(ub.w) * sc) : (uint16_t)0;
+        m.x = w.x >= thr ? f32_to_bf16(bf16_to_f32(u.x) * sc) : (uint16_t)0;
+        m.y = w.y >= thr ? f32_to_bf16(bf16_to_f32(u.y) * sc) : (uint16_t)0;
+        m.z = w.z >= thr ? f32_to_bf16(bf16_to_f32(u.z) * sc) : (uint16_t)0;
+        m.w = w.w >= thr ? f32_to_bf16(bf16_to_f32(u.w) * sc) : (uint16_t)0;
         reinterpret_cast<ushort4*>(drop.DXM + row * D)[lane + 64 * v] = m;
-        dms[4 * v + 0] += bf16_to_f32(m.x);
-        dms[4 * v + 1] += bf16_to_f32(m.y);
-        dms[4 * v + 2] += bf16_to_f32(m.z);
-        dms[4 * v + 3] += bf16_to_f32(m.w);
-      }
-      if constexpr (DXS) {
+        dxs[4 * v + 0] += bf16_to_f32(m.x);
+        dxs[4 * v + 1] += bf16_to_f32(m.y);
+        dxs[4 * v + 2] += bf16_to_f32(m.z);
+        dxs[4 * v + 3] += bf16_to_f32(m.w);
+      } else if constexpr (DXS) {
         dxs[4 * v + 0] += bf16_to_f32(u.x);
         dxs[4 * v + 1] += bf16_to_f32(u.y);
         dxs[4 * v + 2] += bf16_to_f32(u.z);
@@ -256,12 +252,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const uint16_t* __restrict_
       const int c = 4 * (lane + 64 * v) + q;
       red[wid][c] = dg[4 * v + q];
       red[wid][D + c] = db[4 * v + q];
-      if constexpr (DROP) {
-        asm volatile("" ::"v"(dxs[4 * v + q]));  // kept alive for DX's rounding only (see above)
-        red[wid][2 * D + c] = dms[4 * v + q];    // the column sums of DXM
-      } else if constexpr (DXS) {
-        red[wid][2 * D + c] = dxs[4 * v + q];
-      }
+      if constexpr (DXS) red[wid][2 * D + c] = dxs[4 * v + q];
     }
   __syncthreads();
   for (int c = threadIdx.x; c < NS * D; c += 256)
@@ -437,7 +428,9 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(const int64_t* __restric
 // word / position grads: fp32 atomics (the vocabulary rows hit are sparse and spread);
 // token-type grads: per-block partials over the (few) type rows, reduced in fixed order.
 // Embedding backward without atomics (bitwise reproducible):
-//  * word rows: the token ids arrive sorted (stable, host-side torch.sort) with the permutation;
+//  * word rows: the token ids arrive clamped to the table and sorted (stable, host-side torch.sort
+//    of ids.clamp(0, vocab - 1), as ops/transformer.py does) with the permutation: two different
+//    out-of-range ids would otherwise be two runs, and two writers, for the one row they clamp to;
 //    one wave per sorted entry, and the wave that starts a run of equal ids sums that run's
 //    gradient rows in token order and adds the sum to its table row (one writer per row);
 //  * positions / token types: one wave per position sums the B rows of that position in batch
@@ -545,12 +538,13 @@ void launch_embed_bwd(const int64_t* sid, const int64_t* perm, const int64_t* tt
                       hipStream_t st, const int* cu, int B) {
   if (rows <= 0) return;
   const dim3 gw_grid((unsigned)((rows + 3) / 4)), gp_grid((unsigned)((S + 3) / 4)), block(256);
+  const int64_t* tt2 = ntype >= 2 ? tt : nullptr;
 #define MLT_EMB_BWD(V)                                                                                          \
   hipLaunchKernelGGL(embed_bwd_word_kernel<V>, gw_grid, block, 0, st, sid, perm, DX, gw, rows, vocab);         \
   if (cu)                                                                                                       \
-    hipLaunchKernelGGL((embed_bwd_pos_kernel<V, true>), gp_grid, block, 0, st, tt, DX, gp, part, rows, S, cu, B); \
-  else                                                                                                          \
-    hipLaunchKernelGGL((embed_bwd_pos_kernel<V, false>), gp_grid, block, 0, st, tt, DX, gp, part, rows, S, cu, B);
+    hipLaunchKernelGGL((embed_bwd_pos_kernel<V, true>), gp_grid, block, 0, st, tt2, DX, gp, part, rows, S, cu, B); \
+  else                                                                                                           \
+    hipLaunchKernelGGL((embed_bwd_pos_kernel<V, false>), gp_grid, block, 0, st, tt2, DX, gp, part, rows, S, cu, B);
   switch (D / 256) {
     case 1: MLT_EMB_BWD(1) break;
     case 2: MLT_EMB_BWD(2) break;
@@ -559,7 +553,9 @@ void launch_embed_bwd(const int64_t* sid, const int64_t* perm, const int64_t* tt
     default: return;
   }
 #undef MLT_EMB_BWD
-  // token types 0 and 1 (ntype <= 2): the S partial rows summed in position order into gt
+  // token types 0 and 1 (ntype <= 2): the S partial rows summed in position order into gt. A one-row
+  // type table takes every token as type 0, as the forward's clamp reads it (tt is not passed on: with
+  // it the type-1 tokens' gradient went to the partial that is not summed, and was lost).
   SegOut o{{gt, gt + D, nullptr}};
   launch_reduce_rows(part, S, 2 * D, ntype >= 2 ? 2 * D : D, D, o, ntype >= 2 ? 3 : 1, st);
 }

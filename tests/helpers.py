@@ -430,3 +430,299 @@ def attn_edge_inputs(B, S, H, lens, scale, seed, sentinel_keys=True):
                         qv = x[b, qi, 0, h].to(torch.bfloat16).double()
                         x[b, key, 1, h] = (qv * (40.0 / (qv.pow(2).sum().item() * scale * _LOG2E))).float()
     return qkv.to(torch.bfloat16), dout.to(torch.bfloat16)
+
+
+# ---------------------------------------------------------------------------------------------
+# Derived bounds of the row kernels: LayerNorm, embeddings, reduce_rows (layernorm.hip), colsum (gemm.hip)
+# and the classifier head (head.hip). tests/test_rowkernel_bound_cpu.py checks them against a torch fp32
+# emulation of the kernels on the CPU; tests/test_rowkernel_edges_gpu.py uses them on the GPU. All
+# references are fp64 from the bf16 / fp32 inputs, `t` is the allowance on the kernel's fp32 value before
+# its store (bf16 outputs then go through store_bound), u = 2^-24. E = D / 64 is the number of values one
+# lane holds: it sums them in order, then wave_sum adds 6 levels of an xor butterfly.
+# ---------------------------------------------------------------------------------------------
+_RSQRT_REL = 2.0 ** -22  # allowance for rsqrtf: 2 ulp. Not measured on the device; the rstd headroom that
+#                          tests/test_rowkernel_edges_gpu.py prints (and records in its docstring) is its record.
+ROWK_EPS = 1e-5
+ROWK_LN_WIDTHS = (256, 512, 768, 1024)  # VPL = 1 .. 4
+# rows: 1 = three idle waves; 5 = a 1-row tail block; 2053 = five waves walk a second row and every other
+# wave's prefetch clamps to the last row; 4100 = four waves walk a third row (a pipeline register reused twice)
+ROWK_LN_ROWS = (1, 5, 2053, 4100)
+
+
+def _ceil_div(a, b):
+    return -(-a // b)
+
+
+def ln_partial_blocks(rows):
+    """ln_bwd_partial_blocks of layernorm.hip: 4 rows per block, at most 512 blocks."""
+    return min(_ceil_div(rows, 4), 512)
+
+
+def ln_bwd_depth(rows):
+    """Number of fp32 additions behind one column output of the LayerNorm backward: the wave's own rows
+    (ceil(rows / (4 nb))), the 4-wave LDS sum (2 levels), reduce_rows' lane stride over the nb partial rows
+    (ceil(nb / 64)) and its 6-level butterfly."""
+    nb = ln_partial_blocks(rows)
+    return _ceil_div(rows, 4 * nb) + 2 + _ceil_div(nb, 64) + 6
+
+
+def ln_edge_inputs(rows, D, seed):
+    """(x, dy, dres bf16 [rows, D]; gamma, beta fp32 [D]) on the CPU. The rows are 0.5 + 2 N(0, 1), except the
+    ill-conditioned ones a correct kernel must be told apart on:
+      constant row (all 3): var = 0, only eps stands under the root;
+      64 + N(0, 1) and 1000 + N(0, 16) (std 4; bf16's spacing there is 4): mean >> spread, where a one-pass
+      variance E[x^2] - mean^2 loses its digits.
+    They are rows 0, 1 and (rows >= 3) 2, and again the last row (rows >= 5): the constant one at 5 rows, the
+    1000 one at 2053 (the row every clamped prefetch reads), the 64 one at 4100. A single row is the 64 one."""
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(rows, D, generator=g) * 2.0 + 0.5
+    special = lambda k: (torch.full((D,), 3.0), 64.0 + torch.randn(D, generator=g),
+                         1000.0 + 4.0 * torch.randn(D, generator=g))[k]
+    if rows == 1:
+        x[0] = special(1)
+    else:
+        for k in range(min(rows, 3)):
+            x[k] = special(k)
+        if rows >= 5:
+            x[rows - 1] = special({5: 0, 2053: 2}.get(rows, 1))
+    dy = torch.randn(rows, D, generator=g)
+    dres = torch.randn(rows, D, generator=g)
+    gamma = torch.randn(D, generator=g) * 0.2 + 1
+    beta = torch.randn(D, generator=g) * 0.1
+    bf = lambda a: a.to(torch.bfloat16)
+    return bf(x), bf(dy), bf(dres), gamma, beta
+
+
+def ln_fwd_bound(x, gamma, beta, eps):
+    """(mean, t_mean, rstd, t_rstd, Y, t_Y) of ln_fwd_kernel (ln_fwd_row), per row: mu = mean(x),
+    var = mean((x - mu)^2), rs = 1 / sqrt(var + eps) with eps as the kernel holds it (rounded to fp32),
+    Y = (x - mu) rs gamma + beta.
+      t_mean = (E + 8) u mean|x| ... E - 1 + 6 additions whose running sums are bounded by sum|x|, 1 / D
+                  rounded once, one multiply: E + 7, one spare
+      rel_rs = 0.5 (E + 12) u + 0.5 t_mean^2 / (var + eps) + 2^-22 ... the relative error of rs:
+                  (E + 12) u: the second pass sums squares of d = x - mu' (u on d twice, u on d d, E + 5
+                    additions of positive terms, the scaling by 1 / D, the + eps), halved by the root;
+                  t_mean^2: mean((x - mu')^2) = var + (mu - mu')^2 exactly, the kernel's own mean error
+                    re-entering the variance (second order: this is what a two-pass variance buys);
+                  2^-22: rsqrtf (_RSQRT_REL)
+      t_rstd = rs rel_rs
+      t_Y[i] = |gamma_i| rs (t_mean + |x_i - mu| (rel_rs + 3u)) + u |Y_i| + 1e-30 ... mu's error moves every
+                  x_i - mu by t_mean; rs's error and the three roundings of (x - mu) rs gamma scale with
+                  |x_i - mu|; the final + beta rounds at the size of Y.
+    The first-order expansion of the root needs t_mean^2 <= (var + eps) / 4, which is asserted per row."""
+    x, g, b = x.double(), gamma.double(), beta.double()
+    E = x.shape[1] // 64
+    eps = float(torch.tensor(eps, dtype=torch.float32))
+    mu = x.mean(1)
+    xc = x - mu[:, None]
+    var = (xc * xc).mean(1)
+    rs = 1.0 / torch.sqrt(var + eps)
+    t_mean = (E + 8) * _U32 * x.abs().mean(1) + 1e-30
+    bad = t_mean ** 2 > (var + eps) / 4
+    assert not bool(bad.any()), (f"row {int(bad.nonzero()[0])}: t_mean^2 = {float(t_mean[bad][0] ** 2):.3g} exceeds "
+                                 f"(var + eps) / 4 = {float((var + eps)[bad][0] / 4):.3g}: outside the first-order range")
+    rel = 0.5 * (E + 12) * _U32 + 0.5 * t_mean ** 2 / (var + eps) + _RSQRT_REL
+    Y = xc * rs[:, None] * g + b
+    t_Y = g.abs() * rs[:, None] * (t_mean[:, None] + xc.abs() * (rel[:, None] + 3 * _U32)) + _U32 * Y.abs() + 1e-30
+    return mu, t_mean, rs, rs * rel, Y, t_Y
+
+
+def acc_bound(t, prev, s):
+    """Allowance of an accumulating form `prev + s` whose sum s has the allowance t: t + u (|prev| + |s|)."""
+    return t + _U32 * (prev.double().abs() + s.abs())
+
+
+def ln_bwd_bound(dy, x, gamma, mean, rstd, dres=None, depth=None):
+    """dict(dx, t_dx [rows, D]; dgamma, t_dgamma, dbeta, t_dbeta [D]) of ln_bwd_kernel + reduce_rows.
+
+    `mean` and `rstd` are the forward kernel's OWN saved fp32 values, given inputs here as they are to the
+    kernel (attn_bwd_bound takes lse the same way). xh = (x - mean) rstd, t = dy gamma, s1 = mean(t),
+    s2 = mean(t xh), dx = rstd (t - s1 - xh s2) + dres; dgamma = sum_rows dy xh, dbeta = sum_rows dy.
+      t_s1 = (E + 9) u mean|t| ...... u on each product t, E + 5 additions, 1 / D rounded, one multiply
+      t_s2 = (E + 12) u mean|t xh| .. as s1, plus the two roundings of xh and the product t xh
+      t_dx[i] = rstd (t_s1 + |xh_i| t_s2 + 7u (|t_i| + |s1| + |xh_i s2|)) + u |dx_i| + 1e-30 ... the errors of
+                  s1 and s2 as they enter, up to 7 roundings on the three terms of the bracket (t, xh twice,
+                  xh s2, two subtractions, the multiply by rstd), and the final + dres at the size of dx
+      depth = ln_bwd_depth(rows), the additions behind a column output
+      t_dgamma = (depth + 3) u sum_rows |dy xh| ... the 3: the two roundings of xh and the product dy xh
+      t_dbeta = depth u sum_rows |dy|
+    The accumulating forms add acc_bound's u (|previous| + |sum|). dxsum is no function of these inputs alone
+    (it sums the ROUNDED dx): see colsum_stored_bound."""
+    dy, x, g = dy.double(), x.double(), gamma.double()
+    mean, rstd = mean.double()[:, None], rstd.double()[:, None]
+    rows, D = x.shape
+    E = D // 64
+    depth = ln_bwd_depth(rows) if depth is None else depth
+    xh = (x - mean) * rstd
+    t = dy * g
+    s1, s2 = t.mean(1, keepdim=True), (t * xh).mean(1, keepdim=True)
+    dx = rstd * (t - s1 - xh * s2)
+    if dres is not None:
+        dx = dx + dres.double()
+    t_s1 = (E + 9) * _U32 * t.abs().mean(1, keepdim=True)
+    t_s2 = (E + 12) * _U32 * (t * xh).abs().mean(1, keepdim=True)
+    t_dx = rstd * (t_s1 + xh.abs() * t_s2 + 7 * _U32 * (t.abs() + s1.abs() + (xh * s2).abs())) + _U32 * dx.abs() + 1e-30
+    return dict(dx=dx, t_dx=t_dx, dgamma=(dy * xh).sum(0), t_dgamma=(depth + 3) * _U32 * (dy * xh).abs().sum(0) + 1e-30,
+                dbeta=dy.sum(0), t_dbeta=depth * _U32 * dy.abs().sum(0) + 1e-30)
+
+
+def colsum_stored_bound(X, depth):
+    """(sum, t) of a column sum over the rows of a STORED bf16 matrix (the fused dxsum of ln_bwd_kernel, which
+    adds the bf16-rounded DX -- or DXM under dropout -- and colsum): the fp64 column sum of those very values,
+    t = depth u sum_rows |X| + 1e-30 with `depth` the number of additions behind one output."""
+    X = X.double()
+    return X.sum(0), depth * _U32 * X.abs().sum(0) + 1e-30
+
+
+def colsum_geometry(M):
+    """(R, rpb) of colsum_geometry in gemm.hip: R row slabs of rpb rows each (the last one shorter)."""
+    R = 1 if M < 32 else min(_ceil_div(M, 32), 256)
+    rpb = _ceil_div(M, R)
+    return _ceil_div(M, rpb), rpb
+
+
+def colsum_depth(M):
+    """Additions behind one colsum output: a wave's share of its slab (every 4th row: ceil(rpb / 4)), the
+    4-wave LDS sum (2), reduce_rows' lane stride over the R slabs (ceil(R / 64)) and its butterfly (6)."""
+    R, rpb = colsum_geometry(M)
+    return _ceil_div(rpb, 4) + 2 + _ceil_div(R, 64) + 6
+
+
+# (M, N): two slabs, the second of 16 rows | a remainder loop after one unrolled 16-row step | rpb = 33 |
+# one row, N a multiple of the 512-column strip
+ROWK_COLSUM_CASES = [(33, 8), (45, 520), (8193, 16), (1, 1024)]
+
+# Embedding edge cases: (name, B, S, ids, ntype, tt). V = 50 word rows, 40 position rows.
+#   ids: "rand" | "equal" (one run covers the batch) | "clamp" (holds -3 and V + 2: rows 0 and V - 1)
+#   tt: None | "rand" (0 / 1) | "clamp" (0 / 1 / 2: the 2 reads row 1)
+ROWK_EMBED_V, ROWK_EMBED_P = 50, 40
+ROWK_EMBED_CASES = [
+    ("b3s5", 3, 5, "rand", 2, "rand"),         # rows = 15: a 3-row tail block; S = 5: 3 idle waves in the position kernel's block 1
+    ("b2s33", 2, 33, "rand", 1, None),         # S > 32, a one-row type table without token types
+    ("b1s1", 1, 1, "rand", 2, "rand"),         # one token
+    ("equal", 3, 5, "equal", 1, None),         # every id equal: a single run
+    ("clamp", 2, 33, "clamp", 2, "clamp"),     # out-of-range ids and token types
+    ("type1row", 3, 5, "rand", 1, "rand"),     # a one-row type table WITH type-1 tokens: forward and backward clamp to row 0
+]
+
+
+def embed_edge_inputs(name, D, seed):
+    """dict of one embedding case on the CPU: ids, tt (or None) int64 [B * S]; ww [V, D], wp [P, D], wt [ntype, D],
+    dout [B * S, D] bf16; gw0, gp0, gt0 fp32 prefills of the gradient tables."""
+    _, B, S, ik, ntype, tk = next(c for c in ROWK_EMBED_CASES if c[0] == name)
+    V, P = ROWK_EMBED_V, ROWK_EMBED_P
+    g = torch.Generator().manual_seed(seed)
+    n = B * S
+    ids = torch.randint(0, V, (n,), generator=g)
+    if ik == "equal":
+        ids = torch.full((n,), 17)
+    elif ik == "clamp":
+        ids[3], ids[n - 1], ids[n // 2] = -3, V + 2, V + 2
+    tt = None if tk is None else torch.randint(0, 2, (n,), generator=g)
+    if tk is not None and n >= 2:
+        tt[0], tt[n - 1] = 0, 1  # both types present
+    if tk == "clamp":
+        tt[5] = 2
+    bf = lambda *s: torch.randn(*s, generator=g).to(torch.bfloat16)
+    f = lambda *s: torch.randn(*s, generator=g)
+    return dict(B=B, S=S, V=V, P=P, ntype=ntype, ids=ids, tt=tt, ww=bf(V, D), wp=bf(P, D), wt=bf(ntype, D),
+                dout=bf(n, D), gw0=f(V, D), gp0=f(P, D), gt0=f(ntype, D))
+
+
+def embed_rows(ids, tt, S, V, ntype):
+    """The table rows the forward reads for every token: clamped word ids, positions row % S, clamped types."""
+    n = ids.numel()
+    ty = torch.zeros_like(ids) if tt is None else tt.clamp(0, ntype - 1)
+    return ids.clamp(0, V - 1), torch.arange(n, device=ids.device) % S, ty
+
+
+def embed_fwd_bound(ww, wp, wt, ids, tt, S):
+    """(out, t) of embed_fwd_kernel: out = bf16((a + b) + c) with a, b, c the word, position and type rows
+    (bf16, exact in fp32): two fp32 additions, t = u (|a + b| + |a + b + c|) + 1e-30."""
+    wi, pi, ti = embed_rows(ids, tt, S, ww.shape[0], wt.shape[0])
+    ab = ww.double()[wi] + wp.double()[pi]
+    out = ab + wt.double()[ti]
+    return out, _U32 * (ab.abs() + out.abs()) + 1e-30
+
+
+def embed_bwd_bound(dout, ids, tt, B, S, gw0, gp0, gt0):
+    """dict(gw, t_gw, gp, t_gp, gt, t_gt; touched_w [V] bool) of embed_bwd_word_kernel / embed_bwd_pos_kernel +
+    reduce_rows on top of the prefills gw0, gp0, gt0. Each output is previous + a plain fp32 sum of n bf16
+    gradient rows in a fixed order, then one addition onto the previous value:
+        t = (n + 1) u sum|terms| + u |previous| + 1e-30
+    n = the number of tokens naming a word row (its run length); B for a position row (one row per
+    sequence); B + ceil(S / 64) + 6 for a type row (the B rows of a position, then reduce_rows' lane stride
+    over the S positions and its butterfly). ids are the clamped ids the backward is called with; a type
+    table of one row collects every token (the forward clamps their types to row 0)."""
+    d = dout.double()
+    V, P, ntype, D = gw0.shape[0], gp0.shape[0], gt0.shape[0], d.shape[1]
+    wi, pi, ti = embed_rows(ids, tt, S, V, ntype)
+
+    def scatter(idx, nrows, prev, n):
+        z = torch.zeros(nrows, D, dtype=torch.float64, device=d.device)
+        s, a = z.clone().index_add_(0, idx, d), z.clone().index_add_(0, idx, d.abs())
+        return prev.double() + s, (n + 1) * _U32 * a + _U32 * prev.double().abs() + 1e-30
+
+    cnt = torch.zeros(V, dtype=torch.float64, device=d.device).index_add_(0, wi, torch.ones_like(wi, dtype=torch.float64))
+    gw, t_gw = scatter(wi, V, gw0, cnt[:, None])
+    gp, t_gp = scatter(pi, P, gp0, B)
+    gt, t_gt = scatter(ti, ntype, gt0, B + _ceil_div(S, 64) + 6)
+    return dict(gw=gw, t_gw=t_gw, gp=gp, t_gp=t_gp, gt=gt, t_gt=t_gt, touched_w=cnt > 0)
+
+
+# Classifier head (B, h, L): L = 1 | a typical small head | h no multiple of 256 and one label in the second
+# 64-label chunk | three chunks | the backward's limit of 1024 staged labels
+ROWK_HEAD_CASES = [(1, 256, 1), (5, 768, 3), (3, 200, 65), (2, 1024, 130), (2, 64, 1024)]
+
+
+def head_edge_inputs(B, h, L, seed):
+    """dict of one head case on the CPU (all fp32): pooled in (-1, 1) as tanh gives it, wc [L, h], bc [L],
+    dlogits [B, L], and the prefills dw0 [L, h], db0 [L] of the accumulating form."""
+    g = torch.Generator().manual_seed(seed)
+    r = lambda *s: torch.randn(*s, generator=g)
+    return dict(pooled=torch.tanh(1.5 * r(B, h)), wc=r(L, h) * 0.1, bc=r(L) * 0.1, dlogits=r(B, L), dw0=r(L, h), db0=r(L))
+
+
+def head_fwd_bound(pooled, wc, bc=None):
+    """(logits, t) of head_cls_fwd_kernel: each of 256 threads chains ceil(h / 256) fmas, wave_sum adds 6
+    levels, one thread adds the 4 wave partials onto the bias: ceil(h / 256) + 10 roundings on partial sums
+    bounded by sum_j |x_j w_lj| (two spare), the bias entering the last ones at its own size:
+        t = (ceil(h / 256) + 12) u sum_j |x_j w_lj| + u |b_l| + 1e-30."""
+    x, w = pooled.double(), wc.double()
+    h = x.shape[1]
+    out, mag = x @ w.T, x.abs() @ w.abs().T
+    t = (_ceil_div(h, 256) + 12) * _U32 * mag + 1e-30
+    if bc is not None:
+        out, t = out + bc.double(), t + _U32 * bc.double().abs()
+    return out, t
+
+
+def head_bwd_bound(dlogits, pooled, wc, dw0=None, db0=None):
+    """dict(dpre, t_dpre [B, h]; dw, t_dw [L, h]; db, t_db [L]) of head_cls_bwd_x_kernel / head_cls_bwd_w_kernel.
+      dpre_j = (sum_l dl_l w_lj) (1 - y_j^2), y = pooled: L chained fmas, then y y, 1 - y y and the product:
+        t_dpre = u ((L + 3) |1 - y^2| + y^2) sum_l |dl_l w_lj| + 1e-30
+        (the y^2 term: y y rounds by up to u y^2 BEFORE the subtraction from 1, an absolute error in 1 - y^2
+        that does not shrink with it; where the compiler contracts the two into one fma the term is unused)
+      dW_c[l, j] = sum_b dl_bl x_bj, db_c[l] = sum_b dl_bl: B chained operations, two spare:
+        t_dw = (B + 2) u sum_b |dl x|,  t_db = (B + 2) u sum_b |dl|  (+ 1e-30)
+      accumulating onto dw0 / db0 adds u |previous| (the sum's share of that addition is in the two spare)."""
+    dl, x, w = dlogits.double(), pooled.double(), wc.double()
+    B, L = dl.shape
+    y2 = x * x
+    dpre = (dl @ w) * (1 - y2)
+    t_dpre = _U32 * ((L + 3) * (1 - y2).abs() + y2) * (dl.abs() @ w.abs()) + 1e-30
+    dw, t_dw = dl.T @ x, (B + 2) * _U32 * (dl.abs().T @ x.abs()) + 1e-30
+    db, t_db = dl.sum(0), (B + 2) * _U32 * dl.abs().sum(0) + 1e-30
+    if dw0 is not None:
+        dw, t_dw = dw + dw0.double(), t_dw + _U32 * dw0.double().abs()
+    if db0 is not None:
+        db, t_db = db + db0.double(), t_db + _U32 * db0.double().abs()
+    return dict(dpre=dpre, t_dpre=t_dpre, dw=dw, t_dw=t_dw, db=db, t_db=t_db)
+
+
+def guarded_1d(n, dev, pad=64):
+    """(buf, view) of an fp32 vector of n elements in the middle of a sentinel-filled allocation: `pad` floats
+    (a multiple of 4, so the view keeps the bindings' 16-byte alignment) on both sides."""
+    assert pad % 4 == 0
+    buf = sentinel((n + 2 * pad,), torch.float32, dev)
+    return buf, buf[pad:pad + n]

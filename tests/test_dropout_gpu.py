@@ -81,7 +81,7 @@ def test_dropout_autograd(dev):
 
 
 # ---------------------------------------------------------------- LayerNorm kernels
-LN_SHAPES = [(rows, Dm) for Dm in (256, 768, 1024) for rows in (1, 37, 2085)]
+LN_SHAPES = [(rows, Dm) for Dm in (256, 512, 768, 1024) for rows in (1, 37, 2085)]
 # 37 rows leave a partial block; 2085 rows exceed the backward's 512-block x 4-row grid, so its
 # waves walk two rows and the software pipeline's clamped fetch runs
 

@@ -23,7 +23,7 @@ def _close(a, b, tol):
 
 
 # ---------------------------------------------------------------- LayerNorm
-@pytest.mark.parametrize("D", [256, 768, 1024])
+@pytest.mark.parametrize("D", [256, 512, 768, 1024])
 @pytest.mark.parametrize("rows", [1, 37, 1024])
 def test_layernorm_fwd_bwd(dev, D, rows):
     C = require_native()
@@ -40,6 +40,8 @@ def test_layernorm_fwd_bwd(dev, D, rows):
     yr = F.layer_norm(xr, (D,), gr, br, 1e-5)
     _close(y, yr, 1e-2)
     torch.testing.assert_close(mean, xr.detach().mean(1), rtol=1e-4, atol=1e-4)
+    torch.testing.assert_close(rstd, torch.rsqrt(xr.detach().double().var(1, unbiased=False) + 1e-5).float(),
+                               rtol=1e-4, atol=1e-4)
     dy = _bf((rows, D), g)
     yr.backward(dy.float())
     dx = torch.empty_like(x)
