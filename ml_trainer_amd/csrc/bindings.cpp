@@ -656,6 +656,9 @@ void fp8_cast_transpose(Tensor w, Tensor y, Tensor yt, Tensor scale, c10::option
   TORCH_CHECK(R % 4 == 0 && Cc % 4 == 0 && reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0, "w shape/alignment");
   TORCH_CHECK(y.is_cuda() && y.is_contiguous() && is_fp8_storage(y) && y.numel() == R * Cc, "y");
   TORCH_CHECK(yt.is_cuda() && yt.is_contiguous() && is_fp8_storage(yt) && yt.numel() == R * Cc, "yt");
+  // the 64x64 kernel stores dwords to both (the wide one 8 bytes, which cast_transpose_fp8_wide_ok checks itself)
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(y.data_ptr()) % 4 == 0 && reinterpret_cast<uintptr_t>(yt.data_ptr()) % 4 == 0,
+              "fp8_cast_transpose y / yt must be 4-byte aligned");
   check_dev(scale, "scale", at::kFloat, 1, 4);
   float* am = nullptr;
   if (amax.has_value()) {

@@ -11,14 +11,24 @@ __device__ __forceinline__ float fp8_max() {
   return FMT == 0 ? 448.f : 57344.f;
 }
 
-// 4 floats -> 4 saturated fp8 bytes (v_cvt_pk_fp8_f32 / v_cvt_pk_bf8_f32), byte i = value i
+// Saturate to the format's finite range, +-inf included; a NaN stays a NaN. One v_med3_f32 would not keep it:
+// with a NaN operand it returns min3 of the others, so NaN came out as -max, a finite value that neither the
+// GEMM consuming the operand nor the amax (fmaxf drops NaN too) would ever notice. The IEEE-754-2019 maximum /
+// minimum propagate NaN: v_maximum3_f32 + v_minimum3_f32, one instruction more than the med3 (a compare and a
+// select around the med3 would be two more).
+template <int FMT>
+__device__ __forceinline__ float fp8_saturate(float x) {
+  const float m = fp8_max<FMT>();
+  return __builtin_elementwise_minimum(__builtin_elementwise_maximum(x, -m), m);
+}
+
+// 4 floats -> 4 saturated fp8 bytes (v_cvt_pk_fp8_f32 / v_cvt_pk_bf8_f32), byte i = value i; NaN -> the format's NaN
 template <int FMT>
 __device__ __forceinline__ uint32_t pack4_fp8(float a, float b, float c, float d) {
-  const float m = fp8_max<FMT>();  // saturate: one v_med3_f32 per value
-  a = __builtin_amdgcn_fmed3f(a, -m, m);
-  b = __builtin_amdgcn_fmed3f(b, -m, m);
-  c = __builtin_amdgcn_fmed3f(c, -m, m);
-  d = __builtin_amdgcn_fmed3f(d, -m, m);
+  a = fp8_saturate<FMT>(a);
+  b = fp8_saturate<FMT>(b);
+  c = fp8_saturate<FMT>(c);
+  d = fp8_saturate<FMT>(d);
   int r;
   if constexpr (FMT == 0) {
     r = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);

@@ -8,7 +8,8 @@
 //   * amax: max |x| (exact current scaling when there is no history yet);
 //   * update_scale: delayed scaling for n tensors at once -- push each amax into its history
 //     window, scale = fmt_max / (max(history) * 2^margin), inv_scale = 1 / scale, reset amax.
-// Conversions use v_cvt_pk_fp8_f32 / v_cvt_pk_bf8_f32 after clamping to the finite range.
+// Conversions use v_cvt_pk_fp8_f32 / v_cvt_pk_bf8_f32 after clamping to the finite range (+-inf -> +-max; a NaN
+// stays a NaN byte, and amax, being an fmaxf, is the maximum over the non-NaN elements).
 #include "mlt_common.h"
 #include "mlt_fp8.h"
 #include "mlt_kernels.h"

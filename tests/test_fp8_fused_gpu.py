@@ -6,6 +6,9 @@ import pytest
 import torch
 
 from ml_trainer_amd.ops._ext import require_native
+from tests import fp8_ref
+from tests.helpers import (assert_within, dgelu_t, gelu64, gelu_grad64, gelu_out_bound, gemm_expected, gemm_t32,
+                           store_bound)
 
 pytestmark = pytest.mark.gpu
 
@@ -26,10 +29,33 @@ def _gelu_grad(x):
     return 0.5 * (1.0 + torch.erf(x / math.sqrt(2.0))) + x * torch.exp(-0.5 * x * x) / math.sqrt(2.0 * math.pi)
 
 
-@pytest.mark.parametrize("mode", [0, 1, 2])
-@pytest.mark.parametrize("shape", [(256, 256, 128), (512, 768, 384), (1024, 512, 1024),
-                                   (8192, 2048, 512), (4096, 4096, 1024)])  # the last two: >= 240 tiles
-def test_gemm_f8_q_matches_fp32(dev, mode, shape):
+def _bracket(Y, ref, t, s, fo, what):
+    """The derived check of a quantised output: the kernel's fp32 value v obeys |v - ref| <= t (ref fp64, t the
+    fp32-level allowance of tests/helpers.py), v is an fp32 number, so RN32(ref - t) <= v <= RN32(ref + t); the
+    product with the scale and the quantiser Q (tests/fp8_ref.py) are monotone, hence, as signed fp8 values,
+        Q(RN32(ref - t) * s) <= Y <= Q(RN32(ref + t) * s).
+    Also spelled out: where |ref| s - t s > max the byte is exactly +-max. Returns the share of bytes equal to
+    Q(ref) (the headroom figure: how often the allowance was not needed at all)."""
+    yb = Y.view(torch.uint8)
+    assert not bool(fp8_ref.is_nan_code(yb, fo).any()), f"{what}: NaN bytes"
+    yv = fp8_ref.signed_value(yb, fo)
+    lo = fp8_ref.signed_value(fp8_ref.quantize((ref - t).float(), s, fo), fo)
+    hi = fp8_ref.signed_value(fp8_ref.quantize((ref + t).float(), s, fo), fo)
+    bad = (yv < lo) | (yv > hi)
+    if bool(bad.any()):
+        i = tuple(int(k) for k in bad.nonzero()[0])
+        raise AssertionError(f"{what}: {int(bad.sum())} of {bad.numel()} bytes outside [Q(ref - t), Q(ref + t)], first at {i}: "
+                             f"got {float(yv[i]):g}, bracket [{float(lo[i]):g}, {float(hi[i]):g}], ref * s "
+                             f"{float(ref[i]) * s:.9g}, t * s {float(t[i]) * s:.3g}")
+    sat = ref.abs() * s - t * s > FMAX[fo]
+    assert bool((yv[sat] == torch.sign(ref[sat]) * FMAX[fo]).all()), f"{what}: a saturated element is not +-max"
+    return float((yb == fp8_ref.quantize(ref.float(), s, fo)).float().mean())
+
+
+def _gemm_f8_q_case(dev, mode, shape, s, old_checks):
+    """One gemm_f8_q run at output scale s, held to _bracket; with old_checks also to the looser assertions this
+    test had before the bracket existed (they stay, at scale 3). Returns (share of bytes equal to Q(ref), ref * s in
+    fp64, the output format)."""
     C = require_native()
     M, N, K = shape
     g = torch.Generator().manual_seed(M + N + K + mode)
@@ -39,7 +65,7 @@ def test_gemm_f8_q_matches_fp32(dev, mode, shape):
     B = _rand_f8((N, K), 0, g, dev, 2.0)
     isa = torch.tensor([0.5], device=dev)
     isb = torch.tensor([0.125], device=dev)
-    scale = torch.tensor([3.0], device=dev)
+    scale = torch.tensor([s], device=dev)
     amax = torch.zeros(C.FP8_AMAX_SLOTS, device=dev)
     acc = (A.float() @ B.float().t()) * (0.5 * 0.125)
     bias = torch.randn(N, generator=g).to(dev) if mode != 2 else None
@@ -62,16 +88,62 @@ def test_gemm_f8_q_matches_fp32(dev, mode, shape):
     assert torch.equal(Yt.view(torch.uint8), Y.view(torch.uint8).t().contiguous())
     if mode == 1:  # saved pre-activation
         torch.testing.assert_close(aux.float(), acc, rtol=1e-2, atol=1e-2 * acc.abs().max().item())
-    q_ref = (ref * 3.0).clamp(-FMAX[fo], FMAX[fo])
-    # one fp8 ulp (2^-3 e4m3, 2^-2 e5m2 relative) for values near a rounding boundary of a
-    # differently-ordered fp32 accumulation
-    rel = 0.13 if fo == 0 else 0.26
-    torch.testing.assert_close(Y.float(), q_ref, rtol=rel, atol=1e-2 * q_ref.abs().max().item())
-    exact = (Y.float() == q_ref.to(F8[fo]).float()).float().mean().item()
-    assert exact > 0.97, exact
+    if old_checks:
+        q_ref = (ref * s).clamp(-FMAX[fo], FMAX[fo])
+        # one fp8 ulp (2^-3 e4m3, 2^-2 e5m2 relative) for values near a rounding boundary of a
+        # differently-ordered fp32 accumulation
+        rel = 0.13 if fo == 0 else 0.26
+        torch.testing.assert_close(Y.float(), q_ref, rtol=rel, atol=1e-2 * q_ref.abs().max().item())
+        exact = (Y.float() == q_ref.to(F8[fo]).float()).float().mean().item()
+        assert exact > 0.97, exact
     torch.testing.assert_close(amax.max().view(1), ref.abs().max().view(1), rtol=1e-3, atol=1e-5)
     if cs is not None:
         torch.testing.assert_close(cs, 7.0 + ref.sum(0), rtol=1e-3, atol=1e-3 * ref.abs().sum(0).max().item())
+    # the derived bracket, against fp64
+    A64, B64 = A.float().double(), B.float().double().t()
+    terms = {"alpha": 0.5 * 0.125, "bias": None if bias is None else bias.double()}
+    exp, t32 = gemm_expected(A64, B64, terms), gemm_t32(A64, B64, K, terms)
+    what = f"gemm_f8_q mode {mode} {shape} scale {s:g}"
+    if mode == 1:    # GELU of the kernel's OWN saved pre-activation, which is itself held to the bf16 store's bound
+        assert_within(aux, exp, store_bound(exp, t32, torch.bfloat16), what + " aux")
+        ref64, t = gelu64(aux.double()), gelu_out_bound(aux.double())
+    elif mode == 2:
+        ref64, t = exp * gelu_grad64(aux.double()), dgelu_t(exp, t32, aux.double())
+    else:
+        ref64, t = exp, t32
+    share = _bracket(Y, ref64, t, s, fo, what)
+    print(f"headroom gemm_f8_q share of bytes equal to Q(ref) {share:.4f} {what}")
+    return share, ref64 * s, fo
+
+
+@pytest.mark.parametrize("mode", [0, 1, 2])
+@pytest.mark.parametrize("shape", [(256, 256, 128), (512, 768, 384), (1024, 512, 1024),
+                                   (8192, 2048, 512), (4096, 4096, 1024)])  # the last two: >= 240 tiles
+def test_gemm_f8_q_matches_fp32(dev, mode, shape):
+    _gemm_f8_q_case(dev, mode, shape, 3.0, old_checks=True)
+
+
+@pytest.mark.parametrize("mode", [0, 1, 2])
+@pytest.mark.parametrize("kind", ["saturating", "subnormal"])
+def test_gemm_f8_q_extreme_scales(dev, mode, kind):
+    """(256, 256, 128) at an output scale that saturates most outputs (2^14 for e4m3, 2^21 for e5m2: |ref| > 0.027
+    saturates) and at one that puts most of them into the fp8 subnormal range (2^-9 / 2^-17: |ref| < 8), held to the
+    same bracket; the shares are asserted so that the scales keep doing what they are there for."""
+    fo = 1 if mode == 2 else 0
+    s = {("saturating", 0): 2.0 ** 14, ("saturating", 1): 2.0 ** 21,
+         ("subnormal", 0): 2.0 ** -9, ("subnormal", 1): 2.0 ** -17}[kind, fo]
+    _, p, _ = _gemm_f8_q_case(dev, mode, (256, 256, 128), s, old_checks=False)
+    a = p.abs()
+    if kind == "saturating":
+        share = float((a > FMAX[fo]).float().mean())
+        print(f"inputs gemm_f8_q mode {mode} saturating: share above max {share:.3f}")
+        assert share > 0.5, share
+    else:  # below the smallest normal value: subnormal codes, or (GELU's many near-zero outputs) rounding to zero
+        below = float((a < fp8_ref.MIN_NORMAL[fo]).float().mean())
+        half_min = 0.5 * fp8_ref.MIN_NORMAL[fo] / 2 ** (2 if fo else 3)  # half the smallest subnormal: above it, not zero
+        sub = float(((a < fp8_ref.MIN_NORMAL[fo]) & (a > half_min)).float().mean())
+        print(f"inputs gemm_f8_q mode {mode} subnormal: share below the normal range {below:.3f}, on subnormal codes {sub:.3f}")
+        assert below > 0.5 and sub > 0.2, (below, sub)
 
 
 @pytest.mark.parametrize("mode", [1, 2])

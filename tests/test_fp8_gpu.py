@@ -4,6 +4,7 @@ import pytest
 import torch
 
 from ml_trainer_amd.ops._ext import require_native
+from tests import fp8_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -27,9 +28,8 @@ def test_cast_fp8_matches_torch(dev, fmt, src):
     amax = torch.zeros(C.FP8_AMAX_SLOTS, device=dev)
     y = torch.empty(x.numel(), dtype=F8[fmt], device=dev)
     C.fp8_cast(x, y, scale, amax, fmt)
-    ref = (x.float() * 0.75).clamp(-FMAX[fmt], FMAX[fmt]).to(F8[fmt])
-    mism = (y.float() != ref.float()).float().mean().item()
-    assert mism < 1e-3, mism
+    # every byte is the reference's (one fp32 product, saturate, round to nearest even: tests/fp8_ref.py)
+    fp8_ref.assert_exact(y.cpu(), x.cpu(), 0.75, fmt, "fp8_cast")
     assert float(y[5].float()) == FMAX[fmt]
     torch.testing.assert_close(amax.max().view(1), x.float().abs().max().view(1))
 
@@ -43,8 +43,7 @@ def test_cast_transpose_and_scale_update(dev):
     scale = torch.tensor([4.0], device=dev)
     amax = torch.zeros(1, C.FP8_AMAX_SLOTS, device=dev)
     C.fp8_cast_transpose(w, y, yt, scale, amax[0], 0)
-    ref = (w * 4.0).clamp(-448, 448).to(torch.float8_e4m3fn)
-    assert (y.float() != ref.float()).float().mean().item() < 1e-3
+    fp8_ref.assert_exact(y.cpu(), w.cpu(), 4.0, 0, "fp8_cast_transpose")
     assert torch.equal(yt.view(torch.uint8), y.view(torch.uint8).t().contiguous())
     torch.testing.assert_close(amax.max().view(1), w.abs().max().view(1))
     hist = torch.zeros(1, 4, device=dev)
@@ -154,9 +153,7 @@ def test_cast_transpose_bf16_input(dev, fmt, shape):
     scale = torch.tensor([2.0], device=dev)
     amax = torch.zeros(C.FP8_AMAX_SLOTS, device=dev)
     C.fp8_cast_transpose(x, y, yt, scale, amax, fmt)
-    fm = 448.0 if fmt == 0 else 57344.0
-    ref = (x.float() * 2.0).clamp(-fm, fm).to(dt)
-    assert (y.float() != ref.float()).float().mean().item() < 1e-3
+    fp8_ref.assert_exact(y.cpu(), x.cpu(), 2.0, fmt, "fp8_cast_transpose")
     assert torch.equal(yt.view(torch.uint8), y.view(torch.uint8).t().contiguous())
     assert float(amax.max()) == float(x.float().abs().max())
 
