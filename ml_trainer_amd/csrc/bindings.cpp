@@ -428,50 +428,88 @@ static void check_gemm_cfg(int cfg) {
   TORCH_CHECK(cfg != 6, "GEMM configuration 6 (persistent ping-pong) was retired; use 5 (ping-pong) or 7 (4-wave)");
 }
 
+// One matrix operand of a GEMM binding: 2-D, on the device, unit column stride, a row stride that is a
+// multiple of row_mult (0: not checked for this operand) and a 16-byte aligned base. `name` is the
+// binding's; the other texts are the binding's own wording of the condition.
+struct GemmOperandText {
+  const char *name, *device, *col_stride, *row_stride;
+};
+static void check_gemm_operand(const Tensor& t, const GemmOperandText& tx, int64_t row_mult) {
+  TORCH_CHECK(t.dim() == 2, tx.name, " operands must be 2-D");
+  TORCH_CHECK(t.is_cuda(), tx.device);
+  TORCH_CHECK(t.stride(1) == 1, tx.col_stride);
+  TORCH_CHECK(row_mult == 0 || t.stride(0) % row_mult == 0, tx.row_stride);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, tx.name, " operands must be 16-byte aligned");
+}
+
+// The epilogue side operands of a GEMM with an [M, N] output: fp32 bias [N], the bf16 [M, N] GELU
+// pre-activation aux (modes 1 gelu / 2 dgelu; strict_aux: with row stride % 8 == 0 and a 16-byte base as
+// well) and the bf16 [M, N] residual res. no_aux / bad_aux: the binding's texts for a missing / unfit aux.
+struct GemmEpiOperands {
+  const float* bias = nullptr;
+  const uint16_t* aux = nullptr;
+  const uint16_t* res = nullptr;
+  int64_t ldaux = 0, ldres = 0;
+};
+static GemmEpiOperands check_gemm_epilogue(const c10::optional<Tensor>& bias, const c10::optional<Tensor>& aux,
+                                           const c10::optional<Tensor>& res, int64_t M, int64_t N, int mode,
+                                           bool strict_aux, const char* no_aux, const char* bad_aux) {
+  const auto bf16_mn = [&](const Tensor& t) {
+    return t.scalar_type() == at::kBFloat16 && t.dim() == 2 && t.size(0) == M && t.size(1) == N && t.stride(1) == 1 &&
+           t.is_cuda();
+  };
+  GemmEpiOperands e;
+  if (bias.has_value()) {
+    check_dev(*bias, "bias", at::kFloat, N, 4);
+    e.bias = bias->data_ptr<float>();
+  }
+  if (mode == 1 || mode == 2) {  // GELU writes / dGELU reads the pre-activation (tanh needs none)
+    TORCH_CHECK(aux.has_value(), no_aux);
+    TORCH_CHECK(bf16_mn(*aux) && (!strict_aux || (aux->stride(0) % 8 == 0 &&
+                                                   reinterpret_cast<uintptr_t>(aux->data_ptr()) % 16 == 0)),
+                bad_aux);
+    e.aux = bf16_ptr(*aux);
+    e.ldaux = aux->stride(0);
+  }
+  if (res.has_value()) {
+    TORCH_CHECK(bf16_mn(*res), "res must be bf16 [M,N]");
+    e.res = bf16_ptr(*res);
+    e.ldres = res->stride(0);
+  }
+  return e;
+}
+
+// colsum_out[n] (+)= the sum over the rows of part [rows, N]: the column partials a kernel's epilogue
+// left (per 64 or 128 output rows) become the bias gradient, in a fixed order
+static void reduce_col_partials(const Tensor& part, int64_t rows, int64_t N, float* colsum_out, bool accumulate) {
+  SegOut o{{colsum_out, nullptr, nullptr}};
+  launch_reduce_rows(part.data_ptr<float>(), (int)rows, N, (int)N, (int)N, o, accumulate ? 1 : 0, cur_stream());
+}
+
 // A, B, C are 2-D (row-major, unit column stride). a_mn / b_mn describe the storage:
 //   A: [M,K] (a_mn=0) or [K,M] (a_mn=1);  B: [N,K] (b_mn=0) or [K,N] (b_mn=1);  C: [M,N].
 void gemm(Tensor A, Tensor B, Tensor C, bool a_mn, bool b_mn, c10::optional<Tensor> bias, c10::optional<Tensor> aux,
           c10::optional<Tensor> res, double alpha, int mode, bool accumulate, int cfg, int splits,
           c10::optional<Tensor> colsum_out, bool colsum_accumulate) {
   check_gemm_cfg(cfg);
-  TORCH_CHECK(A.dim() == 2 && B.dim() == 2 && C.dim() == 2, "gemm operands must be 2-D");
+  static const GemmOperandText tx{"gemm", "gemm operands must be device tensors",
+                                  "gemm operands need unit column stride",
+                                  "gemm leading dimensions must be multiples of 8"};
+  check_gemm_operand(A, tx, 8);
+  check_gemm_operand(B, tx, 8);
+  check_gemm_operand(C, tx, 0);
   TORCH_CHECK(A.scalar_type() == at::kBFloat16 && B.scalar_type() == at::kBFloat16, "gemm A/B must be bf16");
   TORCH_CHECK(C.scalar_type() == at::kBFloat16 || C.scalar_type() == at::kFloat, "gemm C must be bf16 or fp32");
-  for (const Tensor* t : {&A, &B, &C}) {
-    TORCH_CHECK(t->is_cuda(), "gemm operands must be device tensors");
-    TORCH_CHECK(t->stride(1) == 1, "gemm operands need unit column stride");
-    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0, "gemm operands must be 16-byte aligned");
-  }
   const int64_t M = a_mn ? A.size(1) : A.size(0), K = a_mn ? A.size(0) : A.size(1);
   const int64_t N = b_mn ? B.size(1) : B.size(0), K2 = b_mn ? B.size(0) : B.size(1);
   TORCH_CHECK(K == K2, "gemm inner dimensions differ: ", K, " vs ", K2);
   TORCH_CHECK(C.size(0) == M && C.size(1) == N, "gemm C shape mismatch");
-  TORCH_CHECK(A.stride(0) % 8 == 0 && B.stride(0) % 8 == 0, "gemm leading dimensions must be multiples of 8");
   // 16-byte chunks along the contiguous dimension of each operand
   TORCH_CHECK((a_mn ? M : K) % 8 == 0 && (b_mn ? N : K) % 8 == 0, "contiguous gemm dims must be multiples of 8");
   TORCH_CHECK(M < (1LL << 31) && N < (1LL << 31) && K < (1LL << 31), "gemm dims too large");
-  const float* bp = nullptr;
-  const uint16_t* ap = nullptr;
-  const uint16_t* rp = nullptr;
-  int64_t ldaux = 0, ldres = 0;
-  if (bias.has_value()) {
-    check_dev(*bias, "bias", at::kFloat, N, 4);
-    bp = bias->data_ptr<float>();
-  }
   TORCH_CHECK(mode >= 0 && mode <= 3, "gemm mode (0 none, 1 gelu, 2 dgelu, 3 tanh)");
-  if (mode == 1 || mode == 2) {
-    TORCH_CHECK(aux.has_value(), "gemm GELU modes need aux");
-    TORCH_CHECK(aux->scalar_type() == at::kBFloat16 && aux->dim() == 2 && aux->size(0) == M && aux->size(1) == N &&
-                    aux->stride(1) == 1 && aux->is_cuda(), "aux must be bf16 [M,N]");
-    ap = bf16_ptr(*aux);
-    ldaux = aux->stride(0);
-  }
-  if (res.has_value()) {
-    TORCH_CHECK(res->scalar_type() == at::kBFloat16 && res->dim() == 2 && res->size(0) == M && res->size(1) == N &&
-                    res->stride(1) == 1 && res->is_cuda(), "res must be bf16 [M,N]");
-    rp = bf16_ptr(*res);
-    ldres = res->stride(0);
-  }
+  const GemmEpiOperands ep =
+      check_gemm_epilogue(bias, aux, res, M, N, mode, false, "gemm GELU modes need aux", "aux must be bf16 [M,N]");
   TORCH_CHECK(!accumulate || C.scalar_type() == at::kFloat, "accumulate needs an fp32 output");
   Tensor part;
   if (colsum_out.has_value()) {
@@ -479,8 +517,8 @@ void gemm(Tensor A, Tensor B, Tensor C, bool a_mn, bool b_mn, c10::optional<Tens
     // ping-pong kernel's epilogue: every tile must take its dGELU side-operand pass
     TORCH_CHECK(mode == 2 && !res.has_value() && !accumulate && C.scalar_type() == at::kBFloat16 && !a_mn,
                 "colsum_out: dGELU mode, bf16 output, k-contiguous A, no residual / accumulate");
-    TORCH_CHECK(M % 256 == 0 && N % 256 == 0 && K % 64 == 0 && C.stride(0) % 8 == 0 && ldaux % 8 == 0 &&
-                    reinterpret_cast<uintptr_t>(ap) % 16 == 0,
+    TORCH_CHECK(M % 256 == 0 && N % 256 == 0 && K % 64 == 0 && C.stride(0) % 8 == 0 && ep.ldaux % 8 == 0 &&
+                    reinterpret_cast<uintptr_t>(ep.aux) % 16 == 0,
                 "colsum_out needs M % 256 == 0, N % 256 == 0, K % 64 == 0 and 16-byte aligned rows of C / aux");
     check_dev(*colsum_out, "colsum_out", at::kFloat, N, 16);
     // the 4-wave kernel (cfg 7) when the planner takes it (its epilogue writes the same per-64-row
@@ -496,14 +534,10 @@ void gemm(Tensor A, Tensor B, Tensor C, bool a_mn, bool b_mn, c10::optional<Tens
   Tensor ws;
   if (plan.ws_floats > 0) ws = at::empty({plan.ws_floats}, A.options().dtype(at::kFloat));
   launch_gemm_bf16(plan, a_mn, b_mn, C.scalar_type() == at::kFloat, bf16_ptr(A), bf16_ptr(B), C.data_ptr(), (int)M,
-                   (int)N, (int)K, A.stride(0), B.stride(0), C.stride(0), bp, ap, ldaux, rp, ldres, (float)alpha, mode,
-                   accumulate ? 1 : 0, ws.defined() ? ws.data_ptr<float>() : nullptr, nullptr, cur_stream(),
-                   part.defined() ? part.data_ptr<float>() : nullptr);
-  if (part.defined()) {
-    SegOut o{{colsum_out->data_ptr<float>(), nullptr, nullptr}};
-    launch_reduce_rows(part.data_ptr<float>(), (int)(M / 64), N, (int)N, (int)N, o, colsum_accumulate ? 1 : 0,
-                       cur_stream());
-  }
+                   (int)N, (int)K, A.stride(0), B.stride(0), C.stride(0), ep.bias, ep.aux, ep.ldaux, ep.res, ep.ldres,
+                   (float)alpha, mode, accumulate ? 1 : 0, ws.defined() ? ws.data_ptr<float>() : nullptr, nullptr,
+                   cur_stream(), part.defined() ? part.data_ptr<float>() : nullptr);
+  if (part.defined()) reduce_col_partials(part, M / 64, N, colsum_out->data_ptr<float>(), colsum_accumulate);
 }
 
 // ---------------------------------------------------------------------------- fp8
@@ -517,44 +551,24 @@ void gemm_f8(Tensor A, Tensor B, Tensor C, int fmt_a, int fmt_b, Tensor inv_scal
              c10::optional<Tensor> bias, c10::optional<Tensor> aux, c10::optional<Tensor> res, double alpha, int mode,
              bool accumulate, int cfg, int splits) {
   check_gemm_cfg(cfg);
-  TORCH_CHECK(A.dim() == 2 && B.dim() == 2 && C.dim() == 2, "gemm_f8 operands must be 2-D");
+  static const char* const text = "gemm_f8 operands: device tensors with unit column stride";
+  static const GemmOperandText tx{"gemm_f8", text, text, "gemm_f8 row strides must be multiples of 16"};
+  check_gemm_operand(A, tx, 16);
+  check_gemm_operand(B, tx, 16);
+  check_gemm_operand(C, tx, 0);
   TORCH_CHECK(is_fp8_storage(A) && is_fp8_storage(B), "gemm_f8 A/B must be fp8 (or uint8) storage");
   TORCH_CHECK((fmt_a == 0 || fmt_a == 1) && (fmt_b == 0 || fmt_b == 1) && !(fmt_a == 1 && fmt_b == 1),
               "fp8 formats: 0 = e4m3, 1 = e5m2 (e5m2 x e5m2 not supported)");
   TORCH_CHECK(C.scalar_type() == at::kBFloat16 || C.scalar_type() == at::kFloat, "gemm_f8 C must be bf16 or fp32");
-  for (const Tensor* t : {&A, &B, &C}) {
-    TORCH_CHECK(t->is_cuda() && t->stride(1) == 1, "gemm_f8 operands: device tensors with unit column stride");
-    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0, "gemm_f8 operands must be 16-byte aligned");
-  }
   const int64_t M = A.size(0), K = A.size(1), N = B.size(0);
   TORCH_CHECK(B.size(1) == K, "gemm_f8 inner dimensions differ");
   TORCH_CHECK(C.size(0) == M && C.size(1) == N, "gemm_f8 C shape mismatch");
   TORCH_CHECK(K % 128 == 0 && M >= 64 && N >= 64, "gemm_f8 needs K % 128 == 0 and M, N >= 64");
-  TORCH_CHECK(A.stride(0) % 16 == 0 && B.stride(0) % 16 == 0, "gemm_f8 row strides must be multiples of 16");
   check_dev(inv_scale_a, "inv_scale_a", at::kFloat, 1, 4);
   check_dev(inv_scale_b, "inv_scale_b", at::kFloat, 1, 4);
-  const float* bp = nullptr;
-  const uint16_t* ap = nullptr;
-  const uint16_t* rp = nullptr;
-  int64_t ldaux = 0, ldres = 0;
-  if (bias.has_value()) {
-    check_dev(*bias, "bias", at::kFloat, N, 4);
-    bp = bias->data_ptr<float>();
-  }
   TORCH_CHECK(mode >= 0 && mode <= 3, "gemm mode (0 none, 1 gelu, 2 dgelu, 3 tanh)");
-  if (mode == 1 || mode == 2) {  // GELU writes / dGELU reads the pre-activation (tanh needs none)
-    TORCH_CHECK(aux.has_value() && aux->scalar_type() == at::kBFloat16 && aux->dim() == 2 && aux->size(0) == M &&
-                    aux->size(1) == N && aux->stride(1) == 1 && aux->is_cuda(),
-                "gemm_f8 mode 1/2: aux must be bf16 [M,N]");
-    ap = bf16_ptr(*aux);
-    ldaux = aux->stride(0);
-  }
-  if (res.has_value()) {
-    TORCH_CHECK(res->scalar_type() == at::kBFloat16 && res->dim() == 2 && res->size(0) == M && res->size(1) == N &&
-                    res->stride(1) == 1 && res->is_cuda(), "res must be bf16 [M,N]");
-    rp = bf16_ptr(*res);
-    ldres = res->stride(0);
-  }
+  static const char* const aux_text = "gemm_f8 mode 1/2: aux must be bf16 [M,N]";
+  const GemmEpiOperands ep = check_gemm_epilogue(bias, aux, res, M, N, mode, false, aux_text, aux_text);
   TORCH_CHECK(!accumulate || C.scalar_type() == at::kFloat, "accumulate needs an fp32 output");
   const GemmPlan plan = plan_gemm_f8((int)M, (int)N, (int)K, cfg, splits);
   TORCH_CHECK(plan.cfg >= 1, "no fp8 GEMM configuration for this shape");
@@ -562,8 +576,8 @@ void gemm_f8(Tensor A, Tensor B, Tensor C, int fmt_a, int fmt_b, Tensor inv_scal
   if (plan.ws_floats > 0) ws = at::empty({plan.ws_floats}, C.options().dtype(at::kFloat));
   launch_gemm_f8(plan, fmt_a, fmt_b, C.scalar_type() == at::kFloat, u8(A), u8(B), C.data_ptr(), (int)M, (int)N,
                  (int)K, A.stride(0), B.stride(0), C.stride(0), inv_scale_a.data_ptr<float>(),
-                 inv_scale_b.data_ptr<float>(), bp, ap, ldaux, rp, ldres, (float)alpha, mode, accumulate ? 1 : 0,
-                 ws.defined() ? ws.data_ptr<float>() : nullptr, nullptr, cur_stream());
+                 inv_scale_b.data_ptr<float>(), ep.bias, ep.aux, ep.ldaux, ep.res, ep.ldres, (float)alpha, mode,
+                 accumulate ? 1 : 0, ws.defined() ? ws.data_ptr<float>() : nullptr, nullptr, cur_stream());
 }
 
 // fp8 GEMM whose epilogue quantises its own output: Y (fp8 [M,N]) and Yt (fp8 [N,M]) for the
@@ -571,7 +585,9 @@ void gemm_f8(Tensor A, Tensor B, Tensor C, int fmt_a, int fmt_b, Tensor inv_scal
 void gemm_f8_q(Tensor A, Tensor B, Tensor Y, Tensor Yt, int fmt_a, int fmt_b, Tensor inv_scale_a, Tensor inv_scale_b,
                int out_fmt, Tensor out_scale, Tensor out_amax, c10::optional<Tensor> bias, c10::optional<Tensor> aux,
                int mode, c10::optional<Tensor> colsum_out, bool colsum_accumulate) {
-  TORCH_CHECK(A.dim() == 2 && B.dim() == 2 && Y.dim() == 2 && Yt.dim() == 2, "gemm_f8_q operands must be 2-D");
+  static const char* const text = "gemm_f8_q operands: device tensors, unit column stride, row stride % 16 == 0";
+  static const GemmOperandText tx{"gemm_f8_q", text, text, text};
+  for (const Tensor* t : {&A, &B, &Y, &Yt}) check_gemm_operand(*t, tx, 16);
   TORCH_CHECK(is_fp8_storage(A) && is_fp8_storage(B) && is_fp8_storage(Y) && is_fp8_storage(Yt),
               "gemm_f8_q A/B/Y/Yt must be fp8 (or uint8) storage");
   TORCH_CHECK((fmt_a == 0 || fmt_a == 1) && fmt_b == 0, "gemm_f8_q formats: A e4m3/e5m2, B e4m3");
@@ -580,32 +596,14 @@ void gemm_f8_q(Tensor A, Tensor B, Tensor Y, Tensor Yt, int fmt_a, int fmt_b, Te
   TORCH_CHECK(B.size(1) == K, "gemm_f8_q inner dimensions differ");
   TORCH_CHECK(M % 256 == 0 && N % 256 == 0 && K % 128 == 0 && K > 0,
               "gemm_f8_q needs M % 256 == 0, N % 256 == 0, K % 128 == 0");
-  for (const Tensor* t : {&A, &B, &Y, &Yt}) {
-    TORCH_CHECK(t->is_cuda() && t->stride(1) == 1 && t->stride(0) % 16 == 0,
-                "gemm_f8_q operands: device tensors, unit column stride, row stride % 16 == 0");
-    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0, "gemm_f8_q operands must be 16-byte aligned");
-  }
   TORCH_CHECK(Y.size(0) == M && Y.size(1) == N && Yt.size(0) == N && Yt.size(1) == M, "gemm_f8_q Y / Yt shapes");
   check_dev(inv_scale_a, "inv_scale_a", at::kFloat, 1, 4);
   check_dev(inv_scale_b, "inv_scale_b", at::kFloat, 1, 4);
   check_dev(out_scale, "out_scale", at::kFloat, 1, 4);
   check_dev(out_amax, "out_amax", at::kFloat, kAmaxSlots * kAmaxStride, 4);
-  const float* bp = nullptr;
-  if (bias.has_value()) {
-    check_dev(*bias, "bias", at::kFloat, N, 4);
-    bp = bias->data_ptr<float>();
-  }
   TORCH_CHECK(mode >= 0 && mode <= 2, "gemm_f8_q mode (0 none, 1 gelu, 2 dgelu)");
-  const uint16_t* ap = nullptr;
-  int64_t ldaux = 0;
-  if (mode != 0) {
-    TORCH_CHECK(aux.has_value() && aux->scalar_type() == at::kBFloat16 && aux->dim() == 2 && aux->size(0) == M &&
-                    aux->size(1) == N && aux->stride(1) == 1 && aux->stride(0) % 8 == 0 && aux->is_cuda() &&
-                    reinterpret_cast<uintptr_t>(aux->data_ptr()) % 16 == 0,
-                "aux must be a 16-byte aligned bf16 [M,N] with row stride % 8 == 0");
-    ap = bf16_ptr(*aux);
-    ldaux = aux->stride(0);
-  }
+  static const char* const aux_text = "aux must be a 16-byte aligned bf16 [M,N] with row stride % 8 == 0";
+  const GemmEpiOperands ep = check_gemm_epilogue(bias, aux, c10::nullopt, M, N, mode, true, aux_text, aux_text);
   Tensor part;
   if (colsum_out.has_value()) {
     check_dev(*colsum_out, "colsum_out", at::kFloat, N, 16);
@@ -613,14 +611,10 @@ void gemm_f8_q(Tensor A, Tensor B, Tensor Y, Tensor Yt, int fmt_a, int fmt_b, Te
   }
   launch_gemm_f8_q(fmt_a, fmt_b, u8(A), u8(B), reinterpret_cast<uint8_t*>(Y.data_ptr()),
                    reinterpret_cast<uint8_t*>(Yt.data_ptr()), (int)M, (int)N, (int)K, A.stride(0), B.stride(0),
-                   Y.stride(0), Yt.stride(0), inv_scale_a.data_ptr<float>(), inv_scale_b.data_ptr<float>(), bp, ap,
-                   ldaux, mode, out_fmt, out_scale.data_ptr<float>(), out_amax.data_ptr<float>(),
+                   Y.stride(0), Yt.stride(0), inv_scale_a.data_ptr<float>(), inv_scale_b.data_ptr<float>(), ep.bias,
+                   ep.aux, ep.ldaux, mode, out_fmt, out_scale.data_ptr<float>(), out_amax.data_ptr<float>(),
                    part.defined() ? part.data_ptr<float>() : nullptr, cur_stream());
-  if (part.defined()) {
-    SegOut o{{colsum_out->data_ptr<float>(), nullptr, nullptr}};
-    launch_reduce_rows(part.data_ptr<float>(), (int)(M / 64), N, (int)N, (int)N, o, colsum_accumulate ? 1 : 0,
-                       cur_stream());
-  }
+  if (part.defined()) reduce_col_partials(part, M / 64, N, colsum_out->data_ptr<float>(), colsum_accumulate);
 }
 
 void fp8_cast(Tensor x, Tensor y, Tensor scale, c10::optional<Tensor> amax, int fmt) {
@@ -685,8 +679,7 @@ void fp8_cast_transpose(Tensor w, Tensor y, Tensor yt, Tensor scale, c10::option
       launch_cast_transpose_fp8_bf16(bf16_ptr(w), reinterpret_cast<uint8_t*>(y.data_ptr()),
                                      reinterpret_cast<uint8_t*>(yt.data_ptr()), (int)R, (int)Cc,
                                      scale.data_ptr<float>(), am, fmt, cur_stream(), ws.data_ptr<float>());
-      SegOut o{{cs, nullptr, nullptr}};
-      launch_reduce_rows(ws.data_ptr<float>(), (int)(R / 128), Cc, (int)Cc, (int)Cc, o, acc, cur_stream());
+      reduce_col_partials(ws, R / 128, Cc, cs, colsum_accumulate);
     } else {
       launch_cast_transpose_fp8_bf16(bf16_ptr(w), reinterpret_cast<uint8_t*>(y.data_ptr()),
                                      reinterpret_cast<uint8_t*>(yt.data_ptr()), (int)R, (int)Cc,
@@ -1037,8 +1030,9 @@ void attn_fwd(Tensor qkv, Tensor out, Tensor lse, c10::optional<Tensor> lens, in
   check_bf16_2d(out, "out", T, D);
   check_dev(lse, "lse", at::kFloat, B * H * S, 4);
   const AttnDropArgs ad = make_attn_drop_args(p, seed, site, rank, S);
-  launch_attn_fwd(bf16_ptr(qkv), (uint16_t*)out.data_ptr(), lse.data_ptr<float>(), cu ? nullptr : lens_ptr(lens, B),
-                  (int)B, (int)S, (int)H, (float)scale, cur_stream(), ad, cu, (int)T, causal);
+  const int* lp = cu ? nullptr : lens_ptr(lens, B);
+  const AttnProblem prob{(int)B, (int)S, (int)H, (float)scale, lp, cu, (int)T, causal, ad};
+  launch_attn_fwd(prob, bf16_ptr(qkv), (uint16_t*)out.data_ptr(), lse.data_ptr<float>(), cur_stream());
 }
 
 void attn_bwd(Tensor qkv, Tensor out, Tensor dout, Tensor lse, Tensor delta, c10::optional<Tensor> lens, Tensor dqkv,
@@ -1048,12 +1042,13 @@ void attn_bwd(Tensor qkv, Tensor out, Tensor dout, Tensor lse, Tensor delta, c10
               int64_t rank, c10::optional<Tensor> cu_seqlens, bool causal) {
   const int64_t D = H * 64;
   TORCH_CHECK(B > 0 && S > 0 && H > 0 && B <= 65535 && H <= 65535, "attention dims");
-  TORCH_CHECK(!causal || !q8_y.has_value(), "attn_bwd: causal attention has no fp8 (q8) outputs: the q8 epilogue has "
-              "no causal instantiation");
   const AttnDropArgs ad = make_attn_drop_args(p, seed, site, rank, S);  // the forward's (p, seed, site, rank)
   const int* cu = nullptr;
   const int64_t T = attn_rows(cu_seqlens, qkv, B, S, D, &cu);
-  TORCH_CHECK(!cu || !q8_y.has_value(), "attn_bwd: the fp8 (q8) outputs take padded batches only, not cu_seqlens");
+  const int* lp = cu ? nullptr : lens_ptr(lens, B);
+  const AttnProblem prob{(int)B, (int)S, (int)H, (float)scale, lp, cu, (int)T, causal, ad};
+  // which kernels run it; a combination without a kernel is refused here, before any other q8 check
+  const AttnBwdRoute route = attn_bwd_route(prob, q8_y.has_value());
   check_bf16_2d(qkv, "qkv", T, 3 * D);
   check_bf16_2d(out, "out", T, D);
   check_bf16_2d(dout, "dout", T, D);
@@ -1086,27 +1081,19 @@ void attn_bwd(Tensor qkv, Tensor out, Tensor dout, Tensor lse, Tensor delta, c10
     q8.amax = q8_amax->data_ptr<float>();
     q8.ldt = B * S;
   }
-  int rq = 0, rkv = 0;
-  const bool fused = launch_attn_bwd(bf16_ptr(qkv), bf16_ptr(out), bf16_ptr(dout), lse.data_ptr<float>(),
-                                     delta.data_ptr<float>(), cu ? nullptr : lens_ptr(lens, B),
-                                     (uint16_t*)dqkv.data_ptr(), (int)B, (int)S, (int)H, (float)scale, cur_stream(),
-                                     pq.defined() ? pq.data_ptr<float>() : nullptr,
-                                     pkv.defined() ? pkv.data_ptr<float>() : nullptr, &rq, &rkv, q8, ad, cu, (int)T,
-                                     causal);
-  TORCH_CHECK(!q8.y || !colsum_out.has_value() || fused, "attn_bwd q8: column sums need the ring kernels");
+  launch_attn_bwd(prob, route, bf16_ptr(qkv), bf16_ptr(out), bf16_ptr(dout), lse.data_ptr<float>(),
+                  delta.data_ptr<float>(), (uint16_t*)dqkv.data_ptr(), q8, pq.defined() ? pq.data_ptr<float>() : nullptr,
+                  pkv.defined() ? pkv.data_ptr<float>() : nullptr, cur_stream());
   if (!colsum_out.has_value()) return;
   float* cs = colsum_out->data_ptr<float>();
-  const int acc = colsum_accumulate ? 1 : 0;
-  if (fused) {
-    SegOut oq{{cs, nullptr, nullptr}};
-    launch_reduce_rows(pq.data_ptr<float>(), rq, D, (int)D, (int)D, oq, acc, cur_stream());
-    SegOut okv{{cs + D, cs + 2 * D, nullptr}};
-    launch_reduce_rows(pkv.data_ptr<float>(), rkv, 2 * D, (int)(2 * D), (int)D, okv, acc ? 3 : 0, cur_stream());
+  if (route.ring) {  // the ring kernels left column partials: dQ's into cs[0, D), dK | dV's into cs[D, 3D)
+    reduce_col_partials(pq, route.rows_q, D, cs, colsum_accumulate);
+    reduce_col_partials(pkv, route.rows_kv, 2 * D, cs + D, colsum_accumulate);
   } else {
     Tensor ws = at::empty({std::max<int64_t>(colsum_ws_floats((int)T, (int)(3 * D)), 4)},
                           qkv.options().dtype(at::kFloat));
-    launch_colsum_bf16((const uint16_t*)dqkv.data_ptr(), (int)T, (int)(3 * D), dqkv.stride(0), cs, acc,
-                       ws.data_ptr<float>(), cur_stream());
+    launch_colsum_bf16((const uint16_t*)dqkv.data_ptr(), (int)T, (int)(3 * D), dqkv.stride(0), cs,
+                       colsum_accumulate ? 1 : 0, ws.data_ptr<float>(), cur_stream());
   }
 }
 

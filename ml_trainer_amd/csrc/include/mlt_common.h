@@ -9,6 +9,9 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 #include <stdint.h>
+#include <stdexcept>
+#include <string>
+#include <type_traits>
 
 #define MLT_WAVE 64
 
@@ -40,6 +43,47 @@
   } while (0)
 
 namespace mlt {
+
+// Host-side launch dispatch: a runtime value becomes a template argument of the launcher's generic
+// lambda. Only the listed values are instantiated; a combination without a kernel is left out at the
+// call site with `if constexpr`.
+// dispatch_int<1, 2, 4>(v, f): f(std::integral_constant<int, V>{}) for the listed V == v; whether one matched.
+template <int... Vs, class F>
+constexpr bool dispatch_int(int v, F&& f) {
+  return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
+// dispatch_bools(f, a, b, ...): f(std::bool_constant<a>{}, std::bool_constant<b>{}, ...)
+template <class F>
+constexpr void dispatch_bools(F&& f) {
+  f();
+}
+template <class F, class... Bs>
+constexpr void dispatch_bools(F&& f, bool b, Bs... rest) {
+  if (b)
+    dispatch_bools([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+  else
+    dispatch_bools([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
+// what a launcher throws when dispatch_int reports no match (the bindings reject these values first)
+[[noreturn]] inline void throw_no_kernel(const char* launcher, const char* what, long long v) {
+  throw std::invalid_argument(std::string(launcher) + ": no kernel for " + what + " = " + std::to_string(v));
+}
+
+namespace dispatch_selfcheck {
+constexpr int pick(int v) {  // the matched value, or -1 on a miss
+  int got = -1;
+  return dispatch_int<1, 2, 4>(v, [&](auto c) { got = decltype(c)::value; }) ? got : -1;
+}
+constexpr int flags(bool a, bool b) {
+  int got = -1;
+  dispatch_bools([&](auto ca, auto cb) { got = 2 * decltype(ca)::value + decltype(cb)::value; }, a, b);
+  return got;
+}
+static_assert(pick(1) == 1 && pick(4) == 4, "dispatch_int: hit");
+static_assert(pick(3) == -1 && pick(0) == -1, "dispatch_int: miss");
+static_assert(flags(false, false) == 0 && flags(false, true) == 1 && flags(true, false) == 2 && flags(true, true) == 3,
+              "dispatch_bools: two flags, in argument order");
+}  // namespace dispatch_selfcheck
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -334,21 +334,27 @@ void launch_embed_fwd(const int64_t* ids, const int64_t* tt, const uint16_t* Ww,
 void launch_embed_bwd(const int64_t* sid, const int64_t* perm, const int64_t* tt, const uint16_t* DX, float* gw,
                       float* gp, float* gt, float* part, int64_t rows, int S, int D, int64_t vocab, int ntype,
                       hipStream_t st, const int* cu = nullptr, int B = 0);
-// cu (packed / unpadded mode, or nullptr): cu_seqlens [B + 1] on the device. qkv / out / dout / dqkv then
-// hold rows >= cu[B] token rows (sequence b at rows cu[b] .. cu[b + 1]; rows past cu[B] are untouched).
-// S is max_seqlen: it still sizes the grid, lse [B, H, S], the dropout tile stride and the column
-// partials. lens is unused. Ring kernels and bf16 outputs only.
-// ad (attention-probability dropout, mlt_philox.h): thr8 > 0 launches the dropout instantiations of
-// the forward and the two ring backward kernels; thr8 == 0 the plain ones
-// causal: key j of a sequence is visible to query i of the same sequence iff j <= i and j < len_b (the
-// CAUSAL instantiations: the key / query loops stop at / start from the diagonal). Ring kernels and bf16
-// outputs only; composes with ad and cu.
-void launch_attn_fwd(const uint16_t* qkv, uint16_t* out, float* lse, const int* lens, int B, int S, int H,
-                     float scale, hipStream_t st, const AttnDropArgs& ad = AttnDropArgs{}, const int* cu = nullptr,
-                     int rows = 0, bool causal = false);
-// colpart_q [B * ceil(S/64)][D] and colpart_kv [B * ceil(S/64)][2D] (or nullptr): bias-gradient
-// column partials of dQ and dK|dV; returns whether they were written (ring kernels) and the
-// number of partial rows in rows_q / rows_kv
+// One attention call: what the forward and the backward launchers agree on, besides their tensors.
+struct AttnProblem {
+  int B, S, H;  // batch, (maximum) sequence length, heads of 64 columns; D = 64 H
+  float scale;
+  // padded batch [B, S]: the valid length of every sequence (int32 [B] on the device, or nullptr: all S)
+  const int* lens;
+  // packed / unpadded batch, or nullptr: cu_seqlens [B + 1] on the device. qkv / out / dout / dqkv then
+  // hold rows >= cu[B] token rows (sequence b at rows cu[b] .. cu[b + 1]; rows past cu[B] are untouched).
+  // S is max_seqlen: it still sizes the grid, lse [B, H, S], the dropout tile stride and the column
+  // partials. lens is unused. Ring kernels and bf16 outputs only.
+  const int* cu;
+  int rows;  // token rows of the packed tensors (unused without cu)
+  // key j of a sequence is visible to query i of the same sequence iff j <= i and j < len_b (the CAUSAL
+  // instantiations: the key / query loops stop at / start from the diagonal). Ring kernels and bf16
+  // outputs only; composes with drop and cu.
+  bool causal;
+  // attention-probability dropout (mlt_philox.h): thr8 > 0 launches the dropout instantiations of the
+  // forward and the two ring backward kernels; thr8 == 0 the plain ones
+  AttnDropArgs drop;
+};
+void launch_attn_fwd(const AttnProblem& p, const uint16_t* qkv, uint16_t* out, float* lse, hipStream_t st);
 // q8 (fp8 training, y != nullptr): instead of the bf16 dQKV, the backward kernels write its e5m2
 // copy y [B*S][3D] and transpose yt [3D][B*S] -- each value the bf16 one rounded first, then scaled
 // by *scale and quantised exactly as fp8_cast_transpose would -- and record amax(|dQKV|) into the
@@ -360,11 +366,23 @@ struct AttnQ8 {
   float* amax = nullptr;
   int64_t ldt = 0;  // yt row stride (B * S)
 };
-bool launch_attn_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse, float* delta,
-                     const int* lens, uint16_t* dqkv, int B, int S, int H, float scale, hipStream_t st,
-                     float* colpart_q = nullptr, float* colpart_kv = nullptr, int* rows_q = nullptr,
-                     int* rows_kv = nullptr, const AttnQ8& q8 = AttnQ8{}, const AttnDropArgs& ad = AttnDropArgs{},
-                     const int* cu = nullptr, int rows = 0, bool causal = false);
+// Which backward kernels run a problem. attn_bwd_route decides it, from the problem, whether q8 outputs
+// are asked for and the MLT_ATTN_* environment overrides, and raises every "no kernel for this
+// combination" error (std::runtime_error): the caller routes before it allocates or launches anything.
+struct AttnBwdRoute {
+  bool ring;    // the ring kernels (the default), or the register-staged ones (MLT_ATTN_RING=0)
+  bool k2, q2;  // 2 key / query groups (128 rows) per block in dK/dV / dQ, or 1 (64 rows)
+  bool fullt;   // every 64-row stage is whole (padded, S % 64 == 0): the unclamped-row instantiations
+  bool drop, packed, causal;
+  // rows of column partials the ring kernels write: B x (row blocks of the chosen group count)
+  int rows_q, rows_kv;
+};
+AttnBwdRoute attn_bwd_route(const AttnProblem& p, bool q8);
+// colpart_q [rows_q][D] and colpart_kv [rows_kv][2D] (both or neither; ring kernels only): bias-gradient
+// column partials of dQ and dK|dV. The register-staged kernels write none (the caller reduces dQKV itself).
+void launch_attn_bwd(const AttnProblem& p, const AttnBwdRoute& r, const uint16_t* qkv, const uint16_t* out,
+                     const uint16_t* dout, const float* lse, float* delta, uint16_t* dqkv, const AttnQ8& q8,
+                     float* colpart_q, float* colpart_kv, hipStream_t st);
 
 // ----------------------------------------------------------------------------
 // Masked-LM head (mlm.hip)

@@ -160,22 +160,11 @@ template <bool POST>
 static void launch_w(int W, dim3 g, hipStream_t st, float* grad, int64_t n, const XgmiPeers& P, int rank, int64_t cap,
                      uint64_t* seqs, float scale, unsigned* err, long long timeout, const XgmiPostOpt& post,
                      int fault) {
-#define MLT_XGMI_W(WV)                                                                                       \
-  case WV:                                                                                                   \
-    hipLaunchKernelGGL((xgmi_allreduce_kernel<POST, WV>), g, dim3(256), 0, st, grad, n, P, rank, W, cap, seqs, \
-                       scale, err, timeout, post, fault);                                                    \
-    break;
-  switch (W) {
-    MLT_XGMI_W(2)
-    MLT_XGMI_W(3)
-    MLT_XGMI_W(4)
-    MLT_XGMI_W(5)
-    MLT_XGMI_W(6)
-    MLT_XGMI_W(7)
-    MLT_XGMI_W(8)
-    default: break;
-  }
-#undef MLT_XGMI_W
+  const bool hit = dispatch_int<2, 3, 4, 5, 6, 7, 8>(W, [&](auto w) {
+    hipLaunchKernelGGL((xgmi_allreduce_kernel<POST, decltype(w)::value>), g, dim3(256), 0, st, grad, n, P, rank, W, cap,
+                       seqs, scale, err, timeout, post, fault);
+  });
+  if (!hit) throw_no_kernel("launch_xgmi_allreduce", "W", W);
 }
 
 void launch_xgmi_allreduce(float* grad, int64_t n, const XgmiPeers& P, int rank, int W, int64_t cap, int blocks,
@@ -323,22 +312,11 @@ template <bool POST>
 static void launch_w2(int W, dim3 g, hipStream_t st, float* grad, int64_t n, const XgmiPeers& P, int rank, int64_t S,
                       uint64_t* seqs, float scale, unsigned* err, long long timeout, const XgmiPostOpt& post,
                       int fault) {
-#define MLT_XGMI_W2(WV)                                                                                         \
-  case WV:                                                                                                      \
-    hipLaunchKernelGGL((xgmi_twoshot_kernel<POST, WV>), g, dim3(256), 0, st, grad, n, P, rank, S, seqs, scale, \
-                       err, timeout, post, fault);                                                              \
-    break;
-  switch (W) {
-    MLT_XGMI_W2(2)
-    MLT_XGMI_W2(3)
-    MLT_XGMI_W2(4)
-    MLT_XGMI_W2(5)
-    MLT_XGMI_W2(6)
-    MLT_XGMI_W2(7)
-    MLT_XGMI_W2(8)
-    default: break;
-  }
-#undef MLT_XGMI_W2
+  const bool hit = dispatch_int<2, 3, 4, 5, 6, 7, 8>(W, [&](auto w) {
+    hipLaunchKernelGGL((xgmi_twoshot_kernel<POST, decltype(w)::value>), g, dim3(256), 0, st, grad, n, P, rank, S, seqs,
+                       scale, err, timeout, post, fault);
+  });
+  if (!hit) throw_no_kernel("launch_xgmi_allreduce_2shot", "W", W);
 }
 
 void launch_xgmi_allreduce_2shot(float* grad, int64_t n, const XgmiPeers& P, int rank, int W, int64_t slot,

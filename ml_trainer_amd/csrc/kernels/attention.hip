@@ -1515,137 +1515,108 @@ static int attn_groups(const char* env, int S, int dflt = 2) {
   return S >= 128 ? dflt : 1;
 }
 
-// cu (packed mode, see packed_dcheck): cu_seqlens [B + 1] on the device; qkv / out then hold `rows`
-// (cu[B] <= rows <= B * S) token rows, S is max_seqlen and `lens` is unused. The packed instantiations keep the
-// group counts of the padded ones (forward and dQ 2 groups, dK/dV 2 groups without dropout and 1 with):
-// they are the non-FULLT kernels plus two scalar loads, and build with the same VGPR counts and no scratch.
-void launch_attn_fwd(const uint16_t* qkv, uint16_t* out, float* lse, const int* lens, int B, int S, int H,
-                     float scale, hipStream_t st, const AttnDropArgs& ad, const int* cu, int rows, bool causal) {
-  if (B <= 0 || S <= 0) return;
-  const unsigned g2 = (unsigned)((S + 127) / 128 * H * B), g1 = (unsigned)((S + 63) / 64 * H * B);
-  const bool two = attn_groups("MLT_ATTN_FWD_GROUPS", S, 2) == 2;
-  const int* sl = cu ? cu : lens;
-  auto launch = [&](auto dropc, auto packc, auto causc) {  // the dropout instantiations only when something is dropped
-    constexpr bool DR = decltype(dropc)::value, PK = decltype(packc)::value, CA = decltype(causc)::value;
-    if (two)
-      hipLaunchKernelGGL((attn_fwd_lean_kernel<2, DR, PK, CA>), dim3(g2), dim3(256), 0, st, qkv, out, lse, sl, S, H,
-                         scale, ad, rows);
-    else
-      hipLaunchKernelGGL((attn_fwd_lean_kernel<1, DR, PK, CA>), dim3(g1), dim3(256), 0, st, qkv, out, lse, sl, S, H,
-                         scale, ad, rows);
-  };
-  auto pick = [&](auto causc) {
-    if (cu) {
-      if (ad.thr8 > 0)
-        launch(std::true_type{}, std::true_type{}, causc);
-      else
-        launch(std::false_type{}, std::true_type{}, causc);
-    } else {
-      if (ad.thr8 > 0)
-        launch(std::true_type{}, std::false_type{}, causc);
-      else
-        launch(std::false_type{}, std::false_type{}, causc);
-    }
-  };
-  if (causal)
-    pick(std::true_type{});
-  else
-    pick(std::false_type{});
+// Packed mode (p.cu, see packed_dcheck): qkv / out hold p.rows (cu[B] <= rows <= B * S) token rows. The packed
+// instantiations keep the group counts of the padded ones (forward and dQ 2 groups, dK/dV 2 groups without
+// dropout and 1 with): they are the non-FULLT kernels plus two scalar loads, and build with the same VGPR
+// counts and no scratch.
+void launch_attn_fwd(const AttnProblem& p, const uint16_t* qkv, uint16_t* out, float* lse, hipStream_t st) {
+  if (p.B <= 0 || p.S <= 0) return;
+  const int* sl = p.cu ? p.cu : p.lens;
+  dispatch_bools(
+      [&](auto two, auto drop, auto packed, auto causal) {
+        constexpr int NQ = decltype(two)::value ? 2 : 1;
+        const unsigned grid = (unsigned)((p.S + 64 * NQ - 1) / (64 * NQ) * p.H * p.B);
+        hipLaunchKernelGGL(
+            (attn_fwd_lean_kernel<NQ, decltype(drop)::value, decltype(packed)::value, decltype(causal)::value>),
+            dim3(grid), dim3(256), 0, st, qkv, out, lse, sl, p.S, p.H, p.scale, p.drop, p.rows);
+      },  // the dropout instantiations only when something is dropped
+      attn_groups("MLT_ATTN_FWD_GROUPS", p.S, 2) == 2, p.drop.thr8 > 0, p.cu != nullptr, p.causal);
 }
 
-bool launch_attn_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse, float* delta,
-                     const int* lens, uint16_t* dqkv, int B, int S, int H, float scale, hipStream_t st,
-                     float* colpart_q, float* colpart_kv, int* rows_q, int* rows_kv, const AttnQ8& q8,
-                     const AttnDropArgs& ad, const int* cu, int rows, bool causal) {
+AttnBwdRoute attn_bwd_route(const AttnProblem& p, bool q8) {
+  AttnBwdRoute r{};
   // MLT_ATTN_RING: unset or 4 = the ring kernels, 0 = the register-staged kernels. Those stay in the
   // tree as the bit-for-bit oracle of the ring kernels' test; any other value is an error.
   const char* rv = getenv("MLT_ATTN_RING");
-  const bool ring = !rv || !strcmp(rv, "4");
-  if (!ring && strcmp(rv, "0"))
+  r.ring = !rv || !strcmp(rv, "4");
+  r.drop = p.drop.thr8 > 0;  // the dropout instantiations only when something is dropped
+  r.packed = p.cu != nullptr;
+  r.causal = p.causal;
+  if (!r.ring && strcmp(rv, "0"))
     throw std::runtime_error(std::string("attn_bwd: MLT_ATTN_RING=") + rv + " (accepted: unset or 4 = ring kernels, " +
                              "0 = register-staged kernels)");
-  if (cu && !ring)
+  if (r.packed && !r.ring)
     throw std::runtime_error("attn_bwd: packed sequences (cu_seqlens) need the ring kernels (MLT_ATTN_RING unset or "
                              "4); the register-staged kernels take padded batches only");
-  if (cu && q8.y)
+  if (r.packed && q8)
     throw std::runtime_error("attn_bwd: the fp8 (q8) outputs take padded batches only (their transposed 16-row runs "
                              "sit at b * S offsets), not cu_seqlens");
-  if (causal && !ring)
+  if (r.causal && !r.ring)
     throw std::runtime_error("attn_bwd: causal attention needs the ring kernels (MLT_ATTN_RING unset or 4); the "
                              "register-staged kernels have no causal mask");
-  if (causal && q8.y)
-    throw std::runtime_error("attn_bwd: the fp8 (q8) outputs have no causal instantiation");
-  if (B <= 0 || S <= 0) return false;
-  const int64_t pairs = (int64_t)B * S * H;
-  const dim3 g2((S + 127) / 128 * H * B), g1((S + 63) / 64 * H * B);
-  if (ring) {
-    const bool drop = ad.thr8 > 0;  // the dropout instantiations only when something is dropped
-    // (dK/dV under dropout: 1 key group per wave, the 2-group instantiation would spill)
-    // (packed causal dK/dV as well: its 2-group instantiation needs 24 bytes of scratch per lane)
-    const bool k2 = !drop && !(cu && causal) && attn_groups("MLT_ATTN_DKDV_GROUPS", S, 2) == 2;
-    const bool q2 = attn_groups("MLT_ATTN_DQ_GROUPS", S) == 2;
-    const int* sl = cu ? cu : lens;
-    auto launch = [&](auto fullt, auto dropc, auto packc, auto causc) {
-      constexpr bool FL = decltype(fullt)::value, DR = decltype(dropc)::value, PK = decltype(packc)::value;
-      constexpr bool CA = decltype(causc)::value;
-      if (q2)
-        hipLaunchKernelGGL((attn_bwd_dq_ring_kernel<2, FL, DR, PK, CA>), g2, dim3(256), 0, st, qkv, dout, out, lse,
-                           delta, sl, dqkv, S, H, scale, colpart_q, q8, ad, rows);
-      else
-        hipLaunchKernelGGL((attn_bwd_dq_ring_kernel<1, FL, DR, PK, CA>), g1, dim3(256), 0, st, qkv, dout, out, lse,
-                           delta, sl, dqkv, S, H, scale, colpart_q, q8, ad, rows);
-      if constexpr (!DR && !(PK && CA)) {
-        if (k2) {
-          hipLaunchKernelGGL((attn_bwd_dkdv_ring_kernel<2, FL, false, PK, CA>), g2, dim3(256), 0, st, qkv, dout, lse,
-                             delta, sl, dqkv, S, H, scale, colpart_kv, q8, ad, rows);
-          return;
-        }
-      }
-      hipLaunchKernelGGL((attn_bwd_dkdv_ring_kernel<1, FL, DR, PK, CA>), g1, dim3(256), 0, st, qkv, dout, lse, delta,
-                         sl, dqkv, S, H, scale, colpart_kv, q8, ad, rows);
-    };
-    auto pick = [&](auto causc) {
-      if (cu) {  // packed: a sequence ends anywhere, so always the clamped-row (non-FULLT) stages
-        if (drop)
-          launch(std::false_type{}, std::true_type{}, std::true_type{}, causc);
-        else
-          launch(std::false_type{}, std::false_type{}, std::true_type{}, causc);
-      } else if (S % AB == 0) {
-        if (drop)
-          launch(std::true_type{}, std::true_type{}, std::false_type{}, causc);
-        else
-          launch(std::true_type{}, std::false_type{}, std::false_type{}, causc);
-      } else {
-        if (drop)
-          launch(std::false_type{}, std::true_type{}, std::false_type{}, causc);
-        else
-          launch(std::false_type{}, std::false_type{}, std::false_type{}, causc);
-      }
-    };
-    if (causal)
-      pick(std::true_type{});
-    else
-      pick(std::false_type{});
-    // partial rows actually written: B x (row blocks of the chosen group count)
-    if (rows_kv) *rows_kv = B * ((S + (k2 ? 127 : 63)) / (k2 ? 128 : 64));
-    if (rows_q) *rows_q = B * ((S + (q2 ? 127 : 63)) / (q2 ? 128 : 64));
-    return colpart_q != nullptr && colpart_kv != nullptr;
-  }
-  if (q8.y) throw std::runtime_error("attn_bwd: the fp8 (q8) outputs need the ring kernels (MLT_ATTN_RING unset or 4)");
-  if (ad.thr8 > 0)
+  if (r.causal && q8) throw std::runtime_error("attn_bwd: the fp8 (q8) outputs have no causal instantiation");
+  if (q8 && !r.ring)
+    throw std::runtime_error("attn_bwd: the fp8 (q8) outputs need the ring kernels (MLT_ATTN_RING unset or 4)");
+  if (r.drop && !r.ring)
     throw std::runtime_error("attn_bwd: attention dropout needs the ring kernels (MLT_ATTN_RING unset or 4); the "
                              "register-staged kernels are dropout-free");
+  // packed: a sequence ends anywhere, so always the clamped-row (non-FULLT) stages
+  r.fullt = !r.packed && p.S % AB == 0;
+  // (dK/dV under dropout: 1 key group per wave, the 2-group instantiation would spill)
+  // (packed causal dK/dV as well: its 2-group instantiation needs 24 bytes of scratch per lane)
+  // (register-staged dK/dV: 1 group unless overridden, see attn_groups)
+  r.k2 = !r.drop && !(r.packed && r.causal) && attn_groups("MLT_ATTN_DKDV_GROUPS", p.S, r.ring ? 2 : 1) == 2;
+  r.q2 = attn_groups("MLT_ATTN_DQ_GROUPS", p.S) == 2;
+  r.rows_kv = p.B * ((p.S + (r.k2 ? 127 : 63)) / (r.k2 ? 128 : 64));
+  r.rows_q = p.B * ((p.S + (r.q2 ? 127 : 63)) / (r.q2 ? 128 : 64));
+  return r;
+}
+
+void launch_attn_bwd(const AttnProblem& p, const AttnBwdRoute& r, const uint16_t* qkv, const uint16_t* out,
+                     const uint16_t* dout, const float* lse, float* delta, uint16_t* dqkv, const AttnQ8& q8,
+                     float* colpart_q, float* colpart_kv, hipStream_t st) {
+  const int B = p.B, S = p.S, H = p.H;
+  if (B <= 0 || S <= 0) return;
+  const dim3 gq(r.rows_q * H), gk(r.rows_kv * H);  // one block per (row block of the group count, head, batch)
+  if (r.ring) {
+    const int* sl = p.cu ? p.cu : p.lens;
+    // left out below, as attn_bwd_route never asks for them: FULLT with PACKED, and the 2-group dK/dV
+    // kernel with DROP or with PACKED && CAUSAL (a spill, and 24 bytes of scratch per lane)
+    dispatch_bools(
+        [&](auto q2, auto fullt, auto drop, auto packed, auto causal) {
+          constexpr bool FL = decltype(fullt)::value, DR = decltype(drop)::value, PK = decltype(packed)::value;
+          constexpr bool CA = decltype(causal)::value;
+          if constexpr (!(FL && PK))
+            hipLaunchKernelGGL((attn_bwd_dq_ring_kernel<decltype(q2)::value ? 2 : 1, FL, DR, PK, CA>), gq, dim3(256), 0,
+                               st, qkv, dout, out, lse, delta, sl, dqkv, S, H, p.scale, colpart_q, q8, p.drop, p.rows);
+        },
+        r.q2, r.fullt, r.drop, r.packed, r.causal);
+    dispatch_bools(
+        [&](auto k2, auto fullt, auto drop, auto packed, auto causal) {
+          constexpr bool K2 = decltype(k2)::value, FL = decltype(fullt)::value, DR = decltype(drop)::value;
+          constexpr bool PK = decltype(packed)::value, CA = decltype(causal)::value;
+          if constexpr (!(FL && PK) && !(K2 && (DR || (PK && CA))))
+            hipLaunchKernelGGL((attn_bwd_dkdv_ring_kernel<K2 ? 2 : 1, FL, DR, PK, CA>), gk, dim3(256), 0, st, qkv, dout,
+                               lse, delta, sl, dqkv, S, H, p.scale, colpart_kv, q8, p.drop, p.rows);
+        },
+        r.k2, r.fullt, r.drop, r.packed, r.causal);
+    return;
+  }
+  const int64_t pairs = (int64_t)B * S * H;
   hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((pairs + 15) / 16)), dim3(256), 0, st, dout, out, delta,
                      (int64_t)B * S, H);
-  if (attn_groups("MLT_ATTN_DKDV_GROUPS", S, 1) == 2)
-    hipLaunchKernelGGL(attn_bwd_dkdv_kernel<2>, g2, dim3(256), 0, st, qkv, dout, lse, delta, lens, dqkv, S, H, scale);
-  else
-    hipLaunchKernelGGL(attn_bwd_dkdv_kernel<1>, g1, dim3(256), 0, st, qkv, dout, lse, delta, lens, dqkv, S, H, scale);
-  if (attn_groups("MLT_ATTN_DQ_GROUPS", S) == 2)
-    hipLaunchKernelGGL(attn_bwd_dq_kernel<2>, g2, dim3(256), 0, st, qkv, dout, lse, delta, lens, dqkv, S, H, scale);
-  else
-    hipLaunchKernelGGL(attn_bwd_dq_kernel<1>, g1, dim3(256), 0, st, qkv, dout, lse, delta, lens, dqkv, S, H, scale);
-  return false;  // register-staged kernels: no column partials (the caller reduces dQKV itself)
+  dispatch_bools(
+      [&](auto k2) {
+        hipLaunchKernelGGL(attn_bwd_dkdv_kernel<decltype(k2)::value ? 2 : 1>, gk, dim3(256), 0, st, qkv, dout, lse,
+                           delta, p.lens, dqkv, S, H, p.scale);
+      },
+      r.k2);
+  dispatch_bools(
+      [&](auto q2) {
+        hipLaunchKernelGGL(attn_bwd_dq_kernel<decltype(q2)::value ? 2 : 1>, gq, dim3(256), 0, st, qkv, dout, lse, delta,
+                           p.lens, dqkv, S, H, p.scale);
+      },
+      r.q2);
 }
 
 }  // namespace mlt

@@ -207,19 +207,12 @@ static void launch_one(const uint16_t* A, const uint16_t* B, OutT* C, int M, int
 void launch_gemm_bf16_128(int a_mn, int b_mn, bool out_f32, const uint16_t* A, const uint16_t* B, void* C, int M,
                           int N, int K, int64_t lda, int64_t ldb, int64_t ldc, const GemmEpi& e, hipStream_t st) {
   if (M <= 0 || N <= 0) return;
-#define MLT_GEMM_CASE(AMV, BNV)                                                                          \
-  if (a_mn == AMV && b_mn == BNV) {                                                                      \
-    if (out_f32)                                                                                         \
-      launch_one<AMV, BNV, float>(A, B, (float*)C, M, N, K, lda, ldb, ldc, e, st);                       \
-    else                                                                                                 \
-      launch_one<AMV, BNV, uint16_t>(A, B, (uint16_t*)C, M, N, K, lda, ldb, ldc, e, st);                 \
-    return;                                                                                              \
-  }
-  MLT_GEMM_CASE(0, 0)
-  MLT_GEMM_CASE(0, 1)
-  MLT_GEMM_CASE(1, 0)
-  MLT_GEMM_CASE(1, 1)
-#undef MLT_GEMM_CASE
+  dispatch_bools(
+      [&](auto am, auto bn, auto f32) {
+        using OutT = std::conditional_t<decltype(f32)::value, float, uint16_t>;
+        launch_one<decltype(am)::value, decltype(bn)::value, OutT>(A, B, (OutT*)C, M, N, K, lda, ldb, ldc, e, st);
+      },
+      a_mn != 0, b_mn != 0, out_f32);
 }
 
 // ---- column sums (bias gradients): out[n] (+)= sum_m X[m, n], X bf16 [M, N] ----------

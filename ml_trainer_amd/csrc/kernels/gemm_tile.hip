@@ -1050,7 +1050,7 @@ void launch_cfg(const GemmPlan& p, const uint8_t* A, const uint8_t* B, OutT* C, 
       launch_pp<AM, BNL, OutT, F8A, F8B>(p, A, B, C, M, N, K, lda, ldb, ldc, e, ws, cnt, st);
       break;
     }
-    default: break;
+    default: throw_no_kernel("launch_gemm", "plan.cfg", p.cfg);
   }
 }
 
@@ -1155,21 +1155,14 @@ void launch_gemm_bf16(const GemmPlan& plan, int a_mn, int b_mn, bool out_f32, co
   const bool ext = resolve_split(p, ws, cnt, K, 64) && p.ext;
   const uint8_t* a8 = reinterpret_cast<const uint8_t*>(A);
   const uint8_t* b8 = reinterpret_cast<const uint8_t*>(B);
-#define MLT_TILE_CASE(AMV, BNV)                                                                                  \
-  if (a_mn == AMV && b_mn == BNV) {                                                                              \
-    if (out_f32)                                                                                                 \
-      launch_cfg<AMV, BNV, float, -1, -1>(p, a8, b8, (float*)C, M, N, K, lda, ldb, ldc, e, ws, cnt, st);         \
-    else                                                                                                         \
-      launch_cfg<AMV, BNV, uint16_t, -1, -1>(p, a8, b8, (uint16_t*)C, M, N, K, lda, ldb, ldc, e, ws, cnt, st);   \
-    if (ext && out_f32) launch_split_reduce<float>(p, ws, (float*)C, M, N, ldc, e, st);                          \
-    if (ext && !out_f32) launch_split_reduce<uint16_t>(p, ws, (uint16_t*)C, M, N, ldc, e, st);                   \
-    return;                                                                                                      \
-  }
-  MLT_TILE_CASE(0, 0)
-  MLT_TILE_CASE(0, 1)
-  MLT_TILE_CASE(1, 0)
-  MLT_TILE_CASE(1, 1)
-#undef MLT_TILE_CASE
+  dispatch_bools(
+      [&](auto am, auto bn, auto f32) {
+        using OutT = std::conditional_t<decltype(f32)::value, float, uint16_t>;
+        launch_cfg<decltype(am)::value, decltype(bn)::value, OutT, -1, -1>(p, a8, b8, (OutT*)C, M, N, K, lda, ldb, ldc,
+                                                                            e, ws, cnt, st);
+        if (ext) launch_split_reduce<OutT>(p, ws, (OutT*)C, M, N, ldc, e, st);
+      },
+      a_mn != 0, b_mn != 0, out_f32);
 }
 
 void launch_gemm_f8(const GemmPlan& plan, int fmt_a, int fmt_b, bool out_f32, const uint8_t* A, const uint8_t* B,
@@ -1181,20 +1174,23 @@ void launch_gemm_f8(const GemmPlan& plan, int fmt_a, int fmt_b, bool out_f32, co
   GemmEpi e{bias, aux, res, ldaux, ldres, alpha, mode, accumulate, inv_scale_a, inv_scale_b};
   GemmPlan p = plan;
   const bool ext = resolve_split(p, ws, cnt, K, 128) && p.ext;
-#define MLT_F8_CASE(FA, FB)                                                                                      \
-  if (fmt_a == FA && fmt_b == FB) {                                                                              \
-    if (out_f32)                                                                                                 \
-      launch_cfg<false, false, float, FA, FB>(p, A, B, (float*)C, M, N, K, lda, ldb, ldc, e, ws, cnt, st);       \
-    else                                                                                                         \
-      launch_cfg<false, false, uint16_t, FA, FB>(p, A, B, (uint16_t*)C, M, N, K, lda, ldb, ldc, e, ws, cnt, st); \
-    if (ext && out_f32) launch_split_reduce<float>(p, ws, (float*)C, M, N, ldc, e, st);                          \
-    if (ext && !out_f32) launch_split_reduce<uint16_t>(p, ws, (uint16_t*)C, M, N, ldc, e, st);                   \
-    return;                                                                                                      \
-  }
-  MLT_F8_CASE(0, 0)
-  MLT_F8_CASE(1, 0)
-  MLT_F8_CASE(0, 1)
-#undef MLT_F8_CASE
+  bool hit = false;
+  dispatch_int<0, 1>(fmt_a, [&](auto fa) {
+    dispatch_int<0, 1>(fmt_b, [&](auto fb) {
+      constexpr int FA = decltype(fa)::value, FB = decltype(fb)::value;
+      if constexpr (!(FA == 1 && FB == 1)) {  // e5m2 x e5m2 has no kernel
+        hit = true;
+        dispatch_bools(
+            [&](auto f32) {
+              using OutT = std::conditional_t<decltype(f32)::value, float, uint16_t>;
+              launch_cfg<false, false, OutT, FA, FB>(p, A, B, (OutT*)C, M, N, K, lda, ldb, ldc, e, ws, cnt, st);
+              if (ext) launch_split_reduce<OutT>(p, ws, (OutT*)C, M, N, ldc, e, st);
+            },
+            out_f32);
+      }
+    });
+  });
+  if (!hit) throw_no_kernel("launch_gemm_f8", "fp8 formats (10 * fmt_a + fmt_b)", 10 * fmt_a + fmt_b);
 }
 
 void launch_gemm_f8_q(int fmt_a, int fmt_b, const uint8_t* A, const uint8_t* B, uint8_t* Y, uint8_t* Yt, int M, int N,
@@ -1202,6 +1198,7 @@ void launch_gemm_f8_q(int fmt_a, int fmt_b, const uint8_t* A, const uint8_t* B, 
                       const float* inv_scale_b, const float* bias, const uint16_t* aux, int64_t ldaux, int mode,
                       int out_fmt, const float* out_scale, float* out_amax, float* colpart, hipStream_t st) {
   if (M <= 0 || N <= 0) return;  // the host binding checks M % 256, N % 256, K % 128
+  if (fmt_b != 0) throw_no_kernel("launch_gemm_f8_q", "fmt_b", fmt_b);  // the quantising epilogues take an e4m3 B only
   GemmEpi e{bias, aux, nullptr, ldaux, 0, 1.f, mode, 0, inv_scale_a, inv_scale_b};
   e.qt = Yt;
   e.ldqt = ldyt;
@@ -1221,10 +1218,10 @@ void launch_gemm_f8_q(int fmt_a, int fmt_b, const uint8_t* A, const uint8_t* B, 
   // in the fp8 `large` step GELU at 2 lost (1,254 vs 1,263 samples/s) -- profiles/r5/fp8_q8_w4_group_m.jsonl
   if (g_w4q8 != 0 && launch_gemm_w4_f8_q(fmt_a, A, B, Y, M, N, K, lda, ldb, ldy, e, gemm_group_m(), st)) return;
   GemmPlan p{5, 1, K / 128, 0, 0};
-  if (fmt_a == 0 && fmt_b == 0)
-    launch_pp<false, false, uint8_t, 0, 0>(p, A, B, Y, M, N, K, lda, ldb, ldy, e, nullptr, nullptr, st);
-  else if (fmt_a == 1 && fmt_b == 0)
-    launch_pp<false, false, uint8_t, 1, 0>(p, A, B, Y, M, N, K, lda, ldb, ldy, e, nullptr, nullptr, st);
+  const bool hit = dispatch_int<0, 1>(fmt_a, [&](auto fa) {
+    launch_pp<false, false, uint8_t, decltype(fa)::value, 0>(p, A, B, Y, M, N, K, lda, ldb, ldy, e, nullptr, nullptr, st);
+  });
+  if (!hit) throw_no_kernel("launch_gemm_f8_q", "fmt_a", fmt_a);
 }
 
 }  // namespace mlt

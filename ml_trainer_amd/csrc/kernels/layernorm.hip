@@ -300,19 +300,19 @@ void launch_reduce_rows(const float* part, int R, int64_t ld, int W, int seg, Se
   hipLaunchKernelGGL(reduce_rows_kernel, dim3((W / 4 + 3) / 4), dim3(256), 0, st, part, R, ld, W, seg, outs, accmask);
 }
 
-static int ln_vpl(int D) { return D / 256; }
+// the row kernels are instantiated for 1..4 float4 per lane: D = 256, 512, 768 or 1024
+template <class F>
+static void by_vpl(const char* launcher, int D, F&& f) {
+  if (D % 256 != 0 || !dispatch_int<1, 2, 3, 4>(D / 256, f)) throw_no_kernel(launcher, "D", D);
+}
 
 void launch_ln_fwd(const uint16_t* X, const float* gamma, const float* beta, uint16_t* Y, float* mean, float* rstd,
                    int64_t rows, int D, float eps, hipStream_t st) {
   if (rows <= 0) return;
   const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
-  switch (ln_vpl(D)) {
-    case 1: hipLaunchKernelGGL(ln_fwd_kernel<1>, grid, block, 0, st, X, gamma, beta, Y, mean, rstd, rows, eps); break;
-    case 2: hipLaunchKernelGGL(ln_fwd_kernel<2>, grid, block, 0, st, X, gamma, beta, Y, mean, rstd, rows, eps); break;
-    case 3: hipLaunchKernelGGL(ln_fwd_kernel<3>, grid, block, 0, st, X, gamma, beta, Y, mean, rstd, rows, eps); break;
-    case 4: hipLaunchKernelGGL(ln_fwd_kernel<4>, grid, block, 0, st, X, gamma, beta, Y, mean, rstd, rows, eps); break;
-    default: break;
-  }
+  by_vpl("launch_ln_fwd", D, [&](auto v) {
+    hipLaunchKernelGGL(ln_fwd_kernel<v()>, grid, block, 0, st, X, gamma, beta, Y, mean, rstd, rows, eps);
+  });
 }
 
 void launch_dropout_add_ln_fwd(const uint16_t* Y0, const uint16_t* RES, const float* gamma, const float* beta,
@@ -320,17 +320,10 @@ void launch_dropout_add_ln_fwd(const uint16_t* Y0, const uint16_t* RES, const fl
                                DropArgs dr, hipStream_t st) {
   if (rows <= 0) return;
   const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
-#define MLT_DROP_LN_FWD(V)                                                                                         \
-  hipLaunchKernelGGL(dropout_add_ln_fwd_kernel<V>, grid, block, 0, st, Y0, RES, gamma, beta, Z, Y, mean, rstd, rows, \
-                     eps, dr)
-  switch (ln_vpl(D)) {
-    case 1: MLT_DROP_LN_FWD(1); break;
-    case 2: MLT_DROP_LN_FWD(2); break;
-    case 3: MLT_DROP_LN_FWD(3); break;
-    case 4: MLT_DROP_LN_FWD(4); break;
-    default: break;
-  }
-#undef MLT_DROP_LN_FWD
+  by_vpl("launch_dropout_add_ln_fwd", D, [&](auto v) {
+    hipLaunchKernelGGL(dropout_add_ln_fwd_kernel<v()>, grid, block, 0, st, Y0, RES, gamma, beta, Z, Y, mean, rstd,
+                       rows, eps, dr);
+  });
 }
 
 int ln_bwd_partial_blocks(int64_t rows) {
@@ -344,19 +337,15 @@ void launch_ln_bwd(const uint16_t* DY, const uint16_t* X, const float* gamma, co
   if (rows <= 0) return;
   const int nb = ln_bwd_partial_blocks(rows);
   const dim3 grid(nb), block(256);
-#define MLT_LN_BWD(V)                                                                                              \
-  if (dxsum)                                                                                                       \
-    hipLaunchKernelGGL((ln_bwd_kernel<V, true>), grid, block, 0, st, DY, X, gamma, mean, rstd, DX, part, rows, DRES); \
-  else                                                                                                             \
-    hipLaunchKernelGGL((ln_bwd_kernel<V, false>), grid, block, 0, st, DY, X, gamma, mean, rstd, DX, part, rows, DRES);
-  switch (ln_vpl(D)) {
-    case 1: MLT_LN_BWD(1) break;
-    case 2: MLT_LN_BWD(2) break;
-    case 3: MLT_LN_BWD(3) break;
-    case 4: MLT_LN_BWD(4) break;
-    default: return;
-  }
-#undef MLT_LN_BWD
+  by_vpl("launch_ln_bwd", D, [&](auto v) {
+    constexpr int V = decltype(v)::value;
+    dispatch_bools(
+        [&](auto sum) {
+          hipLaunchKernelGGL((ln_bwd_kernel<V, decltype(sum)::value>), grid, block, 0, st, DY, X, gamma, mean, rstd, DX,
+                             part, rows, DRES);
+        },
+        dxsum != nullptr);
+  });
   SegOut o{{dgamma, dbeta, dxsum}};
   launch_reduce_rows(part, nb, (dxsum ? 3 : 2) * D, (dxsum ? 3 : 2) * D, D, o, (accumulate ? 3 : 0) | (dxsum_acc ? 4 : 0), st);
 }
@@ -371,17 +360,10 @@ void launch_ln_bwd_dropout(const uint16_t* DY, const uint16_t* X, const float* g
   const dim3 grid(nb), block(256);
   const LnBwdDrop d{DXM, dr};
   const uint16_t* no_res = nullptr;
-#define MLT_LN_BWD(V)                                                                                             \
-  hipLaunchKernelGGL((ln_bwd_kernel<V, true, true, LnBwdDrop>), grid, block, 0, st, DY, X, gamma, mean, rstd, DX, \
-                     part, rows, no_res, d);
-  switch (ln_vpl(D)) {
-    case 1: MLT_LN_BWD(1) break;
-    case 2: MLT_LN_BWD(2) break;
-    case 3: MLT_LN_BWD(3) break;
-    case 4: MLT_LN_BWD(4) break;
-    default: return;
-  }
-#undef MLT_LN_BWD
+  by_vpl("launch_ln_bwd_dropout", D, [&](auto v) {
+    hipLaunchKernelGGL((ln_bwd_kernel<v(), true, true, LnBwdDrop>), grid, block, 0, st, DY, X, gamma, mean, rstd, DX,
+                       part, rows, no_res, d);
+  });
   SegOut o{{dgamma, dbeta, dxsum}};
   launch_reduce_rows(part, nb, 3 * D, 3 * D, D, o, (accumulate ? 3 : 0) | (dxsum_acc ? 4 : 0), st);
 }
@@ -524,13 +506,9 @@ void launch_embed_fwd(const int64_t* ids, const int64_t* tt, const uint16_t* Ww,
                       hipStream_t st, const int* pos) {
   if (rows <= 0) return;
   const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
-  switch (D / 256) {
-    case 3: hipLaunchKernelGGL(embed_fwd_kernel<3>, grid, block, 0, st, ids, tt, Ww, Wp, Wt, out, rows, S, vocab, ntype, pos); break;
-    case 4: hipLaunchKernelGGL(embed_fwd_kernel<4>, grid, block, 0, st, ids, tt, Ww, Wp, Wt, out, rows, S, vocab, ntype, pos); break;
-    case 1: hipLaunchKernelGGL(embed_fwd_kernel<1>, grid, block, 0, st, ids, tt, Ww, Wp, Wt, out, rows, S, vocab, ntype, pos); break;
-    case 2: hipLaunchKernelGGL(embed_fwd_kernel<2>, grid, block, 0, st, ids, tt, Ww, Wp, Wt, out, rows, S, vocab, ntype, pos); break;
-    default: break;
-  }
+  by_vpl("launch_embed_fwd", D, [&](auto v) {
+    hipLaunchKernelGGL(embed_fwd_kernel<v()>, grid, block, 0, st, ids, tt, Ww, Wp, Wt, out, rows, S, vocab, ntype, pos);
+  });
 }
 
 void launch_embed_bwd(const int64_t* sid, const int64_t* perm, const int64_t* tt, const uint16_t* DX, float* gw,
@@ -539,20 +517,16 @@ void launch_embed_bwd(const int64_t* sid, const int64_t* perm, const int64_t* tt
   if (rows <= 0) return;
   const dim3 gw_grid((unsigned)((rows + 3) / 4)), gp_grid((unsigned)((S + 3) / 4)), block(256);
   const int64_t* tt2 = ntype >= 2 ? tt : nullptr;
-#define MLT_EMB_BWD(V)                                                                                          \
-  hipLaunchKernelGGL(embed_bwd_word_kernel<V>, gw_grid, block, 0, st, sid, perm, DX, gw, rows, vocab);         \
-  if (cu)                                                                                                       \
-    hipLaunchKernelGGL((embed_bwd_pos_kernel<V, true>), gp_grid, block, 0, st, tt2, DX, gp, part, rows, S, cu, B); \
-  else                                                                                                           \
-    hipLaunchKernelGGL((embed_bwd_pos_kernel<V, false>), gp_grid, block, 0, st, tt2, DX, gp, part, rows, S, cu, B);
-  switch (D / 256) {
-    case 1: MLT_EMB_BWD(1) break;
-    case 2: MLT_EMB_BWD(2) break;
-    case 3: MLT_EMB_BWD(3) break;
-    case 4: MLT_EMB_BWD(4) break;
-    default: return;
-  }
-#undef MLT_EMB_BWD
+  by_vpl("launch_embed_bwd", D, [&](auto v) {
+    constexpr int V = decltype(v)::value;
+    hipLaunchKernelGGL(embed_bwd_word_kernel<V>, gw_grid, block, 0, st, sid, perm, DX, gw, rows, vocab);
+    dispatch_bools(
+        [&](auto packed) {
+          hipLaunchKernelGGL((embed_bwd_pos_kernel<V, decltype(packed)::value>), gp_grid, block, 0, st, tt2, DX, gp,
+                             part, rows, S, cu, B);
+        },
+        cu != nullptr);
+  });
   // token types 0 and 1 (ntype <= 2): the S partial rows summed in position order into gt. A one-row
   // type table takes every token as type 0, as the forward's clamp reads it (tt is not passed on: with
   // it the type-1 tokens' gradient went to the partial that is not summed, and was lost).
