@@ -1,0 +1,147 @@
+"""Cached generation against the uncached baseline: ``BertLMHeadModel.prefill`` + ``decode_step`` (key/value
+cache, the ``attn_decode`` kernel) against the native full causal forward of the growing sequence, once per token.
+
+    python benchmarks/generate_bench.py                                   # bert-base, batch 1,8,64, 128 + 128
+    python benchmarks/generate_bench.py --batch 64 --out profiles/generate/generate_bench.jsonl
+    python benchmarks/generate_bench.py --kernel --batch 64 --pos 255     # attn_decode alone: microseconds, bytes/s
+    rocprofv3 --kernel-trace --stats --output-format csv -d out -o decode -- \\
+        python benchmarks/generate_bench.py --batch 8 --trace-steps 32    # per-kernel share of a decode step
+
+Per batch one JSON line: prefill ms, ms per token over the decode steps (cached), ms per token of the uncached
+baseline, tokens/s. The two are alternated ``--repeats`` times in the same process and reported as medians. The
+loops feed greedy tokens and never read from the device; one synchronisation closes each timed region.
+``--trace-steps N`` runs one prefill and N decode steps and nothing else (the workload of the profiler run).
+``--kernel`` times ``C.attn_decode`` alone on a cache of ``--pos`` tokens per sequence, rotating over enough
+caches to exceed the 256 MiB last-level cache, and reports the bytes of K and V it streams per second.
+Random weights and prompts (no network)."""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+
+def _sync_ms(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3
+
+
+def bench_model(args, dev):
+    from ml_trainer_amd.models.bert import BertLMHeadModel, bert_config
+    torch.manual_seed(0)
+    m = BertLMHeadModel(bert_config(args.model)).to(dev).eval()
+    V, P, N = m.config.vocab_size, args.prompt, args.new
+    recs = []
+    for B in [int(b) for b in args.batch.split(",")]:
+        ids = torch.randint(5, V, (B, P), device=dev)
+        state = {}
+
+        def prefill():
+            state["s"] = m.prefill(ids, max_len=P + N)
+            state["tok"] = m.decode_step(state["s"]).argmax(-1)
+
+        def decode():
+            tok = state["tok"]
+            for _ in range(N - 1):
+                tok = m.decode_step(state["s"], tok).argmax(-1)
+
+        def uncached():
+            with torch.no_grad():
+                seq = torch.cat((ids, torch.zeros(B, N, dtype=ids.dtype, device=dev)), 1)
+                rows = torch.arange(B, device=dev)
+                for t in range(N - 1):
+                    W = P + t + 1
+                    seq[:, W - 1] = state["tok"] if t == 0 else tok
+                    hidden = m(seq[:, :W].contiguous())
+                    tok = m.mlm_logits(hidden, rows * W + W - 1).argmax(-1)
+
+        if args.trace_steps:
+            prefill()
+            tok = state["tok"]
+            for _ in range(args.trace_steps):
+                tok = m.decode_step(state["s"], tok).argmax(-1)
+            torch.cuda.synchronize()
+            continue
+        prefill(), decode()  # warm-up: kernel loading, the padded decoder table
+        t_pre, t_dec, t_unc = [], [], []
+        for _ in range(args.repeats):
+            t_pre.append(_sync_ms(prefill))
+            t_dec.append(_sync_ms(decode) / (N - 1))
+            if not args.no_uncached:
+                t_unc.append(_sync_ms(uncached) / (N - 1))
+        ms = statistics.median(t_dec)
+        rec = {"bench": "generate", "model": args.model, "batch": B, "prompt": P, "new": N,
+               "prefill_ms": statistics.median(t_pre), "cached_ms_per_token": ms, "cached_tokens_per_s": B / ms * 1e3,
+               "uncached_ms_per_token": statistics.median(t_unc) if t_unc else None,
+               "cached_runs": t_dec, "uncached_runs": t_unc}
+        print(json.dumps(rec), flush=True)
+        recs.append(rec)
+    return recs
+
+
+def bench_kernel(args, dev):
+    from ml_trainer_amd.ops._ext import require_native
+    C = require_native()
+    H, Smax = args.heads, args.smax
+    recs = []
+    for B in [int(b) for b in args.batch.split(",")]:
+        D = H * 64
+        per = 2 * B * H * Smax * 64 * 2  # bytes of one cache
+        ncache = max(2, -(-(512 << 20) // per))  # rotate over >= 512 MiB so no launch finds its cache in the LLC
+        caches = [torch.randn(2, B, H, Smax, 64, device=dev).to(torch.bfloat16) for _ in range(ncache)]
+        qkv = (torch.randn(B, 3 * D, device=dev) * 0.5).to(torch.bfloat16)
+        pos = torch.full((B,), args.pos, dtype=torch.int32, device=dev)
+        out = torch.empty(B, D, dtype=torch.bfloat16, device=dev)
+        reps = 4 * ncache
+
+        def run():
+            for i in range(reps):
+                C.attn_decode(qkv, caches[i % ncache], pos, out, H, 0.125)
+
+        run()
+        us = statistics.median(_sync_ms(run) / reps * 1e3 for _ in range(args.repeats))
+        streamed = 2 * B * H * args.pos * 64 * 2  # the K and V rows below pos
+        rec = {"bench": "attn_decode", "batch": B, "heads": H, "smax": Smax, "pos": args.pos, "caches": ncache,
+               "us": us, "kv_bytes": streamed, "tb_per_s": streamed / us * 1e-6}
+        print(json.dumps(rec), flush=True)
+        recs.append(rec)
+    return recs
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--model", default="bert-base")
+    ap.add_argument("--batch", default="1,8,64")
+    ap.add_argument("--prompt", type=int, default=128)
+    ap.add_argument("--new", type=int, default=128)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--no-uncached", action="store_true")
+    ap.add_argument("--trace-steps", type=int, default=0)
+    ap.add_argument("--kernel", action="store_true", help="time C.attn_decode alone")
+    ap.add_argument("--heads", type=int, default=12)
+    ap.add_argument("--smax", type=int, default=256)
+    ap.add_argument("--pos", type=int, default=255)
+    ap.add_argument("--out", default="")
+    args = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    recs = bench_kernel(args, dev) if args.kernel else bench_model(args, dev)
+    if args.out and recs:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "a") as f:
+            for rec in recs:
+                f.write(json.dumps(rec) + "\n")
+
+
+if __name__ == "__main__":
+    main()

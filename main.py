@@ -23,7 +23,10 @@ tokens before the embeddings and run the encoder on the real tokens only), ``--m
 (BERT masked-LM pre-training on synthetic masked text: criterion ``mlm``, ``--metric accuracy`` is the
 masked-token accuracy; ``--mask_prob``, ``--max_predictions``), ``--task clm`` (BERT run as a causal
 language model on synthetic next-token text: causal flash attention, criterion ``clm``, ``--metric accuracy``
-is the next-token accuracy).
+is the next-token accuracy), ``--generate N`` (``--task clm``: after training, rank 0 continues up to 8
+validation rows from their first ``--prompt_len`` tokens by N tokens with the key/value cache, logs a
+``generate`` record with the ``continuation_accuracy`` and writes ``model_dir/generated.json``;
+``--temperature`` / ``--top_k`` sample instead of the greedy argmax).
 """
 from __future__ import annotations
 
@@ -86,6 +89,12 @@ def build_model_and_datasets(args):
         raise ValueError(f"--task {args.task} applies to the BERT models; the LeNet models classify images")
     if not mlm and (args.mask_prob is not None or args.max_predictions is not None):
         raise ValueError("--mask_prob / --max_predictions apply to --task mlm (BERT models)")
+    if args.generate and not clm:
+        raise ValueError("--generate applies to --task clm (the causal language model)")
+    if not args.generate and (args.temperature is not None or args.top_k is not None):
+        raise ValueError("--temperature / --top_k apply to --generate")
+    if args.generate and (args.generate < 0 or args.prompt_len < 1):
+        raise ValueError("--generate and --prompt_len must be positive")
     over = {"hidden_dropout": args.dropout} if args.dropout else {}
     if args.attention_dropout:
         over["attention_dropout"] = args.attention_dropout
@@ -103,6 +112,9 @@ def build_model_and_datasets(args):
         from ml_trainer_amd.data.text import SyntheticTextClassification
         c = model.config
         seq = min(args.seq_len, c.max_position)
+        if args.generate and args.prompt_len + args.generate > seq:
+            raise ValueError(f"--prompt_len + --generate = {args.prompt_len + args.generate} exceeds the sequence "
+                             f"length {seq}")
         n = args.synthetic_size or 4096
         var = {} if args.min_seq_len is None else {"min_len": min(args.min_seq_len, seq), "pad_id": pad_id}
         if clm:
@@ -152,7 +164,38 @@ def main(args):
     trainer = Trainer(model, datasets=datasets, epochs=args.epochs, batch_size=args.batch_size,
                       is_parallel=not args.no_parallel, save_history=True, options=options, **config)
     trainer.fit()
+    if args.generate and trainer.rank == 0:
+        generate_after_fit(args, trainer, datasets[1])
     return trainer
+
+
+def generate_after_fit(args, trainer, val_set, rows: int = 8):
+    """Rank 0 only, no collective: prompt with the first min(--prompt_len, len_b) tokens of up to ``rows``
+    validation rows, generate --generate tokens, log a ``generate`` record and write model_dir/generated.json.
+    ``continuation_accuracy``: the share of generated tokens equal to the row's own next tokens, where it has them."""
+    import torch
+    model = trainer.model
+    while not hasattr(model, "generate") and hasattr(model, "module"):
+        model = model.module  # the data-parallel wrapper
+    n = min(rows, len(val_set))
+    ids, lengths = val_set.ids[:n], val_set.lengths[:n]
+    P, N = args.prompt_len, args.generate
+    plens = lengths.clamp(max=P)
+    mask = (torch.arange(P)[None, :] < plens[:, None]).long()
+    dev = trainer.device
+    tokens, _ = model.generate(ids[:, :P].to(dev), N, attention_mask=mask.to(dev),
+                               temperature=args.temperature or 0.0, top_k=args.top_k, seed=args.seed)
+    tokens = tokens.cpu()
+    at = plens[:, None] + torch.arange(N)[None, :]  # where the continuation sits in the row
+    has = at < lengths[:, None]
+    want = ids.gather(1, at.clamp(max=ids.shape[1] - 1))
+    hits, total = int(((tokens == want) & has).sum()), int(has.sum())
+    acc = hits / total if total else 0.0
+    logger.info("generate", rows=n, prompt_len=P, new_tokens=N, continuation_accuracy=acc, compared=total)
+    os.makedirs(args.model_dir, exist_ok=True)
+    with open(os.path.join(args.model_dir, "generated.json"), "w") as f:
+        json.dump({"prompts": [ids[b, :int(plens[b])].tolist() for b in range(n)], "tokens": tokens.tolist(),
+                   "continuation_accuracy": acc, "compared": total}, f)
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -214,6 +257,15 @@ def build_parser() -> argparse.ArgumentParser:
                         help="--task mlm: share of each row's real tokens chosen as targets (default: 0.15)")
     parser.add_argument("--max_predictions", type=int, default=None,
                         help="--task mlm: target slots per sequence (default: ceil(0.15 * seq_len) rounded up to 8)")
+    parser.add_argument("--generate", type=int, default=0,
+                        help="--task clm: after training, generate this many tokens for up to 8 validation rows "
+                             "(default: 0, off)")
+    parser.add_argument("--prompt_len", type=int, default=8,
+                        help="--generate: tokens of each row used as the prompt (default: 8)")
+    parser.add_argument("--temperature", type=float, default=None,
+                        help="--generate: sample from softmax(logits / temperature) (default: greedy argmax)")
+    parser.add_argument("--top_k", type=int, default=None,
+                        help="--generate with --temperature: restrict the draw to the k largest logits")
     parser.add_argument("--synthetic", action="store_true", help="use the seeded synthetic dataset")
     parser.add_argument("--synthetic_size", type=int, default=0)
     parser.add_argument("--seq_len", type=int, default=512)

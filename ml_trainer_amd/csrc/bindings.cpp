@@ -1035,6 +1035,32 @@ void attn_fwd(Tensor qkv, Tensor out, Tensor lse, c10::optional<Tensor> lens, in
   launch_attn_fwd(prob, bf16_ptr(qkv), (uint16_t*)out.data_ptr(), lse.data_ptr<float>(), cur_stream());
 }
 
+// Single-token attention over one layer's cache kv [2, B, H, Smax, 64], the append of the new token fused in
+// (attn_decode.hip). qkv_new [B, 3 * H * 64] may be a row-strided view. pos int32 [B] stays on the device:
+// pos[b] < Smax cannot be checked here without a read (debug builds check it in the kernel, MLT_DCHECK).
+void attn_decode(Tensor qkv_new, Tensor kv, Tensor pos, Tensor out, int64_t H, double scale) {
+  TORCH_CHECK(qkv_new.is_cuda() && qkv_new.dim() == 2 && qkv_new.scalar_type() == at::kBFloat16,
+              "attn_decode: qkv_new must be a bf16 [B, 3 * H * 64] device tensor");
+  const int64_t B = qkv_new.size(0), D = H * 64;
+  TORCH_CHECK(B > 0 && H > 0 && B <= 65535 && H <= 65535, "attention dims");
+  TORCH_CHECK(qkv_new.size(1) == 3 * D, "attn_decode: qkv_new has ", qkv_new.size(1), " columns, expected 3 * H * 64 = ",
+              3 * D);
+  TORCH_CHECK(qkv_new.stride(1) == 1 && qkv_new.stride(0) >= 3 * D && qkv_new.stride(0) % 8 == 0,
+              "attn_decode: qkv_new needs unit column stride and a row stride that is a multiple of 8");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(qkv_new.data_ptr()) % 16 == 0, "qkv_new must be 16-byte aligned");
+  check_dev(kv, "kv", at::kBFloat16, 0);
+  TORCH_CHECK(kv.dim() == 5 && kv.size(0) == 2 && kv.size(1) == B && kv.size(2) == H && kv.size(3) >= 1 &&
+                  kv.size(4) == 64,
+              "attn_decode: kv must be [2, B, H, Smax, 64] = [2, ", B, ", ", H, ", Smax, 64]");
+  const int64_t Smax = kv.size(3);
+  TORCH_CHECK(kv.numel() == 2 * B * H * Smax * 64 && Smax <= 0x7fffffff, "attn_decode: kv size");
+  check_dev(pos, "pos", at::kInt, B, 4);
+  TORCH_CHECK(pos.numel() == B, "attn_decode: pos must have one entry per sequence");
+  check_bf16_2d(out, "out", B, D);
+  launch_attn_decode(bf16_ptr(qkv_new), qkv_new.stride(0), (uint16_t*)kv.data_ptr(), pos.data_ptr<int>(),
+                     (uint16_t*)out.data_ptr(), (int)B, (int)H, (int)Smax, (float)scale, cur_stream());
+}
+
 void attn_bwd(Tensor qkv, Tensor out, Tensor dout, Tensor lse, Tensor delta, c10::optional<Tensor> lens, Tensor dqkv,
               int64_t B, int64_t S, int64_t H, double scale, c10::optional<Tensor> colsum_out,
               bool colsum_accumulate, c10::optional<Tensor> q8_y, c10::optional<Tensor> q8_yt,
@@ -1745,6 +1771,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_fwd", &attn_fwd, py::arg("qkv"), py::arg("out"), py::arg("lse"), py::arg("lens"), py::arg("B"),
         py::arg("S"), py::arg("H"), py::arg("scale"), py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("site") = 0,
         py::arg("rank") = 0, py::arg("cu_seqlens") = py::none(), py::arg("causal") = false);
+  m.def("attn_decode", &attn_decode, py::arg("qkv_new"), py::arg("kv"), py::arg("pos"), py::arg("out"), py::arg("H"),
+        py::arg("scale"));
   m.def("attn_bwd", &attn_bwd, py::arg("qkv"), py::arg("out"), py::arg("dout"), py::arg("lse"), py::arg("delta"),
         py::arg("lens"), py::arg("dqkv"), py::arg("B"), py::arg("S"), py::arg("H"), py::arg("scale"),
         py::arg("colsum_out") = py::none(), py::arg("colsum_accumulate") = false, py::arg("q8_y") = py::none(),

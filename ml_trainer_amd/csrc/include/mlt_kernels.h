@@ -383,6 +383,12 @@ AttnBwdRoute attn_bwd_route(const AttnProblem& p, bool q8);
 void launch_attn_bwd(const AttnProblem& p, const AttnBwdRoute& r, const uint16_t* qkv, const uint16_t* out,
                      const uint16_t* dout, const float* lse, float* delta, uint16_t* dqkv, const AttnQ8& q8,
                      float* colpart_q, float* colpart_kv, hipStream_t st);
+// Single-token attention over a key/value cache, append fused in (attn_decode.hip). qkv_new [B][ldq >= 3 * 64 H]
+// (q | k | v of the B new tokens, ldq % 8 == 0, 16-byte aligned), kv [2][B][H][Smax][64] (keys, values), pos
+// int32 [B] on the device (0 <= pos[b] < Smax: the row the new token takes = the tokens already cached),
+// out [B][64 H]. Rows pos[b] of the cache are written, rows above are never read.
+void launch_attn_decode(const uint16_t* qkv_new, int64_t ldq, uint16_t* kv, const int* pos, uint16_t* out, int B,
+                        int H, int Smax, float scale, hipStream_t st);
 
 // ----------------------------------------------------------------------------
 // Masked-LM head (mlm.hip)

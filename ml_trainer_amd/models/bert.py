@@ -61,6 +61,17 @@ instantiations skip the key blocks above the diagonal; no S x S mask exists anyw
 hidden dropout, attention dropout and ``unpad``; with ``fp8`` it is rejected. ``BertLMHeadModel`` is the
 encoder run as a next-token decoder (post-LN, learned positions, tied word table: GPT-1's block) under
 the MLM prediction head with one slot per position.
+
+Incremental decoding (``BertLMHeadModel`` only; the bidirectional models have no use for a key/value cache):
+``prefill(input_ids, attention_mask)`` runs the padded causal forward once, keeps every layer's K / V in a
+head-major cache (``ops.decode.KVCache``: ``[2, B, H, Smax, 64]`` per layer) and returns a ``DecodeState``;
+``decode_step(state, token_ids)`` runs one token per sequence through the stack (per layer QKV GEMM, the
+``attn_decode`` kernel over the cache with the append fused in, out-projection + residual, LayerNorm, FFN,
+LayerNorm) and returns fp32 logits; ``generate`` loops it with greedy, temperature / top-k sampling and an EOS
+mask. The position of every sequence lives on the device (ragged prompts continue at their own length) and no
+step reads anything back. On the CPU the same runs in fp32 torch with an fp32 cache;
+``generate_reference`` / ``decode_logits_reference`` are the uncached oracle. Not built: pre-LN blocks,
+hipGraph-captured decode, a weight-streaming decode GEMM, paged caches, beam search.
 """
 from __future__ import annotations
 
@@ -602,3 +613,197 @@ class BertLMHeadModel(BertForMaskedLM):
 
     def lm_loss_reference(self, hidden, labels):
         return self.mlm_loss_reference(hidden, labels)
+
+    # ------------------------------------------------------------------ incremental decoding (ops/decode.py)
+    def _last_rows(self, lens, B, S, device):
+        """Flat row b * S + len_b - 1 of every sequence's last real token (S - 1 without lengths)."""
+        last = (lens.to(device).long() - 1) if lens is not None else torch.full((B,), S - 1, device=device)
+        return torch.arange(B, device=device) * S + last
+
+    @torch.no_grad()
+    def prefill(self, input_ids, attention_mask=None, max_len: Optional[int] = None):
+        """Run the prompt ``input_ids`` [B, S] (right-padded; lengths from ``attention_mask`` or ``pad_id``)
+        through the padded causal forward, layer by layer, keep every layer's K / V in a cache of ``max_len``
+        rows per sequence (default ``config.max_position``) and return the ``DecodeState``: the cache with
+        ``pos = lens`` and the hidden row of each sequence's last real token. No gradients and no dropout,
+        whatever mode the model is in; ``config.unpad`` has no effect (prompts are short)."""
+        from ml_trainer_amd.ops import decode as DC
+        c = self.config
+        B, S = input_ids.shape
+        Smax = c.max_position if max_len is None else int(max_len)
+        if not S <= Smax <= c.max_position:
+            raise ValueError(f"prefill: prompt width {S} <= max_len {Smax} <= max_position {c.max_position} "
+                             f"does not hold")
+        dev = input_ids.device
+        lens = self._lengths(input_ids, attention_mask)
+        cache = DC.KVCache.allocate(c.layers, B, c.heads, Smax, dev)
+        if input_ids.is_cuda:
+            from ml_trainer_amd.ops import transformer as T
+            x = T.embeddings(input_ids, None, self.word_embeddings.weight, self.position_embeddings.weight,
+                             self.token_type_embeddings.weight, S)
+            x, _ = T._ln_fwd(x, self.emb_ln.weight, self.emb_ln.bias, c.ln_eps)
+            for l, L in enumerate(self.layers):
+                a, (_, qkv, _, _) = T._attn_fwd(x, L.qkv.weight, L.qkv.bias, L.out.weight, L.out.bias, lens, B, S,
+                                                c.heads, causal=True)
+                DC.fill_from_prefill(cache, l, qkv, lens, B, S)
+                x, _ = T._ln_fwd(a, L.ln1.weight, L.ln1.bias, c.ln_eps)
+                f, _ = T._ffn_fwd(x, L.ffn1.weight, L.ffn1.bias, L.ffn2.weight, L.ffn2.bias)
+                x, _ = T._ln_fwd(f, L.ln2.weight, L.ln2.bias, c.ln_eps)
+        else:
+            pos = torch.arange(S, device=dev)
+            x = (self.word_embeddings(input_ids) + self.position_embeddings(pos)[None] +
+                 self.token_type_embeddings(torch.zeros_like(input_ids)))
+            x = self.emb_ln(x).view(B * S, -1)
+            mask = None if lens is None else pos[None, :] < lens[:, None]
+            for l, L in enumerate(self.layers):
+                DC.fill_from_prefill(cache, l, L.qkv(x), lens, B, S)
+                x = L.forward_reference(x, mask, B, S)
+        cache.pos.copy_(lens if lens is not None else torch.full((B,), S, dtype=torch.int32, device=dev))
+        return DC.DecodeState(cache, x.index_select(0, self._last_rows(lens, B, S, dev)))
+
+    def _state_logits(self, state):
+        B = state.hidden.shape[0]
+        return self.mlm_logits(state.hidden, torch.arange(B, device=state.hidden.device))
+
+    @torch.no_grad()
+    def decode_step(self, state, token_ids=None):
+        """fp32 logits [B, V] of the next token. Without ``token_ids``: those of the prompt's last token, nothing
+        new is run. With ``token_ids`` [B]: token b enters sequence b at position ``state.pos[b]`` and runs
+        through the stack on one row per sequence (embedding at explicit positions, per layer QKV GEMM ->
+        ``attn_decode`` over the cache -> out-projection + residual -> LayerNorm -> FFN -> LayerNorm), then
+        ``state.pos`` advances by 1 on the device. Nothing is read back from the device. The caller keeps
+        ``state.pos[b]`` below the cache's ``Smax`` (``generate`` does by construction)."""
+        if token_ids is None:
+            return self._state_logits(state)
+        from ml_trainer_amd.ops import decode as DC
+        c = self.config
+        cache = state.cache
+        ids = token_ids.reshape(-1).to(torch.int64).contiguous()
+        B = ids.numel()
+        if ids.is_cuda:
+            from ml_trainer_amd.ops import transformer as T
+            C = T.require_native()
+            x = torch.empty(B, c.hidden, dtype=torch.bfloat16, device=ids.device)
+            C.embed_fwd(ids, None, T.bf16_weight(self.word_embeddings.weight),
+                        T.bf16_weight(self.position_embeddings.weight),
+                        T.bf16_weight(self.token_type_embeddings.weight), x, cache.Smax, pos=cache.pos)
+            x, _ = T._ln_fwd(x, self.emb_ln.weight, self.emb_ln.bias, c.ln_eps)
+            for l, L in enumerate(self.layers):
+                qkv = T.BF16.fwd(x, L.qkv.weight, L.qkv.bias)
+                ctx = DC.attn_decode(qkv, cache.kv[l], cache.pos, c.heads)
+                a = T.BF16.fwd(ctx, L.out.weight, L.out.bias, res=x)
+                x, _ = T._ln_fwd(a, L.ln1.weight, L.ln1.bias, c.ln_eps)
+                f, _ = T._ffn_fwd(x, L.ffn1.weight, L.ffn1.bias, L.ffn2.weight, L.ffn2.bias)
+                x, _ = T._ln_fwd(f, L.ln2.weight, L.ln2.bias, c.ln_eps)
+        else:
+            x = (self.word_embeddings(ids) + self.position_embeddings(cache.pos.long()) +
+                 self.token_type_embeddings(torch.zeros_like(ids)))
+            x = self.emb_ln(x)
+            for l, L in enumerate(self.layers):
+                ctx = DC.attn_decode_reference(L.qkv(x), cache.kv[l], cache.pos, c.heads)
+                x = L.ln1(L.out(ctx) + x)
+                x = L.ln2(L.ffn2(F.gelu(L.ffn1(x))) + x)
+        cache.pos.add_(1)
+        state.hidden = x
+        return self._state_logits(state)
+
+    def _check_generate(self, input_ids, max_new_tokens, temperature, top_k):
+        S = input_ids.shape[1]
+        if max_new_tokens < 1:
+            raise ValueError(f"max_new_tokens must be >= 1, got {max_new_tokens}")
+        if temperature < 0:
+            raise ValueError(f"temperature must be >= 0, got {temperature}")
+        if top_k is not None and top_k < 1:
+            raise ValueError(f"top_k must be >= 1, got {top_k}")
+        if S + max_new_tokens > self.config.max_position:
+            raise ValueError(f"prompt width {S} + max_new_tokens {max_new_tokens} exceeds max_position "
+                             f"{self.config.max_position}")
+
+    def _generate_loop(self, first_logits, step, B, dev, max_new_tokens, temperature, top_k, eos_id, seed,
+                       return_logits):
+        """The token loop shared by ``generate`` and ``generate_reference``: ``first_logits()`` are the prompt's,
+        ``step(tokens)`` feeds [B] tokens and returns the next logits. Always ``max_new_tokens`` steps; EOS is a
+        device-side mask, nothing is read back."""
+        from ml_trainer_amd.ops.decode import sample_tokens
+        gen = None
+        if temperature > 0:
+            gen = torch.Generator(device=dev)
+            if seed is not None:
+                gen.manual_seed(seed)
+        fill = None
+        if eos_id is not None:
+            fill = self.config.pad_id if self.config.pad_id is not None else eos_id
+        finished = torch.zeros(B, dtype=torch.bool, device=dev)
+        lengths = torch.zeros(B, dtype=torch.int64, device=dev)
+        tokens, kept = [], []
+        logits = first_logits()
+        for t in range(max_new_tokens):
+            tok = sample_tokens(logits, temperature, top_k, gen)
+            if eos_id is not None:
+                tok = torch.where(finished, torch.full_like(tok, fill), tok)
+                lengths += (~finished).long()
+                finished = finished | (tok == eos_id)
+            else:
+                lengths += 1
+            tokens.append(tok)
+            if return_logits:
+                kept.append(logits)
+            if t + 1 < max_new_tokens:
+                logits = step(tok)
+        out = (torch.stack(tokens, 1), lengths)
+        return out + (torch.stack(kept, 1),) if return_logits else out
+
+    @torch.no_grad()
+    def generate(self, input_ids, max_new_tokens: int, attention_mask=None, temperature: float = 0.0,
+                 top_k: Optional[int] = None, eos_id: Optional[int] = None, seed: Optional[int] = None,
+                 return_logits: bool = False):
+        """Continue the prompts ``input_ids`` [B, S] (right-padded, ragged lengths allowed: sequence b's new
+        tokens continue at position ``len_b``) by ``max_new_tokens`` tokens with a key/value cache: one
+        ``prefill``, then one ``decode_step`` per token. Returns ``(tokens [B, max_new_tokens], lengths [B])``,
+        plus the per-step logits [B, max_new_tokens, V] with ``return_logits``.
+
+        ``temperature == 0``: greedy argmax. Otherwise a draw from softmax(logits / temperature), restricted to
+        the ``top_k`` largest when given, from a device ``torch.Generator`` seeded with ``seed``. With ``eos_id`` a
+        sequence that has emitted it produces ``config.pad_id`` (``eos_id`` without a pad id) from then on and
+        ``lengths[b]`` counts its tokens up to and including the EOS; the loop still runs every step and never
+        reads from the device. Runs without gradients and without dropout in any mode."""
+        self._check_generate(input_ids, max_new_tokens, temperature, top_k)
+        B, S = input_ids.shape
+        state = self.prefill(input_ids, attention_mask, max_len=S + max_new_tokens)
+        return self._generate_loop(lambda: self.decode_step(state), lambda tok: self.decode_step(state, tok), B,
+                                   input_ids.device, max_new_tokens, temperature, top_k, eos_id, seed, return_logits)
+
+    @torch.no_grad()
+    def decode_logits_reference(self, ids, lens):
+        """fp32 logits [B, V] at every sequence's last real token from the uncached fp32 ``forward_reference``
+        over the whole ``ids`` [B, W] (``lens`` [B]): the oracle of ``decode_step``."""
+        B, W = ids.shape
+        lens = lens.to(ids.device)
+        hidden = self.forward_reference_hidden(ids, lens.to(torch.int32), None, None, None, full=True)
+        if self._pack(ids, lens, None) is not None:  # unpad: packed rows, sequence b ends at cumsum(lens)[b] - 1
+            rows = torch.cumsum(lens.long().clamp(1, W), 0) - 1
+        else:
+            rows = self._last_rows(lens, B, W, ids.device)
+        return self.mlm_logits(hidden.float(), rows)
+
+    @torch.no_grad()
+    def generate_reference(self, input_ids, max_new_tokens: int, attention_mask=None, temperature: float = 0.0,
+                           top_k: Optional[int] = None, eos_id: Optional[int] = None, seed: Optional[int] = None,
+                           return_logits: bool = False):
+        """``generate`` without any cache: ``forward_reference`` over the growing sequence, once per token."""
+        self._check_generate(input_ids, max_new_tokens, temperature, top_k)
+        B, S = input_ids.shape
+        dev = input_ids.device
+        lens = self._lengths(input_ids, attention_mask)
+        lens = torch.full((B,), S, dtype=torch.int64, device=dev) if lens is None else lens.long()
+        ids = torch.cat((input_ids, torch.zeros(B, max_new_tokens, dtype=input_ids.dtype, device=dev)), 1)
+        ar = torch.arange(B, device=dev)
+        grown = [0]
+
+        def step(tok):
+            ids[ar, lens + grown[0]] = tok.to(ids.dtype)
+            grown[0] += 1
+            return self.decode_logits_reference(ids[:, :S + grown[0]], lens + grown[0])
+
+        return self._generate_loop(lambda: self.decode_logits_reference(input_ids, lens), step, B, dev,
+                                   max_new_tokens, temperature, top_k, eos_id, seed, return_logits)
