@@ -4,6 +4,8 @@ cache, the ``attn_decode`` kernel) against the native full causal forward of the
     python benchmarks/generate_bench.py                                   # bert-base, batch 1,8,64, 128 + 128
     python benchmarks/generate_bench.py --batch 64 --out profiles/generate/generate_bench.jsonl
     python benchmarks/generate_bench.py --kernel --batch 64 --pos 255     # attn_decode alone: microseconds, bytes/s
+    python benchmarks/generate_bench.py --linear                          # gemm_skinny against gemm, decode shapes
+    python benchmarks/generate_bench.py --ab --repeats 5                  # MLT_DECODE_GEMM=0 / 1 alternated
     rocprofv3 --kernel-trace --stats --output-format csv -d out -o decode -- \\
         python benchmarks/generate_bench.py --batch 8 --trace-steps 32    # per-kernel share of a decode step
 
@@ -13,6 +15,11 @@ loops feed greedy tokens and never read from the device; one synchronisation clo
 ``--trace-steps N`` runs one prefill and N decode steps and nothing else (the workload of the profiler run).
 ``--kernel`` times ``C.attn_decode`` alone on a cache of ``--pos`` tokens per sequence, rotating over enough
 caches to exceed the 256 MiB last-level cache, and reports the bytes of K and V it streams per second.
+``--linear`` times ``C.gemm_skinny`` and ``C.gemm`` on the five bert-base decode linears (QKV, out-projection, FFN1,
+FFN2, the padded vocabulary decoder) at M = 1, 8, 16, 32, 64, alternated, each rotating over enough weight copies to
+exceed the last-level cache: microseconds per launch and weight bytes per second.
+``--ab`` alternates the cached decode between ``MLT_DECODE_GEMM=0`` (the planner's GEMMs: the launches before the
+skinny kernel) and ``1`` in one process and reports both medians and the spread of the ``0`` runs.
 Random weights and prompts (no network)."""
 from __future__ import annotations
 
@@ -73,18 +80,28 @@ def bench_model(args, dev):
                 tok = m.decode_step(state["s"], tok).argmax(-1)
             torch.cuda.synchronize()
             continue
-        prefill(), decode()  # warm-up: kernel loading, the padded decoder table
-        t_pre, t_dec, t_unc = [], [], []
+        settings = ["0", "1"] if args.ab else [os.environ.get("MLT_DECODE_GEMM", "1")]
+        for s in settings:  # warm-up: kernel loading, the padded decoder table
+            os.environ["MLT_DECODE_GEMM"] = s
+            prefill(), decode()
+        t_pre, t_unc, t_dec = [], [], {s: [] for s in settings}
         for _ in range(args.repeats):
-            t_pre.append(_sync_ms(prefill))
-            t_dec.append(_sync_ms(decode) / (N - 1))
+            for s in settings:
+                os.environ["MLT_DECODE_GEMM"] = s
+                t_pre.append(_sync_ms(prefill))
+                t_dec[s].append(_sync_ms(decode) / (N - 1))
             if not args.no_uncached:
                 t_unc.append(_sync_ms(uncached) / (N - 1))
-        ms = statistics.median(t_dec)
+        ms = statistics.median(t_dec[settings[-1]])
         rec = {"bench": "generate", "model": args.model, "batch": B, "prompt": P, "new": N,
+               "decode_gemm": settings[-1],
                "prefill_ms": statistics.median(t_pre), "cached_ms_per_token": ms, "cached_tokens_per_s": B / ms * 1e3,
                "uncached_ms_per_token": statistics.median(t_unc) if t_unc else None,
-               "cached_runs": t_dec, "uncached_runs": t_unc}
+               "cached_runs": t_dec[settings[-1]], "uncached_runs": t_unc}
+        if args.ab:  # the planner's GEMMs in the same process: median, runs, (max - min) / median
+            r0 = t_dec["0"]
+            rec.update({"gemm0_ms_per_token": statistics.median(r0), "gemm0_runs": r0,
+                        "gemm0_spread": (max(r0) - min(r0)) / statistics.median(r0)})
         print(json.dumps(rec), flush=True)
         recs.append(rec)
     return recs
@@ -119,6 +136,48 @@ def bench_kernel(args, dev):
     return recs
 
 
+DECODE_LINEARS = [("qkv", 2304, 768), ("out", 768, 768), ("ffn1", 3072, 768), ("ffn2", 768, 3072),
+                  ("decoder", 30720, 768)]  # (name, N, K) of bert-base
+
+
+def bench_linear(args, dev):
+    from ml_trainer_amd.ops._ext import require_native
+    C = require_native()
+    recs = []
+    for name, N, K in DECODE_LINEARS:
+        per = N * K * 2
+        ncopy = max(2, -(-(512 << 20) // per))  # rotate over >= 512 MiB of weights: none is found in the LLC
+        ws = [(torch.randn(N, K, device=dev) * 0.02).to(torch.bfloat16) for _ in range(ncopy)]
+        bias = torch.randn(N, device=dev)
+        reps = max(2 * ncopy, 64)
+        for M in [int(m) for m in args.rows.split(",")]:
+            x = torch.randn(M, K, device=dev).to(torch.bfloat16)
+            y = torch.empty(M, N, dtype=torch.float32 if name == "decoder" else torch.bfloat16, device=dev)
+
+            def skinny():
+                for i in range(reps):
+                    C.gemm_skinny(x, ws[i % ncopy], y, bias=bias)
+
+            def gemm():
+                for i in range(reps):
+                    C.gemm(x, ws[i % ncopy], y, False, False, bias=bias)
+
+            skinny(), gemm()
+            t = {"skinny": [], "gemm": []}
+            for _ in range(args.repeats):
+                t["skinny"].append(_sync_ms(skinny) / reps * 1e3)
+                t["gemm"].append(_sync_ms(gemm) / reps * 1e3)
+            us_s, us_g = statistics.median(t["skinny"]), statistics.median(t["gemm"])
+            rec = {"bench": "decode_linear", "linear": name, "M": M, "N": N, "K": K, "copies": ncopy,
+                   "weight_bytes": per, "skinny_us": us_s, "gemm_us": us_g, "skinny_tb_per_s": per / us_s * 1e-6,
+                   "gemm_tb_per_s": per / us_g * 1e-6, "gemm_spread": (max(t["gemm"]) - min(t["gemm"])) / us_g,
+                   "skinny_runs": t["skinny"], "gemm_runs": t["gemm"]}
+            print(json.dumps(rec), flush=True)
+            recs.append(rec)
+        del ws
+    return recs
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="bert-base")
@@ -129,13 +188,16 @@ def main():
     ap.add_argument("--no-uncached", action="store_true")
     ap.add_argument("--trace-steps", type=int, default=0)
     ap.add_argument("--kernel", action="store_true", help="time C.attn_decode alone")
+    ap.add_argument("--linear", action="store_true", help="time C.gemm_skinny and C.gemm on the decode linears")
+    ap.add_argument("--rows", default="1,8,16,32,64", help="row counts of --linear")
+    ap.add_argument("--ab", action="store_true", help="alternate MLT_DECODE_GEMM=0 / 1 in the model timing")
     ap.add_argument("--heads", type=int, default=12)
     ap.add_argument("--smax", type=int, default=256)
     ap.add_argument("--pos", type=int, default=255)
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
-    recs = bench_kernel(args, dev) if args.kernel else bench_model(args, dev)
+    recs = bench_linear(args, dev) if args.linear else bench_kernel(args, dev) if args.kernel else bench_model(args, dev)
     if args.out and recs:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "a") as f:

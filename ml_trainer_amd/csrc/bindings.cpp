@@ -540,6 +540,35 @@ void gemm(Tensor A, Tensor B, Tensor C, bool a_mn, bool b_mn, c10::optional<Tens
   if (part.defined()) reduce_col_partials(part, M / 64, N, colsum_out->data_ptr<float>(), colsum_accumulate);
 }
 
+// Y [M, N] = epilogue(X [M, K] . W [N, K]^T) on the weight-streaming kernel of the decode steps (gemm_skinny.hip):
+// 1 <= M <= gemm_skinny_max_rows(), N % 16 == 0, K % 32 == 0, mode 0 (none) or 1 (GELU, aux receives the
+// pre-activation). Everything else is refused here: there is no fall-back to another kernel.
+void gemm_skinny(Tensor X, Tensor W, Tensor Y, c10::optional<Tensor> bias, c10::optional<Tensor> aux,
+                 c10::optional<Tensor> res, int mode) {
+  static const GemmOperandText tx{"gemm_skinny", "gemm_skinny operands must be device tensors",
+                                  "gemm_skinny operands need unit column stride (k-contiguous X and W)",
+                                  "gemm_skinny leading dimensions must be multiples of 8"};
+  check_gemm_operand(X, tx, 8);
+  check_gemm_operand(W, tx, 8);
+  check_gemm_operand(Y, tx, 0);
+  TORCH_CHECK(X.scalar_type() == at::kBFloat16 && W.scalar_type() == at::kBFloat16, "gemm_skinny X/W must be bf16");
+  TORCH_CHECK(Y.scalar_type() == at::kBFloat16 || Y.scalar_type() == at::kFloat, "gemm_skinny Y must be bf16 or fp32");
+  const int64_t M = X.size(0), K = X.size(1), N = W.size(0);
+  TORCH_CHECK(W.size(1) == K, "gemm_skinny inner dimensions differ: ", K, " vs ", W.size(1));
+  TORCH_CHECK(Y.size(0) == M && Y.size(1) == N, "gemm_skinny Y shape mismatch");
+  TORCH_CHECK(M >= 1 && M <= kSkinnyMaxRows, "gemm_skinny takes 1 .. ", kSkinnyMaxRows, " rows, got ", M);
+  TORCH_CHECK(N % 16 == 0 && K % 32 == 0 && N > 0 && K > 0, "gemm_skinny needs N % 16 == 0 and K % 32 == 0, got N = ", N,
+              ", K = ", K);
+  TORCH_CHECK(N < (1LL << 31) && K < (1LL << 31), "gemm_skinny dims too large");
+  TORCH_CHECK(mode == 0 || mode == 1, "gemm_skinny mode (0 none, 1 gelu); dgelu / tanh run on gemm");
+  TORCH_CHECK(X.stride(0) >= K && W.stride(0) >= K && Y.stride(0) >= N, "gemm_skinny rows overlap");
+  const GemmEpiOperands ep = check_gemm_epilogue(bias, aux, res, M, N, mode, true, "gemm_skinny GELU mode needs aux",
+                                                 "aux must be bf16 [M,N] with 16-byte aligned rows");
+  launch_gemm_skinny(bf16_ptr(X), bf16_ptr(W), Y.data_ptr(), Y.scalar_type() == at::kFloat, (int)M, (int)N, (int)K,
+                     X.stride(0), W.stride(0), Y.stride(0), ep.bias, ep.aux, ep.ldaux, ep.res, ep.ldres, mode,
+                     cur_stream());
+}
+
 // ---------------------------------------------------------------------------- fp8
 static bool is_fp8_storage(const Tensor& t) {
   return t.scalar_type() == at::kByte || t.scalar_type() == at::kFloat8_e4m3fn ||
@@ -1704,6 +1733,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("bias") = py::none(), py::arg("aux") = py::none(), py::arg("res") = py::none(),
         py::arg("alpha") = 1.0, py::arg("mode") = 0, py::arg("accumulate") = false, py::arg("cfg") = -1,
         py::arg("splits") = 0, py::arg("colsum_out") = py::none(), py::arg("colsum_accumulate") = false);
+  m.def("gemm_skinny", &gemm_skinny, py::arg("X"), py::arg("W"), py::arg("Y"), py::arg("bias") = py::none(),
+        py::arg("aux") = py::none(), py::arg("res") = py::none(), py::arg("mode") = 0);
+  m.def("gemm_skinny_max_rows", []() { return kSkinnyMaxRows; });
   m.def("gemm_f8", &gemm_f8, py::arg("A"), py::arg("B"), py::arg("C"), py::arg("fmt_a"), py::arg("fmt_b"),
         py::arg("inv_scale_a"), py::arg("inv_scale_b"), py::arg("bias") = py::none(), py::arg("aux") = py::none(),
         py::arg("res") = py::none(), py::arg("alpha") = 1.0, py::arg("mode") = 0, py::arg("accumulate") = false,

@@ -213,6 +213,14 @@ void launch_gemm_bf16(const GemmPlan& plan, int a_mn, int b_mn, bool out_f32, co
                       void* C, int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc, const float* bias,
                       const uint16_t* aux, int64_t ldaux, const uint16_t* res, int64_t ldres, float alpha, int mode,
                       int accumulate, float* ws, unsigned* cnt, hipStream_t st, float* colpart = nullptr);
+// Weight-streaming GEMM for decode steps (gemm_skinny.hip): Y [M][N] = epilogue(X [M][K] . W [N][K]^T), both
+// operands k-contiguous bf16 with 16-byte aligned rows, 1 <= M <= kSkinnyMaxRows, N % 16 == 0, K % 32 == 0; bias
+// fp32 [N], mode 0 or 1 (GELU, writes the bf16 pre-activation to aux), res bf16 [M][N]. The summation order is a
+// function of (N, K) alone: a row's result does not depend on M. No workspace, nothing allocated.
+constexpr int kSkinnyMaxRows = 64;
+void launch_gemm_skinny(const uint16_t* X, const uint16_t* W, void* Y, bool out_f32, int M, int N, int K, int64_t ldx,
+                        int64_t ldw, int64_t ldy, const float* bias, const uint16_t* aux, int64_t ldaux,
+                        const uint16_t* res, int64_t ldres, int mode, hipStream_t st);
 // fp8 GEMM (gemm_tile.hip): A [M][K], B [N][K] both k-contiguous fp8 (fmt 0 = e4m3, 1 = e5m2),
 // K % 128 == 0; alpha *= inv_scale_a[0] * inv_scale_b[0] (device scalars, delayed scaling).
 GemmPlan plan_gemm_f8(int M, int N, int K, int force_cfg, int force_splits);

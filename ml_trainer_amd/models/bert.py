@@ -662,7 +662,13 @@ class BertLMHeadModel(BertForMaskedLM):
         return DC.DecodeState(cache, x.index_select(0, self._last_rows(lens, B, S, dev)))
 
     def _state_logits(self, state):
-        B = state.hidden.shape[0]
+        from ml_trainer_amd.ops import decode as DC
+        from ml_trainer_amd.ops import mlm as M
+        B, h = state.hidden.shape
+        Vp = M._round_up(self.config.vocab_size, M.VOCAB_MULTIPLE)
+        if (state.hidden.is_cuda and state.hidden.dtype == torch.bfloat16 and
+                DC.decode_linear_path(B, h, h) == "skinny" and DC.decode_linear_path(B, Vp, h) == "skinny"):
+            return M.decode_logits(state.hidden, self.mlm_params())  # B rows, no gather into a 256-row tile
         return self.mlm_logits(state.hidden, torch.arange(B, device=state.hidden.device))
 
     @torch.no_grad()
@@ -689,11 +695,13 @@ class BertLMHeadModel(BertForMaskedLM):
                         T.bf16_weight(self.token_type_embeddings.weight), x, cache.Smax, pos=cache.pos)
             x, _ = T._ln_fwd(x, self.emb_ln.weight, self.emb_ln.bias, c.ln_eps)
             for l, L in enumerate(self.layers):
-                qkv = T.BF16.fwd(x, L.qkv.weight, L.qkv.bias)
+                qkv = DC.linear_small(x, T.bf16_weight(L.qkv.weight), L.qkv.bias)
                 ctx = DC.attn_decode(qkv, cache.kv[l], cache.pos, c.heads)
-                a = T.BF16.fwd(ctx, L.out.weight, L.out.bias, res=x)
+                a = DC.linear_small(ctx, T.bf16_weight(L.out.weight), L.out.bias, res=x)
                 x, _ = T._ln_fwd(a, L.ln1.weight, L.ln1.bias, c.ln_eps)
-                f, _ = T._ffn_fwd(x, L.ffn1.weight, L.ffn1.bias, L.ffn2.weight, L.ffn2.bias)
+                pre = torch.empty(B, L.ffn1.weight.shape[0], dtype=torch.bfloat16, device=x.device)
+                g = DC.linear_small(x, T.bf16_weight(L.ffn1.weight), L.ffn1.bias, gelu_aux=pre)
+                f = DC.linear_small(g, T.bf16_weight(L.ffn2.weight), L.ffn2.bias, res=x)
                 x, _ = T._ln_fwd(f, L.ln2.weight, L.ln2.bias, c.ln_eps)
         else:
             x = (self.word_embeddings(ids) + self.position_embeddings(cache.pos.long()) +

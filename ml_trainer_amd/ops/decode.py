@@ -9,18 +9,29 @@ has cached = the row its next token takes. Rows ``j > pos[b]`` are stale memory 
 fused in); ``attn_decode_reference`` the same function in plain fp32 torch (the CPU path and the oracle of the
 tests). ``fill_from_prefill`` copies a prompt's K / V out of the padded forward's QKV buffer with torch ops: once
 per layer per prompt, not a hot path.
+
+``linear_small`` is the linear layer of a decode step (M = B rows): ``decode_linear_path`` sends it to the
+weight-streaming kernel ``C.gemm_skinny`` (csrc/kernels/gemm_skinny.hip) or to the planner's GEMM. With the skinny
+kernel every kernel of a step works row by row, so a sequence's logits do not depend on the batch it is decoded in.
 """
 from __future__ import annotations
 
+import os
 from dataclasses import dataclass
 from typing import List, Optional
 
 import torch
+import torch.nn.functional as F
 
 from ml_trainer_amd.ops._ext import require_native
 
 HEAD_DIM = 64
 ATTN_SCALE = 1.0 / 8.0  # 1/sqrt(head_dim = 64)
+# rows up to which a decode step's linears take C.gemm_skinny (the kernel itself takes C.gemm_skinny_max_rows() =
+# 64): the largest of 16 / 32 / 64 at which it beat C.gemm at EVERY bert-base decode shape by more than C.gemm's
+# run-to-run spread. At 32 rows the vocabulary decoder ties (20.7 against 20.5 us), at 64 the decoder and FFN2
+# lose: every workgroup re-reads X from L2 (profiles/generate/README.md has the table).
+SKINNY_MAX_ROWS = 16
 
 
 @dataclass
@@ -87,6 +98,47 @@ def attn_decode_reference(qkv_new, cache_layer, pos, H: int, scale: float = ATTN
     V = torch.where(valid[..., None], V, torch.zeros_like(V))
     p = torch.softmax(s, -1)
     return (p[:, :, None, :] @ V)[:, :, 0, :].reshape(B, H * HEAD_DIM)
+
+
+def decode_linear_path(M: int, N: int, K: int) -> str:
+    """Which kernel a decode step's linear ``[M, K] x [N, K]^T`` takes: ``"skinny"`` (the weight-streaming
+    ``C.gemm_skinny``, whose summation order depends on (N, K) only, so a row's result does not depend on the
+    batch) or ``"gemm"`` (the planner's tile kernels). A pure function of the shape and of ``MLT_DECODE_GEMM``
+    (read per call; ``0`` forces ``"gemm"``: the launches of the model before the skinny kernel, the A/B switch)."""
+    if os.environ.get("MLT_DECODE_GEMM", "1") == "0":
+        return "gemm"
+    if 1 <= M <= SKINNY_MAX_ROWS and N > 0 and K > 0 and N % 16 == 0 and K % 32 == 0:
+        return "skinny"
+    return "gemm"
+
+
+def linear_small(x, w16, bias=None, gelu_aux=None, res=None, out=None):
+    """``y = epilogue(x . w16^T)`` for the few rows of a decode step: x [M, K] bf16, w16 [N, K] bf16 (the layout
+    of ``bf16_weight``), fp32 ``bias`` [N], ``gelu_aux`` [M, N] bf16 (GELU epilogue; receives the pre-activation),
+    ``res`` [M, N] bf16 added last, ``out`` [M, N] bf16 or fp32 (default: a new bf16 tensor). The skinny kernel
+    where ``decode_linear_path`` says so, otherwise the launches of ``transformer.linear_fwd``. On the CPU:
+    ``F.linear`` and the same epilogue in fp32."""
+    M, K = x.shape
+    N = w16.shape[0]
+    if not x.is_cuda:
+        y = F.linear(x.float(), w16.float(), None if bias is None else bias.float())
+        if gelu_aux is not None:
+            gelu_aux.copy_(y)
+            y = F.gelu(gelu_aux.float())
+        if res is not None:
+            y = y + res.float()
+        return y if out is None else out.copy_(y)
+    if decode_linear_path(M, N, K) == "skinny":
+        if out is None:
+            out = torch.empty(M, N, dtype=torch.bfloat16, device=x.device)
+        require_native().gemm_skinny(x, w16, out, bias=bias, aux=gelu_aux, res=res, mode=1 if gelu_aux is not None else 0)
+        return out
+    from ml_trainer_amd.ops import transformer as T
+    if out is None:
+        return T.linear_fwd(x, w16, bias, gelu_aux=gelu_aux, res=res)
+    require_native().gemm(x, w16, out, False, False, bias=bias, aux=gelu_aux, res=res,
+                          mode=1 if gelu_aux is not None else 0)
+    return out
 
 
 def fill_from_prefill(cache: KVCache, layer: int, qkv, lens: Optional[torch.Tensor], B: int, S: int) -> None:

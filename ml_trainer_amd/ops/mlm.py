@@ -380,3 +380,22 @@ def mlm_logits(hidden, rows, params: MLMParams):
         out = torch.empty(slot_row.numel(), wp.shape[0], dtype=torch.float32, device=hidden.device)
         C.gemm(t, wp, out, False, False, bias=bp)
     return out[:n, :V]
+
+
+def decode_logits(hidden, params: MLMParams):
+    """fp32 [B, V]: the vocabulary logits of every row of ``hidden`` [B, h] (bf16, on the GPU), for the few rows
+    of a decode step: the transform's dense + GELU and the tied decoder through ``ops.decode.linear_small`` (the
+    weight-streaming kernel where ``decode_linear_path`` says so), the LayerNorm kernel of ``_transform_fwd``
+    between them. B rows in, B rows out: no gather into a 256-row tile, no [256, Vp] logits matrix."""
+    from ml_trainer_amd.ops import decode as DC
+    from ml_trainer_amd.ops import transformer as T
+    V = params.word_w.shape[0]
+    with torch.no_grad():
+        wp, bp = padded_decoder(params.word_w, params.out_bias)
+        x = hidden.contiguous()
+        pre = torch.empty_like(x)
+        a = DC.linear_small(x, T.bf16_weight(params.dense_w), params.dense_b, gelu_aux=pre)
+        t, _ = T._ln_fwd(a, params.ln_w, params.ln_b, params.ln_eps)
+        out = torch.empty(x.shape[0], wp.shape[0], dtype=torch.float32, device=x.device)
+        DC.linear_small(t, wp, bp, out=out)
+    return out[:, :V]
