@@ -18,6 +18,13 @@ caches to exceed the 256 MiB last-level cache, and reports the bytes of K and V 
 ``--linear`` times ``C.gemm_skinny`` and ``C.gemm`` on the five bert-base decode linears (QKV, out-projection, FFN1,
 FFN2, the padded vocabulary decoder) at M = 1, 8, 16, 32, 64, alternated, each rotating over enough weight copies to
 exceed the last-level cache: microseconds per launch and weight bytes per second.
+``--sampler-kernel`` times ``ops.decode.sample_step`` (one launch) against ``ops.decode.sample_tokens`` (torch ops)
+alone on fp32 logits [B, 30720] with 30,522 valid columns, greedy / top-k 50 / top-p 0.9 / both (the torch sampler
+has no top-p: null). One logits buffer, so the row is L2-resident as it is behind the decoder GEMM.
+``--sampler-ab`` alternates three whole token loops (N samples, N - 1 decode steps, prefill outside the timed
+region) in one process: eager with the torch sampler, eager with ``sample_step``, and the captured graph with
+``sample_step``; medians, (max - min) / median of each, and the capture time, greedy and sampled.
+``--sampler device`` / ``--graph`` select the loop of ``--trace-steps`` (the workload of a profiler run).
 ``--ab`` alternates the cached decode between ``MLT_DECODE_GEMM=0`` (the planner's GEMMs: the launches before the
 skinny kernel) and ``1`` in one process and reports both medians and the spread of the ``0`` runs.
 Random weights and prompts (no network)."""
@@ -73,6 +80,11 @@ def bench_model(args, dev):
                     hidden = m(seq[:, :W].contiguous())
                     tok = m.mlm_logits(hidden, rows * W + W - 1).argmax(-1)
 
+        if args.trace_steps and args.sampler == "device":  # the device sampler's loop, eager or graph replay
+            m.generate(ids, args.trace_steps + 1, temperature=0.8, top_k=50, top_p=0.9, seed=1, sampler="device",
+                       graph=args.graph)
+            torch.cuda.synchronize()
+            continue
         if args.trace_steps:
             prefill()
             tok = state["tok"]
@@ -104,6 +116,111 @@ def bench_model(args, dev):
                         "gemm0_spread": (max(r0) - min(r0)) / statistics.median(r0)})
         print(json.dumps(rec), flush=True)
         recs.append(rec)
+    return recs
+
+
+SAMPLER_SETTINGS = [("greedy", dict(temperature=0.0)), ("sampled", dict(temperature=0.8, top_k=50, top_p=0.9, seed=1))]
+
+
+def _spread(runs):
+    return (max(runs) - min(runs)) / statistics.median(runs)
+
+
+def bench_sampler_ab(args, dev):
+    """(eager, torch sampler) = the path before the device sampler, (eager, device sampler), (graph, device sampler),
+    alternated in one process. A timed region is the token loop alone; prefill and capture are outside it."""
+    from ml_trainer_amd.models.bert import BertLMHeadModel, bert_config
+    torch.manual_seed(0)
+    m = BertLMHeadModel(bert_config(args.model)).to(dev).eval()
+    V, P, N = m.config.vocab_size, args.prompt, args.new
+    recs = []
+    for B in [int(b) for b in args.batch.split(",")]:
+        ids = torch.randint(5, V, (B, P), device=dev)
+        dec = m._graphed_decoder(B, P + N, N, dev)
+        for name, kw in SAMPLER_SETTINGS:
+            torch_kw = {k: v for k, v in kw.items() if k != "top_p"}  # the torch sampler has no top-p
+            params = m._sampler_params(kw["temperature"], kw.get("top_k"), kw.get("top_p"), None, kw.get("seed"))
+            box = {}
+
+            def pre_eager():
+                box["s"] = m.prefill(ids, max_len=P + N)
+                box["z"] = m.decode_step(box["s"])
+
+            def step(tok):
+                return m.decode_step(box["s"], tok)
+
+            def run_torch():
+                m._generate_loop(lambda: box["z"], step, B, dev, N, torch_kw["temperature"], torch_kw.get("top_k"),
+                                 None, torch_kw.get("seed"), False)
+
+            def run_device():
+                st = m._new_sampler(B, N, dev, kw["temperature"], kw.get("top_k"), kw.get("top_p"), None, kw.get("seed"))
+                m._device_sampler_loop(lambda: box["z"], step, st, N, False)
+
+            def pre_graph():
+                box["z"] = dec.start(m, ids, None, params)
+
+            def run_graph():
+                dec.run(m, box["z"])
+
+            modes = [("eager_torch", pre_eager, run_torch), ("eager_device", pre_eager, run_device),
+                     ("graph_device", pre_graph, run_graph)]
+            for _, pre, run in modes:  # warm-up
+                pre(), run()
+            t = {k: [] for k, _, _ in modes}
+            for _ in range(args.repeats):
+                for k, pre, run in modes:
+                    pre()
+                    t[k].append(_sync_ms(run) / (N - 1))
+            rec = {"bench": "generate_sampler_ab", "model": args.model, "batch": B, "prompt": P, "new": N,
+                   "setting": name, "capture_s": dec.capture_seconds}
+            for k in t:
+                rec[k + "_ms_per_token"] = statistics.median(t[k])
+                rec[k + "_spread"] = _spread(t[k])
+                rec[k + "_runs"] = t[k]
+            print(json.dumps(rec), flush=True)
+            recs.append(rec)
+    return recs
+
+
+def bench_sampler_kernel(args, dev):
+    from ml_trainer_amd.ops import decode as DC
+    V, Vp, reps = 30522, 30720, 200
+    recs = []
+    settings = [("greedy", dict(temperature=0.0)), ("top_k_50", dict(temperature=0.8, top_k=50)),
+                ("top_p_0.9", dict(temperature=0.8, top_p=0.9)), ("top_k_50_top_p_0.9", dict(temperature=0.8, top_k=50, top_p=0.9)),
+                ("temperature_only", dict(temperature=0.8))]
+    for B in [int(b) for b in args.batch.split(",")]:
+        z = torch.randn(B, Vp, device=dev) * 3.0
+        zv = z[:, :V]
+        gen = torch.Generator(device=dev).manual_seed(1)
+        for name, kw in settings:
+            st = DC.SamplerState.allocate(B, reps, dev, seed=1, **kw)
+
+            def device():
+                st.draws.zero_()
+                for _ in range(reps):
+                    DC.sample_step(zv, V, st)
+
+            def torch_ops():
+                for _ in range(reps):
+                    DC.sample_tokens(zv, kw["temperature"], kw.get("top_k"), gen)
+
+            has_torch = "top_p" not in kw
+            device()
+            t_d, t_t = [], []
+            if has_torch:
+                torch_ops()
+            for _ in range(args.repeats):
+                t_d.append(_sync_ms(device) / reps * 1e3)
+                if has_torch:
+                    t_t.append(_sync_ms(torch_ops) / reps * 1e3)
+            rec = {"bench": "sample_step", "batch": B, "V": V, "ldz": Vp, "setting": name,
+                   "sample_step_us": statistics.median(t_d), "sample_step_spread": _spread(t_d),
+                   "sample_tokens_us": statistics.median(t_t) if t_t else None,
+                   "sample_tokens_spread": _spread(t_t) if t_t else None}
+            print(json.dumps(rec), flush=True)
+            recs.append(rec)
     return recs
 
 
@@ -191,13 +308,23 @@ def main():
     ap.add_argument("--linear", action="store_true", help="time C.gemm_skinny and C.gemm on the decode linears")
     ap.add_argument("--rows", default="1,8,16,32,64", help="row counts of --linear")
     ap.add_argument("--ab", action="store_true", help="alternate MLT_DECODE_GEMM=0 / 1 in the model timing")
+    ap.add_argument("--sampler", choices=["torch", "device"], default="torch", help="the sampler of --trace-steps")
+    ap.add_argument("--graph", action="store_true", help="--trace-steps with --sampler device: replay the captured graph")
+    ap.add_argument("--sampler-kernel", action="store_true", help="time sample_step against sample_tokens alone")
+    ap.add_argument("--sampler-ab", action="store_true",
+                    help="alternate (eager, torch sampler), (eager, device sampler), (graph, device sampler)")
     ap.add_argument("--heads", type=int, default=12)
     ap.add_argument("--smax", type=int, default=256)
     ap.add_argument("--pos", type=int, default=255)
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
-    recs = bench_linear(args, dev) if args.linear else bench_kernel(args, dev) if args.kernel else bench_model(args, dev)
+    if args.graph and args.sampler != "device":
+        raise SystemExit("--graph needs --sampler device")
+    if args.sampler_kernel or args.sampler_ab:
+        recs = bench_sampler_kernel(args, dev) if args.sampler_kernel else bench_sampler_ab(args, dev)
+    else:
+        recs = bench_linear(args, dev) if args.linear else bench_kernel(args, dev) if args.kernel else bench_model(args, dev)
     if args.out and recs:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "a") as f:

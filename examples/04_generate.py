@@ -57,6 +57,13 @@ def main(argv=None):
         print(f"prompt {val.ids[b, :P].tolist()} -> {tokens[b].tolist()}  {marks}")
     acc = float((tokens == want).float().mean())
     print(f"continuation accuracy {acc:.3f} over {want.numel()} tokens")
+    # nucleus sampling with the on-device sampler (reproducible for a seed, independent of the batch); on a GPU the
+    # decode loop is one captured graph replayed per token
+    on_gpu = tr.device.type == "cuda"
+    sampled, _ = tr.model.generate(val.ids[:, :P].to(tr.device), N, temperature=0.7, top_k=20, top_p=0.9,
+                                   seed=args.seed, sampler="device", graph=on_gpu)
+    print(f"top-p 0.9 / top-k 20 / temperature 0.7{' (graph replay)' if on_gpu else ''}: row 0 -> "
+          f"{sampled[0].tolist()}  agreement with the row {float((sampled.cpu() == want).float().mean()):.3f}")
     return acc
 
 

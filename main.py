@@ -26,7 +26,8 @@ language model on synthetic next-token text: causal flash attention, criterion `
 is the next-token accuracy), ``--generate N`` (``--task clm``: after training, rank 0 continues up to 8
 validation rows from their first ``--prompt_len`` tokens by N tokens with the key/value cache, logs a
 ``generate`` record with the ``continuation_accuracy`` and writes ``model_dir/generated.json``;
-``--temperature`` / ``--top_k`` sample instead of the greedy argmax).
+``--temperature`` / ``--top_k`` sample instead of the greedy argmax; ``--sampler device`` takes the on-device
+sampler, which adds ``--top_p`` and, with ``--graph_decode``, a decode loop replayed from one captured graph).
 """
 from __future__ import annotations
 
@@ -93,6 +94,14 @@ def build_model_and_datasets(args):
         raise ValueError("--generate applies to --task clm (the causal language model)")
     if not args.generate and (args.temperature is not None or args.top_k is not None):
         raise ValueError("--temperature / --top_k apply to --generate")
+    if not args.generate and (args.top_p is not None or args.sampler is not None or args.graph_decode):
+        raise ValueError("--top_p / --sampler / --graph_decode apply to --generate")
+    if args.top_p is not None and args.sampler != "device":
+        raise ValueError("--top_p needs --sampler device (nucleus sampling is part of the on-device sampler)")
+    if args.top_p is not None and not 0.0 < args.top_p <= 1.0:
+        raise ValueError(f"--top_p must satisfy 0 < top_p <= 1, got {args.top_p}")
+    if args.graph_decode and args.sampler != "device":
+        raise ValueError("--graph_decode needs --sampler device (the torch sampler cannot be captured)")
     if args.generate and (args.generate < 0 or args.prompt_len < 1):
         raise ValueError("--generate and --prompt_len must be positive")
     over = {"hidden_dropout": args.dropout} if args.dropout else {}
@@ -184,7 +193,9 @@ def generate_after_fit(args, trainer, val_set, rows: int = 8):
     mask = (torch.arange(P)[None, :] < plens[:, None]).long()
     dev = trainer.device
     tokens, _ = model.generate(ids[:, :P].to(dev), N, attention_mask=mask.to(dev),
-                               temperature=args.temperature or 0.0, top_k=args.top_k, seed=args.seed)
+                               temperature=args.temperature or 0.0, top_k=args.top_k, seed=args.seed,
+                               top_p=args.top_p, sampler=args.sampler,
+                               graph=args.graph_decode and dev.type == "cuda")
     tokens = tokens.cpu()
     at = plens[:, None] + torch.arange(N)[None, :]  # where the continuation sits in the row
     has = at < lengths[:, None]
@@ -267,6 +278,14 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--top_k", type=int, default=None,
                         help="--generate with --temperature: restrict the draw to the k largest logits")
     parser.add_argument("--synthetic", action="store_true", help="use the seeded synthetic dataset")
+    parser.add_argument("--top_p", type=float, default=None,
+                        help="--generate with --sampler device: nucleus sampling inside the top-k set, applied as "
+                             "round(top_p * 65536) / 65536")
+    parser.add_argument("--sampler", choices=["device"], default=None,
+                        help="--generate: 'device' samples with the sample_step kernel (reproducible, independent "
+                             "of the batch); default: the torch sampler")
+    parser.add_argument("--graph_decode", action="store_true",
+                        help="--generate with --sampler device on a GPU: replay one captured graph per token")
     parser.add_argument("--synthetic_size", type=int, default=0)
     parser.add_argument("--seq_len", type=int, default=512)
     parser.add_argument("--per_device_batch", action="store_true",

@@ -15,6 +15,7 @@
 #include <memory>
 
 #include "mlt_kernels.h"
+#include "mlt_sample.h"
 #include "mlt_comm.h"
 #include "mlt_runtime.h"
 
@@ -1090,6 +1091,65 @@ void attn_decode(Tensor qkv_new, Tensor kv, Tensor pos, Tensor out, int64_t H, d
                      (uint16_t*)out.data_ptr(), (int)B, (int)H, (int)Smax, (float)scale, cur_stream());
 }
 
+// The logits operand of the sampling kernels: fp32 [B, >= V] with unit column stride, a row stride ldz % 4 == 0
+// and a 16-byte aligned base (16-byte loads), every row readable up to round_up(V, 4) columns. The [B, V] view
+// of the padded [B, Vp] buffer that ops.mlm.decode_logits returns qualifies as it is.
+static int64_t check_sample_logits(const Tensor& logits, int64_t V, const char* who) {
+  TORCH_CHECK(logits.defined() && logits.is_cuda() && logits.dim() == 2 && logits.scalar_type() == at::kFloat, who,
+              ": logits must be an fp32 [B, ldz] device tensor");
+  const int64_t B = logits.size(0), ldz = B > 1 ? logits.stride(0) : (V + 3) / 4 * 4;  // one row: no stride
+  TORCH_CHECK(B >= 1 && B <= 65535, who, ": 1 <= B <= 65535, got ", B);
+  TORCH_CHECK(logits.stride(1) == 1, who, ": logits need unit column stride");
+  TORCH_CHECK(ldz % 4 == 0, who, ": the row stride ldz must be a multiple of 4, got ", ldz);
+  TORCH_CHECK(V >= 1 && V <= logits.size(1) && V <= ldz && ldz < (1LL << 31), who, ": 1 <= V <= ldz does not hold: V = ", V,
+              ", columns = ", logits.size(1), ", ldz = ", ldz);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0, who, ": logits must be 16-byte aligned");
+  const int64_t last = logits.storage_offset() + (B - 1) * ldz + (V + 3) / 4 * 4;  // one past the last element read
+  TORCH_CHECK(ldz >= (V + 3) / 4 * 4, who, ": rows overlap: ldz = ", ldz, " < round_up(V, 4)");
+  TORCH_CHECK(last * 4 <= (int64_t)logits.storage().nbytes(), who, ": the last row is not readable up to round_up(V, 4)");
+  return ldz;
+}
+
+// One sampling step (sample.hip; the definition is the header of mlt_sample.h). params int32 [8] = SampleParams,
+// per-row state on the logits' device. Nothing is allocated, nothing is read back: capturable.
+void sample_step(Tensor logits, int64_t V, Tensor params, Tensor draws, Tensor seq_ids, Tensor finished, Tensor lengths,
+                 Tensor tokens, Tensor next_ids, Tensor n_kept) {
+  const int64_t ldz = check_sample_logits(logits, V, "sample_step");
+  const int64_t B = logits.size(0);
+  check_dev(params, "params", at::kInt, 8, 16);
+  TORCH_CHECK(params.numel() == 8, "sample_step: params must be int32 [8]");
+  check_dev(draws, "draws", at::kInt, B, 4);
+  check_dev(seq_ids, "seq_ids", at::kInt, B, 4);
+  check_dev(finished, "finished", at::kInt, B, 4);
+  check_dev(n_kept, "n_kept", at::kInt, B, 4);
+  check_dev(lengths, "lengths", at::kLong, B, 8);
+  check_dev(next_ids, "next_ids", at::kLong, B, 8);
+  check_dev(tokens, "tokens", at::kLong, B, 8);
+  TORCH_CHECK(draws.numel() == B && seq_ids.numel() == B && finished.numel() == B && n_kept.numel() == B &&
+                  lengths.numel() == B && next_ids.numel() == B,
+              "sample_step: draws / seq_ids / finished / n_kept / lengths / next_ids must have B = ", B, " entries");
+  TORCH_CHECK(tokens.dim() == 2 && tokens.size(0) == B && tokens.size(1) >= 1 && tokens.size(1) <= 0x7fffffff,
+              "sample_step: tokens must be int64 [B, T], T >= 1");
+  for (const Tensor* t : {&params, &draws, &seq_ids, &finished, &n_kept, &lengths, &next_ids, &tokens})
+    TORCH_CHECK(t->device() == logits.device(), "sample_step: every operand must be on the logits' device");
+  launch_sample_step(logits.data_ptr<float>(), ldz, (int)V, (int)B, reinterpret_cast<const SampleParams*>(params.data_ptr<int>()),
+                     draws.data_ptr<int>(), seq_ids.data_ptr<int>(), finished.data_ptr<int>(), lengths.data_ptr<int64_t>(),
+                     tokens.data_ptr<int64_t>(), (int)tokens.size(1), next_ids.data_ptr<int64_t>(),
+                     n_kept.data_ptr<int>(), cur_stream());
+}
+
+// Test support: the integer weights of step 2 (int32 [B, V], values in [0, 2^24]) and the argmax (int32 [B]),
+// from a plain kernel that calls the inline functions sample_step calls.
+std::tuple<Tensor, Tensor> sample_weights(Tensor logits, int64_t V, double inv_t_log2e) {
+  const int64_t ldz = check_sample_logits(logits, V, "sample_weights");
+  const int64_t B = logits.size(0);
+  Tensor w = at::empty({B, V}, logits.options().dtype(at::kInt));
+  Tensor a = at::empty({B}, logits.options().dtype(at::kInt));
+  launch_sample_weights(logits.data_ptr<float>(), ldz, (int)V, (int)B, (float)inv_t_log2e, w.data_ptr<int>(),
+                        a.data_ptr<int>(), cur_stream());
+  return {w, a};
+}
+
 void attn_bwd(Tensor qkv, Tensor out, Tensor dout, Tensor lse, Tensor delta, c10::optional<Tensor> lens, Tensor dqkv,
               int64_t B, int64_t S, int64_t H, double scale, c10::optional<Tensor> colsum_out,
               bool colsum_accumulate, c10::optional<Tensor> q8_y, c10::optional<Tensor> q8_yt,
@@ -1803,6 +1863,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_fwd", &attn_fwd, py::arg("qkv"), py::arg("out"), py::arg("lse"), py::arg("lens"), py::arg("B"),
         py::arg("S"), py::arg("H"), py::arg("scale"), py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("site") = 0,
         py::arg("rank") = 0, py::arg("cu_seqlens") = py::none(), py::arg("causal") = false);
+  m.def("sample_step", &sample_step, py::arg("logits"), py::arg("V"), py::arg("params"), py::arg("draws"),
+        py::arg("seq_ids"), py::arg("finished"), py::arg("lengths"), py::arg("tokens"), py::arg("next_ids"),
+        py::arg("n_kept"));
+  m.def("sample_weights", &sample_weights, py::arg("logits"), py::arg("V"), py::arg("inv_t_log2e"));
   m.def("attn_decode", &attn_decode, py::arg("qkv_new"), py::arg("kv"), py::arg("pos"), py::arg("out"), py::arg("H"),
         py::arg("scale"));
   m.def("attn_bwd", &attn_bwd, py::arg("qkv"), py::arg("out"), py::arg("dout"), py::arg("lse"), py::arg("delta"),

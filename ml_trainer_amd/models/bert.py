@@ -70,8 +70,11 @@ head-major cache (``ops.decode.KVCache``: ``[2, B, H, Smax, 64]`` per layer) and
 LayerNorm) and returns fp32 logits; ``generate`` loops it with greedy, temperature / top-k sampling and an EOS
 mask. The position of every sequence lives on the device (ragged prompts continue at their own length) and no
 step reads anything back. On the CPU the same runs in fp32 torch with an fp32 cache;
-``generate_reference`` / ``decode_logits_reference`` are the uncached oracle. Not built: pre-LN blocks,
-hipGraph-captured decode, a weight-streaming decode GEMM, paged caches, beam search.
+``generate_reference`` / ``decode_logits_reference`` are the uncached oracle. Opt-in: ``sampler="device"`` (the
+``sample_step`` kernel of ``ops.decode``: top-k / top-p and the EOS bookkeeping in one launch, integer-defined,
+independent of the batch), ``top_p``, and ``graph=True`` (``GraphedDecoder``: one captured graph of ``decode_step`` +
+``sample_step`` replayed per token). Not built: pre-LN blocks, paged caches, beam search, repetition penalties,
+``return_logits`` under a graph, a graph for ``prefill``.
 """
 from __future__ import annotations
 
@@ -621,12 +624,14 @@ class BertLMHeadModel(BertForMaskedLM):
         return torch.arange(B, device=device) * S + last
 
     @torch.no_grad()
-    def prefill(self, input_ids, attention_mask=None, max_len: Optional[int] = None):
+    def prefill(self, input_ids, attention_mask=None, max_len: Optional[int] = None, cache=None):
         """Run the prompt ``input_ids`` [B, S] (right-padded; lengths from ``attention_mask`` or ``pad_id``)
         through the padded causal forward, layer by layer, keep every layer's K / V in a cache of ``max_len``
         rows per sequence (default ``config.max_position``) and return the ``DecodeState``: the cache with
         ``pos = lens`` and the hidden row of each sequence's last real token. No gradients and no dropout,
-        whatever mode the model is in; ``config.unpad`` has no effect (prompts are short)."""
+        whatever mode the model is in; ``config.unpad`` has no effect (prompts are short). ``cache``: an existing
+        ``KVCache`` of this shape to fill in place (its ``pos`` is overwritten with ``pos.copy_``, its tensors keep
+        their addresses: what a captured decode step needs) instead of a new one."""
         from ml_trainer_amd.ops import decode as DC
         c = self.config
         B, S = input_ids.shape
@@ -636,7 +641,12 @@ class BertLMHeadModel(BertForMaskedLM):
                              f"does not hold")
         dev = input_ids.device
         lens = self._lengths(input_ids, attention_mask)
-        cache = DC.KVCache.allocate(c.layers, B, c.heads, Smax, dev)
+        if cache is None:
+            cache = DC.KVCache.allocate(c.layers, B, c.heads, Smax, dev)
+        elif (cache.Smax != Smax or len(cache.kv) != c.layers or cache.pos.device != dev or
+              tuple(cache.kv[0].shape) != (2, B, c.heads, Smax, DC.HEAD_DIM)):
+            raise ValueError(f"prefill: the given cache does not hold {c.layers} layers of [2, {B}, {c.heads}, {Smax}, "
+                             f"{DC.HEAD_DIM}] on {dev}")
         if input_ids.is_cuda:
             from ml_trainer_amd.ops import transformer as T
             x = T.embeddings(input_ids, None, self.word_embeddings.weight, self.position_embeddings.weight,
@@ -715,8 +725,23 @@ class BertLMHeadModel(BertForMaskedLM):
         state.hidden = x
         return self._state_logits(state)
 
-    def _check_generate(self, input_ids, max_new_tokens, temperature, top_k):
+    def _check_generate(self, input_ids, max_new_tokens, temperature, top_k, top_p=None, sampler=None, graph=False,
+                        return_logits=False):
         S = input_ids.shape[1]
+        if sampler not in (None, "device"):
+            raise ValueError(f"sampler must be None (the torch sampler) or 'device', got {sampler!r}")
+        if top_p is not None:
+            from ml_trainer_amd.ops.decode import top_p_to_p16
+            if sampler != "device":
+                raise ValueError("top_p needs sampler='device' (the torch sampler has no nucleus sampling)")
+            top_p_to_p16(top_p)  # raises outside (0, 1] and where it rounds to 0 / 65536
+        if graph:
+            if sampler != "device":
+                raise ValueError("graph=True needs sampler='device': the torch sampler cannot be captured")
+            if return_logits:
+                raise ValueError("graph=True cannot return per-step logits (they live in the graph's buffers)")
+            if not input_ids.is_cuda:
+                raise ValueError("graph=True needs the prompts on a GPU")
         if max_new_tokens < 1:
             raise ValueError(f"max_new_tokens must be >= 1, got {max_new_tokens}")
         if temperature < 0:
@@ -761,10 +786,64 @@ class BertLMHeadModel(BertForMaskedLM):
         out = (torch.stack(tokens, 1), lengths)
         return out + (torch.stack(kept, 1),) if return_logits else out
 
+    def _new_sampler(self, B, T, dev, temperature, top_k, top_p, eos_id, seed):
+        from ml_trainer_amd.ops.decode import SamplerState
+        return SamplerState.allocate(B, T, dev, **self._sampler_params(temperature, top_k, top_p, eos_id, seed))
+
+    def _sampler_params(self, temperature, top_k, top_p, eos_id, seed):
+        """``SamplerState.set_params`` arguments of a ``generate`` call: the fill token is ``config.pad_id``
+        (``eos_id`` without one), an unseeded sampling run draws its seed from torch's host generator."""
+        fill = 0
+        if eos_id is not None:
+            fill = self.config.pad_id if self.config.pad_id is not None else eos_id
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if temperature > 0 else 0
+        return dict(seed=seed, temperature=temperature, top_k=top_k, top_p=top_p, eos_id=eos_id, fill_id=fill)
+
+    def _device_sampler_loop(self, first_logits, step, sampler, max_new_tokens, return_logits):
+        """``_generate_loop`` with the on-device sampler: ``sample_step`` (its torch reference on the CPU) draws
+        into ``sampler`` and does the EOS bookkeeping, ``step(sampler.next_ids)`` returns the next logits."""
+        from ml_trainer_amd.ops import decode as DC
+        sample = DC.sample_step if sampler.tokens.is_cuda else DC.sample_step_reference
+        V = self.config.vocab_size
+        kept = []
+        logits = first_logits()
+        for t in range(max_new_tokens):
+            sample(logits, V, sampler)
+            if return_logits:
+                kept.append(logits)
+            if t + 1 < max_new_tokens:
+                logits = step(sampler.next_ids)
+        out = (sampler.tokens, sampler.lengths)
+        return out + (torch.stack(kept, 1),) if return_logits else out
+
+    def _decode_signature(self):
+        """What a captured decode step baked in of the parameters: an in-place edit bumps ``_version`` (and makes
+        ``bf16_weight`` / ``padded_decoder`` hand out new tensors), a re-allocation moves ``data_ptr``."""
+        return tuple((p._version, p.data_ptr()) for p in self.parameters())
+
+    def _graphed_decoder(self, B, Smax, T, dev):
+        key = (B, Smax, T, str(dev))
+        decoders = self.__dict__.setdefault("_graphed_decoders", {})
+        dec = decoders.get(key)
+        sig = self._decode_signature()
+        if dec is None or dec.signature != sig:
+            decoders.pop(key, None)  # free the stale graph's buffers before the new capture
+            del dec
+            dec = decoders[key] = GraphedDecoder(self, B, Smax, T, dev, sig)
+            self._decode_graph_captures = self.decode_graph_captures + 1
+        return dec
+
+    @property
+    def decode_graph_captures(self) -> int:
+        """How many decode graphs this model has captured (``generate(graph=True)``)."""
+        return getattr(self, "_decode_graph_captures", 0)
+
     @torch.no_grad()
     def generate(self, input_ids, max_new_tokens: int, attention_mask=None, temperature: float = 0.0,
                  top_k: Optional[int] = None, eos_id: Optional[int] = None, seed: Optional[int] = None,
-                 return_logits: bool = False):
+                 return_logits: bool = False, top_p: Optional[float] = None, sampler: Optional[str] = None,
+                 graph: bool = False):
         """Continue the prompts ``input_ids`` [B, S] (right-padded, ragged lengths allowed: sequence b's new
         tokens continue at position ``len_b``) by ``max_new_tokens`` tokens with a key/value cache: one
         ``prefill``, then one ``decode_step`` per token. Returns ``(tokens [B, max_new_tokens], lengths [B])``,
@@ -774,12 +853,29 @@ class BertLMHeadModel(BertForMaskedLM):
         the ``top_k`` largest when given, from a device ``torch.Generator`` seeded with ``seed``. With ``eos_id`` a
         sequence that has emitted it produces ``config.pad_id`` (``eos_id`` without a pad id) from then on and
         ``lengths[b]`` counts its tokens up to and including the EOS; the loop still runs every step and never
-        reads from the device. Runs without gradients and without dropout in any mode."""
-        self._check_generate(input_ids, max_new_tokens, temperature, top_k)
+        reads from the device. Runs without gradients and without dropout in any mode.
+
+        ``sampler="device"`` (opt-in; ``None`` keeps the torch sampler and its random stream): every token comes
+        from ``ops.decode.sample_step``, one launch that samples and does the EOS bookkeeping on the device, with
+        an integer-defined result: seeded runs repeat bit for bit and a sequence's tokens do not depend on the batch
+        it is decoded in. ``top_p`` (nucleus sampling inside the top-k set, applied as ``round(top_p * 65536) /
+        65536``) needs it. ``graph=True`` (GPU, device sampler, no ``return_logits``) replays one captured graph
+        of ``decode_step`` + ``sample_step`` per token (``GraphedDecoder``); the graph is captured on the first call
+        of a shape and again after a parameter changed, and ``MLT_DECODE_GEMM`` is read when it is captured."""
+        self._check_generate(input_ids, max_new_tokens, temperature, top_k, top_p, sampler, graph, return_logits)
         B, S = input_ids.shape
+        dev = input_ids.device
+        if graph:
+            dec = self._graphed_decoder(B, S + max_new_tokens, max_new_tokens, dev)
+            return dec.generate(self, input_ids, attention_mask,
+                                self._sampler_params(temperature, top_k, top_p, eos_id, seed))
         state = self.prefill(input_ids, attention_mask, max_len=S + max_new_tokens)
+        if sampler == "device":
+            st = self._new_sampler(B, max_new_tokens, dev, temperature, top_k, top_p, eos_id, seed)
+            return self._device_sampler_loop(lambda: self.decode_step(state), lambda tok: self.decode_step(state, tok),
+                                             st, max_new_tokens, return_logits)
         return self._generate_loop(lambda: self.decode_step(state), lambda tok: self.decode_step(state, tok), B,
-                                   input_ids.device, max_new_tokens, temperature, top_k, eos_id, seed, return_logits)
+                                   dev, max_new_tokens, temperature, top_k, eos_id, seed, return_logits)
 
     @torch.no_grad()
     def decode_logits_reference(self, ids, lens):
@@ -797,9 +893,9 @@ class BertLMHeadModel(BertForMaskedLM):
     @torch.no_grad()
     def generate_reference(self, input_ids, max_new_tokens: int, attention_mask=None, temperature: float = 0.0,
                            top_k: Optional[int] = None, eos_id: Optional[int] = None, seed: Optional[int] = None,
-                           return_logits: bool = False):
+                           return_logits: bool = False, top_p: Optional[float] = None, sampler: Optional[str] = None):
         """``generate`` without any cache: ``forward_reference`` over the growing sequence, once per token."""
-        self._check_generate(input_ids, max_new_tokens, temperature, top_k)
+        self._check_generate(input_ids, max_new_tokens, temperature, top_k, top_p, sampler)
         B, S = input_ids.shape
         dev = input_ids.device
         lens = self._lengths(input_ids, attention_mask)
@@ -813,5 +909,76 @@ class BertLMHeadModel(BertForMaskedLM):
             grown[0] += 1
             return self.decode_logits_reference(ids[:, :S + grown[0]], lens + grown[0])
 
+        if sampler == "device":
+            st = self._new_sampler(B, max_new_tokens, dev, temperature, top_k, top_p, eos_id, seed)
+            return self._device_sampler_loop(lambda: self.decode_logits_reference(input_ids, lens), step, st,
+                                             max_new_tokens, return_logits)
         return self._generate_loop(lambda: self.decode_logits_reference(input_ids, lens), step, B, dev,
                                    max_new_tokens, temperature, top_k, eos_id, seed, return_logits)
+
+
+class GraphedDecoder:
+    """One captured decode loop body of a ``BertLMHeadModel`` for a fixed ``(B, Smax, T, device)``, and everything
+    the capture baked addresses of: the key/value cache (``prefill(cache=)`` refills it in place), the
+    ``SamplerState`` (``set_params`` / ``reset`` rewrite it in place) and, inside the graph's own memory pool, the
+    hidden rows and the logits buffer of a step. The body is ``decode_step(state, sampler.next_ids)`` followed by
+    ``sample_step`` on the logits it returns: token t's sampling closes replay t, so a generation is one eager
+    ``sample_step`` on the prompt's logits and ``T - 1`` replays. Captured on ONE side stream after one eager run
+    of the body on it: the graph is a linear chain of kernel nodes, no branches. ``signature`` is the model's
+    ``_decode_signature()`` at capture; the model recaptures when it no longer matches. ``MLT_DECODE_GEMM`` is
+    read while capturing. Not supported: ``return_logits``, a graph for ``prefill``."""
+
+    def __init__(self, model, B, Smax, T, dev, signature):
+        import time
+        from ml_trainer_amd.ops import decode as DC
+        c = model.config
+        self.signature = signature
+        self.B, self.Smax, self.T = B, Smax, T
+        self.cache = DC.KVCache.allocate(c.layers, B, c.heads, Smax, dev)
+        self.sampler = DC.SamplerState.allocate(B, T, dev)
+        self.state = DC.DecodeState(self.cache, None)
+        self.graph = None
+        self.capture_seconds = 0.0
+        if T < 2:
+            return  # a single token is the eager sample_step alone
+        V = c.vocab_size
+
+        def body():
+            DC.sample_step(model.decode_step(self.state, self.sampler.next_ids), V, self.sampler)
+
+        # The zeroed cache and sampler are a valid state (token 0 at position 0, column 0): the eager run warms the
+        # bf16 weight copies and the allocator, the capture records the same launches. Both leave marks in the
+        # state; every generation starts by resetting it.
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        stream = torch.cuda.Stream(dev)
+        stream.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(stream):
+            body()
+        torch.cuda.current_stream(dev).wait_stream(stream)
+        self.sampler.reset()
+        self.cache.pos.zero_()
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph, stream=stream):
+            body()
+        torch.cuda.synchronize(dev)
+        self.capture_seconds = time.perf_counter() - t0
+
+    def start(self, model, input_ids, attention_mask, params):
+        """Everything before the token loop: the sampler reset and given ``params`` (``SamplerState.set_params``
+        arguments), the prompt prefilled into the captured cache. Returns the prompt's logits."""
+        self.sampler.reset()
+        self.sampler.set_params(**params)
+        return model.decode_step(model.prefill(input_ids, attention_mask, max_len=self.Smax, cache=self.cache))
+
+    def run(self, model, first_logits):
+        """The token loop: one eager ``sample_step`` on the prompt's logits, then ``T - 1`` replays. Results are in
+        ``self.sampler`` (``tokens``, ``lengths``), which the next generation overwrites."""
+        from ml_trainer_amd.ops import decode as DC
+        DC.sample_step(first_logits, model.config.vocab_size, self.sampler)
+        for _ in range(self.T - 1):
+            self.graph.replay()
+
+    def generate(self, model, input_ids, attention_mask, params):
+        self.run(model, self.start(model, input_ids, attention_mask, params))
+        return self.sampler.tokens.clone(), self.sampler.lengths.clone()

@@ -13,10 +13,18 @@ per layer per prompt, not a hot path.
 ``linear_small`` is the linear layer of a decode step (M = B rows): ``decode_linear_path`` sends it to the
 weight-streaming kernel ``C.gemm_skinny`` (csrc/kernels/gemm_skinny.hip) or to the planner's GEMM. With the skinny
 kernel every kernel of a step works row by row, so a sequence's logits do not depend on the batch it is decoded in.
+
+``sample_step`` is the on-device sampler (csrc/kernels/sample.hip): greedy / temperature / top-k / top-p and the
+token / EOS bookkeeping of ``generate`` in one launch per step, over a ``SamplerState``. Its result is defined in
+integers (the definition is the header of csrc/include/mlt_sample.h and the docstring of
+``sample_step_reference``, the same function in plain torch and the CPU path), so it is bitwise reproducible
+and a row's tokens depend on ``(seed, seq_ids[b], draws[b])`` and its own logits only, never on the batch.
+``sample_tokens`` is the older torch sampler (one ``multinomial`` stream for the whole batch); it is unchanged.
 """
 from __future__ import annotations
 
 import os
+import struct
 from dataclasses import dataclass
 from typing import List, Optional
 
@@ -164,3 +172,190 @@ def sample_tokens(logits, temperature: float = 0.0, top_k: Optional[int] = None,
         kth = z.topk(top_k, dim=-1).values[:, -1:]
         z = torch.where(z < kth, torch.full_like(z, float("-inf")), z)
     return torch.multinomial(torch.softmax(z, -1), 1, generator=generator)[:, 0]
+
+
+# ----------------------------------------------------------------------------- the on-device sampler
+SAMPLE_SITE = 0x53414D50  # word 2 of the sampler's Philox counter (kSampleSite in mlt_sample.h)
+SAMPLE_ONE = 1 << 24      # the fixed-point weight of the row maximum
+_LOG2E = 1.4426950408889634
+
+
+def top_p_to_p16(top_p: Optional[float]) -> int:
+    """``p16 = round(top_p * 65536)``: the probability the sampler applies is ``p16 / 65536`` (``None`` = off =
+    65536). A ``top_p`` outside (0, 1], or one that rounds to 0 / 65536, is an error, not a silent greedy."""
+    if top_p is None:
+        return 65536
+    if not 0.0 < top_p <= 1.0:
+        raise ValueError(f"top_p must satisfy 0 < top_p <= 1, got {top_p}")
+    p16 = int(top_p * 65536.0 + 0.5)
+    if p16 == 0:
+        raise ValueError(f"top_p {top_p} rounds to 0 / 65536: no token would be kept (the smallest is 2 ** -16)")
+    return min(p16, 65536)
+
+
+@dataclass
+class SamplerState:
+    """What ``sample_step`` reads and writes, all on one device. ``params`` int32 [8] is the parameter block
+    (``SampleParams`` in mlt_sample.h: inv_t_log2e as fp32 bits, top_k, p16, seed_lo, seed_hi, eos_id, fill_id, 0);
+    per row: ``draws`` int32 (tokens drawn so far = the next output column), ``seq_ids`` int32 (the row's identity
+    in the random stream), ``finished`` int32, ``n_kept`` int32 (size of the last candidate set), ``lengths`` int64,
+    ``next_ids`` int64 (the last token: what the next decode step embeds) and ``tokens`` int64 [B, T]. ``host`` is
+    the parameter block as Python values (what the torch reference reads: nothing comes back from the device)."""
+    params: torch.Tensor
+    draws: torch.Tensor
+    seq_ids: torch.Tensor
+    finished: torch.Tensor
+    n_kept: torch.Tensor
+    lengths: torch.Tensor
+    next_ids: torch.Tensor
+    tokens: torch.Tensor
+    host: dict
+
+    @classmethod
+    def allocate(cls, B: int, T: int, device, seed: int = 0, temperature: float = 0.0, top_k: Optional[int] = None,
+                 top_p: Optional[float] = None, eos_id: Optional[int] = None, fill_id: int = 0,
+                 seq_ids=None) -> "SamplerState":
+        device = torch.device(device)
+        if B < 1 or T < 1:
+            raise ValueError(f"a sampler needs B >= 1 and T >= 1, got B = {B}, T = {T}")
+        i32 = dict(dtype=torch.int32, device=device)
+        if seq_ids is None:
+            ids = torch.arange(B, **i32)
+        else:
+            ids = torch.as_tensor(seq_ids, dtype=torch.int32).reshape(-1).to(device).contiguous()
+            if ids.numel() != B:
+                raise ValueError(f"seq_ids must have B = {B} entries, got {ids.numel()}")
+        st = cls(torch.zeros(8, **i32), torch.zeros(B, **i32), ids, torch.zeros(B, **i32), torch.zeros(B, **i32),
+                 torch.zeros(B, dtype=torch.int64, device=device), torch.zeros(B, dtype=torch.int64, device=device),
+                 torch.zeros(B, T, dtype=torch.int64, device=device), {})
+        st.set_params(seed, temperature, top_k, top_p, eos_id, fill_id)
+        return st
+
+    def set_params(self, seed: int = 0, temperature: float = 0.0, top_k: Optional[int] = None,
+                   top_p: Optional[float] = None, eos_id: Optional[int] = None, fill_id: int = 0) -> None:
+        """Rewrite the parameter block in place: one small host-to-device copy (call it outside a captured
+        region; a captured ``sample_step`` then samples with the new settings)."""
+        if temperature < 0:
+            raise ValueError(f"temperature must be >= 0, got {temperature}")
+        if top_k is not None and top_k < 1:
+            raise ValueError(f"top_k must be >= 1, got {top_k}")
+        p16 = top_p_to_p16(top_p)
+        # log2(e) / temperature in double, rounded once to fp32; 0 = greedy
+        s = 0.0 if temperature == 0 else torch.tensor(_LOG2E / temperature, dtype=torch.float64).float().item()
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.host = dict(inv_t_log2e=s, top_k=0 if top_k is None else int(top_k), p16=p16, seed=seed,
+                         eos_id=-1 if eos_id is None else int(eos_id), fill_id=int(fill_id))
+        words = struct.unpack("8i", struct.pack("<fiiIIiii", s, min(self.host["top_k"], 0x7FFFFFFF), p16,
+                                                seed & 0xFFFFFFFF, seed >> 32, self.host["eos_id"],
+                                                self.host["fill_id"], 0))
+        self.params.copy_(torch.tensor(words, dtype=torch.int32))
+
+    def reset(self) -> None:
+        """Start a new generation in the same buffers: no tokens drawn, nothing finished."""
+        for t in (self.draws, self.finished, self.n_kept, self.lengths, self.next_ids, self.tokens):
+            t.zero_()
+
+
+def _sample_logits_operand(logits, V: int):
+    """``logits`` as the kernel takes them: fp32, unit column stride, 16-byte aligned rows a multiple of 4 apart.
+    The [B, V] view of ``ops.mlm.decode_logits``'s padded buffer passes as it is; anything else is copied."""
+    B, Vr = logits.shape[0], -(-V // 4) * 4  # a row is read up to round_up(V, 4) columns
+    if (logits.dtype == torch.float32 and logits.stride(1) == 1 and logits.data_ptr() % 16 == 0 and
+            (B == 1 or (logits.stride(0) % 4 == 0 and logits.stride(0) >= Vr)) and
+            logits.storage_offset() + (B - 1) * logits.stride(0) + Vr <= logits.untyped_storage().nbytes() // 4):
+        return logits
+    buf = torch.zeros(logits.shape[0], -(-V // 4) * 4, dtype=torch.float32, device=logits.device)
+    buf[:, :V] = logits[:, :V]
+    return buf
+
+
+def sample_step(logits, V: int, state: SamplerState) -> None:
+    """One sampling step on the GPU (``C.sample_step``): row b's next token from ``logits[b, :V]`` (fp32; columns
+    past ``V`` may hold anything) into ``state.tokens[b, state.draws[b]]`` and ``state.next_ids[b]``, with the
+    EOS / ``finished`` / ``lengths`` bookkeeping. One launch, no allocation, nothing read back."""
+    require_native().sample_step(_sample_logits_operand(logits, V), V, state.params, state.draws, state.seq_ids,
+                                 state.finished, state.lengths, state.tokens, state.next_ids, state.n_kept)
+
+
+def sample_weights_reference(logits, V: int, inv_t_log2e: float):
+    """(w int64 [B, V], argmax int64 [B], zc fp32 [B, V]): steps 1-2 of the definition in plain torch, the weights
+    from ``torch.exp2`` in fp32 (the device's ``exp2f`` may differ from it in the last place: the tests feed the
+    reference the device's own weights where they compare tokens)."""
+    z = logits[:, :V].float()
+    nan = torch.isnan(z)
+    ninf = torch.full_like(z, float("-inf"))
+    zc = torch.where(nan, ninf, z)
+    zc = torch.where(zc == 0, torch.zeros_like(zc), zc)  # -0 counts as +0
+    m = zc.max(-1, keepdim=True).values
+    idx = torch.arange(V, device=z.device)
+    a = torch.where(zc == m, idx, torch.full_like(idx, V)).min(-1).values  # the first index of the maximum
+    s = torch.tensor(inv_t_log2e, dtype=torch.float32, device=z.device)
+    e = torch.exp2((zc - m) * s).clamp(max=1.0)  # one fp32 subtract, one fp32 multiply
+    w = torch.floor(e * 16777216.0)
+    w = torch.where(zc == m, torch.full_like(w, float(SAMPLE_ONE)), w)
+    w = torch.where(nan | torch.isnan(w), torch.zeros_like(w), w).to(torch.int64)
+    return w, a, zc
+
+
+def sample_step_reference(logits, V: int, state: SamplerState, weights=None) -> None:
+    """``sample_step`` in plain torch, on any device (the CPU path and the oracle's subject). Per row b, with
+    ``s = state.host["inv_t_log2e"]``:
+
+    1. NaN logits count as -inf, -0 as +0; ``m`` = the maximum, ``a`` = the smallest index attaining it. ``s == 0``:
+       the token is ``a`` (``n_kept`` = 1).
+    2. ``w_i = 2^24`` where ``z_i == m``, else ``floor(min(exp2(s * (z_i - m)), 1) * 2^24)`` in fp32; NaN columns
+       weigh 0. ``weights`` (int [B, V]) substitutes given ones. Everything below is int64 arithmetic.
+    3. ``T_k`` = the k-th largest logit with multiplicity, ``K = {z_i >= T_k}`` (ties kept); k = 0 or k >= V: all.
+    4. ``need = (p16 * W_K + 65535) >> 16``; ``T_p`` = the largest logit value t with ``sum_{K, z_i >= t} w_i >= need``;
+       ``S = {i in K: z_i >= T_p}``; p16 = 65536: ``S = K``. The probability applied is ``p16 / 65536``.
+    5. ``x`` = word 0 of philox4x32-10(counter (draws[b], seq_ids[b], 0x53414D50, 0), key = seed words),
+       ``r = ((x >> 8) * W_S) >> 24``, the token is the smallest i in S with ``sum_{j in S, j <= i} w_j > r``.
+    6. finished rows emit ``fill_id``; others add 1 to ``lengths`` and become finished on ``eos_id``; then
+       ``tokens[b, draws[b]] = next_ids[b] = token`` and ``draws[b] += 1``."""
+    from ml_trainer_amd.ops.dropout import philox4x32
+    h = state.host
+    dev = logits.device
+    B = logits.shape[0]
+    w, a, zc = sample_weights_reference(logits, V, h["inv_t_log2e"])
+    if weights is not None:
+        w = weights.to(device=dev, dtype=torch.int64)
+    token = a
+    kept = torch.ones(B, dtype=torch.int64, device=dev)
+    if h["inv_t_log2e"] != 0:
+        idx = torch.arange(V, device=dev)
+        big = torch.full_like(idx, V)
+        in_k = torch.ones_like(zc, dtype=torch.bool)
+        if 0 < h["top_k"] < V:
+            in_k = zc >= zc.topk(h["top_k"], dim=-1).values[:, -1:]
+        in_s = in_k
+        if h["p16"] < 65536:
+            wk = torch.where(in_k, w, torch.zeros_like(w))
+            need = (h["p16"] * wk.sum(-1, keepdim=True) + 65535) >> 16
+            zs, order = torch.sort(zc, dim=-1, descending=True)
+            cum = torch.cumsum(wk.gather(1, order), -1)
+            n_ge = torch.searchsorted((-zs).contiguous(), (-zs).contiguous(), right=True)  # |{j: z_j >= zs[p]}|
+            g = cum.gather(1, n_ge - 1)  # the weight of {i in K: z_i >= zs[p]}: non-decreasing in p
+            first = torch.where(g >= need, idx, big).min(-1, keepdim=True).values
+            t_p = zs.gather(1, first.clamp(max=V - 1))
+            t_p = torch.where(need > 0, t_p, torch.full_like(t_p, float("-inf")))
+            in_s = in_k & (zc >= t_p)
+        ws = torch.where(in_s, w, torch.zeros_like(w))
+        W = ws.sum(-1)
+        counter = torch.stack((state.draws.long() & 0xFFFFFFFF, state.seq_ids.long() & 0xFFFFFFFF,
+                               torch.full((B,), SAMPLE_SITE, dtype=torch.int64, device=dev),
+                               torch.zeros(B, dtype=torch.int64, device=dev)), -1)
+        key = torch.tensor([h["seed"] & 0xFFFFFFFF, h["seed"] >> 32], dtype=torch.int64, device=dev)
+        u24 = philox4x32(counter, key)[:, 0] >> 8
+        r = u24 * (W >> 24) + ((u24 * (W & 0xFFFFFF)) >> 24)  # (u24 * W) >> 24 without leaving int64
+        hit = torch.where(torch.cumsum(ws, -1) > r[:, None], idx, big).min(-1).values
+        token = torch.where(W > 0, hit, a)
+        kept = in_s.sum(-1)
+    fin = state.finished != 0
+    out = torch.where(fin, torch.full_like(token, h["fill_id"]), token)
+    state.lengths += (~fin).long()
+    state.finished |= ((~fin) & (token == h["eos_id"])).to(state.finished.dtype)
+    col = state.draws.long().clamp(0, state.tokens.shape[1] - 1)
+    state.tokens[torch.arange(B, device=dev), col] = out
+    state.next_ids.copy_(out)
+    state.draws += 1
+    state.n_kept.copy_(kept.to(state.n_kept.dtype))
