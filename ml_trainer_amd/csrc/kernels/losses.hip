@@ -44,7 +44,11 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const T* __restrict__ logit
         bi = c0 + __ffsll((long long)mask) - 1;
       }
       const float nm = fmaxf(m, cm);
-      s = s * __expf(m - nm) + wave_sum(c < C ? __expf(v - nm) : 0.f);
+      // -inf logits (a masked class; the lanes past C): while every logit so far is -inf, m == nm == -inf and
+      // both exponents would be -inf - -inf. The rescale factor is then 1 (as wherever the maximum does not
+      // move: __expf(0)), the lane's term 0, as torch has them.
+      const float r = (m == nm) ? 1.f : __expf(m - nm);
+      s = s * r + wave_sum(v == -INFINITY ? 0.f : __expf(v - nm));  // (a NaN logit still reaches the sum)
       m = nm;
     }
     const float lse = m + __logf(s);
@@ -66,7 +70,9 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const T* __restrict__ logit
     zt = wave_sum(zt);
     zsum = wave_sum(zsum);
     if (ok) {
-      loss = (1.f - label_smoothing) * (lse - zt) + label_smoothing * (lse - zsum / (float)C);
+      // without smoothing the mean-logit term is absent, not 0 * (lse - zsum / C): zsum is -inf with a -inf logit
+      const float sm = label_smoothing != 0.f ? label_smoothing * (lse - zsum / (float)C) : 0.f;
+      loss = (1.f - label_smoothing) * (lse - zt) + sm;
       valid = 1.f;
     }
     corr = (bi == t) ? 1.f : 0.f;

@@ -13,7 +13,15 @@ The other reference criteria (``src/trainer.py:143-148``: 'neg-loss' = NLL,
 the same file: fixed-order two-pass reductions (bitwise reproducible), the
 forward also writing the unscaled elementwise gradient, the backward one
 scale by grad_out / n. Differences from torch: a batch whose NLL targets are
-all ``ignore_index`` gives 0 instead of nan.
+all ``ignore_index`` gives 0 instead of nan; a target outside ``[0, C)`` (other
+than ``ignore_index``) is an error in torch and is treated as ignored here, by
+the cross-entropy and the NLL kernels alike: loss 0, gradient row 0, not
+counted in the denominator (and never a hit for ``accuracy``).
+
+``-inf`` logits (masked classes) follow torch: their gradient is exactly 0 and
+the loss stays finite while the target's own logit is finite (with
+``label_smoothing > 0`` it is ``+inf``, as in torch). A row that is entirely
+``-inf`` is unspecified.
 """
 from __future__ import annotations
 

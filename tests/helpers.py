@@ -726,3 +726,330 @@ def guarded_1d(n, dev, pad=64):
     assert pad % 4 == 0
     buf = sentinel((n + 2 * pad,), torch.float32, dev)
     return buf, buf[pad:pad + n]
+
+
+# ---------------------------------------------------------------------------------------------
+# Derived bounds of the loss and metric kernels (losses.hip): fused softmax-cross-entropy with its
+# backward, accuracy, the L1 / MSE / NLL criteria and mcrmse. tests/test_loss_bound_cpu.py checks them
+# against a torch fp32 emulation of the kernels on the CPU; tests/test_losses_edges_gpu.py uses them on
+# the GPU. Every reference is fp64 from the actual inputs (the bf16 points for bf16 logits, the fp32
+# values for fp32), `t` is the allowance on the kernel's fp32 value before its store, u = 2^-24.
+# ---------------------------------------------------------------------------------------------
+# __expf(x) lowers to v_exp_f32(x * log2e). Relative error allowed: _EXP2_REL + _EXPF_ARG_REL |x|: the
+# 2 ulp of v_exp_f32 that attention's bounds already use, plus the rounding of the product x * log2e and of
+# the fp32 constant log2e (2 u |x| in the base-e exponent), carried through the exponential.
+# __logf(s) lowers to v_log_f32(s) * ln2: absolute allowance _LOGF_ABS max(1, |log s|), the v_log_f32 term
+# attn_fwd_bound uses for t_LSE. NEITHER has been measured on the device: the lse-dependent headroom that
+# tests/test_losses_edges_gpu.py prints (and records in its docstring) is their record.
+_EXPF_ARG_REL = 2.0 ** -23
+_LOGF_ABS = 2.0 ** -21
+_F32_TINY = 2.0 ** -126  # below it a result may be flushed to zero
+
+# (B, C) of the cross-entropy edge cases: loss 0 and gradient 0 | a second block with one row and three idle
+# waves | exactly one chunk | a one-lane tail chunk | the special rows, 3 chunks with a 2-lane tail | the
+# special rows, 16 chunks | 65 chunks
+LOSS_CE_SHAPES = [(1, 1), (5, 10), (3, 64), (3, 65), (12, 130), (12, 1000), (2, 4099)]
+LOSS_CE_SMOOTHING = (0.0, 0.1)
+LOSS_CE_GRAD_OUT = (1.7, -0.5)
+LOSS_CE_TIE = 24.0  # planted maximum: 8 sigma of the 3 N(0, 1) logits, exact in bf16
+# (B, C) = (12, 130) and (12, 1000) carry the special rows (every other row is 3 N(0, 1) with a random target):
+#   0  ascending ramp z_c = 0.25 c: the running maximum rises in every chunk
+#   1  the same ramp reversed: the maximum is in the first chunk, every later term is rescaled by exactly 1
+#   2  -80 everywhere, +80 in column C / 2, the target one column to the right (loss 160, softmax one-hot)
+#   3  two-way tie at the maximum in columns 5 and 70 (two chunks), the target the FIRST tie (a hit)
+#   4  the same tie, the target the SECOND tie (a miss under the first-arg-max rule)
+#   5  columns 0..63 are -inf (the whole first chunk), target 100           } label_smoothing = 0 only: with
+#   6  columns 64..127 are -inf (the whole second chunk), target 3          } smoothing the loss is +inf in
+#      torch too, so under label_smoothing > 0 these two rows stay ordinary random rows
+#   7  the target in column C - 1
+#   8  target -100 (ignored)
+#   9  target C: out of range, which the kernel treats as ignored (loss 0, gradient 0, not in n_valid)
+#   10 two-way tie in columns 7 and 9 (one chunk), the target the first tie: with rows 3 and 4 an odd number
+#      of tie rows, so that a last-arg-max kernel changes the hit COUNT (3 -> 1 and 4 -> 0 alone would swap)
+#   11 ordinary; with an in-range ignore_index its target is that index
+LOSS_CE_SPECIAL = ((12, 130), (12, 1000))
+
+
+def ce_edge_inputs(B, C, dtype, label_smoothing=0.0, ignore_index=-100):
+    """(z [B, C] `dtype`, targets int64 [B]) of one cross-entropy case on the CPU; see LOSS_CE_SPECIAL. With an
+    in-range ignore_index the last row's target is that index (B > 1)."""
+    g = torch.Generator().manual_seed(1000 * B + C)
+    z = 3.0 * torch.randn(B, C, generator=g)
+    y = torch.randint(0, C, (B,), generator=g)
+    if (B, C) in LOSS_CE_SPECIAL:
+        col = torch.arange(C, dtype=torch.float32)
+        z[0], z[1] = 0.25 * col, 0.25 * (C - 1 - col)
+        z[2] = -80.0
+        z[2, C // 2] = 80.0
+        y[2] = C // 2 + 1
+        for r, (i1, i2, tgt) in {3: (5, 70, 5), 4: (5, 70, 70), 10: (7, 9, 7)}.items():
+            z[r, i1] = z[r, i2] = LOSS_CE_TIE
+            y[r] = tgt
+        if label_smoothing == 0.0:
+            z[5, :64] = float("-inf")
+            z[6, 64:128] = float("-inf")
+        y[5], y[6], y[7], y[8], y[9] = 100, 3, C - 1, -100, C
+    if ignore_index >= 0 and B > 1:
+        y[B - 1] = ignore_index
+    return z.to(dtype), y
+
+
+def _first_argmax(z):
+    """Smallest index holding the row maximum, by the explicit rule (no library arg-max)."""
+    C = z.shape[1]
+    idx = torch.arange(C).expand_as(z)
+    return torch.where(z == z.max(1, keepdim=True).values, idx, torch.full_like(idx, C)).min(1).values
+
+
+def ce_bound(z, targets, ignore_index=-100, label_smoothing=0.0, grad_out=1.0):
+    """(expected, t): dicts with loss (scalar), dl [B, C] (the unscaled gradient ce_fwd writes), grad [B, C] (what
+    ce_bwd stores); expected also holds ok [B] (rows that count) and n_valid. Kernels: ce_fwd_kernel (one wave per
+    row, n = ceil(C / 64) chunks), ce_finalize_kernel, ce_bwd_kernel.
+
+    Reference, per row, ls = label_smoothing as fp32 holds it: lse = log sum_c exp z_c,
+    loss_i = (1 - ls)(lse - z_t) + ls (lse - mean z) (the ls term absent at ls = 0, so that -inf logits keep a
+    finite loss as in torch), g = softmax - (1 - ls) onehot - ls / C, exactly 0 on rows that do not count
+    (target == ignore_index or outside [0, C)). Batch: n_valid, loss = sum_i loss_i / max(n_valid, 1),
+    grad = g grad_out / max(n_valid, 1), grad_out as fp32 holds it.
+
+    The sum s = sum_c exp(z_c - m). The kernel adds exp(v - nm_k) in chunk k and multiplies the running s by
+    exp(m_k - nm_k) in every later chunk; the exponents of one term's factors are all <= 0 and add up to
+    x_c = z_c - m. Relative error of s, the terms being positive (p_c = softmax):
+        rel_s = (n + 8) u ............................ per chunk step one rescale multiply and one add, the 6
+                                                       butterfly levels, two spare
+              + (rises + 1) _EXP2_REL ................. one v_exp_f32 per factor; where the maximum does not rise
+                                                       the factor is __expf(0) = 1 exactly (rises = the chunks
+                                                       after the first whose maximum exceeds the running one)
+              + 3 u sum_c p_c |x_c| ................... _EXPF_ARG_REL |x| and the rounding of every subtraction
+                                                       (u |x|), summed along a term's factors
+              + C 2^-126 .............................. terms flushed to zero (s >= 1)
+        t_lse = rel_s + _LOGF_ABS max(1, |log s|) + u |lse| ... log's slope 1 / s, __logf, the add m + log s
+    zsum: a lane chains n additions, the butterfly adds 6 levels: t_zsum = (n + 6) u sum |z|. z_t is exact.
+        t_loss_i = (1 - ls)(t_lse + u |lse - z_t|) + ls (t_lse + (t_zsum + u |zsum|) / C + u |lse - mean z|)
+                   + 2 u (|(1 - ls)(lse - z_t)| + |ls (lse - mean z)|) + u |loss_i|
+                   (each difference, 1 - ls, zsum / C, the two products, the final add)
+        t_loss = (sum_i t_loss_i + (ceil(B / 4) + 4) u sum_i |loss_i|) / n_valid + u |loss| ... the 4 rows of a
+                   block in fixed order, then one atomic per block in no fixed order; the count is exact; the divide
+    Gradient: p = __expf(v - lse) at the row's own lse error:
+        rel_p = t_lse + _EXP2_REL + 3 u |z_c - lse|
+        t_dl = p rel_p + u ((1 - ls) on + ls / C + |p - (1 - ls) on| + |g|) + 1e-30 ... 1 - ls, ls / C, the two
+                   subtractions; 1e-30 takes the values below the normal range
+        t_grad = t_dl |sc| + 2 u |grad| + 1e-30, sc = grad_out / n_valid ... the divide and the multiply
+    A -inf logit has p = 0 and g = -ls / C exactly; its terms enter no sum above."""
+    z = z.double()
+    B, C = z.shape
+    n = _ceil_div(C, 64)
+    ls = float(torch.tensor(float(label_smoothing), dtype=torch.float32))
+    go = float(torch.tensor(float(grad_out), dtype=torch.float32))
+    tg = targets.to(torch.int64)
+    ok = (tg != ignore_index) & (tg >= 0) & (tg < C)
+    fin = torch.isfinite(z)
+    m = z.max(1).values
+    x = z - m[:, None]
+    e = torch.exp(x)
+    s = e.sum(1)
+    lse = m + torch.log(s)
+    a = z - lse[:, None]
+    p = torch.exp(a)
+    zero = torch.zeros_like(z)
+    zp = torch.full((B, n * 64), float("-inf"), dtype=torch.float64)
+    zp[:, :C] = z
+    cm = zp.view(B, n, 64).max(2).values
+    rises = (cm[:, 1:] > torch.cummax(cm, 1).values[:, :-1]).sum(1).double()
+    rel_s = ((n + 8) * _U32 + (rises + 1) * _EXP2_REL + 3 * _U32 * torch.where(fin, e * x.abs(), zero).sum(1) / s
+             + C * _F32_TINY)
+    t_lse = rel_s + _LOGF_ABS * torch.log(s).abs().clamp_min(1.0) + _U32 * lse.abs()
+
+    on = torch.zeros_like(z)
+    on[ok, tg[ok]] = 1.0
+    gfull = p - (1 - ls) * on - ls / C
+    rel_p = t_lse[:, None] + _EXP2_REL + 3 * _U32 * torch.where(fin, a.abs(), zero)
+    t_dl = p * rel_p + _U32 * ((1 - ls) * on + ls / C + (p - (1 - ls) * on).abs() + gfull.abs()) + 1e-30
+    okc = ok[:, None]
+    dl = torch.where(okc, gfull, zero)
+    t_dl = torch.where(okc, t_dl, torch.full_like(z, 1e-30))
+    n_valid = int(ok.sum())
+    den = max(n_valid, 1)
+    sc = go / den
+    grad = dl * sc
+    t_grad = t_dl * abs(sc) + 2 * _U32 * grad.abs() + 1e-30
+
+    zt = z[torch.arange(B), tg.clamp(0, C - 1)]
+    hard = (1 - ls) * (lse - zt)
+    t_li = (1 - ls) * (t_lse + _U32 * (lse - zt).abs()) + 2 * _U32 * hard.abs()
+    li = hard
+    if ls != 0.0:
+        zsum = z.sum(1)
+        t_zsum = (n + 6) * _U32 * z.abs().sum(1)
+        soft = ls * (lse - zsum / C)
+        t_li = t_li + ls * (t_lse + (t_zsum + _U32 * zsum.abs()) / C + _U32 * (lse - zsum / C).abs()) + 2 * _U32 * soft.abs()
+        li = li + soft
+    t_li = t_li + _U32 * li.abs()
+    li, t_li = li[ok], t_li[ok]
+    loss = li.sum() / den
+    t_loss = (t_li.sum() + (_ceil_div(B, 4) + 4) * _U32 * li.abs().sum()) / den + _U32 * loss.abs() + 1e-30
+    return (dict(loss=loss, dl=dl, grad=grad, ok=ok, n_valid=n_valid, lse=lse),
+            dict(loss=t_loss, dl=t_dl, grad=t_grad, lse=t_lse))
+
+
+LOSS_ACC_B = (1, 5, 1000)
+LOSS_ACC_C = (1, 10, 65, 130)
+
+
+def accuracy_edge_inputs(B, C, dtype):
+    """(z [B, C] `dtype`, targets int64 [B]) on the CPU: 3 N(0, 1) logits (in bf16, ties at the maximum occur by
+    themselves in wide rows), random targets, and by the row index i (C >= 2):
+      i % 16 in (0, 8)  a planted two-way tie at the maximum (columns C / 3 and C - 1), the target the first tie: a hit
+      i % 16 == 4       the same tie, the target the second tie: a miss
+      i % 16 == 12      the same tie, the target neither (column 1 of C >= 4, else -100): a miss
+      i % 16 == 6       target -100: a miss that still counts in the denominator B
+    First ties outnumber second ties at B = 1 and B = 1000 (at B = 5 they are one each: a last-arg-max kernel
+    is invisible there)."""
+    g = torch.Generator().manual_seed(77 * B + C)
+    z = 3.0 * torch.randn(B, C, generator=g)
+    y = torch.randint(0, C, (B,), generator=g)
+    i = torch.arange(B)
+    if C >= 2:
+        i1, i2 = C // 3, C - 1
+        tie = (i % 4 == 0)
+        z[tie, i1] = LOSS_CE_TIE
+        z[tie, i2] = LOSS_CE_TIE
+        y[i % 8 == 0] = i1
+        y[i % 16 == 4] = i2
+        y[i % 16 == 12] = 1 if C >= 4 else -100
+    y[i % 16 == 6] = -100
+    return z.to(dtype), y
+
+
+def accuracy_expected(z, targets):
+    """(hits / B, t) of accuracy_kernel and of ce_fwd's fused `correct` output: a hit is a row whose FIRST index
+    holding the row maximum equals its target (explicit rule, computed where it is called: on the CPU). Every
+    block adds (its 0..4 hits) / B atomically: one rounded divide per block and ceil(B / 4) additions of a sum
+    that stays <= 1, hence t = (ceil(B / 4) + 2) u."""
+    B = z.shape[0]
+    hits = int((_first_argmax(z.double()) == targets.to(torch.int64)).sum())
+    return hits / B, (_ceil_div(B, 4) + 2) * _U32
+
+
+LOSS_REG_THREADS, LOSS_REG_MAX_BLOCKS = 256, 1024
+# (a block takes 1024 elements) one element | one block, a wave with an idle lane | one block, one thread on a
+# second trip | two blocks | 293 blocks: a second trip in the finalize block | the first n at which the block cap
+# holds (1024 blocks) and threads walk a second grid stride
+LOSS_POINTWISE_N = (1, 255, 257, 1025, 300001, 2 ** 20 + 5)
+LOSS_NLL_CASES = [(1, 1), (5, 3), (513, 7), (2 ** 20 + 5, 2)]
+LOSS_NLL_IGNORE = (-100, 1)
+# (3, 300): C above the finalize block's 256 threads; (257, 6): a second trip for one thread of every column
+LOSS_MCRMSE_CASES = [(1, 1), (3, 300), (257, 6), (5000, 2)]
+
+
+def reg_blocks(n):
+    """reg_blocks of losses.hip: one block per 1024 elements, at least 1, at most 1024."""
+    return min(max(_ceil_div(n, 4 * LOSS_REG_THREADS), 1), LOSS_REG_MAX_BLOCKS)
+
+
+def reg_geometry(n):
+    """(nb, depth) of the two-pass regression reductions over n terms: nb blocks; depth = the additions behind
+    the result: a thread's ceil(n / (256 nb)) chained terms, the 6-level butterfly, the 4-wave fixed-order sum,
+    then in the finalize block ceil(nb / 256) chained partials, butterfly and 4-wave sum again."""
+    nb = reg_blocks(n)
+    return nb, _ceil_div(n, LOSS_REG_THREADS * nb) + 6 + 4 + _ceil_div(nb, LOSS_REG_THREADS) + 6 + 4
+
+
+def pointwise_edge_inputs(n, dtype=torch.float32):
+    """(p `dtype`, t fp32) [n] on the CPU: N(0, 1); for n > 1 element 0 has p == t (sign(0) = 0, an exact zero term)."""
+    g = torch.Generator().manual_seed(n)
+    p, t = torch.randn(n, generator=g).to(dtype), torch.randn(n, generator=g)
+    if n > 1:
+        t[0] = p[0].float()
+    return p, t
+
+
+def pointwise_loss_bound(p, t, mode, grad_out=1.0):
+    """(expected, t) dicts with loss, g (the unscaled gradient the forward writes) and grad (the prediction's
+    gradient; the target's is its exact negation) of pointwise_loss_partial_kernel + loss_finalize_kernel +
+    loss_scale_grad_kernel. mode 0: mean |d|, g = sign(d) with sign(0) = 0; mode 1: mean d^2, g = 2 d; d = p - t.
+      t_loss = (depth + k) u sum(term) / n + u |loss| + 1e-30: depth = reg_geometry(n) additions of positive
+               terms; k = 1 for L1 (the rounding of d), 3 for MSE (d enters twice, the product); the divide by n
+      g: L1 exact (the rounded difference of two different floats keeps its sign); MSE u |2 d| (d's rounding)
+      grad = g grad_out / n: the divide, the multiply (and d's rounding for MSE): (2 | 3) u |grad| + 1e-30."""
+    d = p.double().reshape(-1) - t.double().reshape(-1)
+    n = d.numel()
+    go = float(torch.tensor(float(grad_out), dtype=torch.float32))
+    term, g, k = (d.abs(), torch.sign(d), 1) if mode == 0 else (d * d, 2 * d, 3)
+    _, depth = reg_geometry(n)
+    loss = term.sum() / n
+    grad = g * go / n
+    return (dict(loss=loss, g=g, grad=grad),
+            dict(loss=(depth + k) * _U32 * term.sum() / n + _U32 * loss.abs() + 1e-30,
+                 g=(0.0 if mode == 0 else _U32) * g.abs() + 1e-30, grad=(2 if mode == 0 else 3) * _U32 * grad.abs() + 1e-30))
+
+
+def nll_edge_inputs(B, C, ignore_index):
+    """(logp fp32 [B, C], targets int64 [B]) on the CPU. From 5 rows on: row 1 has the out-of-range target C,
+    row 2 the target -100, row 3 the target min(1, C - 1) (the in-range ignore_index of LOSS_NLL_IGNORE),
+    row 4 the target C - 1."""
+    g = torch.Generator().manual_seed(31 * B + C + (ignore_index & 0xFF))
+    logp = torch.log_softmax(2.0 * torch.randn(B, C, generator=g), 1)
+    y = torch.randint(0, C, (B,), generator=g)
+    if B >= 5:
+        y[1], y[2], y[3], y[4] = C, -100, min(1, C - 1), C - 1
+    return logp, y
+
+
+def nll_bound(logp, targets, ignore_index=-100):
+    """(expected, t): expected = dict(loss, ok [B], n_valid), t the allowance of the loss, for nll_partial_kernel +
+    loss_finalize_kernel: loss = sum over the rows that count of -logp[i, t_i] / max(n_valid, 1); a row counts when
+    its target is not ignore_index and inside [0, C); no row counting gives 0. The terms are exact, the count is a
+    sum of ones (exact): t = depth u sum |terms| / n_valid + u |loss| + 1e-30 with depth = reg_geometry(B).
+    The gradient needs no allowance: exactly fp32(-grad_out / n_valid) at the target of a counting row, 0 elsewhere
+    (nll_grad_expected)."""
+    lp = logp.double()
+    B, C = lp.shape
+    tg = targets.to(torch.int64)
+    ok = (tg != ignore_index) & (tg >= 0) & (tg < C)
+    terms = -lp[torch.arange(B), tg.clamp(0, C - 1)][ok]
+    den = max(int(ok.sum()), 1)
+    loss = terms.sum() / den
+    _, depth = reg_geometry(B)
+    return dict(loss=loss, ok=ok, n_valid=int(ok.sum())), depth * _U32 * terms.abs().sum() / den + _U32 * loss.abs() + 1e-30
+
+
+def nll_grad_expected(targets, C, ignore_index, grad_out):
+    """fp32 [B, C]: fp32(-grad_out) / fp32(max(n_valid, 1)), one correctly rounded divide, at the targets of the
+    rows that count; 0 elsewhere."""
+    tg = targets.to(torch.int64)
+    ok = (tg != ignore_index) & (tg >= 0) & (tg < C)
+    v = -torch.tensor(float(grad_out), dtype=torch.float32) / torch.tensor(float(max(int(ok.sum()), 1)), dtype=torch.float32)
+    out = torch.zeros(tg.numel(), C, dtype=torch.float32)
+    out[ok, tg[ok]] = v
+    return out
+
+
+def mcrmse_edge_inputs(B, C, zero_col=False):
+    """(p, t) fp32 [B, C] on the CPU; the columns' errors differ in scale (column c: (1 + c % 5) N(0, 1)), so that
+    the mean of the roots is not the root of the mean; zero_col: column 0 of p equals t's (an exact zero)."""
+    g = torch.Generator().manual_seed(5 * B + C)
+    t = torch.randn(B, C, generator=g)
+    p = t + torch.randn(B, C, generator=g) * (1.0 + (torch.arange(C) % 5).float())
+    if zero_col:
+        p[:, 0] = t[:, 0]
+    return p, t
+
+
+def mcrmse_bound(p, t):
+    """(expected, t) dicts with col [C] (colwise_mse_kernel's column means) and out (mcrmse_finalize_kernel).
+      col_c = sum_r d^2 / B, d = t - p: thread chains ceil(B / 256) terms, butterfly 6, 4-wave sum 4; d's rounding
+              twice and the product (3), the divide (1): rel_col = (ceil(B / 256) + 14) u
+      rmse_c = sqrt(col_c): half of rel_col, and u for sqrtf (correctly rounded under the build's flags: no
+              fast-math, so half an ulp): t_rmse = rmse (rel_col / 2 + u); sqrt(0) = 0 exactly
+      out = sum_c rmse_c / C: ceil(C / 256) + 10 additions of positive terms, the divide:
+              t = (sum t_rmse + (ceil(C / 256) + 10) u sum rmse) / C + u |out| + 1e-30."""
+    d = t.double() - p.double()
+    B, C = d.shape
+    col = (d * d).mean(0)
+    rel_col = (_ceil_div(B, LOSS_REG_THREADS) + 14) * _U32
+    rmse = torch.sqrt(col)
+    t_rmse = rmse * (rel_col / 2 + _U32)
+    out = rmse.mean()
+    t_out = (t_rmse.sum() + (_ceil_div(C, LOSS_REG_THREADS) + 10) * _U32 * rmse.sum()) / C + _U32 * out.abs() + 1e-30
+    return dict(col=col, out=out), dict(col=col * rel_col + 1e-30, out=t_out)

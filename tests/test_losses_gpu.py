@@ -4,6 +4,7 @@ import torch
 import torch.nn.functional as F
 
 from ml_trainer_amd.ops.losses import CrossEntropyLoss, accuracy
+from tests import helpers
 
 pytestmark = pytest.mark.gpu
 
@@ -22,15 +23,24 @@ def test_ce_forward_backward(dev, B, C, dtype, ls):
     torch.testing.assert_close(loss.float(), ref, rtol=1e-5, atol=1e-5)
     (loss * 1.7).backward()
     (ref * 1.7).backward()
-    tol = 1e-6 if dtype == torch.float32 else 1e-2
-    torch.testing.assert_close(z.grad.float(), z2.grad, rtol=tol, atol=tol)
+    if dtype == torch.float32:
+        torch.testing.assert_close(z.grad, z2.grad, rtol=1e-6, atol=1e-6)
+    # every element against fp64 within the derived bound (helpers.ce_bound): the mean-reduced gradient is at most
+    # 1.7 / B per element, so that a fixed 1e-2 passed an all-zero bf16 gradient; the bound is relative to each element
+    x, t = helpers.ce_bound(z.detach().cpu(), y.cpu(), -100, ls, 1.7)
+    helpers.assert_within(z.grad.cpu(), x["grad"], helpers.store_bound(x["grad"], t["grad"], dtype),
+                          f"ce gradient ({B},{C}) {dtype} ls {ls}")
+    if B * C > 1:
+        zero = torch.zeros_like(z.grad).cpu()
+        with pytest.raises(AssertionError):
+            helpers.assert_within(zero, x["grad"], helpers.store_bound(x["grad"], t["grad"], dtype), "zero gradient")
 
 
 def test_accuracy(dev):
     z = torch.randn(1000, 10, device=dev)
     y = torch.randint(0, 10, (1000,), device=dev)
-    ref = (z.argmax(-1) == y).float().mean()
-    torch.testing.assert_close(accuracy(z, y), ref)
+    hits, _ = helpers.accuracy_expected(z.cpu(), y.cpu())  # the explicit first-index rule, on the CPU
+    torch.testing.assert_close(accuracy(z, y).cpu(), torch.tensor(hits, dtype=torch.float32))
 
 
 @pytest.mark.parametrize("shape", [(1,), (37, 3), (4096, 5), (300001,)])
