@@ -114,12 +114,15 @@ __device__ __forceinline__ u32x4 ld16(const uint16_t* base, unsigned elem_off) {
 //               weight, as conv1: the dgrad output's x parity dx is in N)
 constexpr int kW1F = 0, kW2F = 4 * 512, kW2D = 11 * 512, kWimg = 26 * 512;
 // followed by the fc weights the per-sample kernel cannot read from the row-major shadow with 16-byte
-// lanes: every layer TRANSPOSED ([in][out], the backward-data B operand) and fc3 with its rows padded
-// to 8 elements; row pitches padded to 8 elements, padding zero. Sized for the largest config.
+// lanes: fc3 TRANSPOSED ([in][out], the backward-data B operand) and with its rows padded to 8
+// elements; row pitches padded to 8 elements, padding zero. Sized for the largest config. (The slots
+// of the transposed fc1 / fc2 copies keep their place but are retired: the per-sample kernel
+// transposes both in LDS, nothing reads them and -- since the fused update never refreshed them --
+// nothing writes them either; they stay zero.)
 constexpr int cmax(int a, int b) { return a > b ? a : b; }
 constexpr int cmin(int a, int b) { return a < b ? a : b; }
-constexpr int kFc1T = kWimg;               // [FLAT][F1]
-constexpr int kFc2T = kFc1T + 400 * 120;   // [F1][round8(F2)]
+constexpr int kFc1T = kWimg;               // [FLAT][F1] (retired)
+constexpr int kFc2T = kFc1T + 400 * 120;   // [F1][round8(F2)] (retired)
 constexpr int kFc3F = kFc2T + 120 * 88;    // [NC][round8(F2)]
 constexpr int kFc3T = kFc3F + 10 * 88;     // [F2][round8(NC)]
 constexpr int kWimgTot = kFc3T + 84 * 16;
@@ -1974,17 +1977,14 @@ __global__ __launch_bounds__(256) void lenet_mpack(const float* __restrict__ p, 
                                                   uint16_t* __restrict__ wimg, int64_t off_w1, int64_t off_w2,
                                                   int64_t off_w3, int64_t off_w4, int64_t off_w5) {
   using F = Fc<D>;
+  (void)off_w3;
+  (void)off_w4;
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i < n) shadow[i] = f32_to_bf16(p[i]);
   if (i < kWimg) {
     const int64_t src = wimg_src<D::C1, D::C2>((int)i, off_w1, off_w2);
     wimg[i] = src >= 0 ? f32_to_bf16(p[src]) : (uint16_t)0;
-  } else if (i < kFc2T) {  // fc1 transposed: [c][r] = W3[r][c]
-    const int e = (int)(i - kFc1T), cc = e / D::F1, r = e - cc * D::F1;
-    wimg[i] = cc < D::FLAT ? f32_to_bf16(p[off_w3 + (int64_t)r * D::FLAT + cc]) : (uint16_t)0;
-  } else if (i < kFc3F) {  // fc2 transposed [F1][P2T]
-    const int e = (int)(i - kFc2T), cc = e / F::P2T, r = e - cc * F::P2T;
-    wimg[i] = cc < D::F1 && r < D::F2 ? f32_to_bf16(p[off_w4 + (int64_t)r * D::F1 + cc]) : (uint16_t)0;
+  } else if (i < kFc3F) {  // (the retired transposed fc1 / fc2 slots: never read, never written)
   } else if (i < kFc3T) {  // fc3 row-padded [NC][P3F]
     const int e = (int)(i - kFc3F), r = e / F::P3F, cc = e - r * F::P3F;
     wimg[i] = r < D::NC && cc < D::F2 ? f32_to_bf16(p[off_w5 + (int64_t)r * D::F2 + cc]) : (uint16_t)0;
@@ -2003,7 +2003,7 @@ template <class D>
 __global__ __launch_bounds__(256) void lenet_mapply(LeNetPtrs P, LeNetOpt O, const unsigned* __restrict__ skip) {
   if (skip && __hip_atomic_load(skip, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u) return;
   using F = Fc<D>;
-  constexpr int C1 = D::C1, F1 = D::F1, F2 = D::F2, FLAT = D::FLAT;
+  constexpr int C1 = D::C1, F2 = D::F2;
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (e >= O.n) return;
   const int64_t step = P.stepinfo[0];
@@ -2029,12 +2029,6 @@ __global__ __launch_bounds__(256) void lenet_mapply(LeNetPtrs P, LeNetOpt O, con
     wi[w2f_slot(oc, ic, tap)] = hb;
     wi[w2d_slot(oc, ic, tap, 0)] = hb;
     wi[w2d_slot(oc, ic, tap, 1)] = hb;
-  } else if (e >= O.off[4] && e < O.off[4] + F1 * FLAT) {
-    const int i = (int)(e - O.off[4]), r = i / FLAT, cc = i - r * FLAT;
-    wi[kFc1T + cc * F1 + r] = hb;
-  } else if (e >= O.off[6] && e < O.off[6] + F2 * F1) {
-    const int i = (int)(e - O.off[6]), r = i / F1, cc = i - r * F1;
-    wi[kFc2T + cc * F::P2T + r] = hb;
   } else if (e >= O.off[8] && e < O.off[8] + D::NC * F2) {
     const int i = (int)(e - O.off[8]), r = i / F2, cc = i - r * F2;
     wi[kFc3F + r * F::P3F + cc] = hb;
