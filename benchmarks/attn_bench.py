@@ -5,7 +5,11 @@ next to ``F.scaled_dot_product_attention(dropout_p=P)``.
 as padded ``lens`` or, with ``--packed``, as one [T, 3D] matrix with ``cu_seqlens``; the SDPA columns stay
 the full-length run and the TFLOP/s count the full B x S x S work, so padded and packed compare by time.
 ``--causal``: the causal instantiations of the native kernels next to ``F.scaled_dot_product_attention(
-is_causal=True)``; the TFLOP/s still count the full B x S x S work, so causal and non-causal compare by time."""
+is_causal=True)``; the TFLOP/s still count the full B x S x S work, so causal and non-causal compare by time.
+``--rope``: times ``rope_qk`` (rotary positions on the q and k columns of the QKV buffer, in place) alone and nothing
+else, at B 512, S 512, H 12 unless ``ATTN_B`` / ``ATTN_S`` say otherwise: microseconds per launch, forward and
+backward sign, the bytes it moves computed from the shapes (2 x rows x 2D x 2: q and k read once and written once;
+1.6 GB, six times the last-level cache) over that time, and the share of the 6.3 TB/s streaming rate."""
 import argparse
 import json
 import os
@@ -22,6 +26,7 @@ ap.add_argument("--dropout", type=float, default=0.0, help="attention-probabilit
 ap.add_argument("--min-len", type=int, default=0, help="variable-length sequences, lengths in [min-len, S]")
 ap.add_argument("--packed", action="store_true", help="packed rows + cu_seqlens instead of padded rows + lens")
 ap.add_argument("--causal", action="store_true", help="causal attention (key <= query), SDPA with is_causal=True")
+ap.add_argument("--rope", action="store_true", help="time rope_qk alone (B 512 unless ATTN_B is set)")
 ARGS = ap.parse_args()
 P = ARGS.dropout
 DROP = dict(p=P, seed=0x123456789ABCDEF, site=0x40000000, rank=0) if P > 0 else {}
@@ -43,6 +48,24 @@ def timeit(fn, iters=20):
     e.synchronize()
     return s.elapsed_time(e) / iters
 
+
+if ARGS.rope:
+    from ml_trainer_amd.ops.rope import rope_table
+    B = int(os.environ.get("ATTN_B", 512))
+    rows = B * S
+    table = rope_table(S, 10000.0, dev)
+    buf = torch.randn(rows, 3 * D, device=dev, dtype=torch.bfloat16)
+    pos = (torch.arange(rows, device=dev) % S).to(torch.int32)
+    nbytes = 2 * rows * 2 * D * 2
+    t = {"fwd": timeit(lambda: C.rope_qk(buf, table, H, S)),
+         "bwd": timeit(lambda: C.rope_qk(buf, table, H, S, sign=-1)),
+         "fwd_pos": timeit(lambda: C.rope_qk(buf, table, H, S, pos=pos))}
+    rec = {"bench": "rope_qk", "B": B, "S": S, "H": H, "rows": rows, "bytes": nbytes,
+           **{f"{k_}_us": round(v_ * 1e3, 2) for k_, v_ in t.items()},
+           **{f"{k_}_tb_per_s": round(nbytes / v_ * 1e-9, 3) for k_, v_ in t.items()},
+           **{f"{k_}_share_of_6.3": round(nbytes / v_ * 1e-9 / 6.3, 3) for k_, v_ in t.items()}}
+    print(json.dumps(rec), flush=True)
+    sys.exit(0)
 
 qkv = torch.randn(B * S, 3 * D, device=dev).to(torch.bfloat16)
 dout = torch.randn(B * S, D, device=dev).to(torch.bfloat16)

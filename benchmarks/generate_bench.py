@@ -27,6 +27,8 @@ region) in one process: eager with the torch sampler, eager with ``sample_step``
 ``--sampler device`` / ``--graph`` select the loop of ``--trace-steps`` (the workload of a profiler run).
 ``--ab`` alternates the cached decode between ``MLT_DECODE_GEMM=0`` (the planner's GEMMs: the launches before the
 skinny kernel) and ``1`` in one process and reports both medians and the spread of the ``0`` runs.
+``--rotary`` builds the model of the model timings with rotary positions (``BertConfig.rotary``) instead of the learned
+position table; the records carry ``"rotary"``.
 Random weights and prompts (no network)."""
 from __future__ import annotations
 
@@ -51,10 +53,15 @@ def _sync_ms(fn):
     return (time.perf_counter() - t0) * 1e3
 
 
-def bench_model(args, dev):
+def _model(args, dev):
     from ml_trainer_amd.models.bert import BertLMHeadModel, bert_config
     torch.manual_seed(0)
-    m = BertLMHeadModel(bert_config(args.model)).to(dev).eval()
+    over = {"rotary": True} if args.rotary else {}
+    return BertLMHeadModel(bert_config(args.model, **over)).to(dev).eval()
+
+
+def bench_model(args, dev):
+    m = _model(args, dev)
     V, P, N = m.config.vocab_size, args.prompt, args.new
     recs = []
     for B in [int(b) for b in args.batch.split(",")]:
@@ -105,7 +112,7 @@ def bench_model(args, dev):
             if not args.no_uncached:
                 t_unc.append(_sync_ms(uncached) / (N - 1))
         ms = statistics.median(t_dec[settings[-1]])
-        rec = {"bench": "generate", "model": args.model, "batch": B, "prompt": P, "new": N,
+        rec = {"bench": "generate", "model": args.model, "rotary": bool(args.rotary), "batch": B, "prompt": P, "new": N,
                "decode_gemm": settings[-1],
                "prefill_ms": statistics.median(t_pre), "cached_ms_per_token": ms, "cached_tokens_per_s": B / ms * 1e3,
                "uncached_ms_per_token": statistics.median(t_unc) if t_unc else None,
@@ -129,9 +136,7 @@ def _spread(runs):
 def bench_sampler_ab(args, dev):
     """(eager, torch sampler) = the path before the device sampler, (eager, device sampler), (graph, device sampler),
     alternated in one process. A timed region is the token loop alone; prefill and capture are outside it."""
-    from ml_trainer_amd.models.bert import BertLMHeadModel, bert_config
-    torch.manual_seed(0)
-    m = BertLMHeadModel(bert_config(args.model)).to(dev).eval()
+    m = _model(args, dev)
     V, P, N = m.config.vocab_size, args.prompt, args.new
     recs = []
     for B in [int(b) for b in args.batch.split(",")]:
@@ -172,7 +177,8 @@ def bench_sampler_ab(args, dev):
                 for k, pre, run in modes:
                     pre()
                     t[k].append(_sync_ms(run) / (N - 1))
-            rec = {"bench": "generate_sampler_ab", "model": args.model, "batch": B, "prompt": P, "new": N,
+            rec = {"bench": "generate_sampler_ab", "model": args.model, "rotary": bool(args.rotary), "batch": B,
+                   "prompt": P, "new": N,
                    "setting": name, "capture_s": dec.capture_seconds}
             for k in t:
                 rec[k + "_ms_per_token"] = statistics.median(t[k])
@@ -313,6 +319,7 @@ def main():
     ap.add_argument("--sampler-kernel", action="store_true", help="time sample_step against sample_tokens alone")
     ap.add_argument("--sampler-ab", action="store_true",
                     help="alternate (eager, torch sampler), (eager, device sampler), (graph, device sampler)")
+    ap.add_argument("--rotary", action="store_true", help="rotary positions in the model timings")
     ap.add_argument("--heads", type=int, default=12)
     ap.add_argument("--smax", type=int, default=256)
     ap.add_argument("--pos", type=int, default=255)

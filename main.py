@@ -17,7 +17,9 @@ large), ``--synthetic``, ``--per_device_batch``, ``--no_engine``,
 ``--no_parallel``, ``--resume``, ``--amp bf16``, ``--precision bf16``, ``--metrics_jsonl``, ``--log_jsonl``, ``--zero_stage``, ``--async_checkpoint``,
 ``--dropout`` (BERT hidden dropout), ``--attention_dropout`` (BERT attention-probability dropout,
 inside the flash attention kernels; applied as round(p * 256) / 256), ``--unpad`` (BERT: drop the pad
-tokens before the embeddings and run the encoder on the real tokens only), ``--min_seq_len L``
+tokens before the embeddings and run the encoder on the real tokens only), ``--rotary`` / ``--rope_base`` (BERT,
+any ``--task``: rotary position embeddings on the queries and keys instead of the learned position table),
+``--min_seq_len L``
 (variable-length synthetic text, lengths uniform in [L, seq_len], right-padded with ``--pad_id``), ``--optimizer lamb`` (layer-wise trust ratios on the flat buffer) and
 ``--no_decay_1d`` (adamw / lamb: biases and LayerNorm parameters take no weight decay), ``--task mlm``
 (BERT masked-LM pre-training on synthetic masked text: criterion ``mlm``, ``--metric accuracy`` is the
@@ -82,6 +84,12 @@ def build_model_and_datasets(args):
         raise ValueError("--attention_dropout applies to the BERT models; the LeNet models have no attention")
     if lenet and args.unpad:
         raise ValueError("--unpad applies to the BERT models; the LeNet models have no sequences to unpad")
+    if lenet and (args.rotary or args.rope_base is not None):
+        raise ValueError("--rotary / --rope_base apply to the BERT models; the LeNet models have no positions")
+    if args.rope_base is not None and not args.rotary:
+        raise ValueError("--rope_base applies to --rotary")
+    if args.rope_base is not None and not args.rope_base > 0:
+        raise ValueError(f"--rope_base must be > 0, got {args.rope_base}")
     if lenet and args.min_seq_len is not None:
         raise ValueError("--min_seq_len applies to the synthetic text data of the BERT models")
     mlm = args.task == "mlm"
@@ -109,6 +117,10 @@ def build_model_and_datasets(args):
         over["attention_dropout"] = args.attention_dropout
     if args.unpad:
         over["unpad"] = True
+    if args.rotary:
+        over["rotary"] = True
+        if args.rope_base is not None:
+            over["rope_base"] = args.rope_base
     pad_id = args.pad_id if args.pad_id is not None else (0 if args.min_seq_len is not None else None)
     if pad_id is not None and not lenet:
         over["pad_id"] = pad_id
@@ -249,6 +261,14 @@ def build_parser() -> argparse.ArgumentParser:
                         help="BERT: drop the pad tokens once, before the embeddings, and run the encoder on the real "
                              "tokens only (needs lengths: --pad_id / --min_seq_len; one small device-to-host read "
                              "per forward; not with the fp8 `large` model). An error for the LeNet models")
+    parser.add_argument("--rotary", action="store_true",
+                        help="BERT, any --task: rotary position embeddings (queries and keys rotated by their "
+                             "position, attention scores depend on i - j only) instead of the learned position "
+                             "table; the model then has no position_embeddings.weight (not with the fp8 `large` "
+                             "preset). An error for the LeNet models")
+    parser.add_argument("--rope_base", type=float, default=None,
+                        help="--rotary: the base of the angles, position p and pair i turn by "
+                             "p * base ** (-2 i / 64) (default: 10000)")
     parser.add_argument("--min_seq_len", type=int, default=None,
                         help="BERT synthetic data: variable-length rows, lengths uniform in [min_seq_len, seq_len], "
                              "right-padded with --pad_id (default: fixed length)")

@@ -961,11 +961,12 @@ void ln_bwd(Tensor DY, Tensor X, Tensor gamma, Tensor mean, Tensor rstd, Tensor 
 
 // pos (packed batches): int32 [rows], the position of every token inside its own sequence (< S);
 // without it the batch is padded [B, S] and pos = row % S
-void embed_fwd(Tensor ids, c10::optional<Tensor> tt, Tensor Ww, Tensor Wp, Tensor Wt, Tensor out, int64_t S,
-               c10::optional<Tensor> pos) {
+// Wp None (rotary positions): no position table, out = word + type
+void embed_fwd(Tensor ids, c10::optional<Tensor> tt, Tensor Ww, c10::optional<Tensor> Wp, Tensor Wt, Tensor out,
+               int64_t S, c10::optional<Tensor> pos) {
   const int64_t rows = ids.numel(), D = Ww.size(1);
   TORCH_CHECK(D % 256 == 0 && D <= 1024, "embedding width must be a multiple of 256 (<= 1024)");
-  TORCH_CHECK(S > 0 && S <= Wp.size(0), "sequence length vs position table");
+  TORCH_CHECK(S > 0 && (!Wp.has_value() || S <= Wp->size(0)), "sequence length vs position table");
   const int* pp = nullptr;
   if (pos.has_value()) {
     check_dev(*pos, "pos", at::kInt, rows, 4);
@@ -981,21 +982,22 @@ void embed_fwd(Tensor ids, c10::optional<Tensor> tt, Tensor Ww, Tensor Wp, Tenso
     tp = tt->data_ptr<int64_t>();
   }
   check_bf16_2d(Ww, "word_emb", Ww.size(0), D);
-  check_bf16_2d(Wp, "pos_emb", Wp.size(0), D);
+  if (Wp.has_value()) check_bf16_2d(*Wp, "pos_emb", Wp->size(0), D);
   check_bf16_2d(Wt, "type_emb", Wt.size(0), D);
   TORCH_CHECK(Wt.size(0) <= 2, "at most 2 token types");
   check_bf16_2d(out, "out", rows, D);
-  launch_embed_fwd(ids.data_ptr<int64_t>(), tp, bf16_ptr(Ww), bf16_ptr(Wp), bf16_ptr(Wt), (uint16_t*)out.data_ptr(),
-                   rows, (int)S, (int)D, Ww.size(0), (int)Wt.size(0), cur_stream(), pp);
+  launch_embed_fwd(ids.data_ptr<int64_t>(), tp, bf16_ptr(Ww), Wp.has_value() ? bf16_ptr(*Wp) : nullptr, bf16_ptr(Wt),
+                   (uint16_t*)out.data_ptr(), rows, (int)S, (int)D, Ww.size(0), (int)Wt.size(0), cur_stream(), pp);
 }
 
 // cu_seqlens (packed batches): int32 [B + 1] on the device, sequence b = rows cu[b] .. cu[b + 1] (each at
 // most S long, cu[B] <= rows); without it the batch is padded [B, S]
-void embed_bwd(Tensor sid, Tensor perm, c10::optional<Tensor> tt, Tensor DX, Tensor gw, Tensor gp, Tensor gt,
-               Tensor part, int64_t S, c10::optional<Tensor> cu_seqlens) {
+// gp None (rotary positions): no position table, no position gradient is written
+void embed_bwd(Tensor sid, Tensor perm, c10::optional<Tensor> tt, Tensor DX, Tensor gw, c10::optional<Tensor> gp,
+               Tensor gt, Tensor part, int64_t S, c10::optional<Tensor> cu_seqlens) {
   const int64_t rows = sid.numel(), D = gw.size(1);
   TORCH_CHECK(D % 256 == 0 && D <= 1024, "embedding width");
-  TORCH_CHECK(S > 0 && S <= gp.size(0), "sequence length vs position table");
+  TORCH_CHECK(S > 0 && (!gp.has_value() || S <= gp->size(0)), "sequence length vs position table");
   const int* cu = nullptr;
   int64_t Bc = 0;
   if (cu_seqlens.has_value()) {
@@ -1015,13 +1017,46 @@ void embed_bwd(Tensor sid, Tensor perm, c10::optional<Tensor> tt, Tensor DX, Ten
   }
   check_bf16_2d(DX, "DX", rows, D);
   check_dev(gw, "gw", at::kFloat, gw.size(0) * D, 16);
-  check_dev(gp, "gp", at::kFloat, gp.size(0) * D, 16);
+  if (gp.has_value()) check_dev(*gp, "gp", at::kFloat, gp->size(0) * D, 16);
   check_dev(gt, "gt", at::kFloat, gt.size(0) * D);
   TORCH_CHECK(gt.size(0) <= 2, "at most 2 token types");
   check_dev(part, "part", at::kFloat, S * 2 * D, 16);
   launch_embed_bwd(sid.data_ptr<int64_t>(), perm.data_ptr<int64_t>(), tp, bf16_ptr(DX), gw.data_ptr<float>(),
-                   gp.data_ptr<float>(), gt.data_ptr<float>(), part.data_ptr<float>(), rows, (int)S, (int)D,
-                   gw.size(0), (int)gt.size(0), cur_stream(), cu, (int)Bc);
+                   gp.has_value() ? gp->data_ptr<float>() : nullptr, gt.data_ptr<float>(), part.data_ptr<float>(), rows,
+                   (int)S, (int)D, gw.size(0), (int)gt.size(0), cur_stream(), cu, (int)Bc);
+}
+
+// Rotary position embedding of the q and k columns of qkv [rows, 3 * H * 64] in place (rope.hip). qkv may be a
+// row-strided view (as attn_decode's qkv_new). table fp32 [P, 32, 2]. The position of a row is pos[row] (int32
+// [rows] on the device; clamped into the table in the kernel, checked there in debug builds) or, without pos,
+// row % S with S <= P. sign = +1: the rotation, -1: the inverse rotation (the backward, on dQKV).
+void rope_qk(Tensor qkv, Tensor table, int64_t H, int64_t S, c10::optional<Tensor> pos, int64_t sign) {
+  TORCH_CHECK(qkv.is_cuda() && qkv.dim() == 2 && qkv.scalar_type() == at::kBFloat16,
+              "rope_qk: qkv must be a bf16 [rows, 3 * H * 64] device tensor");
+  const int64_t rows = qkv.size(0), D = H * 64;
+  TORCH_CHECK(H > 0 && H <= 65535, "rope_qk: heads");
+  TORCH_CHECK(qkv.size(1) == 3 * D, "rope_qk: qkv has ", qkv.size(1), " columns, expected 3 * H * 64 = ", 3 * D);
+  TORCH_CHECK(sign == 1 || sign == -1, "rope_qk: sign must be +1 or -1, got ", sign);
+  check_dev(table, "rope table", at::kFloat, 64, 16);
+  TORCH_CHECK(table.dim() == 3 && table.size(1) == 32 && table.size(2) == 2, "rope_qk: table must be [P, 32, 2]");
+  const int64_t P = table.size(0);
+  TORCH_CHECK(P <= 0x7fffffff, "rope_qk: table rows");
+  if (rows == 0) return;
+  TORCH_CHECK(qkv.stride(1) == 1 && qkv.stride(0) >= 3 * D && qkv.stride(0) % 8 == 0,
+              "rope_qk: qkv needs unit column stride and a row stride that is a multiple of 8");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(qkv.data_ptr()) % 16 == 0, "rope_qk: qkv must be 16-byte aligned");
+  TORCH_CHECK(rows * H * 8 <= 0x7fffffff, "rope_qk: ", rows, " rows x ", H, " heads exceed the kernel's index range");
+  const int* pp = nullptr;
+  if (pos.has_value()) {
+    check_dev(*pos, "pos", at::kInt, rows, 4);
+    TORCH_CHECK(pos->numel() == rows, "rope_qk: pos must have one entry per row");
+    pp = pos->data_ptr<int>();
+    S = 1;
+  } else {
+    TORCH_CHECK(S > 0 && S <= P, "rope_qk: sequence length ", S, " vs a table of ", P, " positions");
+  }
+  launch_rope_qk((uint16_t*)qkv.data_ptr(), qkv.stride(0), rows, (int)H, table.data_ptr<float>(), (int)P, (int)S, pp,
+                 (int)sign, cur_stream());
 }
 
 static const int* lens_ptr(const c10::optional<Tensor>& lens, int64_t B) {
@@ -1068,7 +1103,10 @@ void attn_fwd(Tensor qkv, Tensor out, Tensor lse, c10::optional<Tensor> lens, in
 // Single-token attention over one layer's cache kv [2, B, H, Smax, 64], the append of the new token fused in
 // (attn_decode.hip). qkv_new [B, 3 * H * 64] may be a row-strided view. pos int32 [B] stays on the device:
 // pos[b] < Smax cannot be checked here without a read (debug builds check it in the kernel, MLT_DCHECK).
-void attn_decode(Tensor qkv_new, Tensor kv, Tensor pos, Tensor out, int64_t H, double scale) {
+// rope (fp32 [P >= Smax, 32, 2], the table of ops/rope.py): the ROPE instantiation, q and the new k rotated by
+// pos[b] and rounded to bf16 before use; None: the kernel without rotation.
+void attn_decode(Tensor qkv_new, Tensor kv, Tensor pos, Tensor out, int64_t H, double scale,
+                 c10::optional<Tensor> rope) {
   TORCH_CHECK(qkv_new.is_cuda() && qkv_new.dim() == 2 && qkv_new.scalar_type() == at::kBFloat16,
               "attn_decode: qkv_new must be a bf16 [B, 3 * H * 64] device tensor");
   const int64_t B = qkv_new.size(0), D = H * 64;
@@ -1087,8 +1125,15 @@ void attn_decode(Tensor qkv_new, Tensor kv, Tensor pos, Tensor out, int64_t H, d
   check_dev(pos, "pos", at::kInt, B, 4);
   TORCH_CHECK(pos.numel() == B, "attn_decode: pos must have one entry per sequence");
   check_bf16_2d(out, "out", B, D);
+  const float* rp = nullptr;
+  if (rope.has_value()) {
+    check_dev(*rope, "rope table", at::kFloat, 64, 16);
+    TORCH_CHECK(rope->dim() == 3 && rope->size(1) == 32 && rope->size(2) == 2 && rope->size(0) >= Smax,
+                "attn_decode: the rope table must be [P >= Smax = ", Smax, ", 32, 2]");
+    rp = rope->data_ptr<float>();
+  }
   launch_attn_decode(bf16_ptr(qkv_new), qkv_new.stride(0), (uint16_t*)kv.data_ptr(), pos.data_ptr<int>(),
-                     (uint16_t*)out.data_ptr(), (int)B, (int)H, (int)Smax, (float)scale, cur_stream());
+                     (uint16_t*)out.data_ptr(), (int)B, (int)H, (int)Smax, (float)scale, cur_stream(), rp);
 }
 
 // The logits operand of the sampling kernels: fp32 [B, >= V] with unit column stride, a row stride ldz % 4 == 0
@@ -1868,7 +1913,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("n_kept"));
   m.def("sample_weights", &sample_weights, py::arg("logits"), py::arg("V"), py::arg("inv_t_log2e"));
   m.def("attn_decode", &attn_decode, py::arg("qkv_new"), py::arg("kv"), py::arg("pos"), py::arg("out"), py::arg("H"),
-        py::arg("scale"));
+        py::arg("scale"), py::arg("rope") = py::none());
+  m.def("rope_qk", &rope_qk, py::arg("qkv"), py::arg("table"), py::arg("H"), py::arg("S"), py::arg("pos") = py::none(),
+        py::arg("sign") = 1);
   m.def("attn_bwd", &attn_bwd, py::arg("qkv"), py::arg("out"), py::arg("dout"), py::arg("lse"), py::arg("delta"),
         py::arg("lens"), py::arg("dqkv"), py::arg("B"), py::arg("S"), py::arg("H"), py::arg("scale"),
         py::arg("colsum_out") = py::none(), py::arg("colsum_accumulate") = false, py::arg("q8_y") = py::none(),

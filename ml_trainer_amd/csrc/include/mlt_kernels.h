@@ -332,7 +332,9 @@ void launch_ln_bwd_dropout(const uint16_t* DY, const uint16_t* X, const float* g
                            hipStream_t st);
 // out = keep ? bf16(x * scale) : 0 over numel (% 8 == 0) contiguous bf16 elements (dropout.hip)
 void launch_dropout(const uint16_t* x, uint16_t* out, int64_t numel, DropArgs dr, hipStream_t st);
-// pos (packed batches, or nullptr): the position of every row, each < S; nullptr: row % S
+// pos (packed batches, or nullptr): the position of every row, each < S; nullptr: row % S.
+// Wp == nullptr (rotary positions): out = word + type. launch_embed_bwd with gp == nullptr writes no
+// position gradient.
 void launch_embed_fwd(const int64_t* ids, const int64_t* tt, const uint16_t* Ww, const uint16_t* Wp,
                       const uint16_t* Wt, uint16_t* out, int64_t rows, int S, int D, int64_t vocab, int ntype,
                       hipStream_t st, const int* pos = nullptr);
@@ -394,9 +396,17 @@ void launch_attn_bwd(const AttnProblem& p, const AttnBwdRoute& r, const uint16_t
 // Single-token attention over a key/value cache, append fused in (attn_decode.hip). qkv_new [B][ldq >= 3 * 64 H]
 // (q | k | v of the B new tokens, ldq % 8 == 0, 16-byte aligned), kv [2][B][H][Smax][64] (keys, values), pos
 // int32 [B] on the device (0 <= pos[b] < Smax: the row the new token takes = the tokens already cached),
-// out [B][64 H]. Rows pos[b] of the cache are written, rows above are never read.
+// out [B][64 H]. Rows pos[b] of the cache are written, rows above are never read. rope (or nullptr: the kernel as
+// it is without one): the rotary table [>= Smax][32][2] fp32; q and the new k are rotated by pos[b] and rounded to
+// bf16 before the dot product and the append.
 void launch_attn_decode(const uint16_t* qkv_new, int64_t ldq, uint16_t* kv, const int* pos, uint16_t* out, int B,
-                        int H, int Smax, float scale, hipStream_t st);
+                        int H, int Smax, float scale, hipStream_t st, const float* rope = nullptr);
+// Rotary position embedding of the q and k columns of qkv [rows][ld >= 3 * 64 H] in place (rope.hip): table
+// [P][32][2] fp32 (cos, sin), the position of a row is pos[row] (int32 on the device, clamped into [0, P)) or,
+// without pos, row % S (S <= P). sign >= 0: the rotation; < 0: the inverse rotation (its backward). ld % 8 == 0,
+// 16-byte aligned base, rows * H * 8 < 2^31. The v columns and everything else are untouched.
+void launch_rope_qk(uint16_t* qkv, int64_t ld, int64_t rows, int H, const float* table, int P, int S, const int* pos,
+                    int sign, hipStream_t st);
 
 // ----------------------------------------------------------------------------
 // Masked-LM head (mlm.hip)

@@ -29,6 +29,7 @@
 // pos is read from the device and the launch needs nothing from the host: a decode step is capturable.
 // pos[b] < Smax cannot be checked without a read: debug builds check it (MLT_DCHECK); every build clamps it
 // into the cache, so that a bad value cannot write outside the allocation.
+// With a rotary table (the ROPE instantiation) q and the new k are rotated by pos[b] first; see dec_rotate.
 #include "mlt_common.h"
 #include "mlt_kernels.h"
 
@@ -61,11 +62,33 @@ __device__ __forceinline__ float dec_dot(const float* q, const uint4& kr) {
   return group_sum<8>(s);
 }
 
+// the 8 bf16 of r (four interleaved pairs) rotated by the four (c, s) table entries at t, rounded back to bf16:
+// the arithmetic of rope.hip (uncontracted fp32 products, then one fp32 sum), so that a cached key and a
+// query carry the bits the training path stores in its rotated QKV buffer
+__device__ __forceinline__ uint4 dec_rotate(const uint4& r, const float* t) {
+#pragma clang fp contract(off)  // plain operators, no fma: see rope_rotate8 in rope.hip
+  float f[8];
+  dec_unpack(r, f);
+  uint32_t o[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const float a = f[2 * i], b = f[2 * i + 1], c = t[2 * i], s = t[2 * i + 1];
+    const float ac = a * c, bs = b * s, as = a * s, bc = b * c;
+    const float ya = ac - bs;
+    const float yb = as + bc;
+    o[i] = (uint32_t)f32_to_bf16(ya) | ((uint32_t)f32_to_bf16(yb) << 16);
+  }
+  return make_uint4(o[0], o[1], o[2], o[3]);
+}
+
+// ROPE: q and the new k are rotated by position pos[b] (rope [>= Smax][32][2] fp32, the table of ops/rope.py) in
+// registers and rounded to bf16 BEFORE the dot product and the append; the cache holds rotated keys.
+template <bool ROPE>
 __global__ __launch_bounds__(kDecWaves * 64) void attn_decode_kernel(const uint16_t* __restrict__ qkv_new,
                                                                      int64_t ldq, uint16_t* __restrict__ kv,
                                                                      const int* __restrict__ pos,
                                                                      uint16_t* __restrict__ out, int H, int Smax,
-                                                                     float scale) {
+                                                                     float scale, const float* __restrict__ rope) {
   __shared__ float s_m[kDecWaves];
   __shared__ float s_l[kDecWaves];
   __shared__ float s_o[kDecWaves][kDecHead];
@@ -78,8 +101,15 @@ __global__ __launch_bounds__(kDecWaves * 64) void attn_decode_kernel(const uint1
   const float sl2 = scale * 1.4426950408889634f;  // exponents in base 2
 
   const uint16_t* row = qkv_new + (int64_t)b * ldq + h * kDecHead + c * 8;
-  const uint4 qr = *reinterpret_cast<const uint4*>(row);
-  const uint4 kn = *reinterpret_cast<const uint4*>(row + D);
+  uint4 qr = *reinterpret_cast<const uint4*>(row);
+  uint4 kn = *reinterpret_cast<const uint4*>(row + D);
+  if constexpr (ROPE) {  // this lane's dims 8c .. 8c + 7 are four whole pairs: 32 contiguous bytes of the table
+    const float4* tp = reinterpret_cast<const float4*>(rope + (int64_t)n * kDecHead + c * 8);
+    const float4 t0 = tp[0], t1 = tp[1];
+    const float t[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};
+    qr = dec_rotate(qr, t);
+    kn = dec_rotate(kn, t);
+  }
   const uint4 vn = *reinterpret_cast<const uint4*>(row + 2 * D);
   uint16_t* kc = kv + ((int64_t)b * H + h) * Smax * kDecHead + c * 8;  // this lane's dims of key row 0
   uint16_t* vc = kc + (int64_t)B * H * Smax * kDecHead;
@@ -184,8 +214,12 @@ __global__ __launch_bounds__(kDecWaves * 64) void attn_decode_kernel(const uint1
 }
 
 void launch_attn_decode(const uint16_t* qkv_new, int64_t ldq, uint16_t* kv, const int* pos, uint16_t* out, int B,
-                        int H, int Smax, float scale, hipStream_t st) {
-  attn_decode_kernel<<<dim3(H, B), dim3(kDecWaves * 64), 0, st>>>(qkv_new, ldq, kv, pos, out, H, Smax, scale);
+                        int H, int Smax, float scale, hipStream_t st, const float* rope) {
+  const dim3 grid(H, B), block(kDecWaves * 64);
+  if (rope)
+    attn_decode_kernel<true><<<grid, block, 0, st>>>(qkv_new, ldq, kv, pos, out, H, Smax, scale, rope);
+  else
+    attn_decode_kernel<false><<<grid, block, 0, st>>>(qkv_new, ldq, kv, pos, out, H, Smax, scale, nullptr);
 }
 
 }  // namespace mlt

@@ -394,7 +394,12 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(const int64_t* __restric
   }
   float a[E], b[E], c[E];
   load_row<VPL>(Ww + id * D, a);
-  load_row<VPL>(Wp + (int64_t)pos * D, b);
+  if (Wp) {
+    load_row<VPL>(Wp + (int64_t)pos * D, b);
+  } else {  // no position table (rotary positions): word + type, the sum a zero table gives
+#pragma unroll
+    for (int e = 0; e < E; ++e) b[e] = 0.f;
+  }
   load_row<VPL>(Wt + ty * D, c);
 #pragma unroll
   for (int v = 0; v < VPL; ++v) {
@@ -487,13 +492,15 @@ __global__ __launch_bounds__(256) void embed_bwd_pos_kernel(const int64_t* __res
 #pragma unroll
   for (int v = 0; v < VPL; ++v) {
     const int c = 4 * (lane + 64 * v);
-    float4* g = reinterpret_cast<float4*>(gp + (int64_t)pos * D + c);
-    float4 o = *g;
-    o.x += a[4 * v];
-    o.y += a[4 * v + 1];
-    o.z += a[4 * v + 2];
-    o.w += a[4 * v + 3];
-    *g = o;
+    if (gp) {  // (nullptr: no position table, only the token-type partials are wanted)
+      float4* g = reinterpret_cast<float4*>(gp + (int64_t)pos * D + c);
+      float4 o = *g;
+      o.x += a[4 * v];
+      o.y += a[4 * v + 1];
+      o.z += a[4 * v + 2];
+      o.w += a[4 * v + 3];
+      *g = o;
+    }
     *reinterpret_cast<float4*>(part_t + (int64_t)pos * 2 * D + c) =
         make_float4(t0[4 * v], t0[4 * v + 1], t0[4 * v + 2], t0[4 * v + 3]);
     *reinterpret_cast<float4*>(part_t + (int64_t)pos * 2 * D + D + c) =

@@ -59,7 +59,8 @@ Causal attention (``BertConfig.causal``, default False): key ``j`` of a sequence
 of the same sequence iff ``j <= i`` and ``j < len_b``, inside the flash attention kernels (their causal
 instantiations skip the key blocks above the diagonal; no S x S mask exists anywhere). It composes with
 hidden dropout, attention dropout and ``unpad``; with ``fp8`` it is rejected. ``BertLMHeadModel`` is the
-encoder run as a next-token decoder (post-LN, learned positions, tied word table: GPT-1's block) under
+encoder run as a next-token decoder (post-LN, learned positions -- or rotary ones, below --, tied word table:
+GPT-1's block) under
 the MLM prediction head with one slot per position.
 
 Incremental decoding (``BertLMHeadModel`` only; the bidirectional models have no use for a key/value cache):
@@ -75,6 +76,17 @@ step reads anything back. On the CPU the same runs in fp32 torch with an fp32 ca
 independent of the batch), ``top_p``, and ``graph=True`` (``GraphedDecoder``: one captured graph of ``decode_step`` +
 ``sample_step`` replayed per token). Not built: pre-LN blocks, paged caches, beam search, repetition penalties,
 ``return_logits`` under a graph, a graph for ``prefill``.
+
+Rotary positions (``BertConfig.rotary``, default False; ``rope_base``): instead of a learned position table added at
+the embedding, queries and keys are rotated by an angle proportional to their position (``ops/rope.py`` has the
+definition: interleaved pairs, an fp32 cos / sin table of ``max_position`` rows built once on the host, uncontracted
+fp32 arithmetic, bf16 results), so attention scores depend on ``i - j`` only. The model then has no
+``position_embeddings`` module and no such state-dict key; the table is a non-persistent buffer ``rope_table``. On the
+GPU the ``rope_qk`` kernel rotates the q and k columns of the QKV buffer in place between the QKV GEMM and the flash
+attention kernel and rotates dQKV back in the backward; the key/value cache holds rotated keys and the ROPE
+instantiation of ``attn_decode`` rotates the one new row per sequence. ``max_position`` only sizes the table: it may
+exceed every length seen in training, which is the point (a model trained at 32 tokens can be run past them). It
+composes with ``causal``, ``unpad`` and both dropouts and with all three model classes; with ``fp8`` it is rejected.
 """
 from __future__ import annotations
 
@@ -106,6 +118,8 @@ class BertConfig:
     unpad: bool = False  # run the encoder on the real tokens only (needs lengths; not with fp8)
     max_predictions: Optional[int] = None  # MLM slots per sequence; None: ceil(0.15 * S) rounded up to 8
     causal: bool = False  # key j visible to query i iff j <= i (and j < len_b); not with fp8
+    rotary: bool = False  # rotary positions on q and k instead of a learned position table; not with fp8
+    rope_base: float = 10000.0  # the angle of position p, pair i is p * rope_base ** (-2 i / 64)
 
 
 _PRESETS = {
@@ -135,10 +149,11 @@ class BertLayer(nn.Module):
         self.ffn2 = nn.Linear(c.intermediate, h)
         self.ln2 = nn.LayerNorm(h, eps=c.ln_eps)
 
-    def forward_native(self, x, lens, B, S, drop=None, attn_drop=None, cu_seqlens=None):
+    def forward_native(self, x, lens, B, S, drop=None, attn_drop=None, cu_seqlens=None, rope=None):
         """``drop`` = (p, seed, site of the attention sub-layer, rank); the FFN takes the next site.
         ``attn_drop`` = (p, seed, attention site of this layer, rank): attention-probability dropout.
-        ``cu_seqlens``: x is a packed [T, h] batch (S = max_seqlen, lens unused)."""
+        ``cu_seqlens``: x is a packed [T, h] batch (S = max_seqlen, lens unused).
+        ``rope`` = (table, pos or None): rotary positions (``ops.transformer.attention_block``)."""
         from ml_trainer_amd.ops import transformer as T
         if self.c.fp8:
             from ml_trainer_amd.ops.fp8 import FP8 as impl
@@ -146,18 +161,19 @@ class BertLayer(nn.Module):
             impl = T.BF16
         x = T.attention_ln_block(x, self.qkv.weight, self.qkv.bias, self.out.weight, self.out.bias, self.ln1.weight,
                                  self.ln1.bias, lens, B, S, self.c.heads, self.c.ln_eps, impl, drop, attn_drop,
-                                 cu_seqlens, self.c.causal)
+                                 cu_seqlens, self.c.causal, rope)
         if drop is not None:
             drop = (drop[0], drop[1], drop[2] + 1, drop[3])
         return T.ffn_ln_block(x, self.ffn1.weight, self.ffn1.bias, self.ffn2.weight, self.ffn2.bias, self.ln2.weight,
                               self.ln2.bias, self.c.ln_eps, impl, drop)
 
-    def forward_reference(self, x, mask, B, S, drop=None, attn_drop=None, packed=None):
+    def forward_reference(self, x, mask, B, S, drop=None, attn_drop=None, packed=None, rope=None):
         """fp32 torch reference. x [B*S, h]; mask [B, S] bool (True = valid key); drop and attn_drop
         as in forward_native (the same masks, through ops.dropout). ``packed`` (a PackedBatch): x is
         [T, h]; the linears, LayerNorms and hidden dropout run on the packed rows, attention on a
         padded scratch of the QKV rows (so its dropout mask is the padded run's). With ``config.causal``
-        the lower-triangular mask (key <= query) joins the key mask."""
+        the lower-triangular mask (key <= query) joins the key mask. ``rope`` (the table): q and k are rotated in
+        the dtype of the activations (fp32) at position = column of the padded layout."""
         from ml_trainer_amd.ops import dropout as D
         c = self.c
         H, dh = c.heads, c.hidden // c.heads
@@ -167,6 +183,9 @@ class BertLayer(nn.Module):
             qkv = unpack_rows(qkv, packed)
         qkv = qkv.view(B, S, 3, H, dh).permute(2, 0, 3, 1, 4)
         q, k, v = qkv[0], qkv[1], qkv[2]
+        if rope is not None:
+            from ml_trainer_amd.ops.rope import rotate
+            q, k = rotate(q, rope[:S]).to(q.dtype), rotate(k, rope[:S]).to(k.dtype)
         s = (q @ k.transpose(-1, -2)) / math.sqrt(dh)
         if mask is not None:
             s = s.masked_fill(~mask[:, None, None, :], float("-inf"))
@@ -209,10 +228,19 @@ class BertClassifier(nn.Module):
         if c.causal and c.fp8:
             raise ValueError("causal=True with fp8=True is not supported: the fp8 (q8) attention epilogue has no "
                              "causal instantiation")
+        if c.rotary and c.fp8:
+            raise ValueError("rotary=True with fp8=True is not supported: the fp8 attention backward writes dQKV as "
+                             "e5m2, which the inverse rotation cannot take")
         self.config = c
         self.last_dropout_seed = None  # the seed of the last forward that dropped
         self.word_embeddings = nn.Embedding(c.vocab_size, c.hidden)
-        self.position_embeddings = nn.Embedding(c.max_position, c.hidden)
+        if c.rotary:  # no position table to train: the cos / sin table of ops/rope.py, not part of the state dict
+            from ml_trainer_amd.ops.rope import rope_table
+            self.position_embeddings = None
+            self.register_buffer("rope_table", rope_table(c.max_position, c.rope_base).clone(), persistent=False)
+        else:
+            self.position_embeddings = nn.Embedding(c.max_position, c.hidden)
+            self.rope_table = None
         self.token_type_embeddings = nn.Embedding(c.type_vocab, c.hidden)
         self.emb_ln = nn.LayerNorm(c.hidden, eps=c.ln_eps)
         self.layers = nn.ModuleList([BertLayer(c) for _ in range(c.layers)])
@@ -233,6 +261,23 @@ class BertClassifier(nn.Module):
         elif isinstance(m, nn.LayerNorm):
             nn.init.ones_(m.weight)
             nn.init.zeros_(m.bias)
+
+    def _pos_weight(self):
+        """The learned position table, or None under rotary positions (the embedding kernels then add none)."""
+        return None if self.position_embeddings is None else self.position_embeddings.weight
+
+    def _rope(self, pos=None):
+        """The ``rope`` argument of the native attention blocks: (table, packed positions or None), or None."""
+        return (self.rope_table, pos) if self.config.rotary else None
+
+    def _embed_torch(self, ids, tt, pos, per_batch=False):
+        """word (+ learned position, ``pos`` indexing the table; ``per_batch``: one [S] row of positions for every
+        sequence) + type in plain torch."""
+        x = self.word_embeddings(ids)
+        if self.position_embeddings is not None:
+            p = self.position_embeddings(pos)
+            x = x + (p[None] if per_batch else p)
+        return x + self.token_type_embeddings(tt)
 
     def _lengths(self, input_ids, attention_mask):
         B, S = input_ids.shape
@@ -307,13 +352,14 @@ class BertClassifier(nn.Module):
         """The native encoder on a padded [B, S] batch: the last layer's hidden states [B * S, h] bf16."""
         from ml_trainer_amd.ops import transformer as T
         B, S = input_ids.shape
-        x = T.embeddings(input_ids, token_type_ids, self.word_embeddings.weight, self.position_embeddings.weight,
+        x = T.embeddings(input_ids, token_type_ids, self.word_embeddings.weight, self._pos_weight(),
                          self.token_type_embeddings.weight, S)
         x = T.layer_norm(x, self.emb_ln.weight, self.emb_ln.bias, self.config.ln_eps)
         if drop is not None:
             x = T.dropout(x, *self._site(drop, 0))
+        rope = self._rope()
         for l, layer in enumerate(self.layers):
-            x = layer.forward_native(x, lens, B, S, self._site(drop, 1 + 2 * l), self._attn_site(adrop, l))
+            x = layer.forward_native(x, lens, B, S, self._site(drop, 1 + 2 * l), self._attn_site(adrop, l), rope=rope)
         return x
 
     def _encode_native_packed(self, pk, drop, adrop):
@@ -321,13 +367,14 @@ class BertClassifier(nn.Module):
         that round the count up to the GEMMs' 256-row tile)."""
         from ml_trainer_amd.ops import transformer as T
         B, S, cu = pk.batch, pk.max_seqlen, pk.cu_seqlens
-        x = T.embeddings(pk.ids, pk.tt, self.word_embeddings.weight, self.position_embeddings.weight,
+        x = T.embeddings(pk.ids, pk.tt, self.word_embeddings.weight, self._pos_weight(),
                          self.token_type_embeddings.weight, S, pos=pk.pos, cu_seqlens=cu)
         x = T.layer_norm(x, self.emb_ln.weight, self.emb_ln.bias, self.config.ln_eps)
         if drop is not None:
             x = T.dropout(x, *self._site(drop, 0))
+        rope = self._rope(pk.pos)
         for l, layer in enumerate(self.layers):
-            x = layer.forward_native(x, None, B, S, self._site(drop, 1 + 2 * l), self._attn_site(adrop, l), cu)
+            x = layer.forward_native(x, None, B, S, self._site(drop, 1 + 2 * l), self._attn_site(adrop, l), cu, rope)
         return x
 
     def _forward_native_packed(self, pk, drop, adrop):
@@ -343,14 +390,14 @@ class BertClassifier(nn.Module):
     def _reference_hidden_packed(self, pk, lens, drop, adrop, full=False):
         B, S = pk.batch, pk.max_seqlen
         tt = pk.tt if pk.tt is not None else torch.zeros_like(pk.ids)
-        x = self.word_embeddings(pk.ids) + self.position_embeddings(pk.pos.long()) + self.token_type_embeddings(tt)
-        x = self.emb_ln(x)
+        x = self.emb_ln(self._embed_torch(pk.ids, tt, pk.pos.long()))
         if drop is not None:
             from ml_trainer_amd.ops import dropout as D
             x = D.apply(x, *self._site(drop, 0))
         mask = torch.arange(S, device=x.device)[None, :] < lens.to(x.device).clamp(1, S)[:, None]
         for l, layer in enumerate(self.layers):
-            x = layer.forward_reference(x, mask, B, S, self._site(drop, 1 + 2 * l), self._attn_site(adrop, l), pk)
+            x = layer.forward_reference(x, mask, B, S, self._site(drop, 1 + 2 * l), self._attn_site(adrop, l), pk,
+                                        self.rope_table)
         return x if full else x.index_select(0, pk.cls_rows)
 
     def forward_reference_hidden(self, input_ids, lens=None, token_type_ids=None, drop=None, adrop=None, full=False):
@@ -361,8 +408,7 @@ class BertClassifier(nn.Module):
             return self._reference_hidden_packed(pk, lens, drop, adrop, full)
         pos = torch.arange(S, device=input_ids.device)
         tt = token_type_ids if token_type_ids is not None else torch.zeros_like(input_ids)
-        x = self.word_embeddings(input_ids) + self.position_embeddings(pos)[None] + self.token_type_embeddings(tt)
-        x = self.emb_ln(x).view(B * S, -1)
+        x = self.emb_ln(self._embed_torch(input_ids, tt, pos, per_batch=True)).view(B * S, -1)
         if drop is not None:
             from ml_trainer_amd.ops import dropout as D
             x = D.apply(x, *self._site(drop, 0))
@@ -370,7 +416,8 @@ class BertClassifier(nn.Module):
         if lens is not None:
             mask = torch.arange(S, device=input_ids.device)[None, :] < lens.to(input_ids.device)[:, None]
         for l, layer in enumerate(self.layers):
-            x = layer.forward_reference(x, mask, B, S, self._site(drop, 1 + 2 * l), self._attn_site(adrop, l))
+            x = layer.forward_reference(x, mask, B, S, self._site(drop, 1 + 2 * l), self._attn_site(adrop, l),
+                                        rope=self.rope_table)
         return x if full else x.view(B, S, -1)[:, 0]
 
     def forward_reference(self, input_ids, attention_mask=None, token_type_ids=None, dropout_seed=None):
@@ -415,18 +462,20 @@ class BertClassifier(nn.Module):
             if pk is None:
                 pos = torch.arange(S, device=input_ids.device)
                 tt = token_type_ids if token_type_ids is not None else torch.zeros_like(input_ids)
-                x = (self.word_embeddings(input_ids) + self.position_embeddings(pos)[None] +
-                     self.token_type_embeddings(tt))
+                x = self._embed_torch(input_ids, tt, pos, per_batch=True)
             else:  # the packed rows as a batch of one: x [1, T, h]; attention on a padded scratch of the QKV rows
                 tt = pk.tt if pk.tt is not None else torch.zeros_like(pk.ids)
-                x = (self.word_embeddings(pk.ids) + self.position_embeddings(pk.pos.long()) +
-                     self.token_type_embeddings(tt))[None]
+                x = self._embed_torch(pk.ids, tt, pk.pos.long())[None]
             x = dropped(self.emb_ln(x), 0)
             for l, L in enumerate(self.layers):
                 qkv = L.qkv(x)
                 if pk is not None:
                     qkv = unpack_rows(qkv[0], pk)
                 qkv = qkv.view(B, S, 3, c.heads, 64).permute(2, 0, 3, 1, 4)
+                if c.rotary:  # fp32 rotation of the (bf16) q and k, rounded back as the native path stores them
+                    from ml_trainer_amd.ops.rope import rotate
+                    cs = self.rope_table[:S]
+                    qkv = torch.stack((rotate(qkv[0], cs).to(qkv.dtype), rotate(qkv[1], cs).to(qkv.dtype), qkv[2]))
                 if adrop is None:
                     ctx = F.scaled_dot_product_attention(qkv[0], qkv[1], qkv[2], attn_mask=mask, is_causal=causal)
                 else:
@@ -649,25 +698,28 @@ class BertLMHeadModel(BertForMaskedLM):
                              f"{DC.HEAD_DIM}] on {dev}")
         if input_ids.is_cuda:
             from ml_trainer_amd.ops import transformer as T
-            x = T.embeddings(input_ids, None, self.word_embeddings.weight, self.position_embeddings.weight,
+            x = T.embeddings(input_ids, None, self.word_embeddings.weight, self._pos_weight(),
                              self.token_type_embeddings.weight, S)
             x, _ = T._ln_fwd(x, self.emb_ln.weight, self.emb_ln.bias, c.ln_eps)
             for l, L in enumerate(self.layers):
                 a, (_, qkv, _, _) = T._attn_fwd(x, L.qkv.weight, L.qkv.bias, L.out.weight, L.out.bias, lens, B, S,
-                                                c.heads, causal=True)
+                                                c.heads, causal=True, rope=self._rope())  # (qkv: rotated under rotary)
                 DC.fill_from_prefill(cache, l, qkv, lens, B, S)
                 x, _ = T._ln_fwd(a, L.ln1.weight, L.ln1.bias, c.ln_eps)
                 f, _ = T._ffn_fwd(x, L.ffn1.weight, L.ffn1.bias, L.ffn2.weight, L.ffn2.bias)
                 x, _ = T._ln_fwd(f, L.ln2.weight, L.ln2.bias, c.ln_eps)
         else:
             pos = torch.arange(S, device=dev)
-            x = (self.word_embeddings(input_ids) + self.position_embeddings(pos)[None] +
-                 self.token_type_embeddings(torch.zeros_like(input_ids)))
+            x = self._embed_torch(input_ids, torch.zeros_like(input_ids), pos, per_batch=True)
             x = self.emb_ln(x).view(B * S, -1)
             mask = None if lens is None else pos[None, :] < lens[:, None]
             for l, L in enumerate(self.layers):
-                DC.fill_from_prefill(cache, l, L.qkv(x), lens, B, S)
-                x = L.forward_reference(x, mask, B, S)
+                qkv = L.qkv(x)
+                if c.rotary:  # the cache holds rotated keys
+                    from ml_trainer_amd.ops.rope import rope_qk_reference
+                    qkv = rope_qk_reference(qkv, self.rope_table, c.heads, S)
+                DC.fill_from_prefill(cache, l, qkv, lens, B, S)
+                x = L.forward_reference(x, mask, B, S, rope=self.rope_table)
         cache.pos.copy_(lens if lens is not None else torch.full((B,), S, dtype=torch.int32, device=dev))
         return DC.DecodeState(cache, x.index_select(0, self._last_rows(lens, B, S, dev)))
 
@@ -686,7 +738,8 @@ class BertLMHeadModel(BertForMaskedLM):
         """fp32 logits [B, V] of the next token. Without ``token_ids``: those of the prompt's last token, nothing
         new is run. With ``token_ids`` [B]: token b enters sequence b at position ``state.pos[b]`` and runs
         through the stack on one row per sequence (embedding at explicit positions, per layer QKV GEMM ->
-        ``attn_decode`` over the cache -> out-projection + residual -> LayerNorm -> FFN -> LayerNorm), then
+        ``attn_decode`` over the cache, which under rotary positions rotates q and the new k by ``state.pos[b]`` first
+        -> out-projection + residual -> LayerNorm -> FFN -> LayerNorm), then
         ``state.pos`` advances by 1 on the device. Nothing is read back from the device. The caller keeps
         ``state.pos[b]`` below the cache's ``Smax`` (``generate`` does by construction)."""
         if token_ids is None:
@@ -701,12 +754,12 @@ class BertLMHeadModel(BertForMaskedLM):
             C = T.require_native()
             x = torch.empty(B, c.hidden, dtype=torch.bfloat16, device=ids.device)
             C.embed_fwd(ids, None, T.bf16_weight(self.word_embeddings.weight),
-                        T.bf16_weight(self.position_embeddings.weight),
+                        None if c.rotary else T.bf16_weight(self.position_embeddings.weight),
                         T.bf16_weight(self.token_type_embeddings.weight), x, cache.Smax, pos=cache.pos)
             x, _ = T._ln_fwd(x, self.emb_ln.weight, self.emb_ln.bias, c.ln_eps)
             for l, L in enumerate(self.layers):
                 qkv = DC.linear_small(x, T.bf16_weight(L.qkv.weight), L.qkv.bias)
-                ctx = DC.attn_decode(qkv, cache.kv[l], cache.pos, c.heads)
+                ctx = DC.attn_decode(qkv, cache.kv[l], cache.pos, c.heads, rope=self.rope_table)
                 a = DC.linear_small(ctx, T.bf16_weight(L.out.weight), L.out.bias, res=x)
                 x, _ = T._ln_fwd(a, L.ln1.weight, L.ln1.bias, c.ln_eps)
                 pre = torch.empty(B, L.ffn1.weight.shape[0], dtype=torch.bfloat16, device=x.device)
@@ -714,11 +767,9 @@ class BertLMHeadModel(BertForMaskedLM):
                 f = DC.linear_small(g, T.bf16_weight(L.ffn2.weight), L.ffn2.bias, res=x)
                 x, _ = T._ln_fwd(f, L.ln2.weight, L.ln2.bias, c.ln_eps)
         else:
-            x = (self.word_embeddings(ids) + self.position_embeddings(cache.pos.long()) +
-                 self.token_type_embeddings(torch.zeros_like(ids)))
-            x = self.emb_ln(x)
+            x = self.emb_ln(self._embed_torch(ids, torch.zeros_like(ids), cache.pos.long()))
             for l, L in enumerate(self.layers):
-                ctx = DC.attn_decode_reference(L.qkv(x), cache.kv[l], cache.pos, c.heads)
+                ctx = DC.attn_decode_reference(L.qkv(x), cache.kv[l], cache.pos, c.heads, rope=self.rope_table)
                 x = L.ln1(L.out(ctx) + x)
                 x = L.ln2(L.ffn2(F.gelu(L.ffn1(x))) + x)
         cache.pos.add_(1)

@@ -74,22 +74,33 @@ class DecodeState:
         return self.cache.pos
 
 
-def attn_decode(qkv_new, cache_layer, pos, H: int, scale: float = ATTN_SCALE):
+def attn_decode(qkv_new, cache_layer, pos, H: int, scale: float = ATTN_SCALE, rope=None):
     """out [B, H * 64] bf16 = attention of the B new tokens' queries over their cached keys and themselves;
     rows ``pos[b]`` of ``cache_layer`` become the new tokens' k / v (the native kernel). ``qkv_new``
-    [B, 3 * H * 64] bf16 may be a row-strided view (row stride a multiple of 8)."""
+    [B, 3 * H * 64] bf16 may be a row-strided view (row stride a multiple of 8). ``rope`` (the fp32 table of
+    ``ops.rope.rope_table``, at least Smax rows): the kernel's ROPE instantiation rotates q and the new k by
+    ``pos[b]`` and rounds them to bf16 before the dot product and the append, so the cache holds the rotated keys
+    the training path's QKV buffer holds. Without it the launch is the one before rotary positions existed."""
     C = require_native()
     out = torch.empty(qkv_new.shape[0], H * HEAD_DIM, dtype=torch.bfloat16, device=qkv_new.device)
-    C.attn_decode(qkv_new, cache_layer, pos, out, H, scale)
+    if rope is None:
+        C.attn_decode(qkv_new, cache_layer, pos, out, H, scale)
+    else:
+        C.attn_decode(qkv_new, cache_layer, pos, out, H, scale, rope=rope)
     return out
 
 
-def attn_decode_reference(qkv_new, cache_layer, pos, H: int, scale: float = ATTN_SCALE):
+def attn_decode_reference(qkv_new, cache_layer, pos, H: int, scale: float = ATTN_SCALE, rope=None):
     """``attn_decode`` in plain fp32 torch, on any device: appends into ``cache_layer`` (any float dtype) and
     returns out [B, H * 64] fp32. Stale rows are selected out (scores to -inf, values to 0), never multiplied
-    by zero; nothing is read back from the device."""
+    by zero; nothing is read back from the device. ``rope`` (the table): q and the new k are rotated by
+    ``pos[b]`` (clamped into the cache, as the kernel clamps it) before use, in ``qkv_new``'s own dtype (bf16 in:
+    rounded to bf16 as the kernel rounds them; fp32 in: fp32)."""
     B = qkv_new.shape[0]
     Smax = cache_layer.shape[3]
+    if rope is not None:
+        from ml_trainer_amd.ops.rope import rope_qk_reference
+        qkv_new = rope_qk_reference(qkv_new, rope, H, pos=pos.clamp(0, Smax - 1))
     q, k, v = qkv_new.float().view(B, 3, H, HEAD_DIM).unbind(1)
     idx = pos.long()
     ar = torch.arange(B, device=qkv_new.device)

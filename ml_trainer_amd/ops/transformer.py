@@ -235,19 +235,34 @@ def _causal_kw(causal, impl):
     return dict(causal=True)
 
 
+def _rope_qk(t, rope, S, H, sign=1):
+    """Rotary positions: rotate the q and k columns of ``t`` (QKV, or dQKV with ``sign=-1``) in place.
+    ``rope`` = (table fp32 [P, 32, 2], pos int32 [rows] or None: row % S), see ops/rope.py."""
+    table, pos = rope
+    require_native().rope_qk(t, table, H, S, pos=pos, sign=sign)
+
+
 def _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl=BF16, residual=True, attn_drop=None, cu_seqlens=None,
-              causal: bool = False):
+              causal: bool = False, rope=None):
     """``attn_drop`` = (p, seed, site, rank): attention-probability dropout inside the flash kernels
     (the byte mask of ops/dropout.py, recomputed in the backward); None: no dropout.
     ``cu_seqlens`` (int32 [B + 1], device): packed batch, x is [T, D] with sequence b at rows
     cu[b] .. cu[b + 1]; S is max_seqlen and ``lens`` is unused.
-    ``causal``: key j is visible to query i of its sequence iff j <= i and j < len_b."""
+    ``causal``: key j is visible to query i of its sequence iff j <= i and j < len_b.
+    ``rope`` = (table, pos or None): rotary positions, q and k rotated in place between the QKV GEMM and the
+    attention kernel (``pos`` for packed batches); the saved qkv is the rotated one, which the attention
+    backward needs."""
     C = require_native()
     ckw = _causal_kw(causal, impl)
     if cu_seqlens is not None and impl is not BF16:
         raise ValueError("packed (cu_seqlens) attention runs the bf16 linears only: the fp8 attention epilogue "
                          "writes at b * S offsets")
+    if rope is not None and impl is not BF16:
+        raise ValueError("rotary positions run the bf16 linears only: the fp8 attention backward writes dQKV as "
+                         "e5m2, which the inverse rotation cannot take")
     qkv = impl.fwd(x, wqkv, bqkv)
+    if rope is not None:
+        _rope_qk(qkv, rope, S, H)
     attn = torch.empty(x.shape[0], H * 64, dtype=torch.bfloat16, device=x.device)
     lse = torch.empty(B * H * S, dtype=torch.float32, device=x.device)
     _zero_packed_tail(attn, cu_seqlens)
@@ -258,12 +273,15 @@ def _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl=BF16, residual=True, at
 
 
 def _attn_bwd(saved, params, lens, B, S, H, dy, G, dbo="colsum", impl=BF16, dres=None, attn_drop=None,
-              cu_seqlens=None, causal: bool = False):
+              cu_seqlens=None, causal: bool = False, rope=None):
     """Backward of the attention block. ``dbo``: "colsum" to reduce dy here, otherwise the
     out-proj bias gradient already produced by the LayerNorm backward (tensor or None).
     ``dres``: the gradient of the residual branch when it differs from the out-proj's ``dy``
     (hidden dropout sits between them); defaults to ``dy``. ``attn_drop``, ``cu_seqlens``, ``causal``: the
-    forward's."""
+    forward's. ``rope``: the forward's; dQKV comes out of the attention backward in the rotated frame and is
+    rotated back (``sign=-1``) before anything else reads it. The QKV bias gradient is then the column sum of the
+    rotated-back dQKV: the attention kernels' own column sums are sums in the rotated frame, which differ row by
+    row, so that fused branch is not taken under rotary."""
     C = require_native()
     akw = _attn_drop_kw(attn_drop)
     akw.update(_causal_kw(causal, impl))
@@ -280,7 +298,11 @@ def _attn_bwd(saved, params, lens, B, S, H, dy, G, dbo="colsum", impl=BF16, dres
     _zero_packed_tail(dqkv, cu_seqlens)
     delta = torch.empty(qkv.shape[0] * H, dtype=torch.float32, device=dy.device)
     q8 = impl.attn_dy_q(wqkv, x, qkv.shape[0]) if (impl is not BF16 and hasattr(impl, "attn_dy_q")) else None
-    if q8 is not None or (impl is BF16 and bqkv is not None):
+    if rope is not None:
+        C.attn_bwd(qkv, attn, dattn, lse, delta, lens, dqkv, B, S, H, _ATTN_SCALE, **akw)
+        _rope_qk(dqkv, rope, S, H, sign=-1)
+        dwqkv, dbqkv = G.wgrad_bias(wqkv, bqkv, dqkv, x, impl)
+    elif q8 is not None or (impl is BF16 and bqkv is not None):
         # the QKV bias gradient (column sums of dQKV) from the backward kernels themselves
         db, db_acc, dbqkv = G.out(bqkv, qkv.shape[1], dy.device) if bqkv is not None else (None, False, None)
         if q8 is not None:
@@ -403,11 +425,12 @@ _ATTN_SCALE = 1.0 / 8.0  # 1/sqrt(head_dim = 64)
 
 class _AttentionBlock(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, wqkv, bqkv, wo, bo, lens, B, S, H, impl, attn_drop=None, cu_seqlens=None, causal=False):
+    def forward(ctx, x, wqkv, bqkv, wo, bo, lens, B, S, H, impl, attn_drop=None, cu_seqlens=None, causal=False,
+                rope=None):
         y, saved = _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl, attn_drop=attn_drop, cu_seqlens=cu_seqlens,
-                             causal=causal)
+                             causal=causal, rope=rope)
         ctx.save_for_backward(*saved)
-        ctx.params, ctx.impl = (wqkv, bqkv, wo, bo), impl
+        ctx.params, ctx.impl, ctx.rope = (wqkv, bqkv, wo, bo), impl, rope
         ctx.lens, ctx.dims, ctx.attn_drop, ctx.cu, ctx.causal = lens, (B, S, H), attn_drop, cu_seqlens, causal
         return y
 
@@ -415,9 +438,10 @@ class _AttentionBlock(torch.autograd.Function):
     def backward(ctx, dy):
         G = _Grads()
         grads = _attn_bwd(ctx.saved_tensors, ctx.params, ctx.lens, *ctx.dims, dy.contiguous().to(torch.bfloat16), G,
-                          impl=ctx.impl, attn_drop=ctx.attn_drop, cu_seqlens=ctx.cu, causal=ctx.causal)
+                          impl=ctx.impl, attn_drop=ctx.attn_drop, cu_seqlens=ctx.cu, causal=ctx.causal,
+                          rope=ctx.rope)
         G.done()
-        return grads + (None, None, None, None, None, None, None, None)
+        return grads + (None, None, None, None, None, None, None, None, None)
 
 
 class _FFNBlock(torch.autograd.Function):
@@ -458,19 +482,19 @@ class _AttentionLNBlock(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, wqkv, bqkv, wo, bo, gamma, beta, lens, B, S, H, eps, impl, drop=None, attn_drop=None,
-                cu_seqlens=None, causal=False):
+                cu_seqlens=None, causal=False, rope=None):
         if drop is None:
             a, s1 = _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl, attn_drop=attn_drop, cu_seqlens=cu_seqlens,
-                              causal=causal)
+                              causal=causal, rope=rope)
             y, s2 = _ln_fwd(a, gamma, beta, eps)
         else:  # LN(dropout(out-proj) + x): dropout and the residual add inside the LayerNorm kernel
             a, s1 = _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl, residual=False, attn_drop=attn_drop,
-                              cu_seqlens=cu_seqlens, causal=causal)
+                              cu_seqlens=cu_seqlens, causal=causal, rope=rope)
             y, s2 = _dropout_add_ln_fwd(a, x, gamma, beta, eps, drop)
         ctx.save_for_backward(*s1, *s2)
         ctx.params, ctx.beta, ctx.impl = (wqkv, bqkv, wo, bo), beta, impl
         ctx.lens, ctx.dims, ctx.drop, ctx.attn_drop, ctx.cu = lens, (B, S, H), drop, attn_drop, cu_seqlens
-        ctx.causal = causal
+        ctx.causal, ctx.rope = causal, rope
         return y
 
     @staticmethod
@@ -486,9 +510,9 @@ class _AttentionLNBlock(torch.autograd.Function):
                                             dxsum_param=ctx.params[3], drop=ctx.drop)
         dx, dwqkv, dbqkv, dwo, dbo = _attn_bwd(t[:4], ctx.params, ctx.lens, *ctx.dims, da, G, dbo=dbo,
                                                impl=ctx.impl, dres=dres, attn_drop=ctx.attn_drop, cu_seqlens=ctx.cu,
-                                               causal=ctx.causal)
+                                               causal=ctx.causal, rope=ctx.rope)
         G.done()
-        return dx, dwqkv, dbqkv, dwo, dbo, dg, db, None, None, None, None, None, None, None, None, None, None
+        return dx, dwqkv, dbqkv, dwo, dbo, dg, db, None, None, None, None, None, None, None, None, None, None, None
 
 
 class _FFNLNBlock(torch.autograd.Function):
@@ -532,10 +556,11 @@ class _Embeddings(torch.autograd.Function):
         out = torch.empty(ids.numel(), D, dtype=torch.bfloat16, device=ids.device)
         if (pos is None) != (cu_seqlens is None):
             raise ValueError("packed embeddings take both pos and cu_seqlens")
-        C.embed_fwd(ids, ttf, bf16_weight(ww), bf16_weight(wp), bf16_weight(wt), out, S, pos=pos)
+        C.embed_fwd(ids, ttf, bf16_weight(ww), None if wp is None else bf16_weight(wp), bf16_weight(wt), out, S,
+                    pos=pos)
         ctx.save_for_backward(ids, ttf if ttf is not None else torch.empty(0, dtype=torch.int64))
         ctx.cu = cu_seqlens
-        ctx.meta = (tt is not None, S, ww.shape, wp.shape, wt.shape)
+        ctx.meta = (tt is not None, S, ww.shape, None if wp is None else wp.shape, wt.shape)
         ctx.tables = (ww, wp, wt)
         return out
 
@@ -547,14 +572,14 @@ class _Embeddings(torch.autograd.Function):
         dout = dout.contiguous().to(torch.bfloat16)
         G = _Grads()
         ww, wp, wt = ctx.tables
-        sinks = [G.sink(p) for p in (ww, wp, wt)]
-        if all(s is not None for s in sinks):  # scatter-add straight into the flat gradients
-            gw, gp, gt = sinks
+        sinks = [None if p is None else G.sink(p) for p in (ww, wp, wt)]
+        if all(s is not None or p is None for s, p in zip(sinks, (ww, wp, wt))):
+            gw, gp, gt = sinks  # scatter-add straight into the flat gradients
             ret = (None, None, None)
         else:
             G.ready = []
             gw = torch.zeros(sw, dtype=torch.float32, device=dout.device)
-            gp = torch.zeros(sp, dtype=torch.float32, device=dout.device)
+            gp = None if wp is None else torch.zeros(sp, dtype=torch.float32, device=dout.device)
             gt = torch.zeros(st, dtype=torch.float32, device=dout.device)
             ret = (gw, gp, gt)
         D = sw[1]
@@ -621,7 +646,7 @@ def _mark_training(impl) -> None:
 
 
 def attention_block(x, wqkv, bqkv, wo, bo, lens: Optional[torch.Tensor], B: int, S: int, H: int, impl=BF16,
-                    attn_drop=None, cu_seqlens: Optional[torch.Tensor] = None, causal: bool = False):
+                    attn_drop=None, cu_seqlens: Optional[torch.Tensor] = None, causal: bool = False, rope=None):
     """``attn_drop`` = (p, seed, site, rank): attention-probability dropout inside the flash attention
     kernels (the byte mask of ops/dropout.py: ``p`` is applied as round(p * 256) / 256). None: none.
     ``cu_seqlens`` (int32 [B + 1], device): x is a packed [T, D] batch (``pack_batch``), ``S`` is
@@ -631,9 +656,12 @@ def attention_block(x, wqkv, bqkv, wo, bo, lens: Optional[torch.Tensor], B: int,
     and of dQKV are zeroed (``_zero_packed_tail``).
     ``causal``: key j is visible to query i of the same sequence iff j <= i and j < len_b (the causal
     instantiations of the three kernels, which skip the blocks above the diagonal); bf16 linears only.
-    Composes with ``attn_drop`` (the non-causal run's keep mask, restricted) and ``cu_seqlens``."""
+    Composes with ``attn_drop`` (the non-causal run's keep mask, restricted) and ``cu_seqlens``.
+    ``rope`` = (table fp32 [P, 32, 2], pos): rotary positions (ops/rope.py), q and k rotated in place after the
+    QKV GEMM by ``C.rope_qk`` and dQKV rotated back in the backward; ``pos`` is None for a padded batch
+    (position = row % S) or the packed batch's int32 positions, one per row of x. bf16 linears only."""
     _mark_training(impl)
-    return _AttentionBlock.apply(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl, attn_drop, cu_seqlens, causal)
+    return _AttentionBlock.apply(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl, attn_drop, cu_seqlens, causal, rope)
 
 
 def ffn_block(x, w1, b1, w2, b2, impl=BF16):
@@ -643,15 +671,15 @@ def ffn_block(x, w1, b1, w2, b2, impl=BF16):
 
 def attention_ln_block(x, wqkv, bqkv, wo, bo, gamma, beta, lens: Optional[torch.Tensor], B: int, S: int, H: int,
                        eps: float, impl=BF16, drop=None, attn_drop=None, cu_seqlens: Optional[torch.Tensor] = None,
-                       causal: bool = False):
+                       causal: bool = False, rope=None):
     """``drop`` = (p, seed, site, rank): hidden dropout on the out-projection's output, before the
     residual add, fused into the LayerNorm kernels (mask: ops/dropout.py). None: no dropout.
     ``attn_drop`` = (p, seed, site, rank): attention-probability dropout (see attention_block).
     ``cu_seqlens``: packed batch, with fewer than PACK_ROW_MULTIPLE tail rows (see attention_block);
-    hidden-dropout masks are indexed by packed row. ``causal``: see attention_block."""
+    hidden-dropout masks are indexed by packed row. ``causal``, ``rope``: see attention_block."""
     _mark_training(impl)
     return _AttentionLNBlock.apply(x, wqkv, bqkv, wo, bo, gamma, beta, lens, B, S, H, eps, impl, drop, attn_drop,
-                                   cu_seqlens, causal)
+                                   cu_seqlens, causal, rope)
 
 
 def ffn_ln_block(x, w1, b1, w2, b2, gamma, beta, eps: float, impl=BF16, drop=None):
@@ -691,7 +719,8 @@ def dropout(x, p: float, seed: int, site: int, rank: int):
 
 def embeddings(ids, tt, ww, wp, wt, S: int, pos=None, cu_seqlens=None):
     """Padded form: ids / tt [B, S], position = column. Packed form (``pack_batch``): ids / tt [T],
-    ``pos`` int32 [T] (index inside the token's own sequence), ``cu_seqlens`` int32 [B + 1], S = max_seqlen."""
+    ``pos`` int32 [T] (index inside the token's own sequence), ``cu_seqlens`` int32 [B + 1], S = max_seqlen.
+    ``wp`` None (rotary positions): no position table, the output is word + type."""
     return _Embeddings.apply(ids, tt, ww, wp, wt, S, pos, cu_seqlens)
 
 
