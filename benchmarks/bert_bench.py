@@ -11,6 +11,7 @@ baseline of the same model (torch.autocast + SDPA + hipBLASLt) for comparison.
     python benchmarks/bert_bench.py --impl native --optimizer lamb --no-decay-1d   # LAMB, biases / LayerNorm excluded
     python benchmarks/bert_bench.py --impl native --task mlm   # masked-LM pre-training step (fused vocabulary CE head)
     python benchmarks/bert_bench.py --impl native --task clm --rotary   # rotary positions instead of the learned table
+    python benchmarks/bert_bench.py --impl native --task clm --pre-ln --norm rmsnorm   # pre-norm blocks, RMSNorm
 
 Prints one JSON line per run (samples/s, tokens/s, ms/step, model TFLOP/s; ``tokens`` = the real
 tokens T of the batch, ``fill`` = T / (batch * seq), ``unpad``; tokens/s and TFLOP/s count batch * seq).
@@ -51,6 +52,8 @@ def run(args):
         over["pad_id"] = 0
     if args.rotary:
         over["rotary"] = True
+    if args.pre_ln or args.norm != "layernorm":
+        over.update(pre_ln=bool(args.pre_ln), norm=args.norm)
     cfg = bert_config(args.model, **over)
     m = (BertLMHeadModel if clm else BertForMaskedLM if mlm else BertClassifier)(cfg).to(dev)
     if mlm and args.chunk_rows:
@@ -111,7 +114,8 @@ def run(args):
            "tokens_per_s": tokens / dt, "model_tflops": flops / dt / 1e12, "loss": float(loss.detach()),
            "peak_mem_gb": torch.cuda.max_memory_allocated() / 2 ** 30,
            "min_len": args.min_len, "tokens": real, "fill": real / tokens, "unpad": bool(args.unpad),
-           "optimizer": args.optimizer, "no_decay_1d": bool(args.no_decay_1d), "rotary": bool(args.rotary)}
+           "optimizer": args.optimizer, "no_decay_1d": bool(args.no_decay_1d), "rotary": bool(args.rotary),
+           "pre_ln": bool(args.pre_ln), "norm": args.norm}
     if mlm:
         with torch.no_grad():
             hidden = fwd(ids)
@@ -153,6 +157,9 @@ def main():
     ap.add_argument("--unpad", action="store_true", help="BertConfig.unpad: run the encoder on the real tokens only")
     ap.add_argument("--rotary", action="store_true",
                     help="BertConfig.rotary: rotary positions on q and k (the rope_qk kernel) instead of the learned table")
+    ap.add_argument("--pre-ln", action="store_true", help="BertConfig.pre_ln: pre-norm blocks and a final norm")
+    ap.add_argument("--norm", choices=["layernorm", "rmsnorm"], default="layernorm",
+                    help="BertConfig.norm: the norm of the pre-norm blocks (rmsnorm needs --pre-ln)")
     ap.add_argument("--optimizer", choices=["adamw", "lamb"], default="adamw",
                     help="native optimizer: adamw (one flat launch) or lamb (three launches, layer-wise trust ratio)")
     ap.add_argument("--no-decay-1d", action="store_true",

@@ -28,7 +28,8 @@ region) in one process: eager with the torch sampler, eager with ``sample_step``
 ``--ab`` alternates the cached decode between ``MLT_DECODE_GEMM=0`` (the planner's GEMMs: the launches before the
 skinny kernel) and ``1`` in one process and reports both medians and the spread of the ``0`` runs.
 ``--rotary`` builds the model of the model timings with rotary positions (``BertConfig.rotary``) instead of the learned
-position table; the records carry ``"rotary"``.
+position table; the records carry ``"rotary"``. ``--pre-ln`` / ``--norm {layernorm,rmsnorm}`` build it with pre-norm
+blocks (``BertConfig.pre_ln`` / ``norm``); the records carry ``"pre_ln"`` and ``"norm"``.
 Random weights and prompts (no network)."""
 from __future__ import annotations
 
@@ -57,6 +58,8 @@ def _model(args, dev):
     from ml_trainer_amd.models.bert import BertLMHeadModel, bert_config
     torch.manual_seed(0)
     over = {"rotary": True} if args.rotary else {}
+    if args.pre_ln or args.norm != "layernorm":
+        over.update(pre_ln=bool(args.pre_ln), norm=args.norm)
     return BertLMHeadModel(bert_config(args.model, **over)).to(dev).eval()
 
 
@@ -112,7 +115,8 @@ def bench_model(args, dev):
             if not args.no_uncached:
                 t_unc.append(_sync_ms(uncached) / (N - 1))
         ms = statistics.median(t_dec[settings[-1]])
-        rec = {"bench": "generate", "model": args.model, "rotary": bool(args.rotary), "batch": B, "prompt": P, "new": N,
+        rec = {"bench": "generate", "model": args.model, "rotary": bool(args.rotary), "pre_ln": bool(args.pre_ln),
+               "norm": args.norm, "batch": B, "prompt": P, "new": N,
                "decode_gemm": settings[-1],
                "prefill_ms": statistics.median(t_pre), "cached_ms_per_token": ms, "cached_tokens_per_s": B / ms * 1e3,
                "uncached_ms_per_token": statistics.median(t_unc) if t_unc else None,
@@ -177,7 +181,8 @@ def bench_sampler_ab(args, dev):
                 for k, pre, run in modes:
                     pre()
                     t[k].append(_sync_ms(run) / (N - 1))
-            rec = {"bench": "generate_sampler_ab", "model": args.model, "rotary": bool(args.rotary), "batch": B,
+            rec = {"bench": "generate_sampler_ab", "model": args.model, "rotary": bool(args.rotary),
+                   "pre_ln": bool(args.pre_ln), "norm": args.norm, "batch": B,
                    "prompt": P, "new": N,
                    "setting": name, "capture_s": dec.capture_seconds}
             for k in t:
@@ -320,6 +325,9 @@ def main():
     ap.add_argument("--sampler-ab", action="store_true",
                     help="alternate (eager, torch sampler), (eager, device sampler), (graph, device sampler)")
     ap.add_argument("--rotary", action="store_true", help="rotary positions in the model timings")
+    ap.add_argument("--pre-ln", action="store_true", help="pre-norm blocks in the model timings")
+    ap.add_argument("--norm", choices=["layernorm", "rmsnorm"], default="layernorm",
+                    help="the norm of the pre-norm blocks (rmsnorm needs --pre-ln)")
     ap.add_argument("--heads", type=int, default=12)
     ap.add_argument("--smax", type=int, default=256)
     ap.add_argument("--pos", type=int, default=255)

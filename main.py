@@ -19,6 +19,8 @@ large), ``--synthetic``, ``--per_device_batch``, ``--no_engine``,
 inside the flash attention kernels; applied as round(p * 256) / 256), ``--unpad`` (BERT: drop the pad
 tokens before the embeddings and run the encoder on the real tokens only), ``--rotary`` / ``--rope_base`` (BERT,
 any ``--task``: rotary position embeddings on the queries and keys instead of the learned position table),
+``--pre_ln`` / ``--norm {layernorm,rmsnorm}`` (BERT, any ``--task``: pre-norm blocks ``h + f(norm(h))`` with a final
+norm, and RMSNorm instead of LayerNorm as their norm; ``--norm rmsnorm`` needs ``--pre_ln``),
 ``--min_seq_len L``
 (variable-length synthetic text, lengths uniform in [L, seq_len], right-padded with ``--pad_id``), ``--optimizer lamb`` (layer-wise trust ratios on the flat buffer) and
 ``--no_decay_1d`` (adamw / lamb: biases and LayerNorm parameters take no weight decay), ``--task mlm``
@@ -90,6 +92,10 @@ def build_model_and_datasets(args):
         raise ValueError("--rope_base applies to --rotary")
     if args.rope_base is not None and not args.rope_base > 0:
         raise ValueError(f"--rope_base must be > 0, got {args.rope_base}")
+    if lenet and (args.pre_ln or args.norm != "layernorm"):
+        raise ValueError("--pre_ln / --norm apply to the BERT models; the LeNet models have no transformer blocks")
+    if args.norm == "rmsnorm" and not args.pre_ln:
+        raise ValueError("--norm rmsnorm needs --pre_ln: post-norm RMSNorm blocks are not built")
     if lenet and args.min_seq_len is not None:
         raise ValueError("--min_seq_len applies to the synthetic text data of the BERT models")
     mlm = args.task == "mlm"
@@ -121,6 +127,9 @@ def build_model_and_datasets(args):
         over["rotary"] = True
         if args.rope_base is not None:
             over["rope_base"] = args.rope_base
+    if args.pre_ln:
+        over["pre_ln"] = True
+        over["norm"] = args.norm
     pad_id = args.pad_id if args.pad_id is not None else (0 if args.min_seq_len is not None else None)
     if pad_id is not None and not lenet:
         over["pad_id"] = pad_id
@@ -269,6 +278,12 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--rope_base", type=float, default=None,
                         help="--rotary: the base of the angles, position p and pair i turn by "
                              "p * base ** (-2 i / 64) (default: 10000)")
+    parser.add_argument("--pre_ln", action="store_true",
+                        help="BERT, any --task: pre-norm blocks h + f(norm(h)) and a final norm (final_ln) instead "
+                             "of the post-LN blocks (not with the fp8 `large` preset). An error for the LeNet models")
+    parser.add_argument("--norm", choices=["layernorm", "rmsnorm"], default="layernorm",
+                        help="--pre_ln: the norm of the blocks and the final norm; rmsnorm = x * rsqrt(mean(x^2) + "
+                             "eps) * weight, no centring, no bias (needs --pre_ln)")
     parser.add_argument("--min_seq_len", type=int, default=None,
                         help="BERT synthetic data: variable-length rows, lengths uniform in [min_seq_len, seq_len], "
                              "right-padded with --pad_id (default: fixed length)")

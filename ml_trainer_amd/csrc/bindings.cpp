@@ -959,6 +959,100 @@ void ln_bwd(Tensor DY, Tensor X, Tensor gamma, Tensor mean, Tensor rstd, Tensor 
                 rows, (int)D, accumulate ? 1 : 0, dr, dxs, dxsum_acc ? 1 : 0, cur_stream());
 }
 
+// The dropout form of ln_bwd WITH a residual gradient (pre-norm blocks; ln_bwd itself keeps rejecting the pair):
+// DX = rstd (...) + dres, the total gradient of the residual stream, dxm = mask * scale * DX (the dY of the
+// linear whose dropped output joined the stream) and dxsum = dxm's column sums. All three are required.
+void ln_bwd_dropout_res(Tensor DY, Tensor X, Tensor gamma, Tensor mean, Tensor rstd, Tensor DX, Tensor part,
+                        Tensor dgamma, Tensor dbeta, bool accumulate, Tensor dres, Tensor dxsum, bool dxsum_acc,
+                        Tensor dxm, double p, int64_t seed, int64_t site, int64_t rank) {
+  const int64_t D = gamma.numel(), rows = X.numel() / std::max<int64_t>(D, 1);
+  TORCH_CHECK(D % 256 == 0 && D >= 256 && D <= 1024, "LayerNorm width must be 256/512/768/1024");
+  check_bf16_2d(X, "X", rows, D);
+  check_bf16_2d(DY, "DY", rows, D);
+  check_bf16_2d(DX, "DX", rows, D);
+  check_bf16_2d(dres, "dres", rows, D);
+  check_bf16_2d(dxm, "dxm", rows, D);
+  check_dev(gamma, "gamma", at::kFloat, D);
+  check_dev(mean, "mean", at::kFloat, rows, 4);
+  check_dev(rstd, "rstd", at::kFloat, rows, 4);
+  check_dev(part, "part", at::kFloat, (int64_t)ln_bwd_partial_blocks(rows) * 3 * D);
+  check_dev(dgamma, "dgamma", at::kFloat, D);
+  check_dev(dbeta, "dbeta", at::kFloat, D);
+  check_dev(dxsum, "dxsum", at::kFloat, D);
+  launch_ln_bwd_dropout_res(bf16_ptr(DY), bf16_ptr(X), gamma.data_ptr<float>(), mean.data_ptr<float>(),
+                            rstd.data_ptr<float>(), (uint16_t*)DX.data_ptr(), (uint16_t*)dxm.data_ptr(),
+                            part.data_ptr<float>(), dgamma.data_ptr<float>(), dbeta.data_ptr<float>(), rows, (int)D,
+                            accumulate ? 1 : 0, bf16_ptr(dres), dxsum.data_ptr<float>(), dxsum_acc ? 1 : 0,
+                            make_drop_args(p, seed, site, rank), cur_stream());
+}
+
+// RMSNorm: Y = bf16(X rstd gamma), rstd = rsqrt(mean(X^2) + eps)
+void rms_fwd(Tensor X, Tensor gamma, Tensor Y, Tensor rstd, double eps) {
+  const int64_t D = gamma.numel(), rows = X.numel() / std::max<int64_t>(D, 1);
+  TORCH_CHECK(D % 256 == 0 && D >= 256 && D <= 1024, "RMSNorm width must be 256/512/768/1024");
+  check_bf16_2d(X, "X", rows, D);
+  check_bf16_2d(Y, "Y", rows, D);
+  check_dev(gamma, "gamma", at::kFloat, D);
+  check_dev(rstd, "rstd", at::kFloat, rows, 4);
+  launch_rms_fwd(bf16_ptr(X), gamma.data_ptr<float>(), (uint16_t*)Y.data_ptr(), rstd.data_ptr<float>(), rows, (int)D,
+                 (float)eps, cur_stream());
+}
+
+// Z = bf16(dropout(Y0) + RES); Y, rstd = RMSNorm(Z)
+void dropout_add_rms_fwd(Tensor Y0, Tensor RES, Tensor gamma, Tensor Z, Tensor Y, Tensor rstd, double eps, double p,
+                         int64_t seed, int64_t site, int64_t rank) {
+  const int64_t D = gamma.numel(), rows = Y0.numel() / std::max<int64_t>(D, 1);
+  TORCH_CHECK(D % 256 == 0 && D >= 256 && D <= 1024, "RMSNorm width must be 256/512/768/1024");
+  check_bf16_2d(Y0, "Y0", rows, D);
+  check_bf16_2d(RES, "RES", rows, D);
+  check_bf16_2d(Z, "Z", rows, D);
+  check_bf16_2d(Y, "Y", rows, D);
+  check_dev(gamma, "gamma", at::kFloat, D);
+  check_dev(rstd, "rstd", at::kFloat, rows, 4);
+  launch_dropout_add_rms_fwd(bf16_ptr(Y0), bf16_ptr(RES), gamma.data_ptr<float>(), (uint16_t*)Z.data_ptr(),
+                             (uint16_t*)Y.data_ptr(), rstd.data_ptr<float>(), rows, (int)D, (float)eps,
+                             make_drop_args(p, seed, site, rank), cur_stream());
+}
+
+// dxsum (optional): column sums of DX, accumulated into when dxsum_acc. dxm (optional, needs dxsum): X was
+// dropout(linear) + residual at site (p, seed, site, rank); dxm gets mask * scale * DX and dxsum its column
+// sums instead of DX's. dres (optional, in every form): added into DX. part: ln_partial_blocks(rows) *
+// (dxsum ? 2 : 1) * D floats.
+void rms_bwd(Tensor DY, Tensor X, Tensor gamma, Tensor rstd, Tensor DX, Tensor part, Tensor dgamma, bool accumulate,
+             c10::optional<Tensor> dres, c10::optional<Tensor> dxsum, bool dxsum_acc, c10::optional<Tensor> dxm,
+             double p, int64_t seed, int64_t site, int64_t rank) {
+  const int64_t D = gamma.numel(), rows = X.numel() / std::max<int64_t>(D, 1);
+  TORCH_CHECK(D % 256 == 0 && D >= 256 && D <= 1024, "RMSNorm width must be 256/512/768/1024");
+  check_bf16_2d(X, "X", rows, D);
+  check_bf16_2d(DY, "DY", rows, D);
+  check_bf16_2d(DX, "DX", rows, D);
+  check_dev(gamma, "gamma", at::kFloat, D);
+  check_dev(rstd, "rstd", at::kFloat, rows, 4);
+  check_dev(part, "part", at::kFloat, (int64_t)ln_bwd_partial_blocks(rows) * (dxsum.has_value() ? 2 : 1) * D);
+  check_dev(dgamma, "dgamma", at::kFloat, D);
+  float* dxs = nullptr;
+  if (dxsum.has_value()) {
+    check_dev(*dxsum, "dxsum", at::kFloat, D);
+    dxs = dxsum->data_ptr<float>();
+  }
+  const uint16_t* dr = nullptr;
+  if (dres.has_value()) {
+    check_bf16_2d(*dres, "dres", rows, D);
+    dr = bf16_ptr(*dres);
+  }
+  uint16_t* dm = nullptr;
+  DropArgs da{};
+  if (dxm.has_value()) {
+    TORCH_CHECK(dxs != nullptr, "rms_bwd: dxm needs dxsum");
+    check_bf16_2d(*dxm, "dxm", rows, D);
+    dm = (uint16_t*)dxm->data_ptr();
+    da = make_drop_args(p, seed, site, rank);
+  }
+  launch_rms_bwd(bf16_ptr(DY), bf16_ptr(X), gamma.data_ptr<float>(), rstd.data_ptr<float>(), (uint16_t*)DX.data_ptr(),
+                 dm, part.data_ptr<float>(), dgamma.data_ptr<float>(), rows, (int)D, accumulate ? 1 : 0, dr, dxs,
+                 dxsum_acc ? 1 : 0, da, cur_stream());
+}
+
 // pos (packed batches): int32 [rows], the position of every token inside its own sequence (< S);
 // without it the batch is padded [B, S] and pos = row % S
 // Wp None (rotary positions): no position table, out = word + type
@@ -1901,6 +1995,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("Z"), py::arg("Y"), py::arg("mean"), py::arg("rstd"), py::arg("eps"), py::arg("p"), py::arg("seed"),
         py::arg("site"), py::arg("rank"));
   m.def("ln_partial_blocks", &ln_partial_blocks);
+  m.def("ln_bwd_dropout_res", &ln_bwd_dropout_res, py::arg("DY"), py::arg("X"), py::arg("gamma"), py::arg("mean"),
+        py::arg("rstd"), py::arg("DX"), py::arg("part"), py::arg("dgamma"), py::arg("dbeta"), py::arg("accumulate"),
+        py::arg("dres"), py::arg("dxsum"), py::arg("dxsum_acc"), py::arg("dxm"), py::arg("p"), py::arg("seed"),
+        py::arg("site"), py::arg("rank"));
+  m.def("rms_fwd", &rms_fwd, py::arg("X"), py::arg("gamma"), py::arg("Y"), py::arg("rstd"), py::arg("eps"));
+  m.def("dropout_add_rms_fwd", &dropout_add_rms_fwd, py::arg("Y0"), py::arg("RES"), py::arg("gamma"), py::arg("Z"),
+        py::arg("Y"), py::arg("rstd"), py::arg("eps"), py::arg("p"), py::arg("seed"), py::arg("site"),
+        py::arg("rank"));
+  m.def("rms_bwd", &rms_bwd, py::arg("DY"), py::arg("X"), py::arg("gamma"), py::arg("rstd"), py::arg("DX"),
+        py::arg("part"), py::arg("dgamma"), py::arg("accumulate") = false, py::arg("dres") = py::none(),
+        py::arg("dxsum") = py::none(), py::arg("dxsum_acc") = false, py::arg("dxm") = py::none(), py::arg("p") = 0.0,
+        py::arg("seed") = 0, py::arg("site") = 0, py::arg("rank") = 0);
   m.def("embed_fwd", &embed_fwd, py::arg("ids"), py::arg("tt"), py::arg("Ww"), py::arg("Wp"), py::arg("Wt"),
         py::arg("out"), py::arg("S"), py::arg("pos") = py::none());
   m.def("embed_bwd", &embed_bwd, py::arg("sid"), py::arg("perm"), py::arg("tt"), py::arg("DX"), py::arg("gw"),

@@ -330,6 +330,22 @@ void launch_ln_bwd_dropout(const uint16_t* DY, const uint16_t* X, const float* g
                            const float* rstd, uint16_t* DX, uint16_t* DXM, float* part, float* dgamma, float* dbeta,
                            int64_t rows, int D, int accumulate, float* dxsum, int dxsum_acc, DropArgs dr,
                            hipStream_t st);
+// Pre-norm blocks: the dropout variant with DRES added into DX (the residual stream's own gradient), the
+// same kernel instantiation as launch_ln_bwd_dropout.
+void launch_ln_bwd_dropout_res(const uint16_t* DY, const uint16_t* X, const float* gamma, const float* mean,
+                               const float* rstd, uint16_t* DX, uint16_t* DXM, float* part, float* dgamma,
+                               float* dbeta, int64_t rows, int D, int accumulate, const uint16_t* DRES, float* dxsum,
+                               int dxsum_acc, DropArgs dr, hipStream_t st);
+// RMSNorm (layernorm.hip): Y = bf16(x rstd g), rstd = rsqrt(mean(x^2) + eps) saved. The backward's part holds
+// ln_bwd_partial_blocks(rows) * (dxsum ? 2 : 1) * D floats; DXM != nullptr (needs dxsum) is the dropout
+// variant (dr is read then only); DRES may be given in every form.
+void launch_rms_fwd(const uint16_t* X, const float* gamma, uint16_t* Y, float* rstd, int64_t rows, int D, float eps,
+                    hipStream_t st);
+void launch_dropout_add_rms_fwd(const uint16_t* Y0, const uint16_t* RES, const float* gamma, uint16_t* Z, uint16_t* Y,
+                                float* rstd, int64_t rows, int D, float eps, DropArgs dr, hipStream_t st);
+void launch_rms_bwd(const uint16_t* DY, const uint16_t* X, const float* gamma, const float* rstd, uint16_t* DX,
+                    uint16_t* DXM, float* part, float* dgamma, int64_t rows, int D, int accumulate,
+                    const uint16_t* DRES, float* dxsum, int dxsum_acc, DropArgs dr, hipStream_t st);
 // out = keep ? bf16(x * scale) : 0 over numel (% 8 == 0) contiguous bf16 elements (dropout.hip)
 void launch_dropout(const uint16_t* x, uint16_t* out, int64_t numel, DropArgs dr, hipStream_t st);
 // pos (packed batches, or nullptr): the position of every row, each < S; nullptr: row % S.

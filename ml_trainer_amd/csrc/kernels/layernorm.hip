@@ -541,4 +541,267 @@ void launch_embed_bwd(const int64_t* sid, const int64_t* perm, const int64_t* tt
   launch_reduce_rows(part, S, 2 * D, ntype >= 2 ? 2 * D : D, D, o, ntype >= 2 ? 3 : 1, st);
 }
 
+// ---------------------------------------------------------------------------
+// Pre-norm blocks. The residual stream h and its norm n are separate tensors there, so the norm
+// backward's DX is rstd (...) + DRES with DRES = the stream's own gradient, also under hidden dropout:
+// ln_bwd_kernel<VPL, true, true> reads DRES at run time like the other instantiations, only its launcher
+// passed none so far. DX is then the total stream gradient and DXM its masked, scaled copy.
+// ---------------------------------------------------------------------------
+void launch_ln_bwd_dropout_res(const uint16_t* DY, const uint16_t* X, const float* gamma, const float* mean,
+                               const float* rstd, uint16_t* DX, uint16_t* DXM, float* part, float* dgamma,
+                               float* dbeta, int64_t rows, int D, int accumulate, const uint16_t* DRES, float* dxsum,
+                               int dxsum_acc, DropArgs dr, hipStream_t st) {
+  if (rows <= 0) return;
+  const int nb = ln_bwd_partial_blocks(rows);
+  const dim3 grid(nb), block(256);
+  const LnBwdDrop d{DXM, dr};
+  by_vpl("launch_ln_bwd_dropout_res", D, [&](auto v) {
+    hipLaunchKernelGGL((ln_bwd_kernel<v(), true, true, LnBwdDrop>), grid, block, 0, st, DY, X, gamma, mean, rstd, DX,
+                       part, rows, DRES, d);
+  });
+  SegOut o{{dgamma, dbeta, dxsum}};
+  launch_reduce_rows(part, nb, 3 * D, 3 * D, D, o, (accumulate ? 3 : 0) | (dxsum_acc ? 4 : 0), st);
+}
+
+// ---------------------------------------------------------------------------
+// RMSNorm: y = x * rsqrt(mean(x^2) + eps) * g. No centring, no bias; the row-kernel design of the
+// LayerNorm kernels above (one wave per row, 8-byte bf16 accesses, fp32 statistics, fixed-order
+// partials through reduce_rows). Only rstd is saved.
+// ---------------------------------------------------------------------------
+template <int VPL>
+__device__ __forceinline__ void rms_fwd_row(const float (&x)[VPL * 4], const float* __restrict__ gamma,
+                                            uint16_t* __restrict__ Y, float* __restrict__ rstd, int64_t row,
+                                            float eps) {
+  constexpr int D = VPL * 256, E = VPL * 4;
+  const int lane = threadIdx.x & 63;
+  float q = 0.f;
+#pragma unroll
+  for (int i = 0; i < E; ++i) q += x[i] * x[i];
+  const float rs = rsqrtf(wave_sum(q) * (1.f / D) + eps);
+#pragma unroll
+  for (int v = 0; v < VPL; ++v) {
+    const float4 g = *reinterpret_cast<const float4*>(gamma + 4 * (lane + 64 * v));
+    ushort4 o;
+    o.x = f32_to_bf16(x[4 * v + 0] * rs * g.x);
+    o.y = f32_to_bf16(x[4 * v + 1] * rs * g.y);
+    o.z = f32_to_bf16(x[4 * v + 2] * rs * g.z);
+    o.w = f32_to_bf16(x[4 * v + 3] * rs * g.w);
+    reinterpret_cast<ushort4*>(Y + row * D)[lane + 64 * v] = o;
+  }
+  if (lane == 0) rstd[row] = rs;
+}
+
+template <int VPL>
+__global__ __launch_bounds__(256) void rms_fwd_kernel(const uint16_t* __restrict__ X, const float* __restrict__ gamma,
+                                                      uint16_t* __restrict__ Y, float* __restrict__ rstd,
+                                                      int64_t rows, float eps) {
+  constexpr int D = VPL * 256, E = VPL * 4;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  float x[E];
+  load_row<VPL>(X + row * D, x);
+  rms_fwd_row<VPL>(x, gamma, Y, rstd, row, eps);
+}
+
+// Z = bf16(dropout(Y0) + RES), Y = RMSNorm(Z): mask, scaling and rounding of Z as in
+// dropout_add_ln_fwd_kernel; Y / rstd through rms_fwd_row from the rounded Z, so bitwise rms_fwd_kernel's on Z.
+template <int VPL>
+__global__ __launch_bounds__(256) void dropout_add_rms_fwd_kernel(
+    const uint16_t* __restrict__ Y0, const uint16_t* __restrict__ RES, const float* __restrict__ gamma,
+    uint16_t* __restrict__ Z, uint16_t* __restrict__ Y, float* __restrict__ rstd, int64_t rows, float eps,
+    DropArgs dr) {
+  constexpr int D = VPL * 256, E = VPL * 4;
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  float x[E];
+#pragma unroll
+  for (int v = 0; v < VPL; ++v) {
+    const ushort4 a = reinterpret_cast<const ushort4*>(Y0 + row * D)[lane + 64 * v];
+    const ushort4 r = reinterpret_cast<const ushort4*>(RES + row * D)[lane + 64 * v];
+    const Philox4 w = drop_words((uint64_t)row * (D / 4) + lane + 64 * v, dr);
+    ushort4 z;
+    z.x = f32_to_bf16((w.x >= dr.thr ? __fmul_rn(bf16_to_f32(a.x), dr.scale) : 0.f) + bf16_to_f32(r.x));
+    z.y = f32_to_bf16((w.y >= dr.thr ? __fmul_rn(bf16_to_f32(a.y), dr.scale) : 0.f) + bf16_to_f32(r.y));
+    z.z = f32_to_bf16((w.z >= dr.thr ? __fmul_rn(bf16_to_f32(a.z), dr.scale) : 0.f) + bf16_to_f32(r.z));
+    z.w = f32_to_bf16((w.w >= dr.thr ? __fmul_rn(bf16_to_f32(a.w), dr.scale) : 0.f) + bf16_to_f32(r.w));
+    reinterpret_cast<ushort4*>(Z + row * D)[lane + 64 * v] = z;
+    x[4 * v + 0] = bf16_to_f32(z.x);
+    x[4 * v + 1] = bf16_to_f32(z.y);
+    x[4 * v + 2] = bf16_to_f32(z.z);
+    x[4 * v + 3] = bf16_to_f32(z.w);
+  }
+  rms_fwd_row<VPL>(x, gamma, Y, rstd, row, eps);
+}
+
+// xh = x rstd, t = dy g, s2 = mean(t xh): dx = rstd (t - xh s2) (+ dres); partial dgamma per block.
+// DXS / DROP and the trailing pack as in ln_bwd_kernel; DRES is read at run time in every instantiation
+// (the pre-norm blocks pass the residual stream's gradient there, with and without dropout). Contraction
+// off and explicit fmaf, so DX is bitwise the same in every instantiation.
+template <int VPL, bool DXS, bool DROP = false, typename... DropT>
+__global__ __launch_bounds__(256) void rms_bwd_kernel(const uint16_t* __restrict__ DY, const uint16_t* __restrict__ X,
+                                                      const float* __restrict__ gamma, const float* __restrict__ rstd,
+                                                      uint16_t* __restrict__ DX, float* __restrict__ part, int64_t rows,
+                                                      const uint16_t* __restrict__ DRES, DropT... drop_args) {
+#pragma clang fp contract(off)
+  static_assert(!DROP || DXS, "the dropout variant always reduces DXM's column sums");
+  static_assert(sizeof...(DropT) == (DROP ? 1 : 0), "one LnBwdDrop exactly when DROP");
+  constexpr int D = VPL * 256, E = VPL * 4;
+  constexpr int NS = DXS ? 2 : 1;
+  __shared__ float red[4][NS * D];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  float dg[E], g[E], dxs[DXS ? E : 1];  // dxs: the column sums of DX, or of DXM when DROP
+#pragma unroll
+  for (int i = 0; i < E; ++i) {
+    dg[i] = 0.f;
+    if constexpr (DXS) dxs[i] = 0.f;
+  }
+#pragma unroll
+  for (int v = 0; v < VPL; ++v) {
+    const float4 gv = *reinterpret_cast<const float4*>(gamma + 4 * (lane + 64 * v));
+    g[4 * v] = gv.x;
+    g[4 * v + 1] = gv.y;
+    g[4 * v + 2] = gv.z;
+    g[4 * v + 3] = gv.w;
+  }
+  // software-pipelined over the wave's rows, as in ln_bwd_kernel
+  const int64_t rstep = (int64_t)gridDim.x * 4;
+  int64_t row = (int64_t)blockIdx.x * 4 + wid;
+  ushort4 nx[VPL], ndy[VPL];
+  float nrs = 0.f;
+  auto fetch = [&](int64_t r) {
+    const int64_t rr = r < rows ? r : rows - 1;  // clamped, branch-free
+#pragma unroll
+    for (int v = 0; v < VPL; ++v) {
+      nx[v] = reinterpret_cast<const ushort4*>(X + rr * D)[lane + 64 * v];
+      ndy[v] = reinterpret_cast<const ushort4*>(DY + rr * D)[lane + 64 * v];
+    }
+    nrs = rstd[rr];
+  };
+  if (row < rows) fetch(row);
+  for (; row < rows; row += rstep) {
+    float x[E], dy[E];
+#pragma unroll
+    for (int v = 0; v < VPL; ++v) {
+      x[4 * v + 0] = bf16_to_f32(nx[v].x);
+      x[4 * v + 1] = bf16_to_f32(nx[v].y);
+      x[4 * v + 2] = bf16_to_f32(nx[v].z);
+      x[4 * v + 3] = bf16_to_f32(nx[v].w);
+      dy[4 * v + 0] = bf16_to_f32(ndy[v].x);
+      dy[4 * v + 1] = bf16_to_f32(ndy[v].y);
+      dy[4 * v + 2] = bf16_to_f32(ndy[v].z);
+      dy[4 * v + 3] = bf16_to_f32(ndy[v].w);
+    }
+    const float rs = nrs;
+    fetch(row + rstep);  // unconditional: past the end it re-reads the last row (unused)
+    float s2 = 0.f;
+#pragma unroll
+    for (int i = 0; i < E; ++i) {
+      const float xh = x[i] * rs;
+      x[i] = xh;
+      const float t = dy[i] * g[i];
+      s2 = fmaf(t, xh, s2);
+      dg[i] = fmaf(dy[i], xh, dg[i]);
+      dy[i] = t;
+    }
+    s2 = wave_sum(s2) * (1.f / D);
+    float dres[E];
+    if (DRES) load_row<VPL>(DRES + row * D, dres);
+#pragma unroll
+    for (int v = 0; v < VPL; ++v) {
+      float o[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int i = 4 * v + q;
+        // rs * (t - xh * s2) + dres, one rounding per line
+        const float b = fmaf(-x[i], s2, dy[i]);
+        o[q] = DRES ? fmaf(rs, b, dres[i]) : rs * b;
+      }
+      ushort4 u;
+      u.x = f32_to_bf16(o[0]);
+      u.y = f32_to_bf16(o[1]);
+      u.z = f32_to_bf16(o[2]);
+      u.w = f32_to_bf16(o[3]);
+      reinterpret_cast<ushort4*>(DX + row * D)[lane + 64 * v] = u;
+      if constexpr (DROP) {
+        const LnBwdDrop& drop = ln_bwd_drop_arg(drop_args...);
+        // DXM from the stored (bf16-rounded) DX; the mask of the global row, as in the forward
+        const Philox4 w = drop_words((uint64_t)row * (D / 4) + lane + 64 * v, drop.dr);
+        const uint32_t thr = drop.dr.thr;
+        const float sc = drop.dr.scale;
+        ushort4 m;
+        m.x = w.x >= thr ? f32_to_bf16(bf16_to_f32(u.x) * sc) : (uint16_t)0;
+        m.y = w.y >= thr ? f32_to_bf16(bf16_to_f32(u.y) * sc) : (uint16_t)0;
+        m.z = w.z >= thr ? f32_to_bf16(bf16_to_f32(u.z) * sc) : (uint16_t)0;
+        m.w = w.w >= thr ? f32_to_bf16(bf16_to_f32(u.w) * sc) : (uint16_t)0;
+        reinterpret_cast<ushort4*>(drop.DXM + row * D)[lane + 64 * v] = m;
+        dxs[4 * v + 0] += bf16_to_f32(m.x);
+        dxs[4 * v + 1] += bf16_to_f32(m.y);
+        dxs[4 * v + 2] += bf16_to_f32(m.z);
+        dxs[4 * v + 3] += bf16_to_f32(m.w);
+      } else if constexpr (DXS) {
+        dxs[4 * v + 0] += bf16_to_f32(u.x);
+        dxs[4 * v + 1] += bf16_to_f32(u.y);
+        dxs[4 * v + 2] += bf16_to_f32(u.z);
+        dxs[4 * v + 3] += bf16_to_f32(u.w);
+      }
+    }
+  }
+#pragma unroll
+  for (int v = 0; v < VPL; ++v)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int c = 4 * (lane + 64 * v) + q;
+      red[wid][c] = dg[4 * v + q];
+      if constexpr (DXS) red[wid][D + c] = dxs[4 * v + q];
+    }
+  __syncthreads();
+  for (int c = threadIdx.x; c < NS * D; c += 256)
+    part[(int64_t)blockIdx.x * NS * D + c] = (red[0][c] + red[1][c]) + (red[2][c] + red[3][c]);
+}
+
+void launch_rms_fwd(const uint16_t* X, const float* gamma, uint16_t* Y, float* rstd, int64_t rows, int D, float eps,
+                    hipStream_t st) {
+  if (rows <= 0) return;
+  const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+  by_vpl("launch_rms_fwd", D,
+         [&](auto v) { hipLaunchKernelGGL(rms_fwd_kernel<v()>, grid, block, 0, st, X, gamma, Y, rstd, rows, eps); });
+}
+
+void launch_dropout_add_rms_fwd(const uint16_t* Y0, const uint16_t* RES, const float* gamma, uint16_t* Z, uint16_t* Y,
+                                float* rstd, int64_t rows, int D, float eps, DropArgs dr, hipStream_t st) {
+  if (rows <= 0) return;
+  const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+  by_vpl("launch_dropout_add_rms_fwd", D, [&](auto v) {
+    hipLaunchKernelGGL(dropout_add_rms_fwd_kernel<v()>, grid, block, 0, st, Y0, RES, gamma, Z, Y, rstd, rows, eps, dr);
+  });
+}
+
+// part: ln_bwd_partial_blocks(rows) * (dxsum ? 2 : 1) * D floats. DXM (with dxsum): the dropout variant.
+void launch_rms_bwd(const uint16_t* DY, const uint16_t* X, const float* gamma, const float* rstd, uint16_t* DX,
+                    uint16_t* DXM, float* part, float* dgamma, int64_t rows, int D, int accumulate,
+                    const uint16_t* DRES, float* dxsum, int dxsum_acc, DropArgs dr, hipStream_t st) {
+  if (rows <= 0) return;
+  const int nb = ln_bwd_partial_blocks(rows);
+  const dim3 grid(nb), block(256);
+  const int NS = dxsum ? 2 : 1;
+  by_vpl("launch_rms_bwd", D, [&](auto v) {
+    constexpr int V = decltype(v)::value;
+    if (DXM) {
+      const LnBwdDrop d{DXM, dr};
+      hipLaunchKernelGGL((rms_bwd_kernel<V, true, true, LnBwdDrop>), grid, block, 0, st, DY, X, gamma, rstd, DX, part,
+                         rows, DRES, d);
+    } else {
+      dispatch_bools(
+          [&](auto sum) {
+            hipLaunchKernelGGL((rms_bwd_kernel<V, decltype(sum)::value>), grid, block, 0, st, DY, X, gamma, rstd, DX,
+                               part, rows, DRES);
+          },
+          dxsum != nullptr);
+    }
+  });
+  SegOut o{{dgamma, dxsum, nullptr}};
+  launch_reduce_rows(part, nb, NS * D, NS * D, D, o, (accumulate ? 1 : 0) | (dxsum_acc ? 2 : 0), st);
+}
+
 }  // namespace mlt

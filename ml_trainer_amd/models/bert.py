@@ -74,7 +74,7 @@ step reads anything back. On the CPU the same runs in fp32 torch with an fp32 ca
 ``generate_reference`` / ``decode_logits_reference`` are the uncached oracle. Opt-in: ``sampler="device"`` (the
 ``sample_step`` kernel of ``ops.decode``: top-k / top-p and the EOS bookkeeping in one launch, integer-defined,
 independent of the batch), ``top_p``, and ``graph=True`` (``GraphedDecoder``: one captured graph of ``decode_step`` +
-``sample_step`` replayed per token). Not built: pre-LN blocks, paged caches, beam search, repetition penalties,
+``sample_step`` replayed per token). Not built: paged caches, beam search, repetition penalties,
 ``return_logits`` under a graph, a graph for ``prefill``.
 
 Rotary positions (``BertConfig.rotary``, default False; ``rope_base``): instead of a learned position table added at
@@ -87,6 +87,20 @@ attention kernel and rotates dQKV back in the backward; the key/value cache hold
 instantiation of ``attn_decode`` rotates the one new row per sequence. ``max_position`` only sizes the table: it may
 exceed every length seen in training, which is the point (a model trained at 32 tokens can be run past them). It
 composes with ``causal``, ``unpad`` and both dropouts and with all three model classes; with ``fp8`` it is rejected.
+
+Pre-norm blocks (``BertConfig.pre_ln``, default False) and RMSNorm (``BertConfig.norm = "rmsnorm"``, default
+``"layernorm"``; needs ``pre_ln``): the layer keeps its module names and becomes
+``n = ln1(h); h = h + drop(out(attn(qkv(n)))); n = ln2(h); h = h + drop(ffn2(gelu(ffn1(n))))`` (the hidden-dropout
+sites of the post-LN layer), and one more norm of the same kind, ``final_ln``, follows the last layer: its output is
+what the pooler, the MLM head and the LM head consume. ``norm`` selects the kind of ``ln1``, ``ln2`` and ``final_ln``
+only; ``emb_ln`` and the MLM head's ``mlm_ln`` stay LayerNorm. RMSNorm is ``x * rsqrt(mean(x^2) + ln_eps) * weight``
+with fp32 statistics, no centring and no bias (no ``.bias`` keys). On the GPU a sub-layer is one autograd node
+``(h, n) -> (h', n')`` (``ops.transformer.pre_attention_block`` / ``pre_ffn_block``): the residual stream ``h`` is
+stored in bf16 after every add, the norm of the new stream comes from the kernel that closes the sub-layer, and the
+norm backward adds the stream's gradient in the kernel. The key/value cache and ``attn_decode`` are unchanged
+(``prefill`` caches the QKV of ``n``); ``decode_step`` keeps the normed rows in ``state.hidden``. Composes with
+``causal``, ``unpad``, ``rotary``, both dropouts and all three model classes; with ``fp8`` it is rejected. Not built:
+post-norm RMSNorm, RMSNorm for ``emb_ln`` / ``mlm_ln``, gated FFNs, the norm fused into a GEMM prologue.
 """
 from __future__ import annotations
 
@@ -120,6 +134,8 @@ class BertConfig:
     causal: bool = False  # key j visible to query i iff j <= i (and j < len_b); not with fp8
     rotary: bool = False  # rotary positions on q and k instead of a learned position table; not with fp8
     rope_base: float = 10000.0  # the angle of position p, pair i is p * rope_base ** (-2 i / 64)
+    pre_ln: bool = False  # pre-norm blocks h + f(norm(h)) and a final norm (final_ln); not with fp8
+    norm: str = "layernorm"  # the kind of ln1 / ln2 / final_ln: "layernorm", or "rmsnorm" (needs pre_ln)
 
 
 _PRESETS = {
@@ -137,6 +153,31 @@ def bert_config(name: str = "bert-base", **overrides) -> BertConfig:
     return replace(cfg, **overrides) if overrides else cfg
 
 
+class RMSNorm(nn.Module):
+    """``x * rsqrt(mean(x^2, -1) + eps) * weight``: no centring, no bias. Computed in fp32, returned in the
+    dtype of ``x``."""
+
+    def __init__(self, hidden: int, eps: float):
+        super().__init__()
+        self.weight = nn.Parameter(torch.ones(hidden))
+        self.register_parameter("bias", None)
+        self.eps = eps
+
+    def forward(self, x):
+        xf = x.float()
+        return (xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + self.eps) * self.weight.float()).to(x.dtype)
+
+
+def block_norm(c: BertConfig) -> nn.Module:
+    """A norm of the kind ``c.norm`` selects for ``ln1`` / ``ln2`` / ``final_ln``."""
+    return RMSNorm(c.hidden, c.ln_eps) if c.norm == "rmsnorm" else nn.LayerNorm(c.hidden, eps=c.ln_eps)
+
+
+def _norm_args(m):
+    """(gamma, beta or None, eps) of a LayerNorm / RMSNorm module for the native norm kernels."""
+    return m.weight, m.bias, m.eps
+
+
 class BertLayer(nn.Module):
     def __init__(self, c: BertConfig):
         super().__init__()
@@ -144,10 +185,10 @@ class BertLayer(nn.Module):
         self.c = c
         self.qkv = nn.Linear(h, 3 * h)
         self.out = nn.Linear(h, h)
-        self.ln1 = nn.LayerNorm(h, eps=c.ln_eps)
+        self.ln1 = block_norm(c)
         self.ffn1 = nn.Linear(h, c.intermediate)
         self.ffn2 = nn.Linear(c.intermediate, h)
-        self.ln2 = nn.LayerNorm(h, eps=c.ln_eps)
+        self.ln2 = block_norm(c)
 
     def forward_native(self, x, lens, B, S, drop=None, attn_drop=None, cu_seqlens=None, rope=None):
         """``drop`` = (p, seed, site of the attention sub-layer, rank); the FFN takes the next site.
@@ -167,16 +208,33 @@ class BertLayer(nn.Module):
         return T.ffn_ln_block(x, self.ffn1.weight, self.ffn1.bias, self.ffn2.weight, self.ffn2.bias, self.ln2.weight,
                               self.ln2.bias, self.c.ln_eps, impl, drop)
 
+    def forward_native_pre(self, h, n, next_norm, lens, B, S, drop=None, attn_drop=None, cu_seqlens=None, rope=None):
+        """The pre-norm layer on the native kernels: (h, n = ln1(h)) -> (h', n' = next_norm(h')), where
+        ``next_norm`` is the next layer's ``ln1`` or the model's ``final_ln``. Arguments as in forward_native."""
+        from ml_trainer_amd.ops import transformer as T
+        eps = self.c.ln_eps
+        h, n = T.pre_attention_block(h, n, self.qkv.weight, self.qkv.bias, self.out.weight, self.out.bias,
+                                     self.ln2.weight, self.ln2.bias, lens, B, S, self.c.heads, eps, T.BF16, drop,
+                                     attn_drop, cu_seqlens, self.c.causal, rope)
+        if drop is not None:
+            drop = (drop[0], drop[1], drop[2] + 1, drop[3])
+        return T.pre_ffn_block(h, n, self.ffn1.weight, self.ffn1.bias, self.ffn2.weight, self.ffn2.bias,
+                               next_norm.weight, next_norm.bias, eps, T.BF16, drop)
+
     def forward_reference(self, x, mask, B, S, drop=None, attn_drop=None, packed=None, rope=None):
         """fp32 torch reference. x [B*S, h]; mask [B, S] bool (True = valid key); drop and attn_drop
         as in forward_native (the same masks, through ops.dropout). ``packed`` (a PackedBatch): x is
         [T, h]; the linears, LayerNorms and hidden dropout run on the packed rows, attention on a
         padded scratch of the QKV rows (so its dropout mask is the padded run's). With ``config.causal``
         the lower-triangular mask (key <= query) joins the key mask. ``rope`` (the table): q and k are rotated in
-        the dtype of the activations (fp32) at position = column of the padded layout."""
+        the dtype of the activations (fp32) at position = column of the padded layout. With ``config.pre_ln``
+        x is the residual stream and so is the result (the model applies ``final_ln`` after the last layer)."""
         from ml_trainer_amd.ops import dropout as D
         c = self.c
         H, dh = c.heads, c.hidden // c.heads
+        res = x
+        if c.pre_ln:
+            x = self.ln1(x)
         qkv = self.qkv(x)
         if packed is not None:
             from ml_trainer_amd.ops.transformer import unpack_rows
@@ -202,11 +260,11 @@ class BertLayer(nn.Module):
         a = self.out(ctx)
         if drop is not None:
             a = D.apply(a, *drop)
-        x = self.ln1(a + x)
-        f = self.ffn2(F.gelu(self.ffn1(x)))
+        x = a + res if c.pre_ln else self.ln1(a + x)
+        f = self.ffn2(F.gelu(self.ffn1(self.ln2(x) if c.pre_ln else x)))
         if drop is not None:
             f = D.apply(f, drop[0], drop[1], drop[2] + 1, drop[3])
-        return self.ln2(f + x)
+        return f + x if c.pre_ln else self.ln2(f + x)
 
 
 class BertClassifier(nn.Module):
@@ -231,6 +289,13 @@ class BertClassifier(nn.Module):
         if c.rotary and c.fp8:
             raise ValueError("rotary=True with fp8=True is not supported: the fp8 attention backward writes dQKV as "
                              "e5m2, which the inverse rotation cannot take")
+        if c.norm not in ("layernorm", "rmsnorm"):
+            raise ValueError(f"norm must be 'layernorm' or 'rmsnorm', got {c.norm!r}")
+        if c.norm == "rmsnorm" and not c.pre_ln:
+            raise ValueError("norm='rmsnorm' needs pre_ln=True: post-norm RMSNorm blocks are not built")
+        if (c.pre_ln or c.norm != "layernorm") and c.fp8:
+            raise ValueError("pre_ln=True / norm='rmsnorm' with fp8=True is not supported: the pre-norm blocks run "
+                             "the bf16 linears only")
         self.config = c
         self.last_dropout_seed = None  # the seed of the last forward that dropped
         self.word_embeddings = nn.Embedding(c.vocab_size, c.hidden)
@@ -244,6 +309,8 @@ class BertClassifier(nn.Module):
         self.token_type_embeddings = nn.Embedding(c.type_vocab, c.hidden)
         self.emb_ln = nn.LayerNorm(c.hidden, eps=c.ln_eps)
         self.layers = nn.ModuleList([BertLayer(c) for _ in range(c.layers)])
+        if c.pre_ln:  # the norm of the last layer's stream: what every head consumes
+            self.final_ln = block_norm(c)
         self._build_head(c)
         self.apply(self._init)
 
@@ -278,6 +345,22 @@ class BertClassifier(nn.Module):
             p = self.position_embeddings(pos)
             x = x + (p[None] if per_batch else p)
         return x + self.token_type_embeddings(tt)
+
+    def _final_norm(self, x):
+        """``final_ln`` of a pre-norm model on the stream ``x`` in plain torch; the identity for post-LN."""
+        return self.final_ln(x) if self.config.pre_ln else x
+
+    def _pre_stack_native(self, x, lens, B, S, drop, adrop, cu=None, rope=None):
+        """The pre-norm layers on the native kernels from the embedding output ``x`` (the first stream):
+        ``final_ln`` of the last stream, [rows, h] bf16."""
+        from ml_trainer_amd.ops import transformer as T
+        h, n = T.stream_norm(x, *_norm_args(self.layers[0].ln1))
+        last = len(self.layers) - 1
+        for l, layer in enumerate(self.layers):
+            nxt = self.final_ln if l == last else self.layers[l + 1].ln1
+            h, n = layer.forward_native_pre(h, n, nxt, lens, B, S, self._site(drop, 1 + 2 * l),
+                                            self._attn_site(adrop, l), cu, rope)
+        return n
 
     def _lengths(self, input_ids, attention_mask):
         B, S = input_ids.shape
@@ -358,6 +441,8 @@ class BertClassifier(nn.Module):
         if drop is not None:
             x = T.dropout(x, *self._site(drop, 0))
         rope = self._rope()
+        if self.config.pre_ln:
+            return self._pre_stack_native(x, lens, B, S, drop, adrop, None, rope)
         for l, layer in enumerate(self.layers):
             x = layer.forward_native(x, lens, B, S, self._site(drop, 1 + 2 * l), self._attn_site(adrop, l), rope=rope)
         return x
@@ -373,6 +458,8 @@ class BertClassifier(nn.Module):
         if drop is not None:
             x = T.dropout(x, *self._site(drop, 0))
         rope = self._rope(pk.pos)
+        if self.config.pre_ln:
+            return self._pre_stack_native(x, None, B, S, drop, adrop, cu, rope)
         for l, layer in enumerate(self.layers):
             x = layer.forward_native(x, None, B, S, self._site(drop, 1 + 2 * l), self._attn_site(adrop, l), cu, rope)
         return x
@@ -398,6 +485,7 @@ class BertClassifier(nn.Module):
         for l, layer in enumerate(self.layers):
             x = layer.forward_reference(x, mask, B, S, self._site(drop, 1 + 2 * l), self._attn_site(adrop, l), pk,
                                         self.rope_table)
+        x = self._final_norm(x)
         return x if full else x.index_select(0, pk.cls_rows)
 
     def forward_reference_hidden(self, input_ids, lens=None, token_type_ids=None, drop=None, adrop=None, full=False):
@@ -418,6 +506,7 @@ class BertClassifier(nn.Module):
         for l, layer in enumerate(self.layers):
             x = layer.forward_reference(x, mask, B, S, self._site(drop, 1 + 2 * l), self._attn_site(adrop, l),
                                         rope=self.rope_table)
+        x = self._final_norm(x)
         return x if full else x.view(B, S, -1)[:, 0]
 
     def forward_reference(self, input_ids, attention_mask=None, token_type_ids=None, dropout_seed=None):
@@ -437,6 +526,7 @@ class BertClassifier(nn.Module):
         uses the native path's masks (ops.dropout), each applied in the dtype autocast gives the
         tensor it drops. With attention dropout active the attention is computed explicitly under
         autocast (softmax -> * keep * scale -> @ v) instead of through SDPA, which cannot take our mask.
+        Under ``pre_ln`` the residual stream is rounded to bf16 after every add, as the native path stores it.
         Returns (hidden [B, S, h] -- packed: [1, T, h] --, the PackedBatch or None); the callers add their head."""
         from ml_trainer_amd.ops import dropout as D
         c = self.config
@@ -467,8 +557,10 @@ class BertClassifier(nn.Module):
                 tt = pk.tt if pk.tt is not None else torch.zeros_like(pk.ids)
                 x = self._embed_torch(pk.ids, tt, pk.pos.long())[None]
             x = dropped(self.emb_ln(x), 0)
+            if c.pre_ln:
+                x = x.to(torch.bfloat16)
             for l, L in enumerate(self.layers):
-                qkv = L.qkv(x)
+                qkv = L.qkv(L.ln1(x) if c.pre_ln else x)
                 if pk is not None:
                     qkv = unpack_rows(qkv[0], pk)
                 qkv = qkv.view(B, S, 3, c.heads, 64).permute(2, 0, 3, 1, 4)
@@ -489,9 +581,13 @@ class BertClassifier(nn.Module):
                 ctx = ctx.transpose(1, 2).reshape(B, S, -1)
                 if pk is not None:
                     ctx = ctx.reshape(B * S, -1).index_select(0, pk.index)[None]
+                if c.pre_ln:
+                    x = (dropped(L.out(ctx), 1 + 2 * l) + x).to(torch.bfloat16)
+                    x = (dropped(L.ffn2(F.gelu(L.ffn1(L.ln2(x)))), 2 + 2 * l) + x).to(torch.bfloat16)
+                    continue
                 x = L.ln1(dropped(L.out(ctx), 1 + 2 * l) + x)
                 x = L.ln2(dropped(L.ffn2(F.gelu(L.ffn1(x))), 2 + 2 * l) + x)
-            return x, pk
+            return self._final_norm(x), pk
 
     def num_parameters(self) -> int:
         return sum(p.numel() for p in self.parameters())
@@ -702,6 +798,14 @@ class BertLMHeadModel(BertForMaskedLM):
                              self.token_type_embeddings.weight, S)
             x, _ = T._ln_fwd(x, self.emb_ln.weight, self.emb_ln.bias, c.ln_eps)
             for l, L in enumerate(self.layers):
+                if c.pre_ln:  # x is the stream; the cache holds the K / V of its norm
+                    n, _ = T._norm_fwd(x, *_norm_args(L.ln1))
+                    x, (_, qkv, _, _) = T._attn_fwd(n, L.qkv.weight, L.qkv.bias, L.out.weight, L.out.bias, lens, B, S,
+                                                    c.heads, causal=True, rope=self._rope(), res=x)
+                    DC.fill_from_prefill(cache, l, qkv, lens, B, S)
+                    n, _ = T._norm_fwd(x, *_norm_args(L.ln2))
+                    x, _ = T._ffn_fwd(n, L.ffn1.weight, L.ffn1.bias, L.ffn2.weight, L.ffn2.bias, res=x)
+                    continue
                 a, (_, qkv, _, _) = T._attn_fwd(x, L.qkv.weight, L.qkv.bias, L.out.weight, L.out.bias, lens, B, S,
                                                 c.heads, causal=True, rope=self._rope())  # (qkv: rotated under rotary)
                 DC.fill_from_prefill(cache, l, qkv, lens, B, S)
@@ -714,14 +818,21 @@ class BertLMHeadModel(BertForMaskedLM):
             x = self.emb_ln(x).view(B * S, -1)
             mask = None if lens is None else pos[None, :] < lens[:, None]
             for l, L in enumerate(self.layers):
-                qkv = L.qkv(x)
+                qkv = L.qkv(L.ln1(x) if c.pre_ln else x)
                 if c.rotary:  # the cache holds rotated keys
                     from ml_trainer_amd.ops.rope import rope_qk_reference
                     qkv = rope_qk_reference(qkv, self.rope_table, c.heads, S)
                 DC.fill_from_prefill(cache, l, qkv, lens, B, S)
                 x = L.forward_reference(x, mask, B, S, rope=self.rope_table)
         cache.pos.copy_(lens if lens is not None else torch.full((B,), S, dtype=torch.int32, device=dev))
-        return DC.DecodeState(cache, x.index_select(0, self._last_rows(lens, B, S, dev)))
+        x = x.index_select(0, self._last_rows(lens, B, S, dev))
+        if c.pre_ln:  # rows are independent: the final norm of the last real rows only
+            if x.is_cuda:
+                from ml_trainer_amd.ops import transformer as T
+                x, _ = T._norm_fwd(x, *_norm_args(self.final_ln))
+            else:
+                x = self.final_ln(x)
+        return DC.DecodeState(cache, x)
 
     def _state_logits(self, state):
         from ml_trainer_amd.ops import decode as DC
@@ -739,7 +850,8 @@ class BertLMHeadModel(BertForMaskedLM):
         new is run. With ``token_ids`` [B]: token b enters sequence b at position ``state.pos[b]`` and runs
         through the stack on one row per sequence (embedding at explicit positions, per layer QKV GEMM ->
         ``attn_decode`` over the cache, which under rotary positions rotates q and the new k by ``state.pos[b]`` first
-        -> out-projection + residual -> LayerNorm -> FFN -> LayerNorm), then
+        -> out-projection + residual -> LayerNorm -> FFN -> LayerNorm; pre-norm: norm -> QKV -> ``attn_decode`` ->
+        out-projection + stream -> norm -> FFN + stream per layer, then ``final_ln``), then
         ``state.pos`` advances by 1 on the device. Nothing is read back from the device. The caller keeps
         ``state.pos[b]`` below the cache's ``Smax`` (``generate`` does by construction)."""
         if token_ids is None:
@@ -758,6 +870,16 @@ class BertLMHeadModel(BertForMaskedLM):
                         T.bf16_weight(self.token_type_embeddings.weight), x, cache.Smax, pos=cache.pos)
             x, _ = T._ln_fwd(x, self.emb_ln.weight, self.emb_ln.bias, c.ln_eps)
             for l, L in enumerate(self.layers):
+                if c.pre_ln:  # x is the stream
+                    n, _ = T._norm_fwd(x, *_norm_args(L.ln1))
+                    qkv = DC.linear_small(n, T.bf16_weight(L.qkv.weight), L.qkv.bias)
+                    ctx = DC.attn_decode(qkv, cache.kv[l], cache.pos, c.heads, rope=self.rope_table)
+                    x = DC.linear_small(ctx, T.bf16_weight(L.out.weight), L.out.bias, res=x)
+                    n, _ = T._norm_fwd(x, *_norm_args(L.ln2))
+                    pre = torch.empty(B, L.ffn1.weight.shape[0], dtype=torch.bfloat16, device=x.device)
+                    g = DC.linear_small(n, T.bf16_weight(L.ffn1.weight), L.ffn1.bias, gelu_aux=pre)
+                    x = DC.linear_small(g, T.bf16_weight(L.ffn2.weight), L.ffn2.bias, res=x)
+                    continue
                 qkv = DC.linear_small(x, T.bf16_weight(L.qkv.weight), L.qkv.bias)
                 ctx = DC.attn_decode(qkv, cache.kv[l], cache.pos, c.heads, rope=self.rope_table)
                 a = DC.linear_small(ctx, T.bf16_weight(L.out.weight), L.out.bias, res=x)
@@ -766,12 +888,21 @@ class BertLMHeadModel(BertForMaskedLM):
                 g = DC.linear_small(x, T.bf16_weight(L.ffn1.weight), L.ffn1.bias, gelu_aux=pre)
                 f = DC.linear_small(g, T.bf16_weight(L.ffn2.weight), L.ffn2.bias, res=x)
                 x, _ = T._ln_fwd(f, L.ln2.weight, L.ln2.bias, c.ln_eps)
+            if c.pre_ln:  # state.hidden holds the normed rows, as after a post-LN layer
+                x, _ = T._norm_fwd(x, *_norm_args(self.final_ln))
         else:
             x = self.emb_ln(self._embed_torch(ids, torch.zeros_like(ids), cache.pos.long()))
             for l, L in enumerate(self.layers):
+                if c.pre_ln:
+                    ctx = DC.attn_decode_reference(L.qkv(L.ln1(x)), cache.kv[l], cache.pos, c.heads,
+                                                   rope=self.rope_table)
+                    x = L.out(ctx) + x
+                    x = L.ffn2(F.gelu(L.ffn1(L.ln2(x)))) + x
+                    continue
                 ctx = DC.attn_decode_reference(L.qkv(x), cache.kv[l], cache.pos, c.heads, rope=self.rope_table)
                 x = L.ln1(L.out(ctx) + x)
                 x = L.ln2(L.ffn2(F.gelu(L.ffn1(x))) + x)
+            x = self._final_norm(x)
         cache.pos.add_(1)
         state.hidden = x
         return self._state_logits(state)
@@ -871,7 +1002,8 @@ class BertLMHeadModel(BertForMaskedLM):
     def _decode_signature(self):
         """What a captured decode step baked in of the parameters: an in-place edit bumps ``_version`` (and makes
         ``bf16_weight`` / ``padded_decoder`` hand out new tensors), a re-allocation moves ``data_ptr``."""
-        return tuple((p._version, p.data_ptr()) for p in self.parameters())
+        c = self.config  # (the block kind decides which kernels a step launches)
+        return (c.pre_ln, c.norm) + tuple((p._version, p.data_ptr()) for p in self.parameters())
 
     def _graphed_decoder(self, B, Smax, T, dev):
         key = (B, Smax, T, str(dev))

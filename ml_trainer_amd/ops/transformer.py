@@ -22,6 +22,12 @@ Blocks (one autograd node each, so the backward can fuse across ops):
   and reduces the bias gradient from it. The mask is recomputed, never stored (ops/dropout.py).
   With ``attn_drop`` the attention blocks drop attention probabilities inside the flash kernels
   (forward, dQ, dK/dV), from a byte-per-element mask that is recomputed as well.
+* ``pre_attention_block`` / ``pre_ffn_block`` / ``stream_norm``: the pre-norm blocks. A node maps the residual
+  stream and its norm ``(h, n)`` to ``(h', n')`` with ``n'`` under the next sub-layer's norm weights, LayerNorm or
+  RMSNorm (``beta=None``). The forward reuses the fusions above (residual in the GEMM epilogue, or the
+  dropout_add norm kernel, which writes h' and n'); the norm backward takes the stream's gradient as DRES, so
+  its dx is the total stream gradient: the residual's gradient, the last linear's dY (under dropout its masked
+  copy DXM) and, through the fused column sums, that linear's bias gradient.
 * ``layer_norm``, ``embeddings``, ``dropout`` (the embedding site).
 
 Packed ("unpadded") batches: ``pack_batch`` drops the pad tokens of a right-padded [B, S] batch once
@@ -243,7 +249,7 @@ def _rope_qk(t, rope, S, H, sign=1):
 
 
 def _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl=BF16, residual=True, attn_drop=None, cu_seqlens=None,
-              causal: bool = False, rope=None):
+              causal: bool = False, rope=None, res=None):
     """``attn_drop`` = (p, seed, site, rank): attention-probability dropout inside the flash kernels
     (the byte mask of ops/dropout.py, recomputed in the backward); None: no dropout.
     ``cu_seqlens`` (int32 [B + 1], device): packed batch, x is [T, D] with sequence b at rows
@@ -251,7 +257,8 @@ def _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl=BF16, residual=True, at
     ``causal``: key j is visible to query i of its sequence iff j <= i and j < len_b.
     ``rope`` = (table, pos or None): rotary positions, q and k rotated in place between the QKV GEMM and the
     attention kernel (``pos`` for packed batches); the saved qkv is the rotated one, which the attention
-    backward needs."""
+    backward needs. ``res``: the residual the out-projection adds instead of ``x`` (pre-norm blocks: x is the
+    norm of the stream, ``res`` the stream)."""
     C = require_native()
     ckw = _causal_kw(causal, impl)
     if cu_seqlens is not None and impl is not BF16:
@@ -268,12 +275,12 @@ def _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl=BF16, residual=True, at
     _zero_packed_tail(attn, cu_seqlens)
     C.attn_fwd(qkv, attn, lse, lens, B, S, H, _ATTN_SCALE, cu_seqlens=cu_seqlens, **_attn_drop_kw(attn_drop), **ckw)
     # out-proj + bias + residual (under dropout the residual joins in the LayerNorm kernel instead)
-    y = impl.fwd(attn, wo, bo, res=x if residual else None)
+    y = impl.fwd(attn, wo, bo, res=(x if res is None else res) if residual else None)
     return y, (x, qkv, attn, lse)
 
 
 def _attn_bwd(saved, params, lens, B, S, H, dy, G, dbo="colsum", impl=BF16, dres=None, attn_drop=None,
-              cu_seqlens=None, causal: bool = False, rope=None):
+              cu_seqlens=None, causal: bool = False, rope=None, residual=True):
     """Backward of the attention block. ``dbo``: "colsum" to reduce dy here, otherwise the
     out-proj bias gradient already produced by the LayerNorm backward (tensor or None).
     ``dres``: the gradient of the residual branch when it differs from the out-proj's ``dy``
@@ -281,7 +288,8 @@ def _attn_bwd(saved, params, lens, B, S, H, dy, G, dbo="colsum", impl=BF16, dres
     forward's. ``rope``: the forward's; dQKV comes out of the attention backward in the rotated frame and is
     rotated back (``sign=-1``) before anything else reads it. The QKV bias gradient is then the column sum of the
     rotated-back dQKV: the attention kernels' own column sums are sums in the rotated frame, which differ row by
-    row, so that fused branch is not taken under rotary."""
+    row, so that fused branch is not taken under rotary. ``residual=False`` (pre-norm blocks): the block's input
+    is not its residual, the QKV dgrad adds nothing."""
     C = require_native()
     akw = _attn_drop_kw(attn_drop)
     akw.update(_causal_kw(causal, impl))
@@ -319,25 +327,26 @@ def _attn_bwd(saved, params, lens, B, S, H, dy, G, dbo="colsum", impl=BF16, dres
     else:
         C.attn_bwd(qkv, attn, dattn, lse, delta, lens, dqkv, B, S, H, _ATTN_SCALE, **akw)
         dwqkv, dbqkv = G.wgrad_bias(wqkv, bqkv, dqkv, x, impl)
-    dx = impl.dgrad(dqkv, wqkv, torch.empty_like(x), res=dres)  # dx = dqkv . Wqkv + dres (residual)
+    dx = impl.dgrad(dqkv, wqkv, torch.empty_like(x), res=dres if residual else None)  # dqkv . Wqkv + dres
     return dx, dwqkv, dbqkv, dwo, dbo
 
 
-def _ffn_fwd(x, w1, b1, w2, b2, impl=BF16, residual=True):
+def _ffn_fwd(x, w1, b1, w2, b2, impl=BF16, residual=True, res=None):
     pre = torch.empty(x.shape[0], w1.shape[0], dtype=torch.bfloat16, device=x.device)
     # fp8: FFN1's epilogue may emit FFN2's quantised input directly (Fp8Linear.fwd_gelu_q)
     a = impl.fwd_gelu_q(x, w1, b1, pre, w2) if hasattr(impl, "fwd_gelu_q") else None
     if a is None:
         a = impl.fwd(x, w1, b1, gelu_aux=pre)  # a = gelu(pre), pre saved
-    y = impl.fwd(a, w2, b2, res=x if residual else None)
+    y = impl.fwd(a, w2, b2, res=(x if res is None else res) if residual else None)  # (res: as in _attn_fwd)
     return y, (x, pre, a)
 
 
-def _ffn_bwd(saved, params, dy, G, db2="colsum", impl=BF16, dres=None):
-    """``dres``: the residual branch's gradient when hidden dropout separates it from FFN2's ``dy``."""
+def _ffn_bwd(saved, params, dy, G, db2="colsum", impl=BF16, dres=None, residual=True):
+    """``dres``: the residual branch's gradient when hidden dropout separates it from FFN2's ``dy``.
+    ``residual=False`` (pre-norm blocks): FFN1's dgrad adds no residual gradient."""
     x, pre, a = saved
     w1, b1, w2, b2 = params
-    dres = dy if dres is None else dres
+    dres = (dy if dres is None else dres) if residual else None
     dw2 = G.wgrad(w2, dy, a, impl)
     if isinstance(db2, str):
         db2 = G.colsum(b2, dy)
@@ -384,12 +393,13 @@ def _dropout_add_ln_fwd(y0, res, gamma, beta, eps, drop):
     return y, (z, gamma, mean, rstd)
 
 
-def _ln_bwd(saved, beta, dy, G, dxsum_param=None, drop=None):
+def _ln_bwd(saved, beta, dy, G, dxsum_param=None, drop=None, dres=None):
     """LayerNorm backward; with ``dxsum_param`` also the column sums of dx (= that bias's grad).
     Returns (dx, dgamma|None, dbeta|None, dbias|None).
     ``drop`` = (p, seed, site, rank) (needs ``dxsum_param``): the input was dropout(linear) +
     residual. dx is then the residual's gradient, a fifth result dxm = mask * scale * dx is the
-    linear's dY, and dbias holds dxm's column sums."""
+    linear's dY, and dbias holds dxm's column sums. ``dres`` (pre-norm blocks): added into dx in the kernel,
+    with ``drop`` as well (dxm is then the masked, scaled copy of that total)."""
     C = require_native()
     x, gamma, mean, rstd = saved
     D = gamma.numel()
@@ -413,11 +423,74 @@ def _ln_bwd(saved, beta, dy, G, dxsum_param=None, drop=None):
     if drop is not None:
         dxm = torch.empty_like(x)
         p, seed, site, rank = drop
-        C.ln_bwd(dy, x, gamma, mean, rstd, dx, part, dg_t, db_t, acc, None, dxsum=dxs_t, dxsum_acc=dxs_acc,
-                 dxm=dxm, p=p, seed=seed, site=site, rank=rank)
+        if dres is not None:
+            C.ln_bwd_dropout_res(dy, x, gamma, mean, rstd, dx, part, dg_t, db_t, acc, dres, dxs_t, dxs_acc, dxm, p,
+                                 seed, site, rank)
+        else:
+            C.ln_bwd(dy, x, gamma, mean, rstd, dx, part, dg_t, db_t, acc, None, dxsum=dxs_t, dxsum_acc=dxs_acc,
+                     dxm=dxm, p=p, seed=seed, site=site, rank=rank)
         return dx, dg, db, dxs, dxm
-    C.ln_bwd(dy, x, gamma, mean, rstd, dx, part, dg_t, db_t, acc, None, dxsum=dxs_t, dxsum_acc=dxs_acc)
+    C.ln_bwd(dy, x, gamma, mean, rstd, dx, part, dg_t, db_t, acc, dres, dxsum=dxs_t, dxsum_acc=dxs_acc)
     return dx, dg, db, dxs
+
+
+def _rms_fwd(x, gamma, eps):
+    C = require_native()
+    y = torch.empty_like(x)
+    rstd = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+    C.rms_fwd(x, gamma, y, rstd, eps)
+    return y, (x, gamma, None, rstd)
+
+
+def _dropout_add_rms_fwd(y0, res, gamma, eps, drop):
+    """RMSNorm(dropout(y0) + res) in one kernel, as _dropout_add_ln_fwd."""
+    C = require_native()
+    z = torch.empty_like(y0)
+    y = torch.empty_like(y0)
+    rstd = torch.empty(y0.shape[0], dtype=torch.float32, device=y0.device)
+    C.dropout_add_rms_fwd(y0, res, gamma, z, y, rstd, eps, *drop)
+    return y, (z, gamma, None, rstd)
+
+
+def _rms_bwd(saved, dy, G, dxsum_param=None, drop=None, dres=None):
+    """RMSNorm backward, the arguments of _ln_bwd without beta. Returns (dx, dgamma|None, dbias|None, dxm|None)."""
+    C = require_native()
+    x, gamma, _, rstd = saved
+    D = gamma.numel()
+    dev = x.device
+    dx = torch.empty_like(x)
+    want = dxsum_param is not None
+    part = torch.empty(C.ln_partial_blocks(x.shape[0]) * (2 if want else 1) * D, dtype=torch.float32, device=dev)
+    dg_t, acc, dg = G.out(gamma, D, dev)
+    dxs_t, dxs_acc, dxs = G.out(dxsum_param, D, dev) if want else (None, False, None)
+    dxm, kw = None, {}
+    if drop is not None:
+        dxm = torch.empty_like(x)
+        p, seed, site, rank = drop
+        kw = dict(dxm=dxm, p=p, seed=seed, site=site, rank=rank)
+    C.rms_bwd(dy, x, gamma, rstd, dx, part, dg_t, acc, dres, dxsum=dxs_t, dxsum_acc=dxs_acc, **kw)
+    return dx, dg, dxs, dxm
+
+
+# The norm of a pre-norm block: LayerNorm when ``beta`` is a tensor, RMSNorm when it is None. The saved
+# tuple is (x, gamma, mean | None, rstd) for both.
+def _norm_fwd(x, gamma, beta, eps):
+    return _rms_fwd(x, gamma, eps) if beta is None else _ln_fwd(x, gamma, beta, eps)
+
+
+def _dropout_add_norm_fwd(y0, res, gamma, beta, eps, drop):
+    if beta is None:
+        return _dropout_add_rms_fwd(y0, res, gamma, eps, drop)
+    return _dropout_add_ln_fwd(y0, res, gamma, beta, eps, drop)
+
+
+def _norm_bwd(saved, beta, dy, G, dxsum_param=None, drop=None, dres=None):
+    """(dx, dgamma, dbeta (None under RMSNorm), dbias, dxm (None without ``drop``)) of either norm."""
+    if beta is None:
+        dx, dg, dxs, dxm = _rms_bwd(saved, dy, G, dxsum_param, drop, dres)
+        return dx, dg, None, dxs, dxm
+    r = _ln_bwd(saved, beta, dy, G, dxsum_param, drop, dres)
+    return r if drop is not None else r + (None,)
 
 
 _ATTN_SCALE = 1.0 / 8.0  # 1/sqrt(head_dim = 64)
@@ -544,6 +617,109 @@ class _FFNLNBlock(torch.autograd.Function):
         dx, dw1, db1, dw2, db2 = _ffn_bwd(t[:3], ctx.params, df, G, db2=db2, impl=ctx.impl, dres=dres)
         G.done()
         return dx, dw1, db1, dw2, db2, dg, db, None, None, None
+
+
+def _bf16_grad(g):
+    return None if g is None else g.contiguous().to(torch.bfloat16)
+
+
+def _zero_grad_like(saved_norm):
+    x = saved_norm[0]
+    return torch.zeros_like(x)
+
+
+class _StreamNorm(torch.autograd.Function):
+    """(h, Norm(h)): the entry of a pre-norm stack. The stream h is handed through, so that its two consumers
+    (the first block's residual add and this norm) return one gradient: the norm backward adds dh as DRES."""
+
+    @staticmethod
+    def forward(ctx, h, gamma, beta, eps):
+        n, saved = _norm_fwd(h, gamma, beta, eps)
+        ctx.save_for_backward(*saved)
+        ctx.beta = beta
+        ctx.set_materialize_grads(False)
+        return h.view_as(h), n
+
+    @staticmethod
+    def backward(ctx, dh, dn):
+        if dn is None:
+            return dh, None, None, None
+        G = _Grads()
+        dx, dg, db, _, _ = _norm_bwd(ctx.saved_tensors, ctx.beta, _bf16_grad(dn), G, dres=_bf16_grad(dh))
+        G.done()
+        return dx, dg, db, None
+
+
+class _PreAttentionBlock(torch.autograd.Function):
+    """One pre-norm attention sub-layer as a node (h, n) -> (h', n'): h' = h + drop(Out(Attn(QKV(n)))) and
+    n' = Norm(h') under the NEXT sub-layer's norm weights. Forward: the out-projection adds h in its epilogue
+    and the norm kernel normalises (with ``drop``: the dropout_add norm kernel writes both h' and n').
+    Backward of (dh', dn'): the norm backward with DRES = dh' gives the total stream gradient, which is the
+    residual's gradient and the out-projection's dY (its masked copy DXM under dropout), with that linear's
+    bias gradient as the fused column sums; the QKV dgrad then yields dn with nothing added."""
+
+    @staticmethod
+    def forward(ctx, h, n, wqkv, bqkv, wo, bo, gamma, beta, lens, B, S, H, eps, impl, drop=None, attn_drop=None,
+                cu_seqlens=None, causal=False, rope=None):
+        if drop is None:
+            h2, s1 = _attn_fwd(n, wqkv, bqkv, wo, bo, lens, B, S, H, impl, attn_drop=attn_drop, cu_seqlens=cu_seqlens,
+                               causal=causal, rope=rope, res=h)
+            n2, s2 = _norm_fwd(h2, gamma, beta, eps)
+        else:
+            a, s1 = _attn_fwd(n, wqkv, bqkv, wo, bo, lens, B, S, H, impl, residual=False, attn_drop=attn_drop,
+                              cu_seqlens=cu_seqlens, causal=causal, rope=rope)
+            n2, s2 = _dropout_add_norm_fwd(a, h, gamma, beta, eps, drop)
+            h2 = s2[0]
+        ctx.save_for_backward(*s1, *s2)
+        ctx.params, ctx.beta, ctx.impl = (wqkv, bqkv, wo, bo), beta, impl
+        ctx.lens, ctx.dims, ctx.drop, ctx.attn_drop, ctx.cu = lens, (B, S, H), drop, attn_drop, cu_seqlens
+        ctx.causal, ctx.rope = causal, rope
+        ctx.set_materialize_grads(False)
+        return h2, n2
+
+    @staticmethod
+    def backward(ctx, dh2, dn2):
+        t = ctx.saved_tensors
+        G = _Grads()
+        dn2 = _zero_grad_like(t[4:]) if dn2 is None else _bf16_grad(dn2)
+        dh, dg, db, dbo, dxm = _norm_bwd(t[4:], ctx.beta, dn2, G, dxsum_param=ctx.params[3], drop=ctx.drop,
+                                         dres=_bf16_grad(dh2))
+        da = dh if ctx.drop is None else dxm
+        dn, dwqkv, dbqkv, dwo, dbo = _attn_bwd(t[:4], ctx.params, ctx.lens, *ctx.dims, da, G, dbo=dbo, impl=ctx.impl,
+                                               attn_drop=ctx.attn_drop, cu_seqlens=ctx.cu, causal=ctx.causal,
+                                               rope=ctx.rope, residual=False)
+        G.done()
+        return (dh, dn, dwqkv, dbqkv, dwo, dbo, dg, db) + (None,) * 11
+
+
+class _PreFFNBlock(torch.autograd.Function):
+    """The pre-norm FFN sub-layer (h, n) -> (h', n'), see _PreAttentionBlock."""
+
+    @staticmethod
+    def forward(ctx, h, n, w1, b1, w2, b2, gamma, beta, eps, impl, drop=None):
+        if drop is None:
+            h2, s1 = _ffn_fwd(n, w1, b1, w2, b2, impl, res=h)
+            n2, s2 = _norm_fwd(h2, gamma, beta, eps)
+        else:
+            f, s1 = _ffn_fwd(n, w1, b1, w2, b2, impl, residual=False)
+            n2, s2 = _dropout_add_norm_fwd(f, h, gamma, beta, eps, drop)
+            h2 = s2[0]
+        ctx.save_for_backward(*s1, *s2)
+        ctx.params, ctx.beta, ctx.impl, ctx.drop = (w1, b1, w2, b2), beta, impl, drop
+        ctx.set_materialize_grads(False)
+        return h2, n2
+
+    @staticmethod
+    def backward(ctx, dh2, dn2):
+        t = ctx.saved_tensors
+        G = _Grads()
+        dn2 = _zero_grad_like(t[3:]) if dn2 is None else _bf16_grad(dn2)
+        dh, dg, db, db2, dxm = _norm_bwd(t[3:], ctx.beta, dn2, G, dxsum_param=ctx.params[3], drop=ctx.drop,
+                                         dres=_bf16_grad(dh2))
+        df = dh if ctx.drop is None else dxm
+        dn, dw1, db1, dw2, db2 = _ffn_bwd(t[:3], ctx.params, df, G, db2=db2, impl=ctx.impl, residual=False)
+        G.done()
+        return (dh, dn, dw1, db1, dw2, db2, dg, db) + (None,) * 3
 
 
 class _Embeddings(torch.autograd.Function):
@@ -690,6 +866,36 @@ def ffn_ln_block(x, w1, b1, w2, b2, gamma, beta, eps: float, impl=BF16, drop=Non
 
 def layer_norm(x, gamma, beta, eps: float):
     return _LayerNorm.apply(x, gamma, beta, eps)
+
+
+def _pre_norm_impl(impl):
+    if impl is not BF16:
+        raise ValueError("pre-norm blocks run the bf16 linears only")
+
+
+def stream_norm(h, gamma, beta, eps: float):
+    """(h, Norm(h)) at the entry of a pre-norm stack, or wherever a stream meets a norm on its own: LayerNorm
+    with ``beta``, RMSNorm (``rms_fwd`` / ``rms_bwd``) with ``beta=None``. Use both results: the node's
+    backward adds the stream's gradient into the norm's in the kernel."""
+    return _StreamNorm.apply(h, gamma, beta, eps)
+
+
+def pre_attention_block(h, n, wqkv, bqkv, wo, bo, gamma, beta, lens: Optional[torch.Tensor], B: int, S: int, H: int,
+                        eps: float, impl=BF16, drop=None, attn_drop=None, cu_seqlens: Optional[torch.Tensor] = None,
+                        causal: bool = False, rope=None):
+    """The pre-norm attention sub-layer: (h, n) -> (h + drop(Out(Attn(QKV(n)))), Norm(that sum)) where
+    ``gamma`` / ``beta`` (None: RMSNorm) are the weights of the norm that FOLLOWS (the layer's ``ln2``).
+    Every other argument as in attention_ln_block."""
+    _pre_norm_impl(impl)
+    return _PreAttentionBlock.apply(h, n, wqkv, bqkv, wo, bo, gamma, beta, lens, B, S, H, eps, impl, drop, attn_drop,
+                                    cu_seqlens, causal, rope)
+
+
+def pre_ffn_block(h, n, w1, b1, w2, b2, gamma, beta, eps: float, impl=BF16, drop=None):
+    """The pre-norm FFN sub-layer: (h, n) -> (h + drop(FFN2(gelu(FFN1(n)))), Norm(that sum)); ``gamma`` / ``beta``
+    belong to the next layer's ``ln1``, or to the final norm after the last layer."""
+    _pre_norm_impl(impl)
+    return _PreFFNBlock.apply(h, n, w1, b1, w2, b2, gamma, beta, eps, impl, drop)
 
 
 class _Dropout(torch.autograd.Function):
