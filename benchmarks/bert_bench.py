@@ -54,6 +54,8 @@ def run(args):
         over["rotary"] = True
     if args.pre_ln or args.norm != "layernorm":
         over.update(pre_ln=bool(args.pre_ln), norm=args.norm)
+    if args.kv_heads is not None:
+        over["kv_heads"] = args.kv_heads
     cfg = bert_config(args.model, **over)
     m = (BertLMHeadModel if clm else BertForMaskedLM if mlm else BertClassifier)(cfg).to(dev)
     if mlm and args.chunk_rows:
@@ -115,7 +117,7 @@ def run(args):
            "peak_mem_gb": torch.cuda.max_memory_allocated() / 2 ** 30,
            "min_len": args.min_len, "tokens": real, "fill": real / tokens, "unpad": bool(args.unpad),
            "optimizer": args.optimizer, "no_decay_1d": bool(args.no_decay_1d), "rotary": bool(args.rotary),
-           "pre_ln": bool(args.pre_ln), "norm": args.norm}
+           "pre_ln": bool(args.pre_ln), "norm": args.norm, "kv_heads": args.kv_heads}
     if mlm:
         with torch.no_grad():
             hidden = fwd(ids)
@@ -157,6 +159,8 @@ def main():
     ap.add_argument("--unpad", action="store_true", help="BertConfig.unpad: run the encoder on the real tokens only")
     ap.add_argument("--rotary", action="store_true",
                     help="BertConfig.rotary: rotary positions on q and k (the rope_qk kernel) instead of the learned table")
+    ap.add_argument("--kv-heads", type=int, default=None,
+                    help="BertConfig.kv_heads: grouped-query attention (a divisor of the model's heads)")
     ap.add_argument("--pre-ln", action="store_true", help="BertConfig.pre_ln: pre-norm blocks and a final norm")
     ap.add_argument("--norm", choices=["layernorm", "rmsnorm"], default="layernorm",
                     help="BertConfig.norm: the norm of the pre-norm blocks (rmsnorm needs --pre-ln)")

@@ -29,7 +29,8 @@ region) in one process: eager with the torch sampler, eager with ``sample_step``
 skinny kernel) and ``1`` in one process and reports both medians and the spread of the ``0`` runs.
 ``--rotary`` builds the model of the model timings with rotary positions (``BertConfig.rotary``) instead of the learned
 position table; the records carry ``"rotary"``. ``--pre-ln`` / ``--norm {layernorm,rmsnorm}`` build it with pre-norm
-blocks (``BertConfig.pre_ln`` / ``norm``); the records carry ``"pre_ln"`` and ``"norm"``.
+blocks (``BertConfig.pre_ln`` / ``norm``); the records carry ``"pre_ln"`` and ``"norm"``. ``--kv-heads N`` builds it
+with grouped-query attention (``BertConfig.kv_heads``); the model records then carry ``"kv_heads"``.
 Random weights and prompts (no network)."""
 from __future__ import annotations
 
@@ -60,6 +61,8 @@ def _model(args, dev):
     over = {"rotary": True} if args.rotary else {}
     if args.pre_ln or args.norm != "layernorm":
         over.update(pre_ln=bool(args.pre_ln), norm=args.norm)
+    if args.kv_heads is not None:
+        over["kv_heads"] = args.kv_heads
     return BertLMHeadModel(bert_config(args.model, **over)).to(dev).eval()
 
 
@@ -116,7 +119,7 @@ def bench_model(args, dev):
                 t_unc.append(_sync_ms(uncached) / (N - 1))
         ms = statistics.median(t_dec[settings[-1]])
         rec = {"bench": "generate", "model": args.model, "rotary": bool(args.rotary), "pre_ln": bool(args.pre_ln),
-               "norm": args.norm, "batch": B, "prompt": P, "new": N,
+               "norm": args.norm, "kv_heads": args.kv_heads, "batch": B, "prompt": P, "new": N,
                "decode_gemm": settings[-1],
                "prefill_ms": statistics.median(t_pre), "cached_ms_per_token": ms, "cached_tokens_per_s": B / ms * 1e3,
                "uncached_ms_per_token": statistics.median(t_unc) if t_unc else None,
@@ -182,7 +185,7 @@ def bench_sampler_ab(args, dev):
                     pre()
                     t[k].append(_sync_ms(run) / (N - 1))
             rec = {"bench": "generate_sampler_ab", "model": args.model, "rotary": bool(args.rotary),
-                   "pre_ln": bool(args.pre_ln), "norm": args.norm, "batch": B,
+                   "pre_ln": bool(args.pre_ln), "norm": args.norm, "kv_heads": args.kv_heads, "batch": B,
                    "prompt": P, "new": N,
                    "setting": name, "capture_s": dec.capture_seconds}
             for k in t:
@@ -325,6 +328,8 @@ def main():
     ap.add_argument("--sampler-ab", action="store_true",
                     help="alternate (eager, torch sampler), (eager, device sampler), (graph, device sampler)")
     ap.add_argument("--rotary", action="store_true", help="rotary positions in the model timings")
+    ap.add_argument("--kv-heads", type=int, default=None,
+                    help="BertConfig.kv_heads: grouped-query attention in the model timings (records carry kv_heads)")
     ap.add_argument("--pre-ln", action="store_true", help="pre-norm blocks in the model timings")
     ap.add_argument("--norm", choices=["layernorm", "rmsnorm"], default="layernorm",
                     help="the norm of the pre-norm blocks (rmsnorm needs --pre-ln)")

@@ -20,7 +20,8 @@ inside the flash attention kernels; applied as round(p * 256) / 256), ``--unpad`
 tokens before the embeddings and run the encoder on the real tokens only), ``--rotary`` / ``--rope_base`` (BERT,
 any ``--task``: rotary position embeddings on the queries and keys instead of the learned position table),
 ``--pre_ln`` / ``--norm {layernorm,rmsnorm}`` (BERT, any ``--task``: pre-norm blocks ``h + f(norm(h))`` with a final
-norm, and RMSNorm instead of LayerNorm as their norm; ``--norm rmsnorm`` needs ``--pre_ln``),
+norm, and RMSNorm instead of LayerNorm as their norm; ``--norm rmsnorm`` needs ``--pre_ln``), ``--kv_heads N`` (BERT,
+any ``--task``: grouped-query attention, N key/value heads shared by heads / N query heads each),
 ``--min_seq_len L``
 (variable-length synthetic text, lengths uniform in [L, seq_len], right-padded with ``--pad_id``), ``--optimizer lamb`` (layer-wise trust ratios on the flat buffer) and
 ``--no_decay_1d`` (adamw / lamb: biases and LayerNorm parameters take no weight decay), ``--task mlm``
@@ -96,6 +97,8 @@ def build_model_and_datasets(args):
         raise ValueError("--pre_ln / --norm apply to the BERT models; the LeNet models have no transformer blocks")
     if args.norm == "rmsnorm" and not args.pre_ln:
         raise ValueError("--norm rmsnorm needs --pre_ln: post-norm RMSNorm blocks are not built")
+    if lenet and args.kv_heads is not None:
+        raise ValueError("--kv_heads applies to the BERT models; the LeNet models have no attention")
     if lenet and args.min_seq_len is not None:
         raise ValueError("--min_seq_len applies to the synthetic text data of the BERT models")
     mlm = args.task == "mlm"
@@ -130,6 +133,8 @@ def build_model_and_datasets(args):
     if args.pre_ln:
         over["pre_ln"] = True
         over["norm"] = args.norm
+    if args.kv_heads is not None:
+        over["kv_heads"] = args.kv_heads
     pad_id = args.pad_id if args.pad_id is not None else (0 if args.min_seq_len is not None else None)
     if pad_id is not None and not lenet:
         over["pad_id"] = pad_id
@@ -284,6 +289,11 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--norm", choices=["layernorm", "rmsnorm"], default="layernorm",
                         help="--pre_ln: the norm of the blocks and the final norm; rmsnorm = x * rsqrt(mean(x^2) + "
                              "eps) * weight, no centring, no bias (needs --pre_ln)")
+    parser.add_argument("--kv_heads", type=int, default=None,
+                        help="BERT, any --task: grouped-query attention with this many key/value heads, each shared "
+                             "by heads / kv_heads query heads (a divisor of the model's heads; 1 = multi-query; "
+                             "default: one per query head). The QKV projection and the key/value cache shrink "
+                             "accordingly (not with the fp8 `large` preset). An error for the LeNet models")
     parser.add_argument("--min_seq_len", type=int, default=None,
                         help="BERT synthetic data: variable-length rows, lengths uniform in [min_seq_len, seq_len], "
                              "right-padded with --pad_id (default: fixed length)")

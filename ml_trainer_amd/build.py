@@ -112,7 +112,10 @@ def _run(cmd):
 # kernel's first-load pointers: no s_load round trip of the kernarg segment before its first loads).
 FILE_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"],
               "lenet_mfma.hip": ["-fno-slp-vectorize", "-mllvm", "-amdgpu-sched-strategy=max-memory-clause",
-                                 "-mllvm", "-amdgpu-kernarg-preload-count=12"]}
+                                 "-mllvm", "-amdgpu-kernarg-preload-count=12"],
+              # gqa.hip: gqa_reduce's result is defined bit for bit (a sequential fp32 sum); built without the
+              # packed fp32 forms (v_pk_add_f32), plain v_add_f32 instead: the kernel is bound by its loads
+              "gqa.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 # translation units split off a kernel file for parallel compilation share its flags ({prefix: file})
 FILE_ALIASES = {"lenet_mfma_dp": "lenet_mfma.hip"}  # (lenet_mfma_dp.hip, lenet_mfma_dpw<W>.hip)
 

@@ -1230,6 +1230,84 @@ void attn_decode(Tensor qkv_new, Tensor kv, Tensor pos, Tensor out, int64_t H, d
                      (uint16_t*)out.data_ptr(), (int)B, (int)H, (int)Smax, (float)scale, cur_stream(), rp);
 }
 
+// attn_decode for grouped-query attention (attn_decode_gqa_kernel): kv [2, B, Hkv, Smax, 64] with Hkv = kv.size(2)
+// a divisor of H, qkv_new [B, (H + 2 Hkv) * 64] in the compact layout q | k | v (may be a row-strided view). The
+// checks are attn_decode's. gc: the query heads one workgroup serves (0: the launcher's choice, which depends on the
+// shape and the batch but never changes the output; an explicit value is for benchmarks and tests).
+void attn_decode_gqa(Tensor qkv_new, Tensor kv, Tensor pos, Tensor out, int64_t H, double scale,
+                     c10::optional<Tensor> rope, int64_t gc) {
+  TORCH_CHECK(qkv_new.is_cuda() && qkv_new.dim() == 2 && qkv_new.scalar_type() == at::kBFloat16,
+              "attn_decode_gqa: qkv_new must be a bf16 [B, (H + 2 Hkv) * 64] device tensor");
+  const int64_t B = qkv_new.size(0), D = H * 64;
+  TORCH_CHECK(B > 0 && H > 0 && B <= 65535 && H <= 65535, "attention dims");
+  check_dev(kv, "kv", at::kBFloat16, 0);
+  TORCH_CHECK(kv.dim() == 5 && kv.size(0) == 2 && kv.size(1) == B && kv.size(2) >= 1 && kv.size(3) >= 1 &&
+                  kv.size(4) == 64,
+              "attn_decode_gqa: kv must be [2, B, Hkv, Smax, 64] with B = ", B);
+  const int64_t Hkv = kv.size(2), Smax = kv.size(3), W = (H + 2 * Hkv) * 64;
+  TORCH_CHECK(Hkv <= H && H % Hkv == 0, "attn_decode_gqa: the cache holds ", Hkv, " key/value heads, which does not ",
+              "divide H = ", H);
+  TORCH_CHECK(qkv_new.size(1) == W, "attn_decode_gqa: qkv_new has ", qkv_new.size(1),
+              " columns, expected (H + 2 Hkv) * 64 = ", W);
+  TORCH_CHECK(qkv_new.stride(1) == 1 && qkv_new.stride(0) >= W && qkv_new.stride(0) % 8 == 0,
+              "attn_decode_gqa: qkv_new needs unit column stride and a row stride that is a multiple of 8");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(qkv_new.data_ptr()) % 16 == 0, "qkv_new must be 16-byte aligned");
+  TORCH_CHECK(kv.numel() == 2 * B * Hkv * Smax * 64 && Smax <= 0x7fffffff, "attn_decode_gqa: kv size");
+  check_dev(pos, "pos", at::kInt, B, 4);
+  TORCH_CHECK(pos.numel() == B, "attn_decode_gqa: pos must have one entry per sequence");
+  check_bf16_2d(out, "out", B, D);
+  const float* rp = nullptr;
+  if (rope.has_value()) {
+    check_dev(*rope, "rope table", at::kFloat, 64, 16);
+    TORCH_CHECK(rope->dim() == 3 && rope->size(1) == 32 && rope->size(2) == 2 && rope->size(0) >= Smax,
+                "attn_decode_gqa: the rope table must be [P >= Smax = ", Smax, ", 32, 2]");
+    rp = rope->data_ptr<float>();
+  }
+  const int64_t G = H / Hkv;
+  TORCH_CHECK(gc == 0 || ((gc == 1 || gc == 2 || gc == 3 || gc == 4 || gc == 6 || gc == 8) && G % gc == 0),
+              "attn_decode_gqa: gc = ", gc, " must be 0 or one of 1, 2, 3, 4, 6, 8 that divides H / Hkv = ", G);
+  launch_attn_decode_gqa(bf16_ptr(qkv_new), qkv_new.stride(0), (uint16_t*)kv.data_ptr(), pos.data_ptr<int>(),
+                         (uint16_t*)out.data_ptr(), (int)B, (int)H, (int)Hkv, (int)Smax, (float)scale, cur_stream(),
+                         rp, (int)gc);
+}
+
+// The operands of gqa_expand / gqa_reduce (gqa.hip): compact bf16 [rows, (H + 2 Hkv) * 64], wide bf16
+// [rows, 3 * H * 64], both 2-D device tensors with unit column stride, a row stride that is a multiple of 8 and a
+// 16-byte aligned base (row-strided views pass).
+static int64_t check_gqa(const Tensor& compact, const Tensor& wide, int64_t H, int64_t Hkv, const char* who) {
+  TORCH_CHECK(H > 0 && H <= 65535 && Hkv >= 1 && Hkv <= H && H % Hkv == 0, who, ": kv heads ", Hkv,
+              " must divide heads ", H);
+  const int64_t Wc = (H + 2 * Hkv) * 64, Ww = 3 * H * 64;
+  for (const Tensor* t : {&compact, &wide}) {
+    const bool c = t == &compact;
+    const char* name = c ? "compact" : "wide";
+    TORCH_CHECK(t->defined() && t->is_cuda() && t->dim() == 2 && t->scalar_type() == at::kBFloat16, who, ": ", name,
+                " must be a 2-D bf16 device tensor");
+    TORCH_CHECK(t->size(1) == (c ? Wc : Ww), who, ": ", name, " has ", t->size(1), " columns, expected ", c ? Wc : Ww);
+    TORCH_CHECK(t->size(0) <= 1 || (t->stride(0) >= t->size(1) && t->stride(0) % 8 == 0), who, ": ", name,
+                " needs a row stride that is a multiple of 8");
+    TORCH_CHECK(t->size(0) == 0 || t->stride(1) == 1, who, ": ", name, " needs unit column stride");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0, who, ": ", name, " must be 16-byte aligned");
+  }
+  TORCH_CHECK(compact.size(0) == wide.size(0), who, ": compact has ", compact.size(0), " rows, wide ", wide.size(0));
+  const int64_t rows = compact.size(0);
+  TORCH_CHECK(rows * (H + 2 * Hkv) * 8 <= (int64_t)0x7ffffff0 * 256, who, ": ", rows, " rows exceed the grid");
+  return rows;
+}
+static int64_t gqa_ld(const Tensor& t) { return t.size(0) > 1 ? t.stride(0) : t.size(1); }
+
+void gqa_expand(Tensor compact, Tensor wide, int64_t H, int64_t Hkv) {
+  const int64_t rows = check_gqa(compact, wide, H, Hkv, "gqa_expand");
+  launch_gqa_expand(bf16_ptr(compact), gqa_ld(compact), (uint16_t*)wide.data_ptr(), gqa_ld(wide), rows, (int)H,
+                    (int)Hkv, cur_stream());
+}
+
+void gqa_reduce(Tensor wide, Tensor compact, int64_t H, int64_t Hkv) {
+  const int64_t rows = check_gqa(compact, wide, H, Hkv, "gqa_reduce");
+  launch_gqa_reduce(bf16_ptr(wide), gqa_ld(wide), (uint16_t*)compact.data_ptr(), gqa_ld(compact), rows, (int)H,
+                    (int)Hkv, cur_stream());
+}
+
 // The logits operand of the sampling kernels: fp32 [B, >= V] with unit column stride, a row stride ldz % 4 == 0
 // and a 16-byte aligned base (16-byte loads), every row readable up to round_up(V, 4) columns. The [B, V] view
 // of the padded [B, Vp] buffer that ops.mlm.decode_logits returns qualifies as it is.
@@ -2020,6 +2098,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sample_weights", &sample_weights, py::arg("logits"), py::arg("V"), py::arg("inv_t_log2e"));
   m.def("attn_decode", &attn_decode, py::arg("qkv_new"), py::arg("kv"), py::arg("pos"), py::arg("out"), py::arg("H"),
         py::arg("scale"), py::arg("rope") = py::none());
+  m.def("attn_decode_gqa", &attn_decode_gqa, py::arg("qkv_new"), py::arg("kv"), py::arg("pos"), py::arg("out"),
+        py::arg("H"), py::arg("scale"), py::arg("rope") = py::none(), py::arg("gc") = 0);
+  m.def("attn_decode_gqa_chunk",
+        [](int64_t G, int64_t Hkv, int64_t B) { return attn_decode_gqa_chunk((int)G, (int)Hkv, (int)B); }, py::arg("G"),
+        py::arg("Hkv"), py::arg("B"));
+  m.def("gqa_expand", &gqa_expand, py::arg("compact"), py::arg("wide"), py::arg("H"), py::arg("Hkv"));
+  m.def("gqa_reduce", &gqa_reduce, py::arg("wide"), py::arg("compact"), py::arg("H"), py::arg("Hkv"));
   m.def("rope_qk", &rope_qk, py::arg("qkv"), py::arg("table"), py::arg("H"), py::arg("S"), py::arg("pos") = py::none(),
         py::arg("sign") = 1);
   m.def("attn_bwd", &attn_bwd, py::arg("qkv"), py::arg("out"), py::arg("dout"), py::arg("lse"), py::arg("delta"),

@@ -417,6 +417,24 @@ void launch_attn_bwd(const AttnProblem& p, const AttnBwdRoute& r, const uint16_t
 // bf16 before the dot product and the append.
 void launch_attn_decode(const uint16_t* qkv_new, int64_t ldq, uint16_t* kv, const int* pos, uint16_t* out, int B,
                         int H, int Smax, float scale, hipStream_t st, const float* rope = nullptr);
+// Grouped-query form (attn_decode.hip): Hkv < H key/value heads, query head h reads KV head h / (H / Hkv). qkv_new
+// [B][ldq >= 64 (H + 2 Hkv)] is compact (q H heads | k Hkv | v Hkv), kv [2][B][Hkv][Smax][64]; everything else as
+// launch_attn_decode, whose output on a cache with the KV heads repeated it reproduces bit for bit. One workgroup
+// serves gc query heads of one KV head: gc = 0 takes attn_decode_gqa_chunk(H / Hkv, Hkv, B), the largest of 4, 3, 2
+// that divides H / Hkv and leaves the grid at least 256 workgroups, else 1; an explicit gc (benchmarks, tests) is
+// one of 1, 2, 3, 4, 6, 8 and divides H / Hkv. The output does not depend on gc.
+int attn_decode_gqa_chunk(int G, int Hkv, int B);
+void launch_attn_decode_gqa(const uint16_t* qkv_new, int64_t ldq, uint16_t* kv, const int* pos, uint16_t* out, int B,
+                            int H, int Hkv, int Smax, float scale, hipStream_t st, const float* rope = nullptr,
+                            int gc = 0);
+// Grouped-query layouts around the flash attention kernels (gqa.hip). compact [rows][ldc >= 64 (H + 2 Hkv)], wide
+// [rows][ldw >= 3 * 64 H], both bf16, ld % 8 == 0, 16-byte aligned, H % Hkv == 0. expand: q copied, every k / v
+// head stored H / Hkv times (bitwise). reduce: dq copied, dk / dv summed over the group in ascending head order in
+// fp32 and rounded once to bf16.
+void launch_gqa_expand(const uint16_t* compact, int64_t ldc, uint16_t* wide, int64_t ldw, int64_t rows, int H, int Hkv,
+                       hipStream_t st);
+void launch_gqa_reduce(const uint16_t* wide, int64_t ldw, uint16_t* compact, int64_t ldc, int64_t rows, int H, int Hkv,
+                       hipStream_t st);
 // Rotary position embedding of the q and k columns of qkv [rows][ld >= 3 * 64 H] in place (rope.hip): table
 // [P][32][2] fp32 (cos, sin), the position of a row is pos[row] (int32 on the device, clamped into [0, P)) or,
 // without pos, row % S (S <= P). sign >= 0: the rotation; < 0: the inverse rotation (its backward). ld % 8 == 0,

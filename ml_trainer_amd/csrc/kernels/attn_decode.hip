@@ -222,4 +222,277 @@ void launch_attn_decode(const uint16_t* qkv_new, int64_t ldq, uint16_t* kv, cons
     attn_decode_kernel<false><<<grid, block, 0, st>>>(qkv_new, ldq, kv, pos, out, H, Smax, scale, nullptr);
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Grouped-query attention: Hkv < H key/value heads, query head h reads KV head h / G (G = H / Hkv).
+//
+// Operands: qkv_new [B, ldq >= (H + 2 Hkv) * 64] bf16 in the compact layout q (H heads) | k (Hkv) | v (Hkv);
+// kv [2, B, Hkv, Smax, 64]; pos, out and rope as above.
+//
+// One 256-thread workgroup per (KV head, head chunk, batch): grid (Hkv * chunks, B), chunks = G / GC. A workgroup
+// serves the GC query heads hkv * G + chunk * GC .. + GC - 1 from ONE pass over the KV head's rows: the key ->
+// (wave, load, lane group) mapping, the 4 + 4 loads in flight and the predication of stale rows are those of
+// attn_decode_kernel (they do not depend on GC), and every loaded K fragment is dotted against the GC queries the
+// lane holds, every V fragment feeds GC accumulators. The queries stay packed (bf16 pairs, GC x 4 VGPRs) and are
+// unpacked at use, which is exact. Every (lane group, head) keeps its own (m, l, O[8]) started at THAT head's
+// new-token score, so the arithmetic of one head and its order are attn_decode_kernel's on a cache whose KV heads
+// are repeated G times: the output is bitwise that kernel's (tests/test_gqa_gpu.py), and batch invariant like it.
+// Merge: the same fixed order per head, the LDS arrays with a GC dimension; the final sum of head i is done by
+// lane group i of wave 0 (GC <= 8 groups). The append is done once per (b, KV head): chunk 0 / wave 0 / group 0.
+// Why VALU: an MFMA over the group's heads would need V with keys along the contraction (a transposed cache or
+// an LDS round trip) and P rounded to bf16, which would break the bitwise property.
+// ---------------------------------------------------------------------------------------------------------
+
+// group_sum<8> (xor 4, 2, 1 over the 8 lanes of a group) on DPP operand modifiers instead of three dependent
+// ds_bpermute round trips (about 100 cycles each, GC x 4 x 3 of them per step of the key loop: with GC heads per
+// workgroup they, not the loads, set the kernel's time). Lane i adds the value of lane i ^ 4 (row_shl:4 into
+// lanes 0-3, row_shr:4 into lanes 4-7 of every 8, selected by the bank mask), then i ^ 2 and i ^ 1 (quad_perm):
+// the same operand pairs in the same three levels, and an fp32 add commutes, so the sum has group_sum<8>'s bits
+// in all 8 lanes.
+template <int CTRL, int BANKS>
+__device__ __forceinline__ float dec_dpp(float old, float v) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(v), CTRL, 0xF, BANKS, false));
+}
+__device__ __forceinline__ float dec_group_sum8(float s) {
+  s += dec_dpp<0x114, 0xA>(dec_dpp<0x104, 0x5>(0.f, s), s);  // lane i ^ 4
+  s += dec_dpp<0x4E, 0xF>(0.f, s);                            // quad_perm [2,3,0,1]: lane i ^ 2
+  s += dec_dpp<0xB1, 0xF>(0.f, s);                            // quad_perm [1,0,3,2]: lane i ^ 1
+  return s;
+}
+
+// attn_decode_gqa_kernel carries target features of its own (below), and a device function that is not
+// always_inline is then not inlined into it but CALLED (s_swappc_b64): the HIP header's make_uint4, __syncthreads
+// and __shfl_xor (33 calls per head in the merge alone). So these three are written here on the builtins; the
+// generated code of every instantiation holds no call.
+__device__ __forceinline__ uint4 dec_u4(uint32_t x, uint32_t y, uint32_t z, uint32_t w) {
+  uint4 r;
+  r.x = x, r.y = y, r.z = z, r.w = w;
+  return r;
+}
+__device__ __forceinline__ void dec_barrier() {  // __syncthreads
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+// The exchanges of the merge over the 8 lane groups of a wave. xor 8 is a rotation by 8 inside a row of 16
+// lanes (DPP row_ror:8); xor 16 and 32 cross rows and go through ds_bpermute. Same operand pairs as the xor
+// butterfly of attn_decode_kernel, hence the same bits.
+__device__ __forceinline__ float dec_xor_row8(float v) { return dec_dpp<0x128, 0xF>(0.f, v); }
+__device__ __forceinline__ float dec_xor(float v, int lane, int mask) {
+  return __int_as_float(__builtin_amdgcn_ds_bpermute((lane ^ mask) << 2, __float_as_int(v)));
+}
+__device__ __forceinline__ float dec_groups_sum(float v, int lane) {  // v + xor 8, then 16, then 32
+  v += dec_xor_row8(v);
+  v += dec_xor(v, lane, 16);
+  v += dec_xor(v, lane, 32);
+  return v;
+}
+
+// the dot product of dec_dot with the query still packed and the key already unpacked: the same 8-term fma chain
+// from 0 over this lane's dims, the same three-level sum over the group
+__device__ __forceinline__ float dec_dot_packed(const uint4& qr, const float* k) {
+  float q[8];
+  dec_unpack(qr, q);
+  float s = 0.f;
+#pragma unroll
+  for (int d = 0; d < 8; ++d) s = fmaf(q[d], k[d], s);
+  return dec_group_sum8(s);
+}
+
+// no-packed-fp32-ops: GC heads of independent fp32 work are what the SLP vectoriser packs into v_pk_mul_f32 /
+// v_pk_fma_f32 pairs (2,300 of them over the instantiations); the kernel is built without the packed forms, two
+// scalar VALU ops each, so that its bits never depend on them.
+template <int GC, bool ROPE>
+__attribute__((target("no-packed-fp32-ops"))) __global__
+__launch_bounds__(kDecWaves * 64) void attn_decode_gqa_kernel(const uint16_t* __restrict__ qkv_new,
+                                                                         int64_t ldq, uint16_t* __restrict__ kv,
+                                                                         const int* __restrict__ pos,
+                                                                         uint16_t* __restrict__ out, int H, int Hkv,
+                                                                         int chunks, int Smax, float scale,
+                                                                         const float* __restrict__ rope) {
+  static_assert(GC >= 1 && GC <= 8, "the final sum of head i is lane group i of wave 0");
+  __shared__ float s_m[GC][kDecWaves];
+  __shared__ float s_l[GC][kDecWaves];
+  __shared__ float s_o[GC][kDecWaves][kDecHead];
+  const int hkv = blockIdx.x / chunks, ch = blockIdx.x - hkv * chunks, b = blockIdx.y, B = gridDim.y;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, g = lane >> 3, c = lane & 7;
+  const int h0 = (hkv * chunks + ch) * GC;  // the first query head of this workgroup (G = chunks * GC)
+  const int D = H * kDecHead;
+  int n = pos[b];  // cached keys = the new token's row
+  MLT_DCHECK(n >= 0 && n < Smax);
+  n = min(max(n, 0), Smax - 1);
+  const float sl2 = scale * 1.4426950408889634f;  // exponents in base 2
+
+  const uint16_t* row = qkv_new + (int64_t)b * ldq + c * 8;
+  uint4 qr[GC];
+#pragma unroll
+  for (int i = 0; i < GC; ++i) qr[i] = *reinterpret_cast<const uint4*>(row + (h0 + i) * kDecHead);
+  uint4 kn = *reinterpret_cast<const uint4*>(row + D + hkv * kDecHead);
+  if constexpr (ROPE) {  // one table row for every head: the position is the token's
+    const float4* tp = reinterpret_cast<const float4*>(rope + (int64_t)n * kDecHead + c * 8);
+    const float4 t0 = tp[0], t1 = tp[1];
+    const float t[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};
+#pragma unroll
+    for (int i = 0; i < GC; ++i) qr[i] = dec_rotate(qr[i], t);
+    kn = dec_rotate(kn, t);
+  }
+  const uint4 vn = *reinterpret_cast<const uint4*>(row + D + (Hkv + hkv) * kDecHead);
+  uint16_t* kc = kv + ((int64_t)b * Hkv + hkv) * Smax * kDecHead + c * 8;  // this lane's dims of key row 0
+  uint16_t* vc = kc + (int64_t)B * Hkv * Smax * kDecHead;
+  if (ch == 0 && w == 0 && g == 0) {  // the append, once per (b, KV head)
+    *reinterpret_cast<uint4*>(kc + (int64_t)n * kDecHead) = kn;
+    *reinterpret_cast<uint4*>(vc + (int64_t)n * kDecHead) = vn;
+  }
+
+  // the new token, from registers: head i's scaled score is the first m of every state of head i
+  float m[GC], l[GC], o[GC][8];
+  {
+    float k[8], v[8];
+    dec_unpack(kn, k);
+    dec_unpack(vn, v);
+#pragma unroll
+    for (int i = 0; i < GC; ++i) {
+      const float sn = dec_dot_packed(qr[i], k);
+      m[i] = sn * sl2;
+      l[i] = 0.f;
+#pragma unroll
+      for (int d = 0; d < 8; ++d) o[i][d] = 0.f;
+      if (w == 0 && g == 0) {
+        const float p = dec_exp2(fmaf(sn, sl2, -m[i]));
+        l[i] = p;
+#pragma unroll
+        for (int d = 0; d < 8; ++d) o[i][d] = p * v[d];
+      }
+    }
+  }
+
+  for (int base = w * kDecWaveKeys; base < n; base += kDecBlockKeys) {
+    uint4 kr[kDecUnroll], vr[kDecUnroll];
+    bool ok[kDecUnroll];
+#pragma unroll
+    for (int u = 0; u < kDecUnroll; ++u) {  // all loads first: 8 x 16 bytes in flight per lane, whatever GC
+      const int j = base + u * 8 + g;
+      ok[u] = j < n;
+      kr[u] = ok[u] ? *reinterpret_cast<const uint4*>(kc + (int64_t)j * kDecHead) : dec_u4(0, 0, 0, 0);
+    }
+#pragma unroll
+    for (int u = 0; u < kDecUnroll; ++u) {
+      const int j = base + u * 8 + g;
+      vr[u] = ok[u] ? *reinterpret_cast<const uint4*>(vc + (int64_t)j * kDecHead) : dec_u4(0, 0, 0, 0);
+    }
+    float s[GC][kDecUnroll], mx[GC];
+#pragma unroll
+    for (int i = 0; i < GC; ++i) mx[i] = m[i];
+#pragma unroll
+    for (int u = 0; u < kDecUnroll; ++u) {  // one unpack of a K fragment, GC dot products
+      float k[8];
+      dec_unpack(kr[u], k);
+#pragma unroll
+      for (int i = 0; i < GC; ++i) {
+        s[i][u] = dec_dot_packed(qr[i], k);
+        mx[i] = fmaxf(mx[i], ok[u] ? s[i][u] * sl2 : -INFINITY);
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < GC; ++i) {
+      const float alpha = dec_exp2(m[i] - mx[i]);  // m is finite from the start
+      m[i] = mx[i];
+      l[i] *= alpha;
+#pragma unroll
+      for (int d = 0; d < 8; ++d) o[i][d] *= alpha;
+    }
+#pragma unroll
+    for (int u = 0; u < kDecUnroll; ++u) {  // one unpack of a V fragment, GC accumulators
+      float v[8];
+      dec_unpack(vr[u], v);
+#pragma unroll
+      for (int i = 0; i < GC; ++i) {
+        const float p = ok[u] ? dec_exp2(fmaf(s[i][u], sl2, -m[i])) : 0.f;
+        l[i] += p;
+#pragma unroll
+        for (int d = 0; d < 8; ++d) o[i][d] = fmaf(p, v[d], o[i][d]);
+      }
+    }
+  }
+
+  // merge, per head in attn_decode_kernel's fixed order
+#pragma unroll
+  for (int i = 0; i < GC; ++i) {
+    float mw = m[i];  // uniform inside a lane group: the maximum over the 8 groups (exact in any order)
+    mw = fmaxf(mw, dec_xor_row8(mw));
+    mw = fmaxf(mw, dec_xor(mw, lane, 16));
+    mw = fmaxf(mw, dec_xor(mw, lane, 32));
+    if (lane == 0) s_m[i][w] = mw;
+  }
+  dec_barrier();
+#pragma unroll
+  for (int i = 0; i < GC; ++i) {
+    float M = s_m[i][0];
+#pragma unroll
+    for (int x = 1; x < kDecWaves; ++x) M = fmaxf(M, s_m[i][x]);
+    const float a = dec_exp2(m[i] - M);
+    l[i] *= a;
+#pragma unroll
+    for (int d = 0; d < 8; ++d) o[i][d] *= a;
+    l[i] = dec_groups_sum(l[i], lane);  // the 8 groups of the wave: xor 8, 16, 32
+#pragma unroll
+    for (int d = 0; d < 8; ++d) o[i][d] = dec_groups_sum(o[i][d], lane);
+    if (g == 0) {
+#pragma unroll
+      for (int d = 0; d < 8; ++d) s_o[i][w][c * 8 + d] = o[i][d];
+      if (c == 0) s_l[i][w] = l[i];
+    }
+  }
+  dec_barrier();
+  if (w == 0 && g < GC) {  // lane group g sums head h0 + g over the waves, in wave order
+    float L = s_l[g][0];
+#pragma unroll
+    for (int x = 1; x < kDecWaves; ++x) L += s_l[g][x];
+    const float inv = 1.0f / L;  // L >= the new token's p > 0
+    uint32_t pk[4];
+#pragma unroll
+    for (int d = 0; d < 8; d += 2) {
+      float t0 = s_o[g][0][c * 8 + d], t1 = s_o[g][0][c * 8 + d + 1];
+#pragma unroll
+      for (int x = 1; x < kDecWaves; ++x) {
+        t0 += s_o[g][x][c * 8 + d];
+        t1 += s_o[g][x][c * 8 + d + 1];
+      }
+      pk[d >> 1] = (uint32_t)f32_to_bf16(t0 * inv) | ((uint32_t)f32_to_bf16(t1 * inv) << 16);
+    }
+    *reinterpret_cast<uint4*>(out + (int64_t)b * D + (h0 + g) * kDecHead + c * 8) =
+        dec_u4(pk[0], pk[1], pk[2], pk[3]);
+  }
+}
+
+// The query heads one workgroup serves: the largest of 4, 3, 2 that divides G and still leaves the grid one
+// workgroup per CU (256), else 1. Measured (profiles/gqa/README.md): a workgroup's time grows with GC (its VALU
+// work per loaded key does), so a larger GC pays only while the machine stays full; 6 and 8 lost to 2 x 3 and
+// 2 x 4 at every batch and pos and are reached through an explicit gc only. The choice cannot change a bit of the
+// output (the arithmetic of a head does not depend on GC), so it may depend on the batch.
+constexpr int kDecFillWorkgroups = 256;
+int attn_decode_gqa_chunk(int G, int Hkv, int B) {
+  for (int gc : {4, 3, 2})
+    if (G % gc == 0 && (long long)Hkv * (G / gc) * B >= kDecFillWorkgroups) return gc;
+  return 1;
+}
+
+void launch_attn_decode_gqa(const uint16_t* qkv_new, int64_t ldq, uint16_t* kv, const int* pos, uint16_t* out, int B,
+                            int H, int Hkv, int Smax, float scale, hipStream_t st, const float* rope, int gc) {
+  const int G = H / Hkv;
+  if (gc <= 0) gc = attn_decode_gqa_chunk(G, Hkv, B);
+  if (G * Hkv != H || G % gc != 0) throw_no_kernel("launch_attn_decode_gqa", "heads per KV head", G);
+  const int chunks = G / gc;
+  const dim3 grid(Hkv * chunks, B), block(kDecWaves * 64);
+  const bool hit = dispatch_int<1, 2, 3, 4, 6, 8>(gc, [&](auto c) {
+    constexpr int GC = decltype(c)::value;
+    if (rope)
+      attn_decode_gqa_kernel<GC, true><<<grid, block, 0, st>>>(qkv_new, ldq, kv, pos, out, H, Hkv, chunks, Smax, scale,
+                                                               rope);
+    else
+      attn_decode_gqa_kernel<GC, false><<<grid, block, 0, st>>>(qkv_new, ldq, kv, pos, out, H, Hkv, chunks, Smax,
+                                                                scale, nullptr);
+  });
+  if (!hit) throw_no_kernel("launch_attn_decode_gqa", "GC", gc);
+}
+
 }  // namespace mlt

@@ -101,6 +101,17 @@ norm backward adds the stream's gradient in the kernel. The key/value cache and 
 (``prefill`` caches the QKV of ``n``); ``decode_step`` keeps the normed rows in ``state.hidden``. Composes with
 ``causal``, ``unpad``, ``rotary``, both dropouts and all three model classes; with ``fp8`` it is rejected. Not built:
 post-norm RMSNorm, RMSNorm for ``emb_ln`` / ``mlm_ln``, gated FFNs, the norm fused into a GEMM prologue.
+
+Grouped-query attention (``BertConfig.kv_heads``, default None = ``heads``): ``Hkv = kv_heads`` key/value heads, each
+shared by the ``G = heads / Hkv`` query heads ``hkv * G .. hkv * G + G - 1`` (query head h reads KV head ``h // G``);
+``kv_heads`` must divide ``heads``. With ``kv_heads < heads`` ``layers.N.qkv`` is ``nn.Linear(h, (H + 2 Hkv) * 64)``
+with the compact column layout q (H heads) | k (Hkv) | v (Hkv) (ops/gqa.py); no other parameter changes, and with
+``kv_heads`` None or ``heads`` nothing changes at all. Training and prefill expand the compact rows to the wide
+layout in front of the unchanged rotation and flash attention kernels (``C.gqa_expand``) and reduce the wide dQKV
+behind them (``C.gqa_reduce``); the key/value cache is ``[2, B, Hkv, Smax, 64]`` and a decode step's attention is
+``C.attn_decode_gqa``, which streams every cached row once for its whole group. Composes with ``rotary``, ``pre_ln`` /
+``rmsnorm``, ``unpad`` and both dropouts; with ``fp8`` it is rejected. Not built: ``h // G`` indexing inside the
+flash kernels, the rotation fused into expand / reduce, paged caches.
 """
 from __future__ import annotations
 
@@ -136,6 +147,11 @@ class BertConfig:
     rope_base: float = 10000.0  # the angle of position p, pair i is p * rope_base ** (-2 i / 64)
     pre_ln: bool = False  # pre-norm blocks h + f(norm(h)) and a final norm (final_ln); not with fp8
     norm: str = "layernorm"  # the kind of ln1 / ln2 / final_ln: "layernorm", or "rmsnorm" (needs pre_ln)
+    kv_heads: Optional[int] = None  # grouped-query attention: key/value heads (a divisor of heads); None = heads
+
+    @property
+    def num_kv_heads(self) -> int:
+        return self.heads if self.kv_heads is None else self.kv_heads
 
 
 _PRESETS = {
@@ -183,7 +199,7 @@ class BertLayer(nn.Module):
         super().__init__()
         h = c.hidden
         self.c = c
-        self.qkv = nn.Linear(h, 3 * h)
+        self.qkv = nn.Linear(h, h + 2 * c.num_kv_heads * (h // c.heads))  # 3 h, or compact under kv_heads
         self.out = nn.Linear(h, h)
         self.ln1 = block_norm(c)
         self.ffn1 = nn.Linear(h, c.intermediate)
@@ -239,8 +255,15 @@ class BertLayer(nn.Module):
         if packed is not None:
             from ml_trainer_amd.ops.transformer import unpack_rows
             qkv = unpack_rows(qkv, packed)
-        qkv = qkv.view(B, S, 3, H, dh).permute(2, 0, 3, 1, 4)
-        q, k, v = qkv[0], qkv[1], qkv[2]
+        if c.num_kv_heads != H:  # compact q | k | v: every KV head repeated for the query heads of its group
+            Hkv = c.num_kv_heads
+            q, k, v = qkv.split((H * dh, Hkv * dh, Hkv * dh), dim=-1)
+            q = q.view(B, S, H, dh).permute(0, 2, 1, 3)
+            k = k.view(B, S, Hkv, dh).permute(0, 2, 1, 3).repeat_interleave(H // Hkv, dim=1)
+            v = v.view(B, S, Hkv, dh).permute(0, 2, 1, 3).repeat_interleave(H // Hkv, dim=1)
+        else:
+            qkv = qkv.view(B, S, 3, H, dh).permute(2, 0, 3, 1, 4)
+            q, k, v = qkv[0], qkv[1], qkv[2]
         if rope is not None:
             from ml_trainer_amd.ops.rope import rotate
             q, k = rotate(q, rope[:S]).to(q.dtype), rotate(k, rope[:S]).to(k.dtype)
@@ -296,6 +319,10 @@ class BertClassifier(nn.Module):
         if (c.pre_ln or c.norm != "layernorm") and c.fp8:
             raise ValueError("pre_ln=True / norm='rmsnorm' with fp8=True is not supported: the pre-norm blocks run "
                              "the bf16 linears only")
+        from ml_trainer_amd.ops.gqa import check_kv_heads
+        if check_kv_heads(c.heads, c.kv_heads) != c.heads and c.fp8:
+            raise ValueError("kv_heads < heads with fp8=True is not supported: the fp8 attention backward writes dQKV "
+                             "as e5m2 in the wide layout, which the group reduction cannot take")
         self.config = c
         self.last_dropout_seed = None  # the seed of the last forward that dropped
         self.word_embeddings = nn.Embedding(c.vocab_size, c.hidden)
@@ -563,6 +590,9 @@ class BertClassifier(nn.Module):
                 qkv = L.qkv(L.ln1(x) if c.pre_ln else x)
                 if pk is not None:
                     qkv = unpack_rows(qkv[0], pk)
+                if c.num_kv_heads != c.heads:  # compact rows: the wide layout, k / v repeated per group
+                    from ml_trainer_amd.ops.gqa import gqa_expand_reference
+                    qkv = gqa_expand_reference(qkv.reshape(B * S, -1), c.heads, c.num_kv_heads)
                 qkv = qkv.view(B, S, 3, c.heads, 64).permute(2, 0, 3, 1, 4)
                 if c.rotary:  # fp32 rotation of the (bf16) q and k, rounded back as the native path stores them
                     from ml_trainer_amd.ops.rope import rotate
@@ -787,10 +817,10 @@ class BertLMHeadModel(BertForMaskedLM):
         dev = input_ids.device
         lens = self._lengths(input_ids, attention_mask)
         if cache is None:
-            cache = DC.KVCache.allocate(c.layers, B, c.heads, Smax, dev)
+            cache = DC.KVCache.allocate(c.layers, B, c.num_kv_heads, Smax, dev)
         elif (cache.Smax != Smax or len(cache.kv) != c.layers or cache.pos.device != dev or
-              tuple(cache.kv[0].shape) != (2, B, c.heads, Smax, DC.HEAD_DIM)):
-            raise ValueError(f"prefill: the given cache does not hold {c.layers} layers of [2, {B}, {c.heads}, {Smax}, "
+              tuple(cache.kv[0].shape) != (2, B, c.num_kv_heads, Smax, DC.HEAD_DIM)):
+            raise ValueError(f"prefill: the given cache does not hold {c.layers} layers of [2, {B}, {c.num_kv_heads}, {Smax}, "
                              f"{DC.HEAD_DIM}] on {dev}")
         if input_ids.is_cuda:
             from ml_trainer_amd.ops import transformer as T
@@ -801,14 +831,16 @@ class BertLMHeadModel(BertForMaskedLM):
                 if c.pre_ln:  # x is the stream; the cache holds the K / V of its norm
                     n, _ = T._norm_fwd(x, *_norm_args(L.ln1))
                     x, (_, qkv, _, _) = T._attn_fwd(n, L.qkv.weight, L.qkv.bias, L.out.weight, L.out.bias, lens, B, S,
-                                                    c.heads, causal=True, rope=self._rope(), res=x)
-                    DC.fill_from_prefill(cache, l, qkv, lens, B, S)
+                                                    c.heads, causal=True, rope=self._rope(), res=x,
+                                                    kv_heads=c.kv_heads)
+                    DC.fill_from_prefill(cache, l, qkv, lens, B, S, heads=c.heads)
                     n, _ = T._norm_fwd(x, *_norm_args(L.ln2))
                     x, _ = T._ffn_fwd(n, L.ffn1.weight, L.ffn1.bias, L.ffn2.weight, L.ffn2.bias, res=x)
                     continue
                 a, (_, qkv, _, _) = T._attn_fwd(x, L.qkv.weight, L.qkv.bias, L.out.weight, L.out.bias, lens, B, S,
-                                                c.heads, causal=True, rope=self._rope())  # (qkv: rotated under rotary)
-                DC.fill_from_prefill(cache, l, qkv, lens, B, S)
+                                                c.heads, causal=True, rope=self._rope(), kv_heads=c.kv_heads)
+                # (qkv: rotated under rotary, the wide buffer under kv_heads)
+                DC.fill_from_prefill(cache, l, qkv, lens, B, S, heads=c.heads)
                 x, _ = T._ln_fwd(a, L.ln1.weight, L.ln1.bias, c.ln_eps)
                 f, _ = T._ffn_fwd(x, L.ffn1.weight, L.ffn1.bias, L.ffn2.weight, L.ffn2.bias)
                 x, _ = T._ln_fwd(f, L.ln2.weight, L.ln2.bias, c.ln_eps)
@@ -819,10 +851,13 @@ class BertLMHeadModel(BertForMaskedLM):
             mask = None if lens is None else pos[None, :] < lens[:, None]
             for l, L in enumerate(self.layers):
                 qkv = L.qkv(L.ln1(x) if c.pre_ln else x)
+                if c.num_kv_heads != c.heads:
+                    from ml_trainer_amd.ops.gqa import gqa_expand_reference
+                    qkv = gqa_expand_reference(qkv, c.heads, c.num_kv_heads)
                 if c.rotary:  # the cache holds rotated keys
                     from ml_trainer_amd.ops.rope import rope_qk_reference
                     qkv = rope_qk_reference(qkv, self.rope_table, c.heads, S)
-                DC.fill_from_prefill(cache, l, qkv, lens, B, S)
+                DC.fill_from_prefill(cache, l, qkv, lens, B, S, heads=c.heads)
                 x = L.forward_reference(x, mask, B, S, rope=self.rope_table)
         cache.pos.copy_(lens if lens is not None else torch.full((B,), S, dtype=torch.int32, device=dev))
         x = x.index_select(0, self._last_rows(lens, B, S, dev))
@@ -1003,7 +1038,8 @@ class BertLMHeadModel(BertForMaskedLM):
         """What a captured decode step baked in of the parameters: an in-place edit bumps ``_version`` (and makes
         ``bf16_weight`` / ``padded_decoder`` hand out new tensors), a re-allocation moves ``data_ptr``."""
         c = self.config  # (the block kind decides which kernels a step launches)
-        return (c.pre_ln, c.norm) + tuple((p._version, p.data_ptr()) for p in self.parameters())
+        gqa = (c.kv_heads,) if c.num_kv_heads != c.heads else ()  # (the attention launch and the cache shape)
+        return (c.pre_ln, c.norm) + gqa + tuple((p._version, p.data_ptr()) for p in self.parameters())
 
     def _graphed_decoder(self, B, Smax, T, dev):
         key = (B, Smax, T, str(dev))
@@ -1117,7 +1153,7 @@ class GraphedDecoder:
         c = model.config
         self.signature = signature
         self.B, self.Smax, self.T = B, Smax, T
-        self.cache = DC.KVCache.allocate(c.layers, B, c.heads, Smax, dev)
+        self.cache = DC.KVCache.allocate(c.layers, B, c.num_kv_heads, Smax, dev)
         self.sampler = DC.SamplerState.allocate(B, T, dev)
         self.state = DC.DecodeState(self.cache, None)
         self.graph = None

@@ -80,10 +80,16 @@ def attn_decode(qkv_new, cache_layer, pos, H: int, scale: float = ATTN_SCALE, ro
     [B, 3 * H * 64] bf16 may be a row-strided view (row stride a multiple of 8). ``rope`` (the fp32 table of
     ``ops.rope.rope_table``, at least Smax rows): the kernel's ROPE instantiation rotates q and the new k by
     ``pos[b]`` and rounds them to bf16 before the dot product and the append, so the cache holds the rotated keys
-    the training path's QKV buffer holds. Without it the launch is the one before rotary positions existed."""
+    the training path's QKV buffer holds. Without it the launch is the one before rotary positions existed.
+    A cache of ``Hkv = cache_layer.shape[2] != H`` heads is grouped-query attention: ``qkv_new`` is then the compact
+    [B, (H + 2 Hkv) * 64] row (ops/gqa.py) and the launch ``C.attn_decode_gqa``, which streams every cached row once
+    for the ``H // Hkv`` query heads of its group and returns the bits ``C.attn_decode`` returns on the repeated
+    cache. ``Hkv`` must divide ``H``."""
     C = require_native()
     out = torch.empty(qkv_new.shape[0], H * HEAD_DIM, dtype=torch.bfloat16, device=qkv_new.device)
-    if rope is None:
+    if cache_layer.shape[2] != H:
+        C.attn_decode_gqa(qkv_new, cache_layer, pos, out, H, scale, rope=rope)
+    elif rope is None:
         C.attn_decode(qkv_new, cache_layer, pos, out, H, scale)
     else:
         C.attn_decode(qkv_new, cache_layer, pos, out, H, scale, rope=rope)
@@ -95,22 +101,32 @@ def attn_decode_reference(qkv_new, cache_layer, pos, H: int, scale: float = ATTN
     returns out [B, H * 64] fp32. Stale rows are selected out (scores to -inf, values to 0), never multiplied
     by zero; nothing is read back from the device. ``rope`` (the table): q and the new k are rotated by
     ``pos[b]`` (clamped into the cache, as the kernel clamps it) before use, in ``qkv_new``'s own dtype (bf16 in:
-    rounded to bf16 as the kernel rounds them; fp32 in: fp32)."""
+    rounded to bf16 as the kernel rounds them; fp32 in: fp32). A cache of ``Hkv != H`` heads (``Hkv`` divides ``H``):
+    grouped-query attention on the compact ``qkv_new`` [B, (H + 2 Hkv) * 64]; the Hkv new k / v heads are appended and
+    every query head reads KV head ``h // (H // Hkv)``."""
     B = qkv_new.shape[0]
-    Smax = cache_layer.shape[3]
+    Hkv, Smax = cache_layer.shape[2], cache_layer.shape[3]
+    if Hkv != H:
+        from ml_trainer_amd.ops.gqa import check_kv_heads, gqa_expand_reference
+        check_kv_heads(H, Hkv)
+        qkv_new = gqa_expand_reference(qkv_new, H, Hkv)
     if rope is not None:
         from ml_trainer_amd.ops.rope import rope_qk_reference
         qkv_new = rope_qk_reference(qkv_new, rope, H, pos=pos.clamp(0, Smax - 1))
     q, k, v = qkv_new.float().view(B, 3, H, HEAD_DIM).unbind(1)
+    G = H // Hkv
     idx = pos.long()
     ar = torch.arange(B, device=qkv_new.device)
-    cache_layer[0, ar, :, idx] = k.to(cache_layer.dtype)
-    cache_layer[1, ar, :, idx] = v.to(cache_layer.dtype)
+    cache_layer[0, ar, :, idx] = k[:, ::G].to(cache_layer.dtype)
+    cache_layer[1, ar, :, idx] = v[:, ::G].to(cache_layer.dtype)
     j = torch.arange(Smax, device=qkv_new.device)
     cached = (j[None, :] < idx[:, None])[:, None, :]  # [B, 1, Smax]
     own = (j[None, :] == idx[:, None])[:, None, :]
-    K = torch.where(own[..., None], k[:, :, None, :], cache_layer[0].float())  # the new token from qkv_new itself
-    V = torch.where(own[..., None], v[:, :, None, :], cache_layer[1].float())
+    Kc, Vc = cache_layer[0].float(), cache_layer[1].float()
+    if G > 1:  # every query head sees its group's KV head
+        Kc, Vc = Kc.repeat_interleave(G, dim=1), Vc.repeat_interleave(G, dim=1)
+    K = torch.where(own[..., None], k[:, :, None, :], Kc)  # the new token from qkv_new itself
+    V = torch.where(own[..., None], v[:, :, None, :], Vc)
     valid = cached | own
     s = (K @ q[..., None])[..., 0] * scale  # [B, H, Smax]
     s = torch.where(valid, s, torch.full_like(s, float("-inf")))
@@ -160,17 +176,23 @@ def linear_small(x, w16, bias=None, gelu_aux=None, res=None, out=None):
     return out
 
 
-def fill_from_prefill(cache: KVCache, layer: int, qkv, lens: Optional[torch.Tensor], B: int, S: int) -> None:
+def fill_from_prefill(cache: KVCache, layer: int, qkv, lens: Optional[torch.Tensor], B: int, S: int,
+                      heads: Optional[int] = None) -> None:
     """Copy the K / V columns of a layer's padded ``qkv`` [B * S, 3 * H * 64] into rows 0 .. S - 1 of the
     head-major cache. Rows at and past ``lens[b]`` receive the pad positions' projections: they are stale by
-    the definition of ``pos`` (the caller sets ``pos = lens``) and never read."""
+    the definition of ``pos`` (the caller sets ``pos = lens``) and never read. ``heads`` (default: the cache's own
+    head count): the H of ``qkv`` when the cache holds fewer heads (grouped-query attention: ``qkv`` is the wide
+    buffer, whose k / v heads are equal within a group, and the cache takes every ``H // Hkv``-th of them)."""
     kv = cache.kv[layer]
-    H = kv.shape[2]
+    H = kv.shape[2] if heads is None else heads
+    G = H // kv.shape[2]
+    if G * kv.shape[2] != H:
+        raise ValueError(f"a cache of {kv.shape[2]} heads does not divide heads = {H}")
     if S > cache.Smax:
         raise ValueError(f"a prompt of width {S} does not fit a cache of {cache.Smax} rows")
     x = qkv.view(B, S, 3, H, HEAD_DIM)
-    kv[0, :, :, :S] = x[:, :, 1].permute(0, 2, 1, 3).to(kv.dtype)
-    kv[1, :, :, :S] = x[:, :, 2].permute(0, 2, 1, 3).to(kv.dtype)
+    kv[0, :, :, :S] = x[:, :, 1, ::G].permute(0, 2, 1, 3).to(kv.dtype)
+    kv[1, :, :, :S] = x[:, :, 2, ::G].permute(0, 2, 1, 3).to(kv.dtype)
 
 
 def sample_tokens(logits, temperature: float = 0.0, top_k: Optional[int] = None, generator=None):

@@ -52,6 +52,7 @@ from typing import Optional
 import torch
 
 from ml_trainer_amd.ops._ext import require_native
+from ml_trainer_amd.ops.gqa import gqa_expand, gqa_reduce, infer_kv_heads
 from ml_trainer_amd.utils.flat import FlatParams
 
 
@@ -241,6 +242,12 @@ def _causal_kw(causal, impl):
     return dict(causal=True)
 
 
+def _kv_heads(wqkv, H):
+    """The ``kv_heads`` argument of _attn_fwd / _attn_bwd from the QKV projection's own shape: None for the wide
+    [3 * H * 64, h] weight (every launch as before), Hkv for the compact [(H + 2 Hkv) * 64, h] one."""
+    return infer_kv_heads(wqkv.shape[0], H)
+
+
 def _rope_qk(t, rope, S, H, sign=1):
     """Rotary positions: rotate the q and k columns of ``t`` (QKV, or dQKV with ``sign=-1``) in place.
     ``rope`` = (table fp32 [P, 32, 2], pos int32 [rows] or None: row % S), see ops/rope.py."""
@@ -249,7 +256,7 @@ def _rope_qk(t, rope, S, H, sign=1):
 
 
 def _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl=BF16, residual=True, attn_drop=None, cu_seqlens=None,
-              causal: bool = False, rope=None, res=None):
+              causal: bool = False, rope=None, res=None, kv_heads=None):
     """``attn_drop`` = (p, seed, site, rank): attention-probability dropout inside the flash kernels
     (the byte mask of ops/dropout.py, recomputed in the backward); None: no dropout.
     ``cu_seqlens`` (int32 [B + 1], device): packed batch, x is [T, D] with sequence b at rows
@@ -258,9 +265,17 @@ def _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl=BF16, residual=True, at
     ``rope`` = (table, pos or None): rotary positions, q and k rotated in place between the QKV GEMM and the
     attention kernel (``pos`` for packed batches); the saved qkv is the rotated one, which the attention
     backward needs. ``res``: the residual the out-projection adds instead of ``x`` (pre-norm blocks: x is the
-    norm of the stream, ``res`` the stream)."""
+    norm of the stream, ``res`` the stream).
+    ``kv_heads`` (None or H: none of this): grouped-query attention, ``wqkv`` projects to the compact layout
+    q (H heads) | k (kv_heads) | v (kv_heads) and ``C.gqa_expand`` (ops/gqa.py) repeats every k / v head for its
+    group into the wide [rows, 3 * H * 64] buffer, which the rotation and the attention kernel then take
+    unchanged and which is what is saved."""
     C = require_native()
     ckw = _causal_kw(causal, impl)
+    gqa = kv_heads is not None and kv_heads != H
+    if gqa and impl is not BF16:
+        raise ValueError("grouped-query attention runs the bf16 linears only: the fp8 attention backward writes "
+                         "dQKV as e5m2 in the wide layout")
     if cu_seqlens is not None and impl is not BF16:
         raise ValueError("packed (cu_seqlens) attention runs the bf16 linears only: the fp8 attention epilogue "
                          "writes at b * S offsets")
@@ -268,6 +283,8 @@ def _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl=BF16, residual=True, at
         raise ValueError("rotary positions run the bf16 linears only: the fp8 attention backward writes dQKV as "
                          "e5m2, which the inverse rotation cannot take")
     qkv = impl.fwd(x, wqkv, bqkv)
+    if gqa:
+        qkv = gqa_expand(qkv, H, kv_heads)
     if rope is not None:
         _rope_qk(qkv, rope, S, H)
     attn = torch.empty(x.shape[0], H * 64, dtype=torch.bfloat16, device=x.device)
@@ -280,7 +297,7 @@ def _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl=BF16, residual=True, at
 
 
 def _attn_bwd(saved, params, lens, B, S, H, dy, G, dbo="colsum", impl=BF16, dres=None, attn_drop=None,
-              cu_seqlens=None, causal: bool = False, rope=None, residual=True):
+              cu_seqlens=None, causal: bool = False, rope=None, residual=True, kv_heads=None):
     """Backward of the attention block. ``dbo``: "colsum" to reduce dy here, otherwise the
     out-proj bias gradient already produced by the LayerNorm backward (tensor or None).
     ``dres``: the gradient of the residual branch when it differs from the out-proj's ``dy``
@@ -289,8 +306,12 @@ def _attn_bwd(saved, params, lens, B, S, H, dy, G, dbo="colsum", impl=BF16, dres
     rotated back (``sign=-1``) before anything else reads it. The QKV bias gradient is then the column sum of the
     rotated-back dQKV: the attention kernels' own column sums are sums in the rotated frame, which differ row by
     row, so that fused branch is not taken under rotary. ``residual=False`` (pre-norm blocks): the block's input
-    is not its residual, the QKV dgrad adds nothing."""
+    is not its residual, the QKV dgrad adds nothing. ``kv_heads``: the forward's; the wide dQKV (rotated back
+    under rotary) is reduced to the compact layout by ``C.gqa_reduce`` (dk / dv summed over each group) before the
+    weight gradient, the bias gradient and the dgrad read it. The attention kernels' own column sums are over wide
+    columns, so that fused branch is not taken under grouped-query attention either."""
     C = require_native()
+    gqa = kv_heads is not None and kv_heads != H
     akw = _attn_drop_kw(attn_drop)
     akw.update(_causal_kw(causal, impl))
     if cu_seqlens is not None:
@@ -306,9 +327,12 @@ def _attn_bwd(saved, params, lens, B, S, H, dy, G, dbo="colsum", impl=BF16, dres
     _zero_packed_tail(dqkv, cu_seqlens)
     delta = torch.empty(qkv.shape[0] * H, dtype=torch.float32, device=dy.device)
     q8 = impl.attn_dy_q(wqkv, x, qkv.shape[0]) if (impl is not BF16 and hasattr(impl, "attn_dy_q")) else None
-    if rope is not None:
+    if rope is not None or gqa:
         C.attn_bwd(qkv, attn, dattn, lse, delta, lens, dqkv, B, S, H, _ATTN_SCALE, **akw)
-        _rope_qk(dqkv, rope, S, H, sign=-1)
+        if rope is not None:
+            _rope_qk(dqkv, rope, S, H, sign=-1)
+        if gqa:
+            dqkv = gqa_reduce(dqkv, H, kv_heads)
         dwqkv, dbqkv = G.wgrad_bias(wqkv, bqkv, dqkv, x, impl)
     elif q8 is not None or (impl is BF16 and bqkv is not None):
         # the QKV bias gradient (column sums of dQKV) from the backward kernels themselves
@@ -501,7 +525,7 @@ class _AttentionBlock(torch.autograd.Function):
     def forward(ctx, x, wqkv, bqkv, wo, bo, lens, B, S, H, impl, attn_drop=None, cu_seqlens=None, causal=False,
                 rope=None):
         y, saved = _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl, attn_drop=attn_drop, cu_seqlens=cu_seqlens,
-                             causal=causal, rope=rope)
+                             causal=causal, rope=rope, kv_heads=_kv_heads(wqkv, H))
         ctx.save_for_backward(*saved)
         ctx.params, ctx.impl, ctx.rope = (wqkv, bqkv, wo, bo), impl, rope
         ctx.lens, ctx.dims, ctx.attn_drop, ctx.cu, ctx.causal = lens, (B, S, H), attn_drop, cu_seqlens, causal
@@ -512,7 +536,7 @@ class _AttentionBlock(torch.autograd.Function):
         G = _Grads()
         grads = _attn_bwd(ctx.saved_tensors, ctx.params, ctx.lens, *ctx.dims, dy.contiguous().to(torch.bfloat16), G,
                           impl=ctx.impl, attn_drop=ctx.attn_drop, cu_seqlens=ctx.cu, causal=ctx.causal,
-                          rope=ctx.rope)
+                          rope=ctx.rope, kv_heads=_kv_heads(ctx.params[0], ctx.dims[2]))
         G.done()
         return grads + (None, None, None, None, None, None, None, None, None)
 
@@ -558,11 +582,11 @@ class _AttentionLNBlock(torch.autograd.Function):
                 cu_seqlens=None, causal=False, rope=None):
         if drop is None:
             a, s1 = _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl, attn_drop=attn_drop, cu_seqlens=cu_seqlens,
-                              causal=causal, rope=rope)
+                              causal=causal, rope=rope, kv_heads=_kv_heads(wqkv, H))
             y, s2 = _ln_fwd(a, gamma, beta, eps)
         else:  # LN(dropout(out-proj) + x): dropout and the residual add inside the LayerNorm kernel
             a, s1 = _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl, residual=False, attn_drop=attn_drop,
-                              cu_seqlens=cu_seqlens, causal=causal, rope=rope)
+                              cu_seqlens=cu_seqlens, causal=causal, rope=rope, kv_heads=_kv_heads(wqkv, H))
             y, s2 = _dropout_add_ln_fwd(a, x, gamma, beta, eps, drop)
         ctx.save_for_backward(*s1, *s2)
         ctx.params, ctx.beta, ctx.impl = (wqkv, bqkv, wo, bo), beta, impl
@@ -583,7 +607,8 @@ class _AttentionLNBlock(torch.autograd.Function):
                                             dxsum_param=ctx.params[3], drop=ctx.drop)
         dx, dwqkv, dbqkv, dwo, dbo = _attn_bwd(t[:4], ctx.params, ctx.lens, *ctx.dims, da, G, dbo=dbo,
                                                impl=ctx.impl, dres=dres, attn_drop=ctx.attn_drop, cu_seqlens=ctx.cu,
-                                               causal=ctx.causal, rope=ctx.rope)
+                                               causal=ctx.causal, rope=ctx.rope,
+                                               kv_heads=_kv_heads(ctx.params[0], ctx.dims[2]))
         G.done()
         return dx, dwqkv, dbqkv, dwo, dbo, dg, db, None, None, None, None, None, None, None, None, None, None, None
 
@@ -663,11 +688,11 @@ class _PreAttentionBlock(torch.autograd.Function):
                 cu_seqlens=None, causal=False, rope=None):
         if drop is None:
             h2, s1 = _attn_fwd(n, wqkv, bqkv, wo, bo, lens, B, S, H, impl, attn_drop=attn_drop, cu_seqlens=cu_seqlens,
-                               causal=causal, rope=rope, res=h)
+                               causal=causal, rope=rope, res=h, kv_heads=_kv_heads(wqkv, H))
             n2, s2 = _norm_fwd(h2, gamma, beta, eps)
         else:
             a, s1 = _attn_fwd(n, wqkv, bqkv, wo, bo, lens, B, S, H, impl, residual=False, attn_drop=attn_drop,
-                              cu_seqlens=cu_seqlens, causal=causal, rope=rope)
+                              cu_seqlens=cu_seqlens, causal=causal, rope=rope, kv_heads=_kv_heads(wqkv, H))
             n2, s2 = _dropout_add_norm_fwd(a, h, gamma, beta, eps, drop)
             h2 = s2[0]
         ctx.save_for_backward(*s1, *s2)
@@ -687,7 +712,8 @@ class _PreAttentionBlock(torch.autograd.Function):
         da = dh if ctx.drop is None else dxm
         dn, dwqkv, dbqkv, dwo, dbo = _attn_bwd(t[:4], ctx.params, ctx.lens, *ctx.dims, da, G, dbo=dbo, impl=ctx.impl,
                                                attn_drop=ctx.attn_drop, cu_seqlens=ctx.cu, causal=ctx.causal,
-                                               rope=ctx.rope, residual=False)
+                                               rope=ctx.rope, residual=False,
+                                               kv_heads=_kv_heads(ctx.params[0], ctx.dims[2]))
         G.done()
         return (dh, dn, dwqkv, dbqkv, dwo, dbo, dg, db) + (None,) * 11
 
