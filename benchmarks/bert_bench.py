@@ -56,6 +56,10 @@ def run(args):
         over.update(pre_ln=bool(args.pre_ln), norm=args.norm)
     if args.kv_heads is not None:
         over["kv_heads"] = args.kv_heads
+    if args.ffn != "gelu":
+        over["ffn"] = args.ffn
+    if args.intermediate is not None:
+        over["intermediate"] = args.intermediate
     cfg = bert_config(args.model, **over)
     m = (BertLMHeadModel if clm else BertForMaskedLM if mlm else BertClassifier)(cfg).to(dev)
     if mlm and args.chunk_rows:
@@ -117,7 +121,8 @@ def run(args):
            "peak_mem_gb": torch.cuda.max_memory_allocated() / 2 ** 30,
            "min_len": args.min_len, "tokens": real, "fill": real / tokens, "unpad": bool(args.unpad),
            "optimizer": args.optimizer, "no_decay_1d": bool(args.no_decay_1d), "rotary": bool(args.rotary),
-           "pre_ln": bool(args.pre_ln), "norm": args.norm, "kv_heads": args.kv_heads}
+           "pre_ln": bool(args.pre_ln), "norm": args.norm, "kv_heads": args.kv_heads,
+           "ffn": args.ffn, "intermediate": cfg.intermediate}
     if mlm:
         with torch.no_grad():
             hidden = fwd(ids)
@@ -159,6 +164,9 @@ def main():
     ap.add_argument("--unpad", action="store_true", help="BertConfig.unpad: run the encoder on the real tokens only")
     ap.add_argument("--rotary", action="store_true",
                     help="BertConfig.rotary: rotary positions on q and k (the rope_qk kernel) instead of the learned table")
+    ap.add_argument("--ffn", choices=["gelu", "swiglu"], default="gelu",
+                    help="BertConfig.ffn: the GELU or the gated SwiGLU feed-forward (records carry ffn)")
+    ap.add_argument("--intermediate", type=int, default=None, help="BertConfig.intermediate (records carry it)")
     ap.add_argument("--kv-heads", type=int, default=None,
                     help="BertConfig.kv_heads: grouped-query attention (a divisor of the model's heads)")
     ap.add_argument("--pre-ln", action="store_true", help="BertConfig.pre_ln: pre-norm blocks and a final norm")

@@ -30,7 +30,9 @@ skinny kernel) and ``1`` in one process and reports both medians and the spread 
 ``--rotary`` builds the model of the model timings with rotary positions (``BertConfig.rotary``) instead of the learned
 position table; the records carry ``"rotary"``. ``--pre-ln`` / ``--norm {layernorm,rmsnorm}`` build it with pre-norm
 blocks (``BertConfig.pre_ln`` / ``norm``); the records carry ``"pre_ln"`` and ``"norm"``. ``--kv-heads N`` builds it
-with grouped-query attention (``BertConfig.kv_heads``); the model records then carry ``"kv_heads"``.
+with grouped-query attention (``BertConfig.kv_heads``); the model records then carry ``"kv_heads"``. ``--ffn swiglu``
+(``--intermediate F``) builds it with the gated feed-forward; the records carry ``"ffn"``, ``"intermediate"`` and, in
+the sampler A/B, ``"decode_glu"`` (``MLT_DECODE_GLU``: 0 = FFN1 and the gate as two launches).
 Random weights and prompts (no network)."""
 from __future__ import annotations
 
@@ -63,6 +65,10 @@ def _model(args, dev):
         over.update(pre_ln=bool(args.pre_ln), norm=args.norm)
     if args.kv_heads is not None:
         over["kv_heads"] = args.kv_heads
+    if args.ffn != "gelu":
+        over["ffn"] = args.ffn
+    if args.intermediate is not None:
+        over["intermediate"] = args.intermediate
     return BertLMHeadModel(bert_config(args.model, **over)).to(dev).eval()
 
 
@@ -119,7 +125,8 @@ def bench_model(args, dev):
                 t_unc.append(_sync_ms(uncached) / (N - 1))
         ms = statistics.median(t_dec[settings[-1]])
         rec = {"bench": "generate", "model": args.model, "rotary": bool(args.rotary), "pre_ln": bool(args.pre_ln),
-               "norm": args.norm, "kv_heads": args.kv_heads, "batch": B, "prompt": P, "new": N,
+               "norm": args.norm, "kv_heads": args.kv_heads, "ffn": args.ffn, "intermediate": args.intermediate,
+               "batch": B, "prompt": P, "new": N,
                "decode_gemm": settings[-1],
                "prefill_ms": statistics.median(t_pre), "cached_ms_per_token": ms, "cached_tokens_per_s": B / ms * 1e3,
                "uncached_ms_per_token": statistics.median(t_unc) if t_unc else None,
@@ -185,8 +192,9 @@ def bench_sampler_ab(args, dev):
                     pre()
                     t[k].append(_sync_ms(run) / (N - 1))
             rec = {"bench": "generate_sampler_ab", "model": args.model, "rotary": bool(args.rotary),
-                   "pre_ln": bool(args.pre_ln), "norm": args.norm, "kv_heads": args.kv_heads, "batch": B,
-                   "prompt": P, "new": N,
+                   "pre_ln": bool(args.pre_ln), "norm": args.norm, "kv_heads": args.kv_heads, "ffn": args.ffn,
+                   "intermediate": args.intermediate, "decode_glu": os.environ.get("MLT_DECODE_GLU", "1"),
+                   "batch": B, "prompt": P, "new": N,
                    "setting": name, "capture_s": dec.capture_seconds}
             for k in t:
                 rec[k + "_ms_per_token"] = statistics.median(t[k])
@@ -328,6 +336,9 @@ def main():
     ap.add_argument("--sampler-ab", action="store_true",
                     help="alternate (eager, torch sampler), (eager, device sampler), (graph, device sampler)")
     ap.add_argument("--rotary", action="store_true", help="rotary positions in the model timings")
+    ap.add_argument("--ffn", choices=["gelu", "swiglu"], default="gelu",
+                    help="BertConfig.ffn: the GELU or the gated SwiGLU feed-forward (records carry ffn)")
+    ap.add_argument("--intermediate", type=int, default=None, help="BertConfig.intermediate (records carry it)")
     ap.add_argument("--kv-heads", type=int, default=None,
                     help="BertConfig.kv_heads: grouped-query attention in the model timings (records carry kv_heads)")
     ap.add_argument("--pre-ln", action="store_true", help="pre-norm blocks in the model timings")

@@ -22,6 +22,7 @@ any ``--task``: rotary position embeddings on the queries and keys instead of th
 ``--pre_ln`` / ``--norm {layernorm,rmsnorm}`` (BERT, any ``--task``: pre-norm blocks ``h + f(norm(h))`` with a final
 norm, and RMSNorm instead of LayerNorm as their norm; ``--norm rmsnorm`` needs ``--pre_ln``), ``--kv_heads N`` (BERT,
 any ``--task``: grouped-query attention, N key/value heads shared by heads / N query heads each),
+``--ffn {gelu,swiglu}`` / ``--intermediate F`` (BERT, any ``--task``: the gated SwiGLU feed-forward and the FFN width),
 ``--min_seq_len L``
 (variable-length synthetic text, lengths uniform in [L, seq_len], right-padded with ``--pad_id``), ``--optimizer lamb`` (layer-wise trust ratios on the flat buffer) and
 ``--no_decay_1d`` (adamw / lamb: biases and LayerNorm parameters take no weight decay), ``--task mlm``
@@ -99,6 +100,10 @@ def build_model_and_datasets(args):
         raise ValueError("--norm rmsnorm needs --pre_ln: post-norm RMSNorm blocks are not built")
     if lenet and args.kv_heads is not None:
         raise ValueError("--kv_heads applies to the BERT models; the LeNet models have no attention")
+    if lenet and (args.ffn != "gelu" or args.intermediate is not None):
+        raise ValueError("--ffn / --intermediate apply to the BERT models; the LeNet models have no feed-forward block")
+    if args.intermediate is not None and (args.intermediate < 8 or args.intermediate % 8):
+        raise ValueError(f"--intermediate must be a positive multiple of 8, got {args.intermediate}")
     if lenet and args.min_seq_len is not None:
         raise ValueError("--min_seq_len applies to the synthetic text data of the BERT models")
     mlm = args.task == "mlm"
@@ -135,6 +140,10 @@ def build_model_and_datasets(args):
         over["norm"] = args.norm
     if args.kv_heads is not None:
         over["kv_heads"] = args.kv_heads
+    if args.ffn != "gelu":
+        over["ffn"] = args.ffn
+    if args.intermediate is not None:
+        over["intermediate"] = args.intermediate
     pad_id = args.pad_id if args.pad_id is not None else (0 if args.min_seq_len is not None else None)
     if pad_id is not None and not lenet:
         over["pad_id"] = pad_id
@@ -289,6 +298,13 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--norm", choices=["layernorm", "rmsnorm"], default="layernorm",
                         help="--pre_ln: the norm of the blocks and the final norm; rmsnorm = x * rsqrt(mean(x^2) + "
                              "eps) * weight, no centring, no bias (needs --pre_ln)")
+    parser.add_argument("--ffn", choices=["gelu", "swiglu"], default="gelu",
+                        help="BERT, any --task: the feed-forward block; swiglu = ffn2((g * sigmoid(g)) * u) with ffn1 "
+                             "projecting to gate | up, 2 * intermediate columns (not with the fp8 `large` preset). An "
+                             "error for the LeNet models")
+    parser.add_argument("--intermediate", type=int, default=None,
+                        help="BERT: the feed-forward width F (default: the preset's). A SwiGLU block has the parameters "
+                             "of a GELU block of width 4h at F = 8h / 3 (2048 for bert-base)")
     parser.add_argument("--kv_heads", type=int, default=None,
                         help="BERT, any --task: grouped-query attention with this many key/value heads, each shared "
                              "by heads / kv_heads query heads (a divisor of the model's heads; 1 = multi-query; "

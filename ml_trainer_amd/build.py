@@ -115,7 +115,9 @@ FILE_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-ve
                                  "-mllvm", "-amdgpu-kernarg-preload-count=12"],
               # gqa.hip: gqa_reduce's result is defined bit for bit (a sequential fp32 sum); built without the
               # packed fp32 forms (v_pk_add_f32), plain v_add_f32 instead: the kernel is bound by its loads
-              "gqa.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+              "gqa.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+              # swiglu.hip: uncontracted fp32 products shared bit for bit with the gated decode GEMM; no packed forms
+              "swiglu.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 # translation units split off a kernel file for parallel compilation share its flags ({prefix: file})
 FILE_ALIASES = {"lenet_mfma_dp": "lenet_mfma.hip"}  # (lenet_mfma_dp.hip, lenet_mfma_dpw<W>.hip)
 

@@ -570,6 +570,91 @@ void gemm_skinny(Tensor X, Tensor W, Tensor Y, c10::optional<Tensor> bias, c10::
                      cur_stream());
 }
 
+// Y [M, F] bf16 = swiglu(bf16(X . W[0:F]^T + bias[0:F]), bf16(X . W[F:2F]^T + bias[F:2F])) on the gated
+// weight-streaming kernel (gemm_skinny_glu_kernel): the operand checks of gemm_skinny with W [2F, K]. Bit for bit
+// gemm_skinny (N = 2F) followed by swiglu_fwd.
+void gemm_skinny_glu(Tensor X, Tensor W, Tensor Y, c10::optional<Tensor> bias) {
+  static const GemmOperandText tx{"gemm_skinny_glu", "gemm_skinny_glu operands must be device tensors",
+                                  "gemm_skinny_glu operands need unit column stride (k-contiguous X and W)",
+                                  "gemm_skinny_glu leading dimensions must be multiples of 8"};
+  check_gemm_operand(X, tx, 8);
+  check_gemm_operand(W, tx, 8);
+  check_gemm_operand(Y, tx, 8);
+  TORCH_CHECK(X.scalar_type() == at::kBFloat16 && W.scalar_type() == at::kBFloat16 &&
+                  Y.scalar_type() == at::kBFloat16,
+              "gemm_skinny_glu X/W/Y must be bf16");
+  const int64_t M = X.size(0), K = X.size(1), F = Y.size(1);
+  TORCH_CHECK(W.size(1) == K, "gemm_skinny_glu inner dimensions differ: ", K, " vs ", W.size(1));
+  TORCH_CHECK(W.size(0) == 2 * F, "gemm_skinny_glu W must hold gate and up rows: W.shape[0] = ", W.size(0),
+              ", expected 2 * Y.shape[1] = ", 2 * F);
+  TORCH_CHECK(Y.size(0) == M, "gemm_skinny_glu Y shape mismatch");
+  TORCH_CHECK(M >= 1 && M <= kSkinnyMaxRows, "gemm_skinny_glu takes 1 .. ", kSkinnyMaxRows, " rows, got ", M);
+  TORCH_CHECK(F % 16 == 0 && K % 32 == 0 && F > 0 && K > 0, "gemm_skinny_glu needs F % 16 == 0 and K % 32 == 0, got F = ",
+              F, ", K = ", K);
+  TORCH_CHECK(F < (1LL << 30) && K < (1LL << 31), "gemm_skinny_glu dims too large");
+  TORCH_CHECK(X.stride(0) >= K && W.stride(0) >= K && Y.stride(0) >= F, "gemm_skinny_glu rows overlap");
+  const float* bp = nullptr;
+  if (bias.has_value()) {
+    check_dev(*bias, "bias", at::kFloat, 2 * F, 4);
+    bp = bias->data_ptr<float>();
+  }
+  launch_gemm_skinny_glu(bf16_ptr(X), bf16_ptr(W), (uint16_t*)Y.data_ptr(), (int)M, (int)F, (int)K, X.stride(0),
+                         W.stride(0), Y.stride(0), bp, cur_stream());
+}
+
+// The bf16 operands of swiglu_fwd / swiglu_bwd (swiglu.hip): 2-D device tensors with unit column stride, a row
+// stride that is a multiple of 8 and a 16-byte aligned base (row-strided views pass).
+static void check_glu(const Tensor& t, const char* name, int64_t rows, int64_t cols, const char* who) {
+  TORCH_CHECK(t.defined() && t.is_cuda() && t.dim() == 2 && t.scalar_type() == at::kBFloat16, who, ": ", name,
+              " must be a 2-D bf16 device tensor");
+  TORCH_CHECK(t.size(0) == rows && t.size(1) == cols, who, ": ", name, " is [", t.size(0), ", ", t.size(1),
+              "], expected [", rows, ", ", cols, "]");
+  TORCH_CHECK(t.size(0) <= 1 || (t.stride(0) >= cols && t.stride(0) % 8 == 0), who, ": ", name,
+              " needs a row stride that is a multiple of 8");
+  TORCH_CHECK(t.size(0) == 0 || t.stride(1) == 1, who, ": ", name, " needs unit column stride");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, who, ": ", name, " must be 16-byte aligned");
+}
+static int64_t glu_ld(const Tensor& t) { return t.size(0) > 1 ? t.stride(0) : t.size(1); }
+static int64_t check_glu_width(const Tensor& H1, const char* who) {
+  TORCH_CHECK(H1.defined() && H1.dim() == 2, who, ": H1 must be 2-D");
+  const int64_t F = H1.size(1) / 2;
+  TORCH_CHECK(H1.size(1) == 2 * F && F > 0 && F % 8 == 0 && F < (1LL << 30), who, ": H1 has ", H1.size(1),
+              " columns, expected 2 F with F % 8 == 0");
+  return F;
+}
+
+// A [rows, F] = bf16((g * s) * u) from H1 [rows, 2F] = g | u (mlt_swiglu.h)
+void swiglu_fwd(Tensor H1, Tensor A) {
+  const int64_t F = check_glu_width(H1, "swiglu_fwd"), rows = H1.size(0);
+  check_glu(H1, "H1", rows, 2 * F, "swiglu_fwd");
+  check_glu(A, "A", rows, F, "swiglu_fwd");
+  TORCH_CHECK(rows * (F / 8) <= (int64_t)0x7ffffff0 * 256, "swiglu_fwd: ", rows, " rows exceed the grid");
+  launch_swiglu_fwd(bf16_ptr(H1), glu_ld(H1), (uint16_t*)A.data_ptr(), glu_ld(A), rows, (int)F, cur_stream());
+}
+
+int64_t swiglu_partial_blocks(int64_t rows) { return swiglu_bwd_row_blocks(rows); }
+
+// dH1 [rows, 2F] = dg | du from dA [rows, F] and H1, and db1 [2F] (+)= the column sums of the stored dH1: the
+// kernel leaves part [swiglu_partial_blocks(rows), 2F] (one row per 64 rows), reduce_col_partials sums it.
+void swiglu_bwd(Tensor dA, Tensor H1, Tensor dH1, Tensor part, Tensor db1, bool accumulate) {
+  const int64_t F = check_glu_width(H1, "swiglu_bwd"), rows = H1.size(0);
+  check_glu(H1, "H1", rows, 2 * F, "swiglu_bwd");
+  check_glu(dA, "dA", rows, F, "swiglu_bwd");
+  check_glu(dH1, "dH1", rows, 2 * F, "swiglu_bwd");
+  const int64_t nrb = swiglu_bwd_row_blocks(rows);
+  check_dev(part, "part", at::kFloat, nrb * 2 * F, 16);
+  check_dev(db1, "db1", at::kFloat, 2 * F, 16);
+  TORCH_CHECK(db1.numel() == 2 * F, "swiglu_bwd: db1 has ", db1.numel(), " elements, expected ", 2 * F);
+  TORCH_CHECK(nrb * ((F + 511) / 512) < (1LL << 31) && nrb < (1LL << 31), "swiglu_bwd: ", rows, " rows exceed the grid");
+  if (rows == 0) {
+    if (!accumulate) db1.zero_();
+    return;
+  }
+  launch_swiglu_bwd(bf16_ptr(dA), glu_ld(dA), bf16_ptr(H1), glu_ld(H1), (uint16_t*)dH1.data_ptr(), glu_ld(dH1),
+                    part.data_ptr<float>(), rows, (int)F, cur_stream());
+  reduce_col_partials(part, nrb, 2 * F, db1.data_ptr<float>(), accumulate);
+}
+
 // ---------------------------------------------------------------------------- fp8
 static bool is_fp8_storage(const Tensor& t) {
   return t.scalar_type() == at::kByte || t.scalar_type() == at::kFloat8_e4m3fn ||
@@ -2013,6 +2098,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_skinny", &gemm_skinny, py::arg("X"), py::arg("W"), py::arg("Y"), py::arg("bias") = py::none(),
         py::arg("aux") = py::none(), py::arg("res") = py::none(), py::arg("mode") = 0);
   m.def("gemm_skinny_max_rows", []() { return kSkinnyMaxRows; });
+  m.def("gemm_skinny_glu", &gemm_skinny_glu, py::arg("X"), py::arg("W"), py::arg("Y"), py::arg("bias") = py::none());
+  m.def("swiglu_fwd", &swiglu_fwd, py::arg("H1"), py::arg("A"));
+  m.def("swiglu_bwd", &swiglu_bwd, py::arg("dA"), py::arg("H1"), py::arg("dH1"), py::arg("part"), py::arg("db1"),
+        py::arg("accumulate") = false);
+  m.def("swiglu_partial_blocks", &swiglu_partial_blocks);
   m.def("gemm_f8", &gemm_f8, py::arg("A"), py::arg("B"), py::arg("C"), py::arg("fmt_a"), py::arg("fmt_b"),
         py::arg("inv_scale_a"), py::arg("inv_scale_b"), py::arg("bias") = py::none(), py::arg("aux") = py::none(),
         py::arg("res") = py::none(), py::arg("alpha") = 1.0, py::arg("mode") = 0, py::arg("accumulate") = false,

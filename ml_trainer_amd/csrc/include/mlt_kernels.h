@@ -221,6 +221,18 @@ constexpr int kSkinnyMaxRows = 64;
 void launch_gemm_skinny(const uint16_t* X, const uint16_t* W, void* Y, bool out_f32, int M, int N, int K, int64_t ldx,
                         int64_t ldw, int64_t ldy, const float* bias, const uint16_t* aux, int64_t ldaux,
                         const uint16_t* res, int64_t ldres, int mode, hipStream_t st);
+// The gated variant (gemm_skinny_glu_kernel): Y [M][F] bf16 = swiglu(bf16(X . W[0:F]^T + bias[0:F]),
+// bf16(X . W[F:2F]^T + bias[F:2F])), W [2F][K]; F % 16 == 0, K % 32 == 0, Y rows 8-byte aligned. Bit for bit
+// launch_gemm_skinny with N = 2F followed by launch_swiglu_fwd.
+void launch_gemm_skinny_glu(const uint16_t* X, const uint16_t* W, uint16_t* Y, int M, int F, int K, int64_t ldx,
+                            int64_t ldw, int64_t ldy, const float* bias, hipStream_t st);
+// SwiGLU (swiglu.hip, definition in mlt_swiglu.h): H1 [rows][ldh >= 2F] bf16 = gate | up, A [rows][F], F % 8 == 0,
+// row strides multiples of 8, 16-byte aligned bases. The backward also writes part [swiglu_bwd_row_blocks(rows)][2F]
+// fp32, the column sums of the rounded dH1 per block of 64 rows (reduced by launch_reduce_rows).
+int64_t swiglu_bwd_row_blocks(int64_t rows);
+void launch_swiglu_fwd(const uint16_t* H1, int64_t ldh, uint16_t* A, int64_t lda, int64_t rows, int F, hipStream_t st);
+void launch_swiglu_bwd(const uint16_t* DA, int64_t ldda, const uint16_t* H1, int64_t ldh, uint16_t* DH1, int64_t lddh,
+                       float* part, int64_t rows, int F, hipStream_t st);
 // fp8 GEMM (gemm_tile.hip): A [M][K], B [N][K] both k-contiguous fp8 (fmt 0 = e4m3, 1 = e5m2),
 // K % 128 == 0; alpha *= inv_scale_a[0] * inv_scale_b[0] (device scalars, delayed scaling).
 GemmPlan plan_gemm_f8(int M, int N, int K, int force_cfg, int force_splits);

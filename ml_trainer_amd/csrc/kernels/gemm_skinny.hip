@@ -40,9 +40,13 @@
 // shapes launch 48 - 192 workgroups on 256 CUs (one 4-wave workgroup per CU, one wave per SIMD, whatever the
 // limit), and what hides the latency is the 12 - 30 loads each wave has outstanding. Only the vocabulary decoder
 // (1,920 workgroups, 7.5 per CU) fills a CU: with MG = 1 all of them are resident at once.
+//
+// gemm_skinny_glu_kernel (below) is the gated FFN1 of a SwiGLU decode step on the same partition: two weight
+// streams, two accumulator sets, the activation in the epilogue.
 #include "mlt_common.h"
 #include "mlt_gemm.h"
 #include "mlt_kernels.h"
+#include "mlt_swiglu.h"
 
 namespace mlt {
 
@@ -150,6 +154,135 @@ void launch_gemm_skinny(const uint16_t* X, const uint16_t* W, void* Y, bool out_
         out_f32);
   });
   if (!hit) throw_no_kernel("launch_gemm_skinny", "row groups", mg);
+}
+
+// The gated FFN1 of a decode step: Y[M, F] = swiglu(bf16(X . Wg^T + bg), bf16(X . Wu^T + bu)) with Wg = W[0:F] and
+// Wu = W[F:2F] rows of the layer's one [2F, K] weight (no re-packed copy) and bias = bg | bu.
+//
+// The partition is gemm_skinny_kernel's with N = F: one workgroup per 16 output columns, the same k-step to wave
+// mapping and kSkBatch, the partials summed through LDS in wave order. Each step loads TWO W fragments (rows
+// n0 + r and F + n0 + r) and one X fragment, which feeds both MFMAs into two accumulator sets: X is read once for
+// both halves and the [M, 2F] intermediate never exists. Epilogue: both sets in wave order, the two bias slices,
+// g and u each rounded to bf16 (FFN1's store in the unfused pair), the shared device function of mlt_swiglu.h,
+// four consecutive bf16 columns stored. The k-order depends on K only and g, u are rounded before the activation,
+// so the output EQUALS, bit for bit, gemm_skinny with N = 2F followed by swiglu_fwd (tests/test_swiglu_gpu.py),
+// which is what lets a cached decode step agree with prefill.
+//
+// no-packed-fp32-ops: the kernel's bits never depend on the packed fp32 forms (as attn_decode_gqa_kernel). A
+// device function that is not always_inline would then be CALLED, not inlined, so the body uses builtins and
+// __forceinline__ helpers only: no lambda, no min(), no __syncthreads().
+//
+// Registers (-Rpass-analysis=kernel-resource-usage), scratch 0 everywhere:
+//   MG = 1:  86 VGPRs +  8 AGPRs,  8 KB LDS, 5 waves per SIMD
+//   MG = 2: 128 VGPRs + 16 AGPRs, 16 KB LDS, 3 waves per SIMD
+//   MG = 4: 192 VGPRs + 32 AGPRs, 32 KB LDS, 2 waves per SIMD
+// (the kSkBatch x (2 + MG) fragments in flight; decode_linear_path routes M <= 16, i.e. MG = 1, only.)
+template <int MG>
+__attribute__((target("no-packed-fp32-ops"))) __global__
+__launch_bounds__(kSkWaves * 64) void gemm_skinny_glu_kernel(const uint16_t* __restrict__ X,
+                                                             const uint16_t* __restrict__ W, uint16_t* __restrict__ Y,
+                                                             int M, int F, int K, int64_t ldx, int64_t ldw,
+                                                             int64_t ldy, const float* __restrict__ bias) {
+  __shared__ f32x4 red[kSkWaves][2][MG][64];
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int r = lane & 15, kq = lane >> 4;
+  const int n0 = blockIdx.x * 16;
+
+  // this wave's steps, exactly as gemm_skinny_kernel numbers them
+  const int nsteps = K >> 5, npairs = nsteps >> 1;
+  int nj = npairs > w ? 2 * ((npairs - w + kSkWaves - 1) / kSkWaves) : 0;
+  if ((nsteps & 1) && npairs % kSkWaves == w) ++nj;
+
+  const uint16_t* wg = W + (int64_t)(n0 + r) * ldw + 8 * kq;
+  const uint16_t* wu = wg + (int64_t)F * ldw;
+  const uint16_t* xp[MG];
+  bool live[MG];
+#pragma unroll
+  for (int g = 0; g < MG; ++g) {
+    live[g] = 16 * g + r < M;
+    xp[g] = X + (int64_t)(16 * g + r) * ldx + 8 * kq;
+  }
+
+  f32x4 accg[MG], accu[MG];
+#pragma unroll
+  for (int g = 0; g < MG; ++g) accg[g] = accu[g] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  for (int j0 = 0; j0 < nj; j0 += kSkBatch) {
+    bf16x8 gf[kSkBatch], uf[kSkBatch], xf[MG][kSkBatch];
+    int koff[kSkBatch];
+#pragma unroll
+    for (int u = 0; u < kSkBatch; ++u) {
+      const int j = j0 + u < nj ? j0 + u : nj - 1;  // surplus slots re-load the wave's last step
+      koff[u] = 32 * (2 * (w + (j >> 1) * kSkWaves) + (j & 1));
+      gf[u] = *reinterpret_cast<const bf16x8*>(wg + koff[u]);
+      uf[u] = *reinterpret_cast<const bf16x8*>(wu + koff[u]);
+    }
+#pragma unroll
+    for (int g = 0; g < MG; ++g) {
+#pragma unroll
+      for (int u = 0; u < kSkBatch; ++u) xf[g][u] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+      if (live[g]) {
+#pragma unroll
+        for (int u = 0; u < kSkBatch; ++u) xf[g][u] = *reinterpret_cast<const bf16x8*>(xp[g] + koff[u]);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kSkBatch; ++u) {
+      if (j0 + u < nj) {  // wave-uniform
+#pragma unroll
+        for (int g = 0; g < MG; ++g) {
+          accg[g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(gf[u], xf[g][u], accg[g], 0, 0, 0);
+          accu[g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(uf[u], xf[g][u], accu[g], 0, 0, 0);
+        }
+      }
+    }
+  }
+
+#pragma unroll
+  for (int g = 0; g < MG; ++g) {
+    red[w][0][g][lane] = accg[g];
+    red[w][1][g][lane] = accu[g];
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  if (w >= MG) return;
+  // wave g finishes row group g: both sets in wave order, bias, the bf16 rounding of FFN1's store, the gate
+  f32x4 sg = red[0][0][w][lane], su = red[0][1][w][lane];
+#pragma unroll
+  for (int i = 1; i < kSkWaves; ++i) {
+    sg += red[i][0][w][lane];
+    su += red[i][1][w][lane];
+  }
+  const int gm = 16 * w + r, gn = n0 + 4 * kq;
+  if (gm >= M) return;
+  float vg[4] = {sg[0], sg[1], sg[2], sg[3]}, vu[4] = {su[0], su[1], su[2], su[3]};
+  if (bias) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      vg[q] += bias[gn + q];
+      vu[q] += bias[F + gn + q];
+    }
+  }
+  uint16_t o[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+    o[q] = glu_bf16(swiglu_act(bf16_to_f32(glu_bf16(vg[q])), bf16_to_f32(glu_bf16(vu[q]))));
+  uint2 st;
+  st.x = (uint32_t)o[0] | ((uint32_t)o[1] << 16);
+  st.y = (uint32_t)o[2] | ((uint32_t)o[3] << 16);
+  *reinterpret_cast<uint2*>(Y + (int64_t)gm * ldy + gn) = st;
+}
+
+void launch_gemm_skinny_glu(const uint16_t* X, const uint16_t* W, uint16_t* Y, int M, int F, int K, int64_t ldx,
+                            int64_t ldw, int64_t ldy, const float* bias, hipStream_t st) {
+  const int mg = M <= 16 ? 1 : M <= 32 ? 2 : M <= kSkinnyMaxRows ? 4 : 0;
+  const bool hit = dispatch_int<1, 2, 4>(mg, [&](auto g) {
+    hipLaunchKernelGGL(gemm_skinny_glu_kernel<decltype(g)::value>, dim3(F / 16), dim3(kSkWaves * 64), 0, st, X, W, Y, M,
+                       F, K, ldx, ldw, ldy, bias);
+  });
+  if (!hit) throw_no_kernel("launch_gemm_skinny_glu", "row groups", mg);
 }
 
 }  // namespace mlt

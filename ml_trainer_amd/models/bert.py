@@ -100,7 +100,7 @@ stored in bf16 after every add, the norm of the new stream comes from the kernel
 norm backward adds the stream's gradient in the kernel. The key/value cache and ``attn_decode`` are unchanged
 (``prefill`` caches the QKV of ``n``); ``decode_step`` keeps the normed rows in ``state.hidden``. Composes with
 ``causal``, ``unpad``, ``rotary``, both dropouts and all three model classes; with ``fp8`` it is rejected. Not built:
-post-norm RMSNorm, RMSNorm for ``emb_ln`` / ``mlm_ln``, gated FFNs, the norm fused into a GEMM prologue.
+post-norm RMSNorm, RMSNorm for ``emb_ln`` / ``mlm_ln``, the norm fused into a GEMM prologue.
 
 Grouped-query attention (``BertConfig.kv_heads``, default None = ``heads``): ``Hkv = kv_heads`` key/value heads, each
 shared by the ``G = heads / Hkv`` query heads ``hkv * G .. hkv * G + G - 1`` (query head h reads KV head ``h // G``);
@@ -112,6 +112,18 @@ behind them (``C.gqa_reduce``); the key/value cache is ``[2, B, Hkv, Smax, 64]``
 ``C.attn_decode_gqa``, which streams every cached row once for its whole group. Composes with ``rotary``, ``pre_ln`` /
 ``rmsnorm``, ``unpad`` and both dropouts; with ``fp8`` it is rejected. Not built: ``h // G`` indexing inside the
 flash kernels, the rotation fused into expand / reduce, paged caches.
+
+SwiGLU feed-forward (``BertConfig.ffn = "swiglu"``, default ``"gelu"``): ``layers.N.ffn1`` becomes
+``nn.Linear(h, 2 * intermediate)`` whose output columns ``[0, F)`` are the gate ``g`` and ``[F, 2F)`` the up-projection
+``u`` (``F = intermediate``), the block computes ``ffn2(bf16((g * s) * u))`` with ``s = 1 / (1 + exp(-g))`` (ops/swiglu.py
+has the definition, its gradient and the rounding points), and no other parameter changes; with ``"gelu"`` nothing
+changes at all. Training and prefill run FFN1 with the plain bias epilogue, then the streaming kernel ``C.swiglu_fwd``;
+the backward's ``C.swiglu_bwd`` writes dg | du and FFN1's bias gradient in one pass. A decode step runs FFN1 and the
+gate as ONE launch, ``C.gemm_skinny_glu`` (two weight streams of the one [2F, h] weight, the activation in the
+epilogue), bit for bit the unfused pair (``MLT_DECODE_GLU=0``). Parameter parity with a GELU FFN of width 4h needs
+``intermediate = 8h / 3`` (2048 for ``bert-base``). Composes with ``rotary``, ``pre_ln`` / ``rmsnorm``, ``kv_heads``,
+``unpad`` and both dropouts and with all three model classes; with ``fp8`` it is rejected. Not built: the gate fused
+into the FFN1 tile-GEMM epilogue (interleaved gate / up weight rows), GeGLU / ReGLU, recomputing ``a`` in the backward.
 """
 from __future__ import annotations
 
@@ -148,6 +160,7 @@ class BertConfig:
     pre_ln: bool = False  # pre-norm blocks h + f(norm(h)) and a final norm (final_ln); not with fp8
     norm: str = "layernorm"  # the kind of ln1 / ln2 / final_ln: "layernorm", or "rmsnorm" (needs pre_ln)
     kv_heads: Optional[int] = None  # grouped-query attention: key/value heads (a divisor of heads); None = heads
+    ffn: str = "gelu"  # the feed-forward: "gelu", or "swiglu" (ffn1 is [2 * intermediate, hidden]); not with fp8
 
     @property
     def num_kv_heads(self) -> int:
@@ -202,7 +215,7 @@ class BertLayer(nn.Module):
         self.qkv = nn.Linear(h, h + 2 * c.num_kv_heads * (h // c.heads))  # 3 h, or compact under kv_heads
         self.out = nn.Linear(h, h)
         self.ln1 = block_norm(c)
-        self.ffn1 = nn.Linear(h, c.intermediate)
+        self.ffn1 = nn.Linear(h, (2 if c.ffn == "swiglu" else 1) * c.intermediate)  # swiglu: gate rows | up rows
         self.ffn2 = nn.Linear(c.intermediate, h)
         self.ln2 = block_norm(c)
 
@@ -222,7 +235,7 @@ class BertLayer(nn.Module):
         if drop is not None:
             drop = (drop[0], drop[1], drop[2] + 1, drop[3])
         return T.ffn_ln_block(x, self.ffn1.weight, self.ffn1.bias, self.ffn2.weight, self.ffn2.bias, self.ln2.weight,
-                              self.ln2.bias, self.c.ln_eps, impl, drop)
+                              self.ln2.bias, self.c.ln_eps, impl, drop, self.c.ffn)
 
     def forward_native_pre(self, h, n, next_norm, lens, B, S, drop=None, attn_drop=None, cu_seqlens=None, rope=None):
         """The pre-norm layer on the native kernels: (h, n = ln1(h)) -> (h', n' = next_norm(h')), where
@@ -235,7 +248,16 @@ class BertLayer(nn.Module):
         if drop is not None:
             drop = (drop[0], drop[1], drop[2] + 1, drop[3])
         return T.pre_ffn_block(h, n, self.ffn1.weight, self.ffn1.bias, self.ffn2.weight, self.ffn2.bias,
-                               next_norm.weight, next_norm.bias, eps, T.BF16, drop)
+                               next_norm.weight, next_norm.bias, eps, T.BF16, drop, self.c.ffn)
+
+    def ffn_torch(self, x, round_bf16=False):
+        """``ffn2(act(ffn1(x)))`` in plain torch: GELU, or the SwiGLU of ops/swiglu.py on ffn1's gate | up columns.
+        ``round_bf16`` (the eager bf16 baseline): h1 and a rounded to bf16, as the native path stores them."""
+        h1 = self.ffn1(x)
+        if self.c.ffn != "swiglu":
+            return self.ffn2(F.gelu(h1))
+        from ml_trainer_amd.ops.swiglu import swiglu
+        return self.ffn2(swiglu(h1.to(torch.bfloat16) if round_bf16 else h1))
 
     def forward_reference(self, x, mask, B, S, drop=None, attn_drop=None, packed=None, rope=None):
         """fp32 torch reference. x [B*S, h]; mask [B, S] bool (True = valid key); drop and attn_drop
@@ -284,7 +306,7 @@ class BertLayer(nn.Module):
         if drop is not None:
             a = D.apply(a, *drop)
         x = a + res if c.pre_ln else self.ln1(a + x)
-        f = self.ffn2(F.gelu(self.ffn1(self.ln2(x) if c.pre_ln else x)))
+        f = self.ffn_torch(self.ln2(x) if c.pre_ln else x)
         if drop is not None:
             f = D.apply(f, drop[0], drop[1], drop[2] + 1, drop[3])
         return f + x if c.pre_ln else self.ln2(f + x)
@@ -319,6 +341,10 @@ class BertClassifier(nn.Module):
         if (c.pre_ln or c.norm != "layernorm") and c.fp8:
             raise ValueError("pre_ln=True / norm='rmsnorm' with fp8=True is not supported: the pre-norm blocks run "
                              "the bf16 linears only")
+        if c.ffn not in ("gelu", "swiglu"):
+            raise ValueError(f"ffn must be 'gelu' or 'swiglu', got {c.ffn!r}")
+        if c.ffn == "swiglu" and c.fp8:
+            raise ValueError("ffn='swiglu' with fp8=True is not supported: the fp8 FFN fusions are GELU epilogues")
         from ml_trainer_amd.ops.gqa import check_kv_heads
         if check_kv_heads(c.heads, c.kv_heads) != c.heads and c.fp8:
             raise ValueError("kv_heads < heads with fp8=True is not supported: the fp8 attention backward writes dQKV "
@@ -613,10 +639,10 @@ class BertClassifier(nn.Module):
                     ctx = ctx.reshape(B * S, -1).index_select(0, pk.index)[None]
                 if c.pre_ln:
                     x = (dropped(L.out(ctx), 1 + 2 * l) + x).to(torch.bfloat16)
-                    x = (dropped(L.ffn2(F.gelu(L.ffn1(L.ln2(x)))), 2 + 2 * l) + x).to(torch.bfloat16)
+                    x = (dropped(L.ffn_torch(L.ln2(x), True), 2 + 2 * l) + x).to(torch.bfloat16)
                     continue
                 x = L.ln1(dropped(L.out(ctx), 1 + 2 * l) + x)
-                x = L.ln2(dropped(L.ffn2(F.gelu(L.ffn1(x))), 2 + 2 * l) + x)
+                x = L.ln2(dropped(L.ffn_torch(x, True), 2 + 2 * l) + x)
             return self._final_norm(x), pk
 
     def num_parameters(self) -> int:
@@ -626,6 +652,8 @@ class BertClassifier(nn.Module):
         """Training FLOPs per token (fwd + bwd = 3x fwd) of the encoder stack."""
         c = self.config
         h, f = c.hidden, c.intermediate
+        if c.ffn == "swiglu":
+            f = 3 * f // 2  # three h x f matrices instead of two
         per_layer = 2 * (3 * h * h + h * h + 2 * h * f) + 2 * 2 * seq_len * h  # linears + QK^T / PV
         return 3.0 * c.layers * per_layer
 
@@ -835,14 +863,14 @@ class BertLMHeadModel(BertForMaskedLM):
                                                     kv_heads=c.kv_heads)
                     DC.fill_from_prefill(cache, l, qkv, lens, B, S, heads=c.heads)
                     n, _ = T._norm_fwd(x, *_norm_args(L.ln2))
-                    x, _ = T._ffn_fwd(n, L.ffn1.weight, L.ffn1.bias, L.ffn2.weight, L.ffn2.bias, res=x)
+                    x, _ = T._ffn_fwd(n, L.ffn1.weight, L.ffn1.bias, L.ffn2.weight, L.ffn2.bias, res=x, act=c.ffn)
                     continue
                 a, (_, qkv, _, _) = T._attn_fwd(x, L.qkv.weight, L.qkv.bias, L.out.weight, L.out.bias, lens, B, S,
                                                 c.heads, causal=True, rope=self._rope(), kv_heads=c.kv_heads)
                 # (qkv: rotated under rotary, the wide buffer under kv_heads)
                 DC.fill_from_prefill(cache, l, qkv, lens, B, S, heads=c.heads)
                 x, _ = T._ln_fwd(a, L.ln1.weight, L.ln1.bias, c.ln_eps)
-                f, _ = T._ffn_fwd(x, L.ffn1.weight, L.ffn1.bias, L.ffn2.weight, L.ffn2.bias)
+                f, _ = T._ffn_fwd(x, L.ffn1.weight, L.ffn1.bias, L.ffn2.weight, L.ffn2.bias, act=c.ffn)
                 x, _ = T._ln_fwd(f, L.ln2.weight, L.ln2.bias, c.ln_eps)
         else:
             pos = torch.arange(S, device=dev)
@@ -879,6 +907,16 @@ class BertLMHeadModel(BertForMaskedLM):
             return M.decode_logits(state.hidden, self.mlm_params())  # B rows, no gather into a 256-row tile
         return self.mlm_logits(state.hidden, torch.arange(B, device=state.hidden.device))
 
+    def _ffn1_decode(self, L, x):
+        """act(ffn1(x)) [B, F] bf16 of a native decode step: FFN1 with the GELU epilogue, or under SwiGLU the gated
+        skinny GEMM (``ops.decode.linear_small_glu``)."""
+        from ml_trainer_amd.ops import decode as DC
+        from ml_trainer_amd.ops.transformer import bf16_weight
+        if self.config.ffn == "swiglu":
+            return DC.linear_small_glu(x, bf16_weight(L.ffn1.weight), L.ffn1.bias)
+        pre = torch.empty(x.shape[0], L.ffn1.weight.shape[0], dtype=torch.bfloat16, device=x.device)
+        return DC.linear_small(x, bf16_weight(L.ffn1.weight), L.ffn1.bias, gelu_aux=pre)
+
     @torch.no_grad()
     def decode_step(self, state, token_ids=None):
         """fp32 logits [B, V] of the next token. Without ``token_ids``: those of the prompt's last token, nothing
@@ -911,17 +949,13 @@ class BertLMHeadModel(BertForMaskedLM):
                     ctx = DC.attn_decode(qkv, cache.kv[l], cache.pos, c.heads, rope=self.rope_table)
                     x = DC.linear_small(ctx, T.bf16_weight(L.out.weight), L.out.bias, res=x)
                     n, _ = T._norm_fwd(x, *_norm_args(L.ln2))
-                    pre = torch.empty(B, L.ffn1.weight.shape[0], dtype=torch.bfloat16, device=x.device)
-                    g = DC.linear_small(n, T.bf16_weight(L.ffn1.weight), L.ffn1.bias, gelu_aux=pre)
-                    x = DC.linear_small(g, T.bf16_weight(L.ffn2.weight), L.ffn2.bias, res=x)
+                    x = DC.linear_small(self._ffn1_decode(L, n), T.bf16_weight(L.ffn2.weight), L.ffn2.bias, res=x)
                     continue
                 qkv = DC.linear_small(x, T.bf16_weight(L.qkv.weight), L.qkv.bias)
                 ctx = DC.attn_decode(qkv, cache.kv[l], cache.pos, c.heads, rope=self.rope_table)
                 a = DC.linear_small(ctx, T.bf16_weight(L.out.weight), L.out.bias, res=x)
                 x, _ = T._ln_fwd(a, L.ln1.weight, L.ln1.bias, c.ln_eps)
-                pre = torch.empty(B, L.ffn1.weight.shape[0], dtype=torch.bfloat16, device=x.device)
-                g = DC.linear_small(x, T.bf16_weight(L.ffn1.weight), L.ffn1.bias, gelu_aux=pre)
-                f = DC.linear_small(g, T.bf16_weight(L.ffn2.weight), L.ffn2.bias, res=x)
+                f = DC.linear_small(self._ffn1_decode(L, x), T.bf16_weight(L.ffn2.weight), L.ffn2.bias, res=x)
                 x, _ = T._ln_fwd(f, L.ln2.weight, L.ln2.bias, c.ln_eps)
             if c.pre_ln:  # state.hidden holds the normed rows, as after a post-LN layer
                 x, _ = T._norm_fwd(x, *_norm_args(self.final_ln))
@@ -932,11 +966,11 @@ class BertLMHeadModel(BertForMaskedLM):
                     ctx = DC.attn_decode_reference(L.qkv(L.ln1(x)), cache.kv[l], cache.pos, c.heads,
                                                    rope=self.rope_table)
                     x = L.out(ctx) + x
-                    x = L.ffn2(F.gelu(L.ffn1(L.ln2(x)))) + x
+                    x = L.ffn_torch(L.ln2(x)) + x
                     continue
                 ctx = DC.attn_decode_reference(L.qkv(x), cache.kv[l], cache.pos, c.heads, rope=self.rope_table)
                 x = L.ln1(L.out(ctx) + x)
-                x = L.ln2(L.ffn2(F.gelu(L.ffn1(x))) + x)
+                x = L.ln2(L.ffn_torch(x) + x)
             x = self._final_norm(x)
         cache.pos.add_(1)
         state.hidden = x
@@ -1039,7 +1073,8 @@ class BertLMHeadModel(BertForMaskedLM):
         ``bf16_weight`` / ``padded_decoder`` hand out new tensors), a re-allocation moves ``data_ptr``."""
         c = self.config  # (the block kind decides which kernels a step launches)
         gqa = (c.kv_heads,) if c.num_kv_heads != c.heads else ()  # (the attention launch and the cache shape)
-        return (c.pre_ln, c.norm) + gqa + tuple((p._version, p.data_ptr()) for p in self.parameters())
+        ffn = (c.ffn,) if c.ffn != "gelu" else ()  # (which FFN1 launch a step makes)
+        return (c.pre_ln, c.norm) + gqa + ffn + tuple((p._version, p.data_ptr()) for p in self.parameters())
 
     def _graphed_decoder(self, B, Smax, T, dev):
         key = (B, Smax, T, str(dev))

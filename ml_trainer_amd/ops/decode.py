@@ -13,6 +13,7 @@ per layer per prompt, not a hot path.
 ``linear_small`` is the linear layer of a decode step (M = B rows): ``decode_linear_path`` sends it to the
 weight-streaming kernel ``C.gemm_skinny`` (csrc/kernels/gemm_skinny.hip) or to the planner's GEMM. With the skinny
 kernel every kernel of a step works row by row, so a sequence's logits do not depend on the batch it is decoded in.
+``linear_small_glu`` is the gated FFN1 of a SwiGLU model's step: ``C.gemm_skinny_glu``, or the unfused pair.
 
 ``sample_step`` is the on-device sampler (csrc/kernels/sample.hip): greedy / temperature / top-k / top-p and the
 token / EOS bookkeeping of ``generate`` in one launch per step, over a ``SamplerState``. Its result is defined in
@@ -174,6 +175,25 @@ def linear_small(x, w16, bias=None, gelu_aux=None, res=None, out=None):
     require_native().gemm(x, w16, out, False, False, bias=bias, aux=gelu_aux, res=res,
                           mode=1 if gelu_aux is not None else 0)
     return out
+
+
+def linear_small_glu(x, w16, bias=None):
+    """The gated FFN1 of a SwiGLU decode step: ``swiglu(x . w16^T + bias)`` [M, F] for x [M, K] bf16 and w16 [2F, K]
+    bf16 (gate rows, then up rows: ops/swiglu.py), fp32 ``bias`` [2F]. Where ``decode_linear_path(M, F, K)`` says
+    ``"skinny"`` it is ONE launch, ``C.gemm_skinny_glu`` (two weight streams, the activation in the epilogue);
+    otherwise, and with ``MLT_DECODE_GLU=0`` (read per call: the A/B baseline), ``linear_small`` into the [M, 2F]
+    intermediate followed by ``swiglu_fwd``. The two agree bit for bit. On the CPU: ``F.linear`` and the torch
+    definition."""
+    from ml_trainer_amd.ops import swiglu as SG
+    M, K = x.shape
+    Fh = w16.shape[0] // 2
+    if not x.is_cuda:
+        return SG.swiglu_reference(F.linear(x.float(), w16.float(), None if bias is None else bias.float()))
+    if os.environ.get("MLT_DECODE_GLU", "1") != "0" and decode_linear_path(M, Fh, K) == "skinny":
+        out = torch.empty(M, Fh, dtype=torch.bfloat16, device=x.device)
+        require_native().gemm_skinny_glu(x, w16, out, bias=bias)
+        return out
+    return SG.swiglu_fwd(linear_small(x, w16, bias))
 
 
 def fill_from_prefill(cache: KVCache, layer: int, qkv, lens: Optional[torch.Tensor], B: int, S: int,

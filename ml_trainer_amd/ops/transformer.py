@@ -13,7 +13,9 @@ Blocks (one autograd node each, so the backward can fuse across ops):
   gradient folded into the GEMM epilogue.
 * ``ffn_block``: x -> FFN1 GEMM (+bias, GELU epilogue that also stores the
   pre-activation) -> FFN2 GEMM (+bias +residual). Backward: FFN2's dgrad GEMM
-  applies gelu'(pre) in its epilogue (no separate elementwise pass).
+  applies gelu'(pre) in its epilogue (no separate elementwise pass). With ``act="swiglu"`` (every FFN block):
+  FFN1 [2F, h] with the plain bias epilogue -> ``swiglu_fwd`` -> FFN2; backward FFN2 wgrad, plain dgrad,
+  ``swiglu_bwd`` (dh1 and FFN1's bias gradient), FFN1 wgrad and dgrad (ops/swiglu.py, csrc/kernels/swiglu.hip).
 * ``attention_ln_block`` / ``ffn_ln_block``: the block followed by its post-LayerNorm as one
   node; the LayerNorm backward kernel also produces the column sums of its dx, which are the
   bias gradient of the block's last linear layer (no separate pass over dy). With ``drop`` they
@@ -53,6 +55,7 @@ import torch
 
 from ml_trainer_amd.ops._ext import require_native
 from ml_trainer_amd.ops.gqa import gqa_expand, gqa_reduce, infer_kv_heads
+from ml_trainer_amd.ops.swiglu import swiglu_bwd, swiglu_fwd
 from ml_trainer_amd.utils.flat import FlatParams
 
 
@@ -355,7 +358,22 @@ def _attn_bwd(saved, params, lens, B, S, H, dy, G, dbo="colsum", impl=BF16, dres
     return dx, dwqkv, dbqkv, dwo, dbo
 
 
-def _ffn_fwd(x, w1, b1, w2, b2, impl=BF16, residual=True, res=None):
+def _check_act(act, impl):
+    if act not in ("gelu", "swiglu"):
+        raise ValueError(f"act must be 'gelu' or 'swiglu', got {act!r}")
+    if act == "swiglu" and impl is not BF16:
+        raise ValueError("the SwiGLU feed-forward runs the bf16 linears only: the fp8 FFN fusions are GELU epilogues")
+
+
+def _ffn_fwd(x, w1, b1, w2, b2, impl=BF16, residual=True, res=None, act="gelu"):
+    """``act="swiglu"``: ``w1`` is [2F, h] (gate rows, then up rows); FFN1 runs with the plain bias epilogue into
+    ``h1`` [rows, 2F], ``swiglu_fwd`` (ops/swiglu.py) makes ``a`` [rows, F], FFN2 as ever. Saves (x, h1, a)."""
+    _check_act(act, impl)
+    if act == "swiglu":
+        h1 = impl.fwd(x, w1, b1)
+        a = swiglu_fwd(h1)
+        y = impl.fwd(a, w2, b2, res=(x if res is None else res) if residual else None)
+        return y, (x, h1, a)
     pre = torch.empty(x.shape[0], w1.shape[0], dtype=torch.bfloat16, device=x.device)
     # fp8: FFN1's epilogue may emit FFN2's quantised input directly (Fp8Linear.fwd_gelu_q)
     a = impl.fwd_gelu_q(x, w1, b1, pre, w2) if hasattr(impl, "fwd_gelu_q") else None
@@ -365,15 +383,25 @@ def _ffn_fwd(x, w1, b1, w2, b2, impl=BF16, residual=True, res=None):
     return y, (x, pre, a)
 
 
-def _ffn_bwd(saved, params, dy, G, db2="colsum", impl=BF16, dres=None, residual=True):
+def _ffn_bwd(saved, params, dy, G, db2="colsum", impl=BF16, dres=None, residual=True, act="gelu"):
     """``dres``: the residual branch's gradient when hidden dropout separates it from FFN2's ``dy``.
-    ``residual=False`` (pre-norm blocks): FFN1's dgrad adds no residual gradient."""
+    ``residual=False`` (pre-norm blocks): FFN1's dgrad adds no residual gradient. ``act="swiglu"``: FFN2's plain
+    dgrad gives ``da``, ``swiglu_bwd`` gives dh1 = dg | du and FFN1's bias gradient (the column sums of the rounded
+    dh1, set or accumulated into the flat-gradient sink), then FFN1's wgrad and dgrad as the GELU branch ends."""
+    _check_act(act, impl)
     x, pre, a = saved
     w1, b1, w2, b2 = params
     dres = (dy if dres is None else dres) if residual else None
     dw2 = G.wgrad(w2, dy, a, impl)
     if isinstance(db2, str):
         db2 = G.colsum(b2, dy)
+    if act == "swiglu":
+        da = impl.dgrad(dy, w2, torch.empty_like(a))
+        db, db_acc, db1 = G.out(b1, w1.shape[0], dy.device)
+        dh1 = swiglu_bwd(da, pre, db, db_acc)
+        dw1 = G.wgrad(w1, dh1, x, impl)
+        dx = impl.dgrad(dh1, w1, torch.empty_like(x), res=dres)
+        return dx, dw1, db1, dw2, db2
     if a.dtype == torch.float8_e4m3fn and impl.dgrad_gelu_q_ready(w1, x):
         # fp8 FFN fusion: FFN2's dgrad epilogue emits FFN1's e5m2 dY, dY^T and bias gradient
         db, db_acc, db1 = G.out(b1, w1.shape[0], dy.device)
@@ -543,18 +571,19 @@ class _AttentionBlock(torch.autograd.Function):
 
 class _FFNBlock(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, w1, b1, w2, b2, impl):
-        y, saved = _ffn_fwd(x, w1, b1, w2, b2, impl)
+    def forward(ctx, x, w1, b1, w2, b2, impl, act="gelu"):
+        y, saved = _ffn_fwd(x, w1, b1, w2, b2, impl, act=act)
         ctx.save_for_backward(*saved)
-        ctx.params, ctx.impl = (w1, b1, w2, b2), impl
+        ctx.params, ctx.impl, ctx.act = (w1, b1, w2, b2), impl, act
         return y
 
     @staticmethod
     def backward(ctx, dy):
         G = _Grads()
-        grads = _ffn_bwd(ctx.saved_tensors, ctx.params, dy.contiguous().to(torch.bfloat16), G, impl=ctx.impl)
+        grads = _ffn_bwd(ctx.saved_tensors, ctx.params, dy.contiguous().to(torch.bfloat16), G, impl=ctx.impl,
+                         act=ctx.act)
         G.done()
-        return grads + (None,)
+        return grads + (None, None)
 
 
 class _LayerNorm(torch.autograd.Function):
@@ -617,15 +646,15 @@ class _FFNLNBlock(torch.autograd.Function):
     """LN(ffn_block(x)) as one node (FFN2 bias gradient fused into the LayerNorm backward)."""
 
     @staticmethod
-    def forward(ctx, x, w1, b1, w2, b2, gamma, beta, eps, impl, drop=None):
+    def forward(ctx, x, w1, b1, w2, b2, gamma, beta, eps, impl, drop=None, act="gelu"):
         if drop is None:
-            f, s1 = _ffn_fwd(x, w1, b1, w2, b2, impl)
+            f, s1 = _ffn_fwd(x, w1, b1, w2, b2, impl, act=act)
             y, s2 = _ln_fwd(f, gamma, beta, eps)
         else:  # LN(dropout(FFN2) + x)
-            f, s1 = _ffn_fwd(x, w1, b1, w2, b2, impl, residual=False)
+            f, s1 = _ffn_fwd(x, w1, b1, w2, b2, impl, residual=False, act=act)
             y, s2 = _dropout_add_ln_fwd(f, x, gamma, beta, eps, drop)
         ctx.save_for_backward(*s1, *s2)
-        ctx.params, ctx.beta, ctx.impl, ctx.drop = (w1, b1, w2, b2), beta, impl, drop
+        ctx.params, ctx.beta, ctx.impl, ctx.drop, ctx.act = (w1, b1, w2, b2), beta, impl, drop, act
         return y
 
     @staticmethod
@@ -639,9 +668,9 @@ class _FFNLNBlock(torch.autograd.Function):
         else:
             dres, dg, db, db2, df = _ln_bwd(t[3:], ctx.beta, dy.contiguous().to(torch.bfloat16), G,
                                             dxsum_param=ctx.params[3], drop=ctx.drop)
-        dx, dw1, db1, dw2, db2 = _ffn_bwd(t[:3], ctx.params, df, G, db2=db2, impl=ctx.impl, dres=dres)
+        dx, dw1, db1, dw2, db2 = _ffn_bwd(t[:3], ctx.params, df, G, db2=db2, impl=ctx.impl, dres=dres, act=ctx.act)
         G.done()
-        return dx, dw1, db1, dw2, db2, dg, db, None, None, None
+        return dx, dw1, db1, dw2, db2, dg, db, None, None, None, None
 
 
 def _bf16_grad(g):
@@ -722,16 +751,16 @@ class _PreFFNBlock(torch.autograd.Function):
     """The pre-norm FFN sub-layer (h, n) -> (h', n'), see _PreAttentionBlock."""
 
     @staticmethod
-    def forward(ctx, h, n, w1, b1, w2, b2, gamma, beta, eps, impl, drop=None):
+    def forward(ctx, h, n, w1, b1, w2, b2, gamma, beta, eps, impl, drop=None, act="gelu"):
         if drop is None:
-            h2, s1 = _ffn_fwd(n, w1, b1, w2, b2, impl, res=h)
+            h2, s1 = _ffn_fwd(n, w1, b1, w2, b2, impl, res=h, act=act)
             n2, s2 = _norm_fwd(h2, gamma, beta, eps)
         else:
-            f, s1 = _ffn_fwd(n, w1, b1, w2, b2, impl, residual=False)
+            f, s1 = _ffn_fwd(n, w1, b1, w2, b2, impl, residual=False, act=act)
             n2, s2 = _dropout_add_norm_fwd(f, h, gamma, beta, eps, drop)
             h2 = s2[0]
         ctx.save_for_backward(*s1, *s2)
-        ctx.params, ctx.beta, ctx.impl, ctx.drop = (w1, b1, w2, b2), beta, impl, drop
+        ctx.params, ctx.beta, ctx.impl, ctx.drop, ctx.act = (w1, b1, w2, b2), beta, impl, drop, act
         ctx.set_materialize_grads(False)
         return h2, n2
 
@@ -743,9 +772,10 @@ class _PreFFNBlock(torch.autograd.Function):
         dh, dg, db, db2, dxm = _norm_bwd(t[3:], ctx.beta, dn2, G, dxsum_param=ctx.params[3], drop=ctx.drop,
                                          dres=_bf16_grad(dh2))
         df = dh if ctx.drop is None else dxm
-        dn, dw1, db1, dw2, db2 = _ffn_bwd(t[:3], ctx.params, df, G, db2=db2, impl=ctx.impl, residual=False)
+        dn, dw1, db1, dw2, db2 = _ffn_bwd(t[:3], ctx.params, df, G, db2=db2, impl=ctx.impl, residual=False,
+                                          act=ctx.act)
         G.done()
-        return (dh, dn, dw1, db1, dw2, db2, dg, db) + (None,) * 3
+        return (dh, dn, dw1, db1, dw2, db2, dg, db) + (None,) * 4
 
 
 class _Embeddings(torch.autograd.Function):
@@ -866,9 +896,11 @@ def attention_block(x, wqkv, bqkv, wo, bo, lens: Optional[torch.Tensor], B: int,
     return _AttentionBlock.apply(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl, attn_drop, cu_seqlens, causal, rope)
 
 
-def ffn_block(x, w1, b1, w2, b2, impl=BF16):
+def ffn_block(x, w1, b1, w2, b2, impl=BF16, act: str = "gelu"):
+    """``act``: ``"gelu"``, or ``"swiglu"`` (``w1`` [2F, h], ``b1`` [2F]: gate rows, then up rows; ops/swiglu.py;
+    bf16 linears only)."""
     _mark_training(impl)
-    return _FFNBlock.apply(x, w1, b1, w2, b2, impl)
+    return _FFNBlock.apply(x, w1, b1, w2, b2, impl, act)
 
 
 def attention_ln_block(x, wqkv, bqkv, wo, bo, gamma, beta, lens: Optional[torch.Tensor], B: int, S: int, H: int,
@@ -884,10 +916,11 @@ def attention_ln_block(x, wqkv, bqkv, wo, bo, gamma, beta, lens: Optional[torch.
                                    cu_seqlens, causal, rope)
 
 
-def ffn_ln_block(x, w1, b1, w2, b2, gamma, beta, eps: float, impl=BF16, drop=None):
-    """``drop`` = (p, seed, site, rank): hidden dropout on FFN2's output (see attention_ln_block)."""
+def ffn_ln_block(x, w1, b1, w2, b2, gamma, beta, eps: float, impl=BF16, drop=None, act: str = "gelu"):
+    """``drop`` = (p, seed, site, rank): hidden dropout on FFN2's output (see attention_ln_block). ``act``: see
+    ffn_block."""
     _mark_training(impl)
-    return _FFNLNBlock.apply(x, w1, b1, w2, b2, gamma, beta, eps, impl, drop)
+    return _FFNLNBlock.apply(x, w1, b1, w2, b2, gamma, beta, eps, impl, drop, act)
 
 
 def layer_norm(x, gamma, beta, eps: float):
@@ -917,11 +950,11 @@ def pre_attention_block(h, n, wqkv, bqkv, wo, bo, gamma, beta, lens: Optional[to
                                     cu_seqlens, causal, rope)
 
 
-def pre_ffn_block(h, n, w1, b1, w2, b2, gamma, beta, eps: float, impl=BF16, drop=None):
+def pre_ffn_block(h, n, w1, b1, w2, b2, gamma, beta, eps: float, impl=BF16, drop=None, act: str = "gelu"):
     """The pre-norm FFN sub-layer: (h, n) -> (h + drop(FFN2(gelu(FFN1(n)))), Norm(that sum)); ``gamma`` / ``beta``
-    belong to the next layer's ``ln1``, or to the final norm after the last layer."""
+    belong to the next layer's ``ln1``, or to the final norm after the last layer. ``act``: see ffn_block."""
     _pre_norm_impl(impl)
-    return _PreFFNBlock.apply(h, n, w1, b1, w2, b2, gamma, beta, eps, impl, drop)
+    return _PreFFNBlock.apply(h, n, w1, b1, w2, b2, gamma, beta, eps, impl, drop, act)
 
 
 class _Dropout(torch.autograd.Function):
