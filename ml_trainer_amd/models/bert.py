@@ -135,6 +135,8 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
+from ml_trainer_amd.ops.transformer import AttnSpec, _norm_fwd
+
 
 @dataclass
 class BertConfig:
@@ -207,6 +209,79 @@ def _norm_args(m):
     return m.weight, m.bias, m.eps
 
 
+def _norm_native(x, m):
+    """The norm module ``m`` of bf16 rows ``x`` on its native forward kernel, nothing kept for a backward."""
+    return _norm_fwd(x, m.weight, m.bias, m.eps)[0]
+
+
+def _fp8_exclusions(c: BertConfig):
+    """(the switch is on, the refusal) for everything that runs the bf16 linears only."""
+    return (
+        (c.unpad, "unpad=True with fp8=True is not supported: the fp8 attention epilogue writes 16-row transposed "
+                  "runs at b * S offsets and cannot take packed row offsets"),
+        (c.causal, "causal=True with fp8=True is not supported: the fp8 (q8) attention epilogue has no causal "
+                   "instantiation"),
+        (c.rotary, "rotary=True with fp8=True is not supported: the fp8 attention backward writes dQKV as e5m2, "
+                   "which the inverse rotation cannot take"),
+        (c.pre_ln or c.norm != "layernorm", "pre_ln=True / norm='rmsnorm' with fp8=True is not supported: the "
+                                            "pre-norm blocks run the bf16 linears only"),
+        (c.ffn == "swiglu", "ffn='swiglu' with fp8=True is not supported: the fp8 FFN fusions are GELU epilogues"),
+        (c.num_kv_heads != c.heads, "kv_heads < heads with fp8=True is not supported: the fp8 attention backward "
+                                    "writes dQKV as e5m2 in the wide layout, which the group reduction cannot take"),
+    )
+
+
+def _sites(l: int):
+    """The dropout sites of layer ``l`` (ops/dropout.py): hidden dropout of its attention and of its FFN sub-layer,
+    and its attention probabilities. Site 0 is the embedding output."""
+    from ml_trainer_amd.ops.dropout import attention_site
+    return 1 + 2 * l, 2 + 2 * l, attention_site(l)
+
+
+@dataclass
+class _Batch:
+    """What the encoder needs to know of its input, padded or packed. Padded: ``ids`` / ``tt`` (or None) [B, S],
+    ``pos`` and ``cu`` None, rows are b * S + s. Packed (``packed``, the ``PackedBatch``): ``ids`` / ``tt`` / ``pos``
+    [rows], ``cu`` = cu_seqlens, ``S`` = max_seqlen. ``lens`` [B] or None either way."""
+    ids: torch.Tensor
+    tt: Optional[torch.Tensor]
+    lens: Optional[torch.Tensor]
+    B: int
+    S: int
+    pos: Optional[torch.Tensor] = None
+    cu: Optional[torch.Tensor] = None
+    packed: object = None
+
+    @classmethod
+    def of(cls, input_ids, lens, token_type_ids, pk=None):
+        B, S = input_ids.shape
+        if pk is None:
+            return cls(input_ids, token_type_ids, lens, B, S)
+        return cls(pk.ids, pk.tt, lens, B, S, pk.pos, pk.cu_seqlens, pk)
+
+    def attn_spec(self, c: BertConfig, rope_table, attn_drop=None):
+        """The ``AttnSpec`` of a layer of the model ``c`` on this batch (a packed batch has no use for ``lens``)."""
+        return AttnSpec(self.B, self.S, c.heads, self.lens if self.cu is None else None, self.cu, c.causal,
+                        (rope_table, self.pos) if c.rotary else None, attn_drop, c.kv_heads)
+
+    def key_mask(self, device):
+        """[B, S] bool, True = a real key; None without lengths."""
+        if self.lens is None:
+            return None
+        lens = self.lens.to(device)
+        if self.packed is not None:
+            lens = lens.clamp(1, self.S)
+        return torch.arange(self.S, device=device)[None, :] < lens[:, None]
+
+    def cls_rows(self, x):
+        """The CLS rows [B, h] of hidden states ``x`` [rows, h]; for a padded batch a strided view."""
+        return x.view(self.B, self.S, -1)[:, 0] if self.packed is None else x.index_select(0, self.packed.cls_rows)
+
+    def last_batch(self):
+        """(B, S, lens, cu_seqlens) as the MLM head takes them: ``lens`` only without ``cu_seqlens``."""
+        return self.B, self.S, self.lens if self.cu is None else None, self.cu
+
+
 class BertLayer(nn.Module):
     def __init__(self, c: BertConfig):
         super().__init__()
@@ -219,36 +294,31 @@ class BertLayer(nn.Module):
         self.ffn2 = nn.Linear(c.intermediate, h)
         self.ln2 = block_norm(c)
 
-    def forward_native(self, x, lens, B, S, drop=None, attn_drop=None, cu_seqlens=None, rope=None):
-        """``drop`` = (p, seed, site of the attention sub-layer, rank); the FFN takes the next site.
-        ``attn_drop`` = (p, seed, attention site of this layer, rank): attention-probability dropout.
-        ``cu_seqlens``: x is a packed [T, h] batch (S = max_seqlen, lens unused).
-        ``rope`` = (table, pos or None): rotary positions (``ops.transformer.attention_block``)."""
+    def attn_params(self):
+        return self.qkv.weight, self.qkv.bias, self.out.weight, self.out.bias
+
+    def ffn_params(self):
+        return self.ffn1.weight, self.ffn1.bias, self.ffn2.weight, self.ffn2.bias
+
+    def forward_native(self, x, n, spec, closing, drops=(None, None)):
+        """The layer on the native kernels, attention then FFN sub-layer, each one block node of
+        ``ops.transformer``. Post-LN: ``x -> closing(core(x) + x)``, ``n`` is None and stays so. Pre-norm: ``x`` is
+        the residual stream and ``n`` its norm, ``(x, n) -> (x + core(n), closing(that sum))``. ``closing``: the two
+        norm modules that close the sub-layers: the layer's own ``(ln1, ln2)`` for post-LN; ``ln2`` and the next
+        layer's ``ln1`` (the model's ``final_ln`` after the last layer) for pre-norm. ``spec``: the layer's
+        ``AttnSpec``. ``drops``: hidden dropout (p, seed, site, rank) of the two sub-layers. Returns ``(x, n)``."""
         from ml_trainer_amd.ops import transformer as T
         if self.c.fp8:
             from ml_trainer_amd.ops.fp8 import FP8 as impl
         else:
             impl = T.BF16
-        x = T.attention_ln_block(x, self.qkv.weight, self.qkv.bias, self.out.weight, self.out.bias, self.ln1.weight,
-                                 self.ln1.bias, lens, B, S, self.c.heads, self.c.ln_eps, impl, drop, attn_drop,
-                                 cu_seqlens, self.c.causal, rope)
-        if drop is not None:
-            drop = (drop[0], drop[1], drop[2] + 1, drop[3])
-        return T.ffn_ln_block(x, self.ffn1.weight, self.ffn1.bias, self.ffn2.weight, self.ffn2.bias, self.ln2.weight,
-                              self.ln2.bias, self.c.ln_eps, impl, drop, self.c.ffn)
-
-    def forward_native_pre(self, h, n, next_norm, lens, B, S, drop=None, attn_drop=None, cu_seqlens=None, rope=None):
-        """The pre-norm layer on the native kernels: (h, n = ln1(h)) -> (h', n' = next_norm(h')), where
-        ``next_norm`` is the next layer's ``ln1`` or the model's ``final_ln``. Arguments as in forward_native."""
-        from ml_trainer_amd.ops import transformer as T
-        eps = self.c.ln_eps
-        h, n = T.pre_attention_block(h, n, self.qkv.weight, self.qkv.bias, self.out.weight, self.out.bias,
-                                     self.ln2.weight, self.ln2.bias, lens, B, S, self.c.heads, eps, T.BF16, drop,
-                                     attn_drop, cu_seqlens, self.c.causal, rope)
-        if drop is not None:
-            drop = (drop[0], drop[1], drop[2] + 1, drop[3])
-        return T.pre_ffn_block(h, n, self.ffn1.weight, self.ffn1.bias, self.ffn2.weight, self.ffn2.bias,
-                               next_norm.weight, next_norm.bias, eps, T.BF16, drop, self.c.ffn)
+        cores = ((T.attn_core(spec, impl), self.attn_params()), (T.ffn_core(self.c.ffn, impl), self.ffn_params()))
+        for (core, params), norm, drop in zip(cores, closing, drops):
+            if self.c.pre_ln:
+                x, n = T.pre_norm_block(core, x, n, params, _norm_args(norm), drop)
+            else:
+                x = T.post_norm_block(core, x, params, _norm_args(norm), drop)
+        return x, n
 
     def ffn_torch(self, x, round_bf16=False):
         """``ffn2(act(ffn1(x)))`` in plain torch: GELU, or the SwiGLU of ops/swiglu.py on ffn1's gate | up columns.
@@ -325,30 +395,17 @@ class BertClassifier(nn.Module):
         if c.attention_dropout > 0:
             from ml_trainer_amd.ops.dropout import attention_threshold
             attention_threshold(c.attention_dropout)  # a p that rounds to 0/256 (or 256/256) is an error
-        if c.unpad and c.fp8:
-            raise ValueError("unpad=True with fp8=True is not supported: the fp8 attention epilogue writes 16-row "
-                             "transposed runs at b * S offsets and cannot take packed row offsets")
-        if c.causal and c.fp8:
-            raise ValueError("causal=True with fp8=True is not supported: the fp8 (q8) attention epilogue has no "
-                             "causal instantiation")
-        if c.rotary and c.fp8:
-            raise ValueError("rotary=True with fp8=True is not supported: the fp8 attention backward writes dQKV as "
-                             "e5m2, which the inverse rotation cannot take")
         if c.norm not in ("layernorm", "rmsnorm"):
             raise ValueError(f"norm must be 'layernorm' or 'rmsnorm', got {c.norm!r}")
         if c.norm == "rmsnorm" and not c.pre_ln:
             raise ValueError("norm='rmsnorm' needs pre_ln=True: post-norm RMSNorm blocks are not built")
-        if (c.pre_ln or c.norm != "layernorm") and c.fp8:
-            raise ValueError("pre_ln=True / norm='rmsnorm' with fp8=True is not supported: the pre-norm blocks run "
-                             "the bf16 linears only")
         if c.ffn not in ("gelu", "swiglu"):
             raise ValueError(f"ffn must be 'gelu' or 'swiglu', got {c.ffn!r}")
-        if c.ffn == "swiglu" and c.fp8:
-            raise ValueError("ffn='swiglu' with fp8=True is not supported: the fp8 FFN fusions are GELU epilogues")
         from ml_trainer_amd.ops.gqa import check_kv_heads
-        if check_kv_heads(c.heads, c.kv_heads) != c.heads and c.fp8:
-            raise ValueError("kv_heads < heads with fp8=True is not supported: the fp8 attention backward writes dQKV "
-                             "as e5m2 in the wide layout, which the group reduction cannot take")
+        check_kv_heads(c.heads, c.kv_heads)
+        for on, message in _fp8_exclusions(c):
+            if on and c.fp8:
+                raise ValueError(message)
         self.config = c
         self.last_dropout_seed = None  # the seed of the last forward that dropped
         self.word_embeddings = nn.Embedding(c.vocab_size, c.hidden)
@@ -386,10 +443,6 @@ class BertClassifier(nn.Module):
         """The learned position table, or None under rotary positions (the embedding kernels then add none)."""
         return None if self.position_embeddings is None else self.position_embeddings.weight
 
-    def _rope(self, pos=None):
-        """The ``rope`` argument of the native attention blocks: (table, packed positions or None), or None."""
-        return (self.rope_table, pos) if self.config.rotary else None
-
     def _embed_torch(self, ids, tt, pos, per_batch=False):
         """word (+ learned position, ``pos`` indexing the table; ``per_batch``: one [S] row of positions for every
         sequence) + type in plain torch."""
@@ -402,18 +455,6 @@ class BertClassifier(nn.Module):
     def _final_norm(self, x):
         """``final_ln`` of a pre-norm model on the stream ``x`` in plain torch; the identity for post-LN."""
         return self.final_ln(x) if self.config.pre_ln else x
-
-    def _pre_stack_native(self, x, lens, B, S, drop, adrop, cu=None, rope=None):
-        """The pre-norm layers on the native kernels from the embedding output ``x`` (the first stream):
-        ``final_ln`` of the last stream, [rows, h] bf16."""
-        from ml_trainer_amd.ops import transformer as T
-        h, n = T.stream_norm(x, *_norm_args(self.layers[0].ln1))
-        last = len(self.layers) - 1
-        for l, layer in enumerate(self.layers):
-            nxt = self.final_ln if l == last else self.layers[l + 1].ln1
-            h, n = layer.forward_native_pre(h, n, nxt, lens, B, S, self._site(drop, 1 + 2 * l),
-                                            self._attn_site(adrop, l), cu, rope)
-        return n
 
     def _lengths(self, input_ids, attention_mask):
         B, S = input_ids.shape
@@ -444,9 +485,24 @@ class BertClassifier(nn.Module):
         return None if drop is None else (drop[0], drop[1], site, drop[2])
 
     @classmethod
-    def _attn_site(cls, adrop, l):
-        from ml_trainer_amd.ops.dropout import attention_site
-        return cls._site(adrop, attention_site(l))
+    def _layer_drops(cls, drop, adrop, l):
+        """(p, seed, site, rank) or None of layer ``l``'s three sites, in the order of ``_sites``."""
+        s_attn, s_ffn, s_prob = _sites(l)
+        return cls._site(drop, s_attn), cls._site(drop, s_ffn), cls._site(adrop, s_prob)
+
+    def _batch(self, input_ids, lens, token_type_ids, native=False) -> _Batch:
+        """The ``_Batch`` of this forward: packed when ``unpad`` is on and lengths are known (``native``: with the
+        row count rounded up to the GEMM tile), else padded."""
+        from ml_trainer_amd.ops.transformer import PACK_ROW_MULTIPLE
+        pk = self._pack(input_ids, lens, token_type_ids, PACK_ROW_MULTIPLE if native else 1)
+        return _Batch.of(input_ids, lens, token_type_ids, pk)
+
+    def _embed_batch_torch(self, bt):
+        """``_embed_torch`` of a ``_Batch``: [B, S, h], or [T, h] for a packed one."""
+        tt = bt.tt if bt.tt is not None else torch.zeros_like(bt.ids)
+        if bt.packed is None:
+            return self._embed_torch(bt.ids, tt, torch.arange(bt.S, device=bt.ids.device), per_batch=True)
+        return self._embed_torch(bt.ids, tt, bt.pos.long())
 
     def _pack(self, input_ids, lens, token_type_ids, row_multiple=1):
         """The PackedBatch of this forward when ``unpad`` is on and lengths are known, else None."""
@@ -462,7 +518,6 @@ class BertClassifier(nn.Module):
         token count) per forward. Without lengths the padded path runs."""
         if isinstance(input_ids, (tuple, list)):
             input_ids, attention_mask = input_ids[0], input_ids[1] if len(input_ids) > 1 else None
-        B, S = input_ids.shape
         lens = self._lengths(input_ids, attention_mask)
         drop, adrop = self._dropout(dropout_seed)
         if input_ids.is_cuda:
@@ -470,11 +525,9 @@ class BertClassifier(nn.Module):
             if self.config.fp8 and torch.is_grad_enabled():
                 from ml_trainer_amd.ops.fp8 import context
                 context(input_ids.device).update()  # delayed scaling: fold last step's amaxes
-            pk = self._pack(input_ids, lens, token_type_ids, T.PACK_ROW_MULTIPLE)
-            if pk is not None:
-                return self._forward_native_packed(pk, drop, adrop)
-            x = self._encode_native(input_ids, lens, token_type_ids, drop, adrop)
-            cls = x.view(B, S, -1)[:, 0]  # strided row view: the pooler GEMM reads it in place
+            bt = self._batch(input_ids, lens, token_type_ids, native=True)
+            # (padded: a strided row view, which the pooler GEMM reads in place; packed: rows cu_seqlens[:-1])
+            cls = bt.cls_rows(self._encode_native(bt, drop, adrop))
             if cls.shape[1] % 8 == 0 and self.pooler.weight.shape[0] % 8 == 0:
                 return T.classifier_head(cls, self.pooler.weight, self.pooler.bias, self.classifier.weight,
                                          self.classifier.bias)
@@ -484,83 +537,43 @@ class BertClassifier(nn.Module):
         pooled = torch.tanh(self.pooler(cls))
         return self.classifier(pooled)
 
-    def _encode_native(self, input_ids, lens, token_type_ids, drop, adrop):
-        """The native encoder on a padded [B, S] batch: the last layer's hidden states [B * S, h] bf16."""
+    def _encode_native(self, bt, drop, adrop):
+        """The native encoder on a ``_Batch``: the hidden states every head consumes, [rows, h] bf16 (padded:
+        B * S rows; packed: the T tokens, then the inert tail rows that round the count up to the GEMMs' 256-row
+        tile). Post-LN: the last layer's output; pre-norm: ``final_ln`` of the last stream."""
         from ml_trainer_amd.ops import transformer as T
-        B, S = input_ids.shape
-        x = T.embeddings(input_ids, token_type_ids, self.word_embeddings.weight, self._pos_weight(),
-                         self.token_type_embeddings.weight, S)
-        x = T.layer_norm(x, self.emb_ln.weight, self.emb_ln.bias, self.config.ln_eps)
+        c, layers = self.config, self.layers
+        x = T.embeddings(bt.ids, bt.tt, self.word_embeddings.weight, self._pos_weight(),
+                         self.token_type_embeddings.weight, bt.S, pos=bt.pos, cu_seqlens=bt.cu)
+        x = T.layer_norm(x, self.emb_ln.weight, self.emb_ln.bias, c.ln_eps)
         if drop is not None:
             x = T.dropout(x, *self._site(drop, 0))
-        rope = self._rope()
-        if self.config.pre_ln:
-            return self._pre_stack_native(x, lens, B, S, drop, adrop, None, rope)
-        for l, layer in enumerate(self.layers):
-            x = layer.forward_native(x, lens, B, S, self._site(drop, 1 + 2 * l), self._attn_site(adrop, l), rope=rope)
-        return x
-
-    def _encode_native_packed(self, pk, drop, adrop):
-        """The native encoder on a PackedBatch: [rows, h] throughout (the T tokens, then the inert tail rows
-        that round the count up to the GEMMs' 256-row tile)."""
-        from ml_trainer_amd.ops import transformer as T
-        B, S, cu = pk.batch, pk.max_seqlen, pk.cu_seqlens
-        x = T.embeddings(pk.ids, pk.tt, self.word_embeddings.weight, self._pos_weight(),
-                         self.token_type_embeddings.weight, S, pos=pk.pos, cu_seqlens=cu)
-        x = T.layer_norm(x, self.emb_ln.weight, self.emb_ln.bias, self.config.ln_eps)
-        if drop is not None:
-            x = T.dropout(x, *self._site(drop, 0))
-        rope = self._rope(pk.pos)
-        if self.config.pre_ln:
-            return self._pre_stack_native(x, None, B, S, drop, adrop, cu, rope)
-        for l, layer in enumerate(self.layers):
-            x = layer.forward_native(x, None, B, S, self._site(drop, 1 + 2 * l), self._attn_site(adrop, l), cu, rope)
-        return x
-
-    def _forward_native_packed(self, pk, drop, adrop):
-        """The native path on a PackedBatch, CLS rows at cu_seqlens[:-1]."""
-        from ml_trainer_amd.ops import transformer as T
-        x = self._encode_native_packed(pk, drop, adrop)
-        cls = x.index_select(0, pk.cls_rows)  # contiguous [B, h]
-        if cls.shape[1] % 8 == 0 and self.pooler.weight.shape[0] % 8 == 0:
-            return T.classifier_head(cls, self.pooler.weight, self.pooler.bias, self.classifier.weight,
-                                     self.classifier.bias)
-        return self.classifier(torch.tanh(self.pooler(cls.float())))
-
-    def _reference_hidden_packed(self, pk, lens, drop, adrop, full=False):
-        B, S = pk.batch, pk.max_seqlen
-        tt = pk.tt if pk.tt is not None else torch.zeros_like(pk.ids)
-        x = self.emb_ln(self._embed_torch(pk.ids, tt, pk.pos.long()))
-        if drop is not None:
-            from ml_trainer_amd.ops import dropout as D
-            x = D.apply(x, *self._site(drop, 0))
-        mask = torch.arange(S, device=x.device)[None, :] < lens.to(x.device).clamp(1, S)[:, None]
-        for l, layer in enumerate(self.layers):
-            x = layer.forward_reference(x, mask, B, S, self._site(drop, 1 + 2 * l), self._attn_site(adrop, l), pk,
-                                        self.rope_table)
-        x = self._final_norm(x)
-        return x if full else x.index_select(0, pk.cls_rows)
+        n = None
+        if c.pre_ln:  # x becomes the residual stream, n its norm under the next sub-layer's weights
+            x, n = T.stream_norm(x, *_norm_args(layers[0].ln1))
+        for l, layer in enumerate(layers):
+            d_attn, d_ffn, d_prob = self._layer_drops(drop, adrop, l)
+            closing = (layer.ln1, layer.ln2)
+            if c.pre_ln:
+                closing = (layer.ln2, layers[l + 1].ln1 if l + 1 < len(layers) else self.final_ln)
+            x, n = layer.forward_native(x, n, bt.attn_spec(c, self.rope_table, d_prob), closing, (d_attn, d_ffn))
+        return n if c.pre_ln else x
 
     def forward_reference_hidden(self, input_ids, lens=None, token_type_ids=None, drop=None, adrop=None, full=False):
         """The CLS rows [B, h] of the fp32 torch encoder; ``full``: every row, [B * S, h] (packed: [T, h])."""
-        B, S = input_ids.shape
-        pk = self._pack(input_ids, lens, token_type_ids)
-        if pk is not None:
-            return self._reference_hidden_packed(pk, lens, drop, adrop, full)
-        pos = torch.arange(S, device=input_ids.device)
-        tt = token_type_ids if token_type_ids is not None else torch.zeros_like(input_ids)
-        x = self.emb_ln(self._embed_torch(input_ids, tt, pos, per_batch=True)).view(B * S, -1)
+        return self._reference_hidden(self._batch(input_ids, lens, token_type_ids), drop, adrop, full)
+
+    def _reference_hidden(self, bt, drop, adrop, full=False):
+        x = self.emb_ln(self._embed_batch_torch(bt)).view(-1, self.config.hidden)
         if drop is not None:
             from ml_trainer_amd.ops import dropout as D
             x = D.apply(x, *self._site(drop, 0))
-        mask = None
-        if lens is not None:
-            mask = torch.arange(S, device=input_ids.device)[None, :] < lens.to(input_ids.device)[:, None]
+        mask = bt.key_mask(x.device)
         for l, layer in enumerate(self.layers):
-            x = layer.forward_reference(x, mask, B, S, self._site(drop, 1 + 2 * l), self._attn_site(adrop, l),
-                                        rope=self.rope_table)
+            d_attn, _, d_prob = self._layer_drops(drop, adrop, l)
+            x = layer.forward_reference(x, mask, bt.B, bt.S, d_attn, d_prob, bt.packed, self.rope_table)
         x = self._final_norm(x)
-        return x if full else x.view(B, S, -1)[:, 0]
+        return x if full else bt.cls_rows(x)
 
     def forward_reference(self, input_ids, attention_mask=None, token_type_ids=None, dropout_seed=None):
         lens = self._lengths(input_ids, attention_mask)
@@ -569,8 +582,8 @@ class BertClassifier(nn.Module):
 
     def forward_torch_bf16(self, input_ids, attention_mask=None, token_type_ids=None, dropout_seed=None):
         with torch.autocast(input_ids.device.type, dtype=torch.bfloat16):
-            x, pk = self._hidden_torch_bf16(input_ids, attention_mask, token_type_ids, dropout_seed)
-            cls = x[:, 0] if pk is None else x[0].index_select(0, pk.cls_rows)
+            x, bt = self._hidden_torch_bf16(input_ids, attention_mask, token_type_ids, dropout_seed)
+            cls = bt.cls_rows(x.reshape(-1, x.shape[-1]))
             return self.classifier(torch.tanh(self.pooler(cls.float())))
 
     def _hidden_torch_bf16(self, input_ids, attention_mask=None, token_type_ids=None, dropout_seed=None):
@@ -580,7 +593,7 @@ class BertClassifier(nn.Module):
         tensor it drops. With attention dropout active the attention is computed explicitly under
         autocast (softmax -> * keep * scale -> @ v) instead of through SDPA, which cannot take our mask.
         Under ``pre_ln`` the residual stream is rounded to bf16 after every add, as the native path stores it.
-        Returns (hidden [B, S, h] -- packed: [1, T, h] --, the PackedBatch or None); the callers add their head."""
+        Returns (hidden [B, S, h] -- packed: [1, T, h] --, the ``_Batch``); the callers add their head."""
         from ml_trainer_amd.ops import dropout as D
         c = self.config
         drop, adrop = self._dropout(dropout_seed)
@@ -590,7 +603,8 @@ class BertClassifier(nn.Module):
 
         B, S = input_ids.shape
         lens = self._lengths(input_ids, attention_mask)
-        pk = self._pack(input_ids, lens, token_type_ids)
+        bt = self._batch(input_ids, lens, token_type_ids)
+        pk = bt.packed
         if pk is not None:
             from ml_trainer_amd.ops.transformer import unpack_rows
         mask = None
@@ -602,17 +616,14 @@ class BertClassifier(nn.Module):
             mask = tril if mask is None else mask & tril
             causal = False
         with torch.autocast(input_ids.device.type, dtype=torch.bfloat16):
-            if pk is None:
-                pos = torch.arange(S, device=input_ids.device)
-                tt = token_type_ids if token_type_ids is not None else torch.zeros_like(input_ids)
-                x = self._embed_torch(input_ids, tt, pos, per_batch=True)
-            else:  # the packed rows as a batch of one: x [1, T, h]; attention on a padded scratch of the QKV rows
-                tt = pk.tt if pk.tt is not None else torch.zeros_like(pk.ids)
-                x = self._embed_torch(pk.ids, tt, pk.pos.long())[None]
+            x = self._embed_batch_torch(bt)
+            if pk is not None:  # the packed rows as a batch of one, [1, T, h]; attention on a padded scratch of QKV
+                x = x[None]
             x = dropped(self.emb_ln(x), 0)
             if c.pre_ln:
                 x = x.to(torch.bfloat16)
             for l, L in enumerate(self.layers):
+                s_attn, s_ffn, s_prob = _sites(l)
                 qkv = L.qkv(L.ln1(x) if c.pre_ln else x)
                 if pk is not None:
                     qkv = unpack_rows(qkv[0], pk)
@@ -627,7 +638,7 @@ class BertClassifier(nn.Module):
                 if adrop is None:
                     ctx = F.scaled_dot_product_attention(qkv[0], qkv[1], qkv[2], attn_mask=mask, is_causal=causal)
                 else:
-                    pa, seed, site, rank = self._attn_site(adrop, l)
+                    pa, seed, site, rank = self._site(adrop, s_prob)
                     sc = (qkv[0] @ qkv[1].transpose(-1, -2)) / 8.0
                     if mask is not None:
                         sc = sc.masked_fill(~mask, float("-inf"))
@@ -638,12 +649,12 @@ class BertClassifier(nn.Module):
                 if pk is not None:
                     ctx = ctx.reshape(B * S, -1).index_select(0, pk.index)[None]
                 if c.pre_ln:
-                    x = (dropped(L.out(ctx), 1 + 2 * l) + x).to(torch.bfloat16)
-                    x = (dropped(L.ffn_torch(L.ln2(x), True), 2 + 2 * l) + x).to(torch.bfloat16)
+                    x = (dropped(L.out(ctx), s_attn) + x).to(torch.bfloat16)
+                    x = (dropped(L.ffn_torch(L.ln2(x), True), s_ffn) + x).to(torch.bfloat16)
                     continue
-                x = L.ln1(dropped(L.out(ctx), 1 + 2 * l) + x)
-                x = L.ln2(dropped(L.ffn_torch(x, True), 2 + 2 * l) + x)
-            return self._final_norm(x), pk
+                x = L.ln1(dropped(L.out(ctx), s_attn) + x)
+                x = L.ln2(dropped(L.ffn_torch(x, True), s_ffn) + x)
+            return self._final_norm(x), bt
 
     def num_parameters(self) -> int:
         return sum(p.numel() for p in self.parameters())
@@ -705,24 +716,20 @@ class BertForMaskedLM(BertClassifier):
     def forward(self, input_ids, attention_mask=None, token_type_ids=None, dropout_seed=None):
         if isinstance(input_ids, (tuple, list)):
             input_ids, attention_mask = input_ids[0], input_ids[1] if len(input_ids) > 1 else None
-        B, S = input_ids.shape
         lens = self._lengths(input_ids, attention_mask)
         drop, adrop = self._dropout(dropout_seed)
         if not input_ids.is_cuda:
             return self._hidden_reference(input_ids, lens, token_type_ids, drop, adrop)
-        from ml_trainer_amd.ops import transformer as T
-        pk = self._pack(input_ids, lens, token_type_ids, T.PACK_ROW_MULTIPLE)
-        if pk is not None:
-            self._last_batch = (B, S, None, pk.cu_seqlens)
-            return self._encode_native_packed(pk, drop, adrop)
-        self._last_batch = (B, S, lens, None)
-        return self._encode_native(input_ids, lens, token_type_ids, drop, adrop)
+        bt = self._remember(self._batch(input_ids, lens, token_type_ids, native=True))
+        return self._encode_native(bt, drop, adrop)
+
+    def _remember(self, bt):
+        self._last_batch = bt.last_batch()  # what mlm_loss needs of this forward
+        return bt
 
     def _hidden_reference(self, input_ids, lens, token_type_ids, drop, adrop):
-        B, S = input_ids.shape
-        pk = self._pack(input_ids, lens, token_type_ids)
-        self._last_batch = (B, S, lens if pk is None else None, None if pk is None else pk.cu_seqlens)
-        return self.forward_reference_hidden(input_ids, lens, token_type_ids, drop, adrop, full=True)
+        bt = self._remember(self._batch(input_ids, lens, token_type_ids))
+        return self._reference_hidden(bt, drop, adrop, full=True)
 
     def forward_reference(self, input_ids, attention_mask=None, token_type_ids=None, dropout_seed=None):
         """The hidden states in fp32 torch on any device (the numerics oracle of ``forward``)."""
@@ -731,11 +738,9 @@ class BertForMaskedLM(BertClassifier):
 
     def forward_torch_bf16(self, input_ids, attention_mask=None, token_type_ids=None, dropout_seed=None):
         """The hidden states of the PyTorch-eager bf16 baseline, [B * S, h] (packed: [T, h])."""
-        B, S = input_ids.shape
         with torch.autocast(input_ids.device.type, dtype=torch.bfloat16):
-            x, pk = self._hidden_torch_bf16(input_ids, attention_mask, token_type_ids, dropout_seed)
-        lens = self._lengths(input_ids, attention_mask)
-        self._last_batch = (B, S, lens if pk is None else None, None if pk is None else pk.cu_seqlens)
+            x, bt = self._hidden_torch_bf16(input_ids, attention_mask, token_type_ids, dropout_seed)
+        self._remember(bt)
         return x.reshape(-1, x.shape[-1])
 
     def _head(self, fn, hidden, labels, **kw):
@@ -854,24 +859,19 @@ class BertLMHeadModel(BertForMaskedLM):
             from ml_trainer_amd.ops import transformer as T
             x = T.embeddings(input_ids, None, self.word_embeddings.weight, self._pos_weight(),
                              self.token_type_embeddings.weight, S)
-            x, _ = T._ln_fwd(x, self.emb_ln.weight, self.emb_ln.bias, c.ln_eps)
+            x = _norm_native(x, self.emb_ln)
+            spec = _Batch.of(input_ids, lens, None).attn_spec(c, self.rope_table)
             for l, L in enumerate(self.layers):
-                if c.pre_ln:  # x is the stream; the cache holds the K / V of its norm
-                    n, _ = T._norm_fwd(x, *_norm_args(L.ln1))
-                    x, (_, qkv, _, _) = T._attn_fwd(n, L.qkv.weight, L.qkv.bias, L.out.weight, L.out.bias, lens, B, S,
-                                                    c.heads, causal=True, rope=self._rope(), res=x,
-                                                    kv_heads=c.kv_heads)
-                    DC.fill_from_prefill(cache, l, qkv, lens, B, S, heads=c.heads)
-                    n, _ = T._norm_fwd(x, *_norm_args(L.ln2))
-                    x, _ = T._ffn_fwd(n, L.ffn1.weight, L.ffn1.bias, L.ffn2.weight, L.ffn2.bias, res=x, act=c.ffn)
-                    continue
-                a, (_, qkv, _, _) = T._attn_fwd(x, L.qkv.weight, L.qkv.bias, L.out.weight, L.out.bias, lens, B, S,
-                                                c.heads, causal=True, rope=self._rope(), kv_heads=c.kv_heads)
+                # pre-norm: x is the stream, a sub-layer reads its norm (the cache holds the K / V of that norm) and
+                # its sum is the new stream; post-LN: a sub-layer reads x and its normed sum is the new x
+                n = _norm_native(x, L.ln1) if c.pre_ln else x
+                y, (_, qkv, _, _) = T._attn_fwd(n, L.attn_params(), x, spec)
                 # (qkv: rotated under rotary, the wide buffer under kv_heads)
                 DC.fill_from_prefill(cache, l, qkv, lens, B, S, heads=c.heads)
-                x, _ = T._ln_fwd(a, L.ln1.weight, L.ln1.bias, c.ln_eps)
-                f, _ = T._ffn_fwd(x, L.ffn1.weight, L.ffn1.bias, L.ffn2.weight, L.ffn2.bias, act=c.ffn)
-                x, _ = T._ln_fwd(f, L.ln2.weight, L.ln2.bias, c.ln_eps)
+                x = y if c.pre_ln else _norm_native(y, L.ln1)
+                n = _norm_native(x, L.ln2) if c.pre_ln else x
+                y, _ = T._ffn_fwd(n, L.ffn_params(), x, c.ffn)
+                x = y if c.pre_ln else _norm_native(y, L.ln2)
         else:
             pos = torch.arange(S, device=dev)
             x = self._embed_torch(input_ids, torch.zeros_like(input_ids), pos, per_batch=True)
@@ -890,11 +890,7 @@ class BertLMHeadModel(BertForMaskedLM):
         cache.pos.copy_(lens if lens is not None else torch.full((B,), S, dtype=torch.int32, device=dev))
         x = x.index_select(0, self._last_rows(lens, B, S, dev))
         if c.pre_ln:  # rows are independent: the final norm of the last real rows only
-            if x.is_cuda:
-                from ml_trainer_amd.ops import transformer as T
-                x, _ = T._norm_fwd(x, *_norm_args(self.final_ln))
-            else:
-                x = self.final_ln(x)
+            x = _norm_native(x, self.final_ln) if x.is_cuda else self.final_ln(x)
         return DC.DecodeState(cache, x)
 
     def _state_logits(self, state):
@@ -941,36 +937,27 @@ class BertLMHeadModel(BertForMaskedLM):
             C.embed_fwd(ids, None, T.bf16_weight(self.word_embeddings.weight),
                         None if c.rotary else T.bf16_weight(self.position_embeddings.weight),
                         T.bf16_weight(self.token_type_embeddings.weight), x, cache.Smax, pos=cache.pos)
-            x, _ = T._ln_fwd(x, self.emb_ln.weight, self.emb_ln.bias, c.ln_eps)
-            for l, L in enumerate(self.layers):
-                if c.pre_ln:  # x is the stream
-                    n, _ = T._norm_fwd(x, *_norm_args(L.ln1))
-                    qkv = DC.linear_small(n, T.bf16_weight(L.qkv.weight), L.qkv.bias)
-                    ctx = DC.attn_decode(qkv, cache.kv[l], cache.pos, c.heads, rope=self.rope_table)
-                    x = DC.linear_small(ctx, T.bf16_weight(L.out.weight), L.out.bias, res=x)
-                    n, _ = T._norm_fwd(x, *_norm_args(L.ln2))
-                    x = DC.linear_small(self._ffn1_decode(L, n), T.bf16_weight(L.ffn2.weight), L.ffn2.bias, res=x)
-                    continue
-                qkv = DC.linear_small(x, T.bf16_weight(L.qkv.weight), L.qkv.bias)
+            x = _norm_native(x, self.emb_ln)
+            for l, L in enumerate(self.layers):  # (x, n and the sums as in prefill)
+                n = _norm_native(x, L.ln1) if c.pre_ln else x
+                qkv = DC.linear_small(n, T.bf16_weight(L.qkv.weight), L.qkv.bias)
                 ctx = DC.attn_decode(qkv, cache.kv[l], cache.pos, c.heads, rope=self.rope_table)
-                a = DC.linear_small(ctx, T.bf16_weight(L.out.weight), L.out.bias, res=x)
-                x, _ = T._ln_fwd(a, L.ln1.weight, L.ln1.bias, c.ln_eps)
-                f = DC.linear_small(self._ffn1_decode(L, x), T.bf16_weight(L.ffn2.weight), L.ffn2.bias, res=x)
-                x, _ = T._ln_fwd(f, L.ln2.weight, L.ln2.bias, c.ln_eps)
+                y = DC.linear_small(ctx, T.bf16_weight(L.out.weight), L.out.bias, res=x)
+                x = y if c.pre_ln else _norm_native(y, L.ln1)
+                n = _norm_native(x, L.ln2) if c.pre_ln else x
+                y = DC.linear_small(self._ffn1_decode(L, n), T.bf16_weight(L.ffn2.weight), L.ffn2.bias, res=x)
+                x = y if c.pre_ln else _norm_native(y, L.ln2)
             if c.pre_ln:  # state.hidden holds the normed rows, as after a post-LN layer
-                x, _ = T._norm_fwd(x, *_norm_args(self.final_ln))
+                x = _norm_native(x, self.final_ln)
         else:
             x = self.emb_ln(self._embed_torch(ids, torch.zeros_like(ids), cache.pos.long()))
             for l, L in enumerate(self.layers):
-                if c.pre_ln:
-                    ctx = DC.attn_decode_reference(L.qkv(L.ln1(x)), cache.kv[l], cache.pos, c.heads,
-                                                   rope=self.rope_table)
-                    x = L.out(ctx) + x
-                    x = L.ffn_torch(L.ln2(x)) + x
-                    continue
-                ctx = DC.attn_decode_reference(L.qkv(x), cache.kv[l], cache.pos, c.heads, rope=self.rope_table)
-                x = L.ln1(L.out(ctx) + x)
-                x = L.ln2(L.ffn_torch(x) + x)
+                n = L.ln1(x) if c.pre_ln else x
+                ctx = DC.attn_decode_reference(L.qkv(n), cache.kv[l], cache.pos, c.heads, rope=self.rope_table)
+                y = L.out(ctx) + x
+                x = y if c.pre_ln else L.ln1(y)
+                y = L.ffn_torch(L.ln2(x) if c.pre_ln else x) + x
+                x = y if c.pre_ln else L.ln2(y)
             x = self._final_norm(x)
         cache.pos.add_(1)
         state.hidden = x

@@ -331,7 +331,7 @@ class _MLMHead(torch.autograd.Function):
         else:
             gb = db.mul_(scale)[:V]
         dts = (dt.float() * scale).to(torch.bfloat16)
-        da, dg, dbeta, _ = T._ln_bwd((a, gamma, mean, rstd), p.ln_b, dts, G)
+        da, dg, dbeta, _, _ = T._ln_bwd((a, gamma, mean, rstd), p.ln_b, dts, G)
         dpre = _dgelu(da, pre)
         dwd, dbd = G.wgrad_bias(p.dense_w, p.dense_b, dpre, x)
         dx = T.BF16.dgrad(dpre, p.dense_w, torch.empty_like(x))

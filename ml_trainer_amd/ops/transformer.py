@@ -5,6 +5,16 @@ optimizer/DDP owns them); compute reads their bf16 *shadow* (refreshed by the
 fused optimizer kernel in the same pass that updates the master, so there is
 no separate cast per step). Weight / bias gradients come back in fp32.
 
+Structure: an attention call is described by one ``AttnSpec`` (the Python side of the host layer's ``AttnProblem``),
+which goes through ``_attn_fwd`` / ``_attn_bwd`` and onto ``ctx`` whole. The attention and the FFN are two *cores* of
+one shape (``fwd(x, params, res) -> (y, saved)``, ``bwd(saved, params, dy, G, dbias_last, dres) -> grads``;
+``attn_core`` / ``ffn_core``), and three autograd nodes take a core as an argument: ``block`` (core(x) + x),
+``post_norm_block`` (x -> Norm(core(x) + x)) and ``pre_norm_block`` ((h, n) -> (h', Norm(h'))), the last two with the
+hidden-dropout fork written once (``_sublayer_fwd``). Every block reaches the norm kernels through ``_norm_fwd`` /
+``_dropout_add_norm_fwd`` / ``_norm_bwd`` (LayerNorm with ``beta``, RMSNorm without), and ``_check_bf16_only`` is the
+one place that refuses a feature under the fp8 linears. The public blocks below keep their loose arguments and build
+the spec and the core from them.
+
 Blocks (one autograd node each, so the backward can fuse across ops):
 
 * ``attention_block``: x -> QKV GEMM(+bias) -> fused flash attention -> out-proj
@@ -49,7 +59,8 @@ Linear layout conventions (nn.Linear weight [out, in]):
 from __future__ import annotations
 
 import os
-from typing import Optional
+from dataclasses import dataclass
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -218,12 +229,68 @@ class _Grads:
         self.ready = []
 
 
-def _attn_drop_kw(attn_drop):
-    """Keyword arguments of C.attn_fwd / C.attn_bwd for ``attn_drop`` = (p, seed, site, rank) or None."""
-    if attn_drop is None:
-        return {}
-    p, seed, site, rank = attn_drop
-    return dict(p=p, seed=seed, site=site, rank=rank)
+@dataclass(frozen=True, eq=False)
+class AttnSpec:
+    """Everything of one attention call that is not an activation or a weight; the Python side of the host
+    layer's ``AttnProblem``. ``lens`` int32 [B] or None. ``cu_seqlens`` (int32 [B + 1], device): packed batch, x is
+    [T, D] with sequence b at rows cu[b] .. cu[b + 1]; S is then max_seqlen and ``lens`` is unused. ``causal``: key j
+    is visible to query i of its sequence iff j <= i and j < len_b. ``rope`` = (table fp32 [P, 32, 2], pos int32
+    [rows] or None: row % S), see ops/rope.py. ``attn_drop`` = (p, seed, site, rank): attention-probability dropout
+    inside the flash kernels (the byte mask of ops/dropout.py, recomputed in the backward). ``kv_heads`` (None or H:
+    none of this): grouped-query attention with the compact QKV layout of ops/gqa.py."""
+    B: int
+    S: int
+    H: int
+    lens: Optional[torch.Tensor] = None
+    cu_seqlens: Optional[torch.Tensor] = None
+    causal: bool = False
+    rope: Optional[tuple] = None
+    attn_drop: Optional[tuple] = None
+    kv_heads: Optional[int] = None
+
+    @property
+    def gqa(self) -> bool:
+        return self.kv_heads is not None and self.kv_heads != self.H
+
+    def kernel_kw(self) -> dict:
+        """Keyword arguments of C.attn_fwd / C.attn_bwd; a keyword goes out only when set."""
+        kw = {}
+        if self.attn_drop is not None:
+            kw["p"], kw["seed"], kw["site"], kw["rank"] = self.attn_drop
+        if self.causal:
+            kw["causal"] = True
+        if self.cu_seqlens is not None:
+            kw["cu_seqlens"] = self.cu_seqlens
+        return kw
+
+
+def attn_spec(wqkv, lens, B, S, H, attn_drop=None, cu_seqlens=None, causal=False, rope=None) -> AttnSpec:
+    """The spec of the public blocks' loose arguments. ``kv_heads`` comes from the QKV projection's own shape: None
+    for the wide [3 * H * 64, h] weight (every launch as before), Hkv for the compact [(H + 2 Hkv) * 64, h] one."""
+    return AttnSpec(B, S, H, lens, cu_seqlens, causal, rope, attn_drop, infer_kv_heads(wqkv.shape[0], H))
+
+
+# What runs the bf16 linears only, in raising order: (feature, message).
+_BF16_ONLY = (
+    ("pre_norm", "pre-norm blocks run the bf16 linears only"),
+    ("causal", "causal attention runs the bf16 linears only: the fp8 (q8) attention epilogue has no causal "
+               "instantiation"),
+    ("gqa", "grouped-query attention runs the bf16 linears only: the fp8 attention backward writes dQKV as e5m2 in "
+            "the wide layout"),
+    ("packed", "packed (cu_seqlens) attention runs the bf16 linears only: the fp8 attention epilogue writes at "
+               "b * S offsets"),
+    ("rotary", "rotary positions run the bf16 linears only: the fp8 attention backward writes dQKV as e5m2, which "
+               "the inverse rotation cannot take"),
+    ("swiglu", "the SwiGLU feed-forward runs the bf16 linears only: the fp8 FFN fusions are GELU epilogues"),
+)
+
+
+def _check_bf16_only(impl, **features):
+    """Refuse the requested ``features`` (names of _BF16_ONLY) under any linear implementation but BF16."""
+    if impl is not BF16:
+        for name, message in _BF16_ONLY:
+            if features.get(name):
+                raise ValueError(message)
 
 
 def _zero_packed_tail(t, cu_seqlens):
@@ -235,22 +302,6 @@ def _zero_packed_tail(t, cu_seqlens):
         t[-min(PACK_ROW_MULTIPLE - 1, t.shape[0]):].zero_()
 
 
-def _causal_kw(causal, impl):
-    """Keyword arguments of C.attn_fwd / C.attn_bwd for ``causal``; the keyword goes out only when set."""
-    if not causal:
-        return {}
-    if impl is not BF16:
-        raise ValueError("causal attention runs the bf16 linears only: the fp8 (q8) attention epilogue has no "
-                         "causal instantiation")
-    return dict(causal=True)
-
-
-def _kv_heads(wqkv, H):
-    """The ``kv_heads`` argument of _attn_fwd / _attn_bwd from the QKV projection's own shape: None for the wide
-    [3 * H * 64, h] weight (every launch as before), Hkv for the compact [(H + 2 Hkv) * 64, h] one."""
-    return infer_kv_heads(wqkv.shape[0], H)
-
-
 def _rope_qk(t, rope, S, H, sign=1):
     """Rotary positions: rotate the q and k columns of ``t`` (QKV, or dQKV with ``sign=-1``) in place.
     ``rope`` = (table fp32 [P, 32, 2], pos int32 [rows] or None: row % S), see ops/rope.py."""
@@ -258,84 +309,66 @@ def _rope_qk(t, rope, S, H, sign=1):
     require_native().rope_qk(t, table, H, S, pos=pos, sign=sign)
 
 
-def _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl=BF16, residual=True, attn_drop=None, cu_seqlens=None,
-              causal: bool = False, rope=None, res=None, kv_heads=None):
-    """``attn_drop`` = (p, seed, site, rank): attention-probability dropout inside the flash kernels
-    (the byte mask of ops/dropout.py, recomputed in the backward); None: no dropout.
-    ``cu_seqlens`` (int32 [B + 1], device): packed batch, x is [T, D] with sequence b at rows
-    cu[b] .. cu[b + 1]; S is max_seqlen and ``lens`` is unused.
-    ``causal``: key j is visible to query i of its sequence iff j <= i and j < len_b.
-    ``rope`` = (table, pos or None): rotary positions, q and k rotated in place between the QKV GEMM and the
-    attention kernel (``pos`` for packed batches); the saved qkv is the rotated one, which the attention
-    backward needs. ``res``: the residual the out-projection adds instead of ``x`` (pre-norm blocks: x is the
-    norm of the stream, ``res`` the stream).
-    ``kv_heads`` (None or H: none of this): grouped-query attention, ``wqkv`` projects to the compact layout
-    q (H heads) | k (kv_heads) | v (kv_heads) and ``C.gqa_expand`` (ops/gqa.py) repeats every k / v head for its
-    group into the wide [rows, 3 * H * 64] buffer, which the rotation and the attention kernel then take
+# The two sub-layer cores share one shape, which is all the block nodes below know of them:
+#   fwd(x, params, res, what, impl) -> (y, saved)     res: what the last linear adds in its epilogue, or None
+#   bwd(saved, params, dy, G, dbias_last, dres, what, impl) -> (dx, dw_first, db_first, dw_last, db_last)
+# ``params`` = (w_first, b_first, w_last, b_last); ``what`` is the core's one non-tensor argument (an AttnSpec, or
+# the FFN's ``act``). ``dbias_last``: "colsum" to reduce dy here, otherwise the last linear's bias gradient as the
+# norm backward already produced it (tensor or None). ``dres``: what the first linear's dgrad adds in its epilogue:
+# the gradient of the residual branch (``dy`` itself, or the norm backward's dx when hidden dropout sits between
+# them), or None where the core's input is not its residual (pre-norm blocks).
+def _attn_fwd(x, params, res, spec: AttnSpec, impl=BF16):
+    """Under ``spec.rope`` q and k are rotated in place between the QKV GEMM and the attention kernel; the saved qkv
+    is the rotated one, which the attention backward needs. Under ``spec.gqa`` ``wqkv`` projects to the compact
+    layout q (H heads) | k (kv_heads) | v (kv_heads) and ``C.gqa_expand`` (ops/gqa.py) repeats every k / v head for
+    its group into the wide [rows, 3 * H * 64] buffer, which the rotation and the attention kernel then take
     unchanged and which is what is saved."""
+    _check_bf16_only(impl, causal=spec.causal, gqa=spec.gqa, packed=spec.cu_seqlens is not None,
+                     rotary=spec.rope is not None)
     C = require_native()
-    ckw = _causal_kw(causal, impl)
-    gqa = kv_heads is not None and kv_heads != H
-    if gqa and impl is not BF16:
-        raise ValueError("grouped-query attention runs the bf16 linears only: the fp8 attention backward writes "
-                         "dQKV as e5m2 in the wide layout")
-    if cu_seqlens is not None and impl is not BF16:
-        raise ValueError("packed (cu_seqlens) attention runs the bf16 linears only: the fp8 attention epilogue "
-                         "writes at b * S offsets")
-    if rope is not None and impl is not BF16:
-        raise ValueError("rotary positions run the bf16 linears only: the fp8 attention backward writes dQKV as "
-                         "e5m2, which the inverse rotation cannot take")
+    wqkv, bqkv, wo, bo = params
+    B, S, H = spec.B, spec.S, spec.H
     qkv = impl.fwd(x, wqkv, bqkv)
-    if gqa:
-        qkv = gqa_expand(qkv, H, kv_heads)
-    if rope is not None:
-        _rope_qk(qkv, rope, S, H)
+    if spec.gqa:
+        qkv = gqa_expand(qkv, H, spec.kv_heads)
+    if spec.rope is not None:
+        _rope_qk(qkv, spec.rope, S, H)
     attn = torch.empty(x.shape[0], H * 64, dtype=torch.bfloat16, device=x.device)
     lse = torch.empty(B * H * S, dtype=torch.float32, device=x.device)
-    _zero_packed_tail(attn, cu_seqlens)
-    C.attn_fwd(qkv, attn, lse, lens, B, S, H, _ATTN_SCALE, cu_seqlens=cu_seqlens, **_attn_drop_kw(attn_drop), **ckw)
-    # out-proj + bias + residual (under dropout the residual joins in the LayerNorm kernel instead)
-    y = impl.fwd(attn, wo, bo, res=(x if res is None else res) if residual else None)
+    _zero_packed_tail(attn, spec.cu_seqlens)
+    C.attn_fwd(qkv, attn, lse, spec.lens, B, S, H, _ATTN_SCALE, **{"cu_seqlens": None, **spec.kernel_kw()})
+    # out-proj + bias + residual (under dropout the residual joins in the norm kernel instead)
+    y = impl.fwd(attn, wo, bo, res=res)
     return y, (x, qkv, attn, lse)
 
 
-def _attn_bwd(saved, params, lens, B, S, H, dy, G, dbo="colsum", impl=BF16, dres=None, attn_drop=None,
-              cu_seqlens=None, causal: bool = False, rope=None, residual=True, kv_heads=None):
-    """Backward of the attention block. ``dbo``: "colsum" to reduce dy here, otherwise the
-    out-proj bias gradient already produced by the LayerNorm backward (tensor or None).
-    ``dres``: the gradient of the residual branch when it differs from the out-proj's ``dy``
-    (hidden dropout sits between them); defaults to ``dy``. ``attn_drop``, ``cu_seqlens``, ``causal``: the
-    forward's. ``rope``: the forward's; dQKV comes out of the attention backward in the rotated frame and is
-    rotated back (``sign=-1``) before anything else reads it. The QKV bias gradient is then the column sum of the
-    rotated-back dQKV: the attention kernels' own column sums are sums in the rotated frame, which differ row by
-    row, so that fused branch is not taken under rotary. ``residual=False`` (pre-norm blocks): the block's input
-    is not its residual, the QKV dgrad adds nothing. ``kv_heads``: the forward's; the wide dQKV (rotated back
-    under rotary) is reduced to the compact layout by ``C.gqa_reduce`` (dk / dv summed over each group) before the
-    weight gradient, the bias gradient and the dgrad read it. The attention kernels' own column sums are over wide
-    columns, so that fused branch is not taken under grouped-query attention either."""
+def _attn_bwd(saved, params, dy, G, dbo, dres, spec: AttnSpec, impl=BF16):
+    """Under ``spec.rope`` dQKV comes out of the attention backward in the rotated frame and is rotated back
+    (``sign=-1``) before anything else reads it. The QKV bias gradient is then the column sum of the rotated-back
+    dQKV: the attention kernels' own column sums are sums in the rotated frame, which differ row by row, so that
+    fused branch is not taken under rotary. Under ``spec.gqa`` the wide dQKV (rotated back under rotary) is reduced
+    to the compact layout by ``C.gqa_reduce`` (dk / dv summed over each group) before the weight gradient, the bias
+    gradient and the dgrad read it. The attention kernels' own column sums are over wide columns, so that fused
+    branch is not taken under grouped-query attention either."""
     C = require_native()
-    gqa = kv_heads is not None and kv_heads != H
-    akw = _attn_drop_kw(attn_drop)
-    akw.update(_causal_kw(causal, impl))
-    if cu_seqlens is not None:
-        akw["cu_seqlens"] = cu_seqlens
+    B, S, H, lens, rope = spec.B, spec.S, spec.H, spec.lens, spec.rope
+    akw = spec.kernel_kw()
     x, qkv, attn, lse = saved
     wqkv, bqkv, wo, bo = params
-    dres = dy if dres is None else dres
     dwo = G.wgrad(wo, dy, attn, impl)
     if isinstance(dbo, str):
         dbo = G.colsum(bo, dy)
     dattn = impl.dgrad(dy, wo, torch.empty_like(attn))
     dqkv = torch.empty_like(qkv)
-    _zero_packed_tail(dqkv, cu_seqlens)
+    _zero_packed_tail(dqkv, spec.cu_seqlens)
     delta = torch.empty(qkv.shape[0] * H, dtype=torch.float32, device=dy.device)
     q8 = impl.attn_dy_q(wqkv, x, qkv.shape[0]) if (impl is not BF16 and hasattr(impl, "attn_dy_q")) else None
-    if rope is not None or gqa:
+    if rope is not None or spec.gqa:
         C.attn_bwd(qkv, attn, dattn, lse, delta, lens, dqkv, B, S, H, _ATTN_SCALE, **akw)
         if rope is not None:
             _rope_qk(dqkv, rope, S, H, sign=-1)
-        if gqa:
-            dqkv = gqa_reduce(dqkv, H, kv_heads)
+        if spec.gqa:
+            dqkv = gqa_reduce(dqkv, H, spec.kv_heads)
         dwqkv, dbqkv = G.wgrad_bias(wqkv, bqkv, dqkv, x, impl)
     elif q8 is not None or (impl is BF16 and bqkv is not None):
         # the QKV bias gradient (column sums of dQKV) from the backward kernels themselves
@@ -354,44 +387,35 @@ def _attn_bwd(saved, params, lens, B, S, H, dy, G, dbo="colsum", impl=BF16, dres
     else:
         C.attn_bwd(qkv, attn, dattn, lse, delta, lens, dqkv, B, S, H, _ATTN_SCALE, **akw)
         dwqkv, dbqkv = G.wgrad_bias(wqkv, bqkv, dqkv, x, impl)
-    dx = impl.dgrad(dqkv, wqkv, torch.empty_like(x), res=dres if residual else None)  # dqkv . Wqkv + dres
+    dx = impl.dgrad(dqkv, wqkv, torch.empty_like(x), res=dres)  # dqkv . Wqkv + dres
     return dx, dwqkv, dbqkv, dwo, dbo
 
 
-def _check_act(act, impl):
-    if act not in ("gelu", "swiglu"):
-        raise ValueError(f"act must be 'gelu' or 'swiglu', got {act!r}")
-    if act == "swiglu" and impl is not BF16:
-        raise ValueError("the SwiGLU feed-forward runs the bf16 linears only: the fp8 FFN fusions are GELU epilogues")
-
-
-def _ffn_fwd(x, w1, b1, w2, b2, impl=BF16, residual=True, res=None, act="gelu"):
+def _ffn_fwd(x, params, res, act="gelu", impl=BF16):
     """``act="swiglu"``: ``w1`` is [2F, h] (gate rows, then up rows); FFN1 runs with the plain bias epilogue into
     ``h1`` [rows, 2F], ``swiglu_fwd`` (ops/swiglu.py) makes ``a`` [rows, F], FFN2 as ever. Saves (x, h1, a)."""
-    _check_act(act, impl)
+    if act not in ("gelu", "swiglu"):
+        raise ValueError(f"act must be 'gelu' or 'swiglu', got {act!r}")
+    _check_bf16_only(impl, swiglu=act == "swiglu")
+    w1, b1, w2, b2 = params
     if act == "swiglu":
         h1 = impl.fwd(x, w1, b1)
         a = swiglu_fwd(h1)
-        y = impl.fwd(a, w2, b2, res=(x if res is None else res) if residual else None)
-        return y, (x, h1, a)
+        return impl.fwd(a, w2, b2, res=res), (x, h1, a)
     pre = torch.empty(x.shape[0], w1.shape[0], dtype=torch.bfloat16, device=x.device)
     # fp8: FFN1's epilogue may emit FFN2's quantised input directly (Fp8Linear.fwd_gelu_q)
     a = impl.fwd_gelu_q(x, w1, b1, pre, w2) if hasattr(impl, "fwd_gelu_q") else None
     if a is None:
         a = impl.fwd(x, w1, b1, gelu_aux=pre)  # a = gelu(pre), pre saved
-    y = impl.fwd(a, w2, b2, res=(x if res is None else res) if residual else None)  # (res: as in _attn_fwd)
-    return y, (x, pre, a)
+    return impl.fwd(a, w2, b2, res=res), (x, pre, a)
 
 
-def _ffn_bwd(saved, params, dy, G, db2="colsum", impl=BF16, dres=None, residual=True, act="gelu"):
-    """``dres``: the residual branch's gradient when hidden dropout separates it from FFN2's ``dy``.
-    ``residual=False`` (pre-norm blocks): FFN1's dgrad adds no residual gradient. ``act="swiglu"``: FFN2's plain
-    dgrad gives ``da``, ``swiglu_bwd`` gives dh1 = dg | du and FFN1's bias gradient (the column sums of the rounded
-    dh1, set or accumulated into the flat-gradient sink), then FFN1's wgrad and dgrad as the GELU branch ends."""
-    _check_act(act, impl)
+def _ffn_bwd(saved, params, dy, G, db2, dres, act="gelu", impl=BF16):
+    """``act="swiglu"``: FFN2's plain dgrad gives ``da``, ``swiglu_bwd`` gives dh1 = dg | du and FFN1's bias gradient
+    (the column sums of the rounded dh1, set or accumulated into the flat-gradient sink), then FFN1's wgrad and
+    dgrad as the GELU branch ends."""
     x, pre, a = saved
     w1, b1, w2, b2 = params
-    dres = (dy if dres is None else dres) if residual else None
     dw2 = G.wgrad(w2, dy, a, impl)
     if isinstance(db2, str):
         db2 = G.colsum(b2, dy)
@@ -422,6 +446,30 @@ def _ffn_bwd(saved, params, dy, G, db2="colsum", impl=BF16, dres=None, residual=
     return dx, dw1, db1, dw2, db2
 
 
+class _Core(NamedTuple):
+    """A sub-layer core bound to its non-tensor argument and linear implementation; ``n_saved`` tensors of what a
+    node saves are the core's."""
+    fwd_fn: object
+    bwd_fn: object
+    n_saved: int
+    what: object
+    impl: object
+
+    def fwd(self, x, params, res):
+        return self.fwd_fn(x, params, res, self.what, self.impl)
+
+    def bwd(self, saved, params, dy, G, dbias_last, dres):
+        return self.bwd_fn(saved, params, dy, G, dbias_last, dres, self.what, self.impl)
+
+
+def attn_core(spec: AttnSpec, impl=BF16) -> _Core:
+    return _Core(_attn_fwd, _attn_bwd, 4, spec, impl)
+
+
+def ffn_core(act: str = "gelu", impl=BF16) -> _Core:
+    return _Core(_ffn_fwd, _ffn_bwd, 3, act, impl)
+
+
 def _ln_fwd(x, gamma, beta, eps):
     C = require_native()
     rows = x.shape[0]
@@ -447,10 +495,10 @@ def _dropout_add_ln_fwd(y0, res, gamma, beta, eps, drop):
 
 def _ln_bwd(saved, beta, dy, G, dxsum_param=None, drop=None, dres=None):
     """LayerNorm backward; with ``dxsum_param`` also the column sums of dx (= that bias's grad).
-    Returns (dx, dgamma|None, dbeta|None, dbias|None).
+    Returns (dx, dgamma|None, dbeta|None, dbias|None, dxm|None).
     ``drop`` = (p, seed, site, rank) (needs ``dxsum_param``): the input was dropout(linear) +
-    residual. dx is then the residual's gradient, a fifth result dxm = mask * scale * dx is the
-    linear's dY, and dbias holds dxm's column sums. ``dres`` (pre-norm blocks): added into dx in the kernel,
+    residual. dx is then the residual's gradient, dxm = mask * scale * dx is the linear's dY (None without
+    ``drop``), and dbias holds dxm's column sums. ``dres`` (pre-norm blocks): added into dx in the kernel,
     with ``drop`` as well (dxm is then the masked, scaled copy of that total)."""
     C = require_native()
     x, gamma, mean, rstd = saved
@@ -483,7 +531,7 @@ def _ln_bwd(saved, beta, dy, G, dxsum_param=None, drop=None, dres=None):
                      dxm=dxm, p=p, seed=seed, site=site, rank=rank)
         return dx, dg, db, dxs, dxm
     C.ln_bwd(dy, x, gamma, mean, rstd, dx, part, dg_t, db_t, acc, dres, dxsum=dxs_t, dxsum_acc=dxs_acc)
-    return dx, dg, db, dxs
+    return dx, dg, db, dxs, None
 
 
 def _rms_fwd(x, gamma, eps):
@@ -505,7 +553,7 @@ def _dropout_add_rms_fwd(y0, res, gamma, eps, drop):
 
 
 def _rms_bwd(saved, dy, G, dxsum_param=None, drop=None, dres=None):
-    """RMSNorm backward, the arguments of _ln_bwd without beta. Returns (dx, dgamma|None, dbias|None, dxm|None)."""
+    """RMSNorm backward, the arguments of _ln_bwd without beta and its five results (dbeta is None)."""
     C = require_native()
     x, gamma, _, rstd = saved
     D = gamma.numel()
@@ -521,10 +569,10 @@ def _rms_bwd(saved, dy, G, dxsum_param=None, drop=None, dres=None):
         p, seed, site, rank = drop
         kw = dict(dxm=dxm, p=p, seed=seed, site=site, rank=rank)
     C.rms_bwd(dy, x, gamma, rstd, dx, part, dg_t, acc, dres, dxsum=dxs_t, dxsum_acc=dxs_acc, **kw)
-    return dx, dg, dxs, dxm
+    return dx, dg, None, dxs, dxm
 
 
-# The norm of a pre-norm block: LayerNorm when ``beta`` is a tensor, RMSNorm when it is None. The saved
+# The norm every block calls: LayerNorm when ``beta`` is a tensor, RMSNorm when it is None. The saved
 # tuple is (x, gamma, mean | None, rstd) for both.
 def _norm_fwd(x, gamma, beta, eps):
     return _rms_fwd(x, gamma, eps) if beta is None else _ln_fwd(x, gamma, beta, eps)
@@ -539,51 +587,39 @@ def _dropout_add_norm_fwd(y0, res, gamma, beta, eps, drop):
 def _norm_bwd(saved, beta, dy, G, dxsum_param=None, drop=None, dres=None):
     """(dx, dgamma, dbeta (None under RMSNorm), dbias, dxm (None without ``drop``)) of either norm."""
     if beta is None:
-        dx, dg, dxs, dxm = _rms_bwd(saved, dy, G, dxsum_param, drop, dres)
-        return dx, dg, None, dxs, dxm
-    r = _ln_bwd(saved, beta, dy, G, dxsum_param, drop, dres)
-    return r if drop is not None else r + (None,)
+        return _rms_bwd(saved, dy, G, dxsum_param, drop, dres)
+    return _ln_bwd(saved, beta, dy, G, dxsum_param, drop, dres)
 
 
 _ATTN_SCALE = 1.0 / 8.0  # 1/sqrt(head_dim = 64)
 
 
-class _AttentionBlock(torch.autograd.Function):
+def _bf16_grad(g):
+    return None if g is None else g.contiguous().to(torch.bfloat16)
+
+
+def _input_grads(ctx, *grads):
+    """A backward's result: ``grads`` for the leading inputs of the node's forward, None for all the others."""
+    return grads + (None,) * (len(ctx.needs_input_grad) - len(grads))
+
+
+class _Block(torch.autograd.Function):
+    """core(x) + x, without a norm: ``attention_block`` / ``ffn_block``."""
+
     @staticmethod
-    def forward(ctx, x, wqkv, bqkv, wo, bo, lens, B, S, H, impl, attn_drop=None, cu_seqlens=None, causal=False,
-                rope=None):
-        y, saved = _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl, attn_drop=attn_drop, cu_seqlens=cu_seqlens,
-                             causal=causal, rope=rope, kv_heads=_kv_heads(wqkv, H))
+    def forward(ctx, x, w1, b1, w2, b2, core):
+        y, saved = core.fwd(x, (w1, b1, w2, b2), x)
         ctx.save_for_backward(*saved)
-        ctx.params, ctx.impl, ctx.rope = (wqkv, bqkv, wo, bo), impl, rope
-        ctx.lens, ctx.dims, ctx.attn_drop, ctx.cu, ctx.causal = lens, (B, S, H), attn_drop, cu_seqlens, causal
+        ctx.params, ctx.core = (w1, b1, w2, b2), core
         return y
 
     @staticmethod
     def backward(ctx, dy):
         G = _Grads()
-        grads = _attn_bwd(ctx.saved_tensors, ctx.params, ctx.lens, *ctx.dims, dy.contiguous().to(torch.bfloat16), G,
-                          impl=ctx.impl, attn_drop=ctx.attn_drop, cu_seqlens=ctx.cu, causal=ctx.causal,
-                          rope=ctx.rope, kv_heads=_kv_heads(ctx.params[0], ctx.dims[2]))
+        dy = _bf16_grad(dy)
+        grads = ctx.core.bwd(ctx.saved_tensors, ctx.params, dy, G, "colsum", dy)
         G.done()
-        return grads + (None, None, None, None, None, None, None, None, None)
-
-
-class _FFNBlock(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, w1, b1, w2, b2, impl, act="gelu"):
-        y, saved = _ffn_fwd(x, w1, b1, w2, b2, impl, act=act)
-        ctx.save_for_backward(*saved)
-        ctx.params, ctx.impl, ctx.act = (w1, b1, w2, b2), impl, act
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        G = _Grads()
-        grads = _ffn_bwd(ctx.saved_tensors, ctx.params, dy.contiguous().to(torch.bfloat16), G, impl=ctx.impl,
-                         act=ctx.act)
-        G.done()
-        return grads + (None, None)
+        return _input_grads(ctx, *grads)
 
 
 class _LayerNorm(torch.autograd.Function):
@@ -597,89 +633,46 @@ class _LayerNorm(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         G = _Grads()
-        dx, dg, db, _ = _ln_bwd(ctx.saved_tensors, ctx.beta, dy.contiguous().to(torch.bfloat16), G)
+        dx, dg, db, _, _ = _ln_bwd(ctx.saved_tensors, ctx.beta, _bf16_grad(dy), G)
         G.done()
-        return dx, dg, db, None
+        return _input_grads(ctx, dx, dg, db)
 
 
-class _AttentionLNBlock(torch.autograd.Function):
-    """LN(attention_block(x)) as one node: the LayerNorm backward also emits the out-proj bias
-    gradient (column sums of its dx), so no separate pass over dy."""
+def _sublayer_fwd(core, x, res, params, gamma, beta, eps, drop):
+    """z = drop(core(x)) + res and Norm(z), the forward of both block nodes: (z, Norm(z), what the core saves,
+    what the norm saves). Without ``drop`` the core's last linear adds ``res`` in its epilogue and the norm kernel
+    normalises; with ``drop`` = (p, seed, site, rank) the dropout_add norm kernel drops, adds and normalises, and
+    its bf16 sum z takes the saved slot the GEMM output has without dropout."""
+    if drop is None:
+        z, s1 = core.fwd(x, params, res)
+        y, s2 = _norm_fwd(z, gamma, beta, eps)
+    else:
+        y0, s1 = core.fwd(x, params, None)
+        y, s2 = _dropout_add_norm_fwd(y0, res, gamma, beta, eps, drop)
+    return s2[0], y, s1, s2
+
+
+class _PostNormBlock(torch.autograd.Function):
+    """x -> Norm(drop(core(x)) + x) as one node: the norm backward also emits the bias gradient of the core's last
+    linear (column sums of its dx), so no separate pass over dy. Under ``drop`` its dx is the gradient of the
+    residual x and its masked, scaled copy DXM the last linear's dY."""
 
     @staticmethod
-    def forward(ctx, x, wqkv, bqkv, wo, bo, gamma, beta, lens, B, S, H, eps, impl, drop=None, attn_drop=None,
-                cu_seqlens=None, causal=False, rope=None):
-        if drop is None:
-            a, s1 = _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl, attn_drop=attn_drop, cu_seqlens=cu_seqlens,
-                              causal=causal, rope=rope, kv_heads=_kv_heads(wqkv, H))
-            y, s2 = _ln_fwd(a, gamma, beta, eps)
-        else:  # LN(dropout(out-proj) + x): dropout and the residual add inside the LayerNorm kernel
-            a, s1 = _attn_fwd(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl, residual=False, attn_drop=attn_drop,
-                              cu_seqlens=cu_seqlens, causal=causal, rope=rope, kv_heads=_kv_heads(wqkv, H))
-            y, s2 = _dropout_add_ln_fwd(a, x, gamma, beta, eps, drop)
+    def forward(ctx, x, w1, b1, w2, b2, gamma, beta, eps, core, drop):
+        params = (w1, b1, w2, b2)
+        _, y, s1, s2 = _sublayer_fwd(core, x, x, params, gamma, beta, eps, drop)
         ctx.save_for_backward(*s1, *s2)
-        ctx.params, ctx.beta, ctx.impl = (wqkv, bqkv, wo, bo), beta, impl
-        ctx.lens, ctx.dims, ctx.drop, ctx.attn_drop, ctx.cu = lens, (B, S, H), drop, attn_drop, cu_seqlens
-        ctx.causal, ctx.rope = causal, rope
+        ctx.params, ctx.beta, ctx.core, ctx.drop = params, beta, core, drop
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        t = ctx.saved_tensors
+        t, k = ctx.saved_tensors, ctx.core.n_saved
         G = _Grads()
-        if ctx.drop is None:
-            da, dg, db, dbo = _ln_bwd(t[4:], ctx.beta, dy.contiguous().to(torch.bfloat16), G,
-                                      dxsum_param=ctx.params[3])  # da = out-proj dY
-            dres = None
-        else:  # dres: gradient of the residual x; da = its masked, scaled copy, the out-proj dY
-            dres, dg, db, dbo, da = _ln_bwd(t[4:], ctx.beta, dy.contiguous().to(torch.bfloat16), G,
-                                            dxsum_param=ctx.params[3], drop=ctx.drop)
-        dx, dwqkv, dbqkv, dwo, dbo = _attn_bwd(t[:4], ctx.params, ctx.lens, *ctx.dims, da, G, dbo=dbo,
-                                               impl=ctx.impl, dres=dres, attn_drop=ctx.attn_drop, cu_seqlens=ctx.cu,
-                                               causal=ctx.causal, rope=ctx.rope,
-                                               kv_heads=_kv_heads(ctx.params[0], ctx.dims[2]))
+        dz, dg, db, dbl, dxm = _norm_bwd(t[k:], ctx.beta, _bf16_grad(dy), G, dxsum_param=ctx.params[3], drop=ctx.drop)
+        grads = ctx.core.bwd(t[:k], ctx.params, dz if ctx.drop is None else dxm, G, dbl, dz)
         G.done()
-        return dx, dwqkv, dbqkv, dwo, dbo, dg, db, None, None, None, None, None, None, None, None, None, None, None
-
-
-class _FFNLNBlock(torch.autograd.Function):
-    """LN(ffn_block(x)) as one node (FFN2 bias gradient fused into the LayerNorm backward)."""
-
-    @staticmethod
-    def forward(ctx, x, w1, b1, w2, b2, gamma, beta, eps, impl, drop=None, act="gelu"):
-        if drop is None:
-            f, s1 = _ffn_fwd(x, w1, b1, w2, b2, impl, act=act)
-            y, s2 = _ln_fwd(f, gamma, beta, eps)
-        else:  # LN(dropout(FFN2) + x)
-            f, s1 = _ffn_fwd(x, w1, b1, w2, b2, impl, residual=False, act=act)
-            y, s2 = _dropout_add_ln_fwd(f, x, gamma, beta, eps, drop)
-        ctx.save_for_backward(*s1, *s2)
-        ctx.params, ctx.beta, ctx.impl, ctx.drop, ctx.act = (w1, b1, w2, b2), beta, impl, drop, act
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        t = ctx.saved_tensors
-        G = _Grads()
-        if ctx.drop is None:
-            df, dg, db, db2 = _ln_bwd(t[3:], ctx.beta, dy.contiguous().to(torch.bfloat16), G,
-                                      dxsum_param=ctx.params[3])  # df = FFN2 dY
-            dres = None
-        else:
-            dres, dg, db, db2, df = _ln_bwd(t[3:], ctx.beta, dy.contiguous().to(torch.bfloat16), G,
-                                            dxsum_param=ctx.params[3], drop=ctx.drop)
-        dx, dw1, db1, dw2, db2 = _ffn_bwd(t[:3], ctx.params, df, G, db2=db2, impl=ctx.impl, dres=dres, act=ctx.act)
-        G.done()
-        return dx, dw1, db1, dw2, db2, dg, db, None, None, None, None
-
-
-def _bf16_grad(g):
-    return None if g is None else g.contiguous().to(torch.bfloat16)
-
-
-def _zero_grad_like(saved_norm):
-    x = saved_norm[0]
-    return torch.zeros_like(x)
+        return _input_grads(ctx, *grads, dg, db)
 
 
 class _StreamNorm(torch.autograd.Function):
@@ -697,85 +690,40 @@ class _StreamNorm(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dh, dn):
         if dn is None:
-            return dh, None, None, None
+            return _input_grads(ctx, dh)
         G = _Grads()
         dx, dg, db, _, _ = _norm_bwd(ctx.saved_tensors, ctx.beta, _bf16_grad(dn), G, dres=_bf16_grad(dh))
         G.done()
-        return dx, dg, db, None
+        return _input_grads(ctx, dx, dg, db)
 
 
-class _PreAttentionBlock(torch.autograd.Function):
-    """One pre-norm attention sub-layer as a node (h, n) -> (h', n'): h' = h + drop(Out(Attn(QKV(n)))) and
-    n' = Norm(h') under the NEXT sub-layer's norm weights. Forward: the out-projection adds h in its epilogue
-    and the norm kernel normalises (with ``drop``: the dropout_add norm kernel writes both h' and n').
-    Backward of (dh', dn'): the norm backward with DRES = dh' gives the total stream gradient, which is the
-    residual's gradient and the out-projection's dY (its masked copy DXM under dropout), with that linear's
-    bias gradient as the fused column sums; the QKV dgrad then yields dn with nothing added."""
+class _PreNormBlock(torch.autograd.Function):
+    """One pre-norm sub-layer as a node (h, n) -> (h', n'): h' = h + drop(core(n)) and n' = Norm(h') under the NEXT
+    sub-layer's norm weights. Forward: the core's last linear adds h in its epilogue and the norm kernel normalises
+    (with ``drop``: the dropout_add norm kernel writes both h' and n'). Backward of (dh', dn'): the norm backward
+    with DRES = dh' gives the total stream gradient, which is the residual's gradient and the last linear's dY (its
+    masked copy DXM under dropout), with that linear's bias gradient as the fused column sums; the core's first
+    dgrad then yields dn with nothing added."""
 
     @staticmethod
-    def forward(ctx, h, n, wqkv, bqkv, wo, bo, gamma, beta, lens, B, S, H, eps, impl, drop=None, attn_drop=None,
-                cu_seqlens=None, causal=False, rope=None):
-        if drop is None:
-            h2, s1 = _attn_fwd(n, wqkv, bqkv, wo, bo, lens, B, S, H, impl, attn_drop=attn_drop, cu_seqlens=cu_seqlens,
-                               causal=causal, rope=rope, res=h, kv_heads=_kv_heads(wqkv, H))
-            n2, s2 = _norm_fwd(h2, gamma, beta, eps)
-        else:
-            a, s1 = _attn_fwd(n, wqkv, bqkv, wo, bo, lens, B, S, H, impl, residual=False, attn_drop=attn_drop,
-                              cu_seqlens=cu_seqlens, causal=causal, rope=rope, kv_heads=_kv_heads(wqkv, H))
-            n2, s2 = _dropout_add_norm_fwd(a, h, gamma, beta, eps, drop)
-            h2 = s2[0]
+    def forward(ctx, h, n, w1, b1, w2, b2, gamma, beta, eps, core, drop):
+        params = (w1, b1, w2, b2)
+        h2, n2, s1, s2 = _sublayer_fwd(core, n, h, params, gamma, beta, eps, drop)
         ctx.save_for_backward(*s1, *s2)
-        ctx.params, ctx.beta, ctx.impl = (wqkv, bqkv, wo, bo), beta, impl
-        ctx.lens, ctx.dims, ctx.drop, ctx.attn_drop, ctx.cu = lens, (B, S, H), drop, attn_drop, cu_seqlens
-        ctx.causal, ctx.rope = causal, rope
+        ctx.params, ctx.beta, ctx.core, ctx.drop = params, beta, core, drop
         ctx.set_materialize_grads(False)
         return h2, n2
 
     @staticmethod
     def backward(ctx, dh2, dn2):
-        t = ctx.saved_tensors
+        t, k = ctx.saved_tensors, ctx.core.n_saved
         G = _Grads()
-        dn2 = _zero_grad_like(t[4:]) if dn2 is None else _bf16_grad(dn2)
-        dh, dg, db, dbo, dxm = _norm_bwd(t[4:], ctx.beta, dn2, G, dxsum_param=ctx.params[3], drop=ctx.drop,
+        dn2 = torch.zeros_like(t[k]) if dn2 is None else _bf16_grad(dn2)
+        dh, dg, db, dbl, dxm = _norm_bwd(t[k:], ctx.beta, dn2, G, dxsum_param=ctx.params[3], drop=ctx.drop,
                                          dres=_bf16_grad(dh2))
-        da = dh if ctx.drop is None else dxm
-        dn, dwqkv, dbqkv, dwo, dbo = _attn_bwd(t[:4], ctx.params, ctx.lens, *ctx.dims, da, G, dbo=dbo, impl=ctx.impl,
-                                               attn_drop=ctx.attn_drop, cu_seqlens=ctx.cu, causal=ctx.causal,
-                                               rope=ctx.rope, residual=False,
-                                               kv_heads=_kv_heads(ctx.params[0], ctx.dims[2]))
+        dn, *grads = ctx.core.bwd(t[:k], ctx.params, dh if ctx.drop is None else dxm, G, dbl, None)
         G.done()
-        return (dh, dn, dwqkv, dbqkv, dwo, dbo, dg, db) + (None,) * 11
-
-
-class _PreFFNBlock(torch.autograd.Function):
-    """The pre-norm FFN sub-layer (h, n) -> (h', n'), see _PreAttentionBlock."""
-
-    @staticmethod
-    def forward(ctx, h, n, w1, b1, w2, b2, gamma, beta, eps, impl, drop=None, act="gelu"):
-        if drop is None:
-            h2, s1 = _ffn_fwd(n, w1, b1, w2, b2, impl, res=h, act=act)
-            n2, s2 = _norm_fwd(h2, gamma, beta, eps)
-        else:
-            f, s1 = _ffn_fwd(n, w1, b1, w2, b2, impl, residual=False, act=act)
-            n2, s2 = _dropout_add_norm_fwd(f, h, gamma, beta, eps, drop)
-            h2 = s2[0]
-        ctx.save_for_backward(*s1, *s2)
-        ctx.params, ctx.beta, ctx.impl, ctx.drop, ctx.act = (w1, b1, w2, b2), beta, impl, drop, act
-        ctx.set_materialize_grads(False)
-        return h2, n2
-
-    @staticmethod
-    def backward(ctx, dh2, dn2):
-        t = ctx.saved_tensors
-        G = _Grads()
-        dn2 = _zero_grad_like(t[3:]) if dn2 is None else _bf16_grad(dn2)
-        dh, dg, db, db2, dxm = _norm_bwd(t[3:], ctx.beta, dn2, G, dxsum_param=ctx.params[3], drop=ctx.drop,
-                                         dres=_bf16_grad(dh2))
-        df = dh if ctx.drop is None else dxm
-        dn, dw1, db1, dw2, db2 = _ffn_bwd(t[:3], ctx.params, df, G, db2=db2, impl=ctx.impl, residual=False,
-                                          act=ctx.act)
-        G.done()
-        return (dh, dn, dw1, db1, dw2, db2, dg, db) + (None,) * 4
+        return _input_grads(ctx, dh, dn, *grads, dg, db)
 
 
 class _Embeddings(torch.autograd.Function):
@@ -877,6 +825,27 @@ def _mark_training(impl) -> None:
         type(impl).training = torch.is_grad_enabled()
 
 
+def block(core: _Core, x, params):
+    """core(x) + x as one node; ``params`` = (w_first, b_first, w_last, b_last)."""
+    _mark_training(core.impl)
+    return _Block.apply(x, *params, core)
+
+
+def post_norm_block(core: _Core, x, params, norm, drop=None):
+    """Norm(drop(core(x)) + x) as one node. ``norm`` = (gamma, beta, eps) of the norm that closes the sub-layer.
+    ``drop`` = (p, seed, site, rank): hidden dropout on the last linear's output, before the residual add, fused
+    into the norm kernels (mask: ops/dropout.py; indexed by packed row for a packed batch). None: no dropout."""
+    _mark_training(core.impl)
+    return _PostNormBlock.apply(x, *params, *norm, core, drop)
+
+
+def pre_norm_block(core: _Core, h, n, params, norm, drop=None):
+    """(h, n) -> (h + drop(core(n)), Norm(that sum)) as one node; ``norm`` = (gamma, beta or None: RMSNorm, eps) of
+    the norm that FOLLOWS. ``drop`` as in post_norm_block."""
+    _check_bf16_only(core.impl, pre_norm=True)
+    return _PreNormBlock.apply(h, n, *params, *norm, core, drop)
+
+
 def attention_block(x, wqkv, bqkv, wo, bo, lens: Optional[torch.Tensor], B: int, S: int, H: int, impl=BF16,
                     attn_drop=None, cu_seqlens: Optional[torch.Tensor] = None, causal: bool = False, rope=None):
     """``attn_drop`` = (p, seed, site, rank): attention-probability dropout inside the flash attention
@@ -892,44 +861,33 @@ def attention_block(x, wqkv, bqkv, wo, bo, lens: Optional[torch.Tensor], B: int,
     ``rope`` = (table fp32 [P, 32, 2], pos): rotary positions (ops/rope.py), q and k rotated in place after the
     QKV GEMM by ``C.rope_qk`` and dQKV rotated back in the backward; ``pos`` is None for a padded batch
     (position = row % S) or the packed batch's int32 positions, one per row of x. bf16 linears only."""
-    _mark_training(impl)
-    return _AttentionBlock.apply(x, wqkv, bqkv, wo, bo, lens, B, S, H, impl, attn_drop, cu_seqlens, causal, rope)
+    spec = attn_spec(wqkv, lens, B, S, H, attn_drop, cu_seqlens, causal, rope)
+    return block(attn_core(spec, impl), x, (wqkv, bqkv, wo, bo))
 
 
 def ffn_block(x, w1, b1, w2, b2, impl=BF16, act: str = "gelu"):
     """``act``: ``"gelu"``, or ``"swiglu"`` (``w1`` [2F, h], ``b1`` [2F]: gate rows, then up rows; ops/swiglu.py;
     bf16 linears only)."""
-    _mark_training(impl)
-    return _FFNBlock.apply(x, w1, b1, w2, b2, impl, act)
+    return block(ffn_core(act, impl), x, (w1, b1, w2, b2))
 
 
 def attention_ln_block(x, wqkv, bqkv, wo, bo, gamma, beta, lens: Optional[torch.Tensor], B: int, S: int, H: int,
                        eps: float, impl=BF16, drop=None, attn_drop=None, cu_seqlens: Optional[torch.Tensor] = None,
                        causal: bool = False, rope=None):
-    """``drop`` = (p, seed, site, rank): hidden dropout on the out-projection's output, before the
-    residual add, fused into the LayerNorm kernels (mask: ops/dropout.py). None: no dropout.
-    ``attn_drop`` = (p, seed, site, rank): attention-probability dropout (see attention_block).
-    ``cu_seqlens``: packed batch, with fewer than PACK_ROW_MULTIPLE tail rows (see attention_block);
-    hidden-dropout masks are indexed by packed row. ``causal``, ``rope``: see attention_block."""
-    _mark_training(impl)
-    return _AttentionLNBlock.apply(x, wqkv, bqkv, wo, bo, gamma, beta, lens, B, S, H, eps, impl, drop, attn_drop,
-                                   cu_seqlens, causal, rope)
+    """post_norm_block around the attention core. ``drop``: hidden dropout on the out-projection's output.
+    ``attn_drop``, ``causal``, ``rope``: see attention_block. ``cu_seqlens``: packed batch, with fewer than
+    PACK_ROW_MULTIPLE tail rows (see attention_block)."""
+    spec = attn_spec(wqkv, lens, B, S, H, attn_drop, cu_seqlens, causal, rope)
+    return post_norm_block(attn_core(spec, impl), x, (wqkv, bqkv, wo, bo), (gamma, beta, eps), drop)
 
 
 def ffn_ln_block(x, w1, b1, w2, b2, gamma, beta, eps: float, impl=BF16, drop=None, act: str = "gelu"):
-    """``drop`` = (p, seed, site, rank): hidden dropout on FFN2's output (see attention_ln_block). ``act``: see
-    ffn_block."""
-    _mark_training(impl)
-    return _FFNLNBlock.apply(x, w1, b1, w2, b2, gamma, beta, eps, impl, drop, act)
+    """post_norm_block around the FFN core. ``drop``: hidden dropout on FFN2's output. ``act``: see ffn_block."""
+    return post_norm_block(ffn_core(act, impl), x, (w1, b1, w2, b2), (gamma, beta, eps), drop)
 
 
 def layer_norm(x, gamma, beta, eps: float):
     return _LayerNorm.apply(x, gamma, beta, eps)
-
-
-def _pre_norm_impl(impl):
-    if impl is not BF16:
-        raise ValueError("pre-norm blocks run the bf16 linears only")
 
 
 def stream_norm(h, gamma, beta, eps: float):
@@ -945,16 +903,14 @@ def pre_attention_block(h, n, wqkv, bqkv, wo, bo, gamma, beta, lens: Optional[to
     """The pre-norm attention sub-layer: (h, n) -> (h + drop(Out(Attn(QKV(n)))), Norm(that sum)) where
     ``gamma`` / ``beta`` (None: RMSNorm) are the weights of the norm that FOLLOWS (the layer's ``ln2``).
     Every other argument as in attention_ln_block."""
-    _pre_norm_impl(impl)
-    return _PreAttentionBlock.apply(h, n, wqkv, bqkv, wo, bo, gamma, beta, lens, B, S, H, eps, impl, drop, attn_drop,
-                                    cu_seqlens, causal, rope)
+    spec = attn_spec(wqkv, lens, B, S, H, attn_drop, cu_seqlens, causal, rope)
+    return pre_norm_block(attn_core(spec, impl), h, n, (wqkv, bqkv, wo, bo), (gamma, beta, eps), drop)
 
 
 def pre_ffn_block(h, n, w1, b1, w2, b2, gamma, beta, eps: float, impl=BF16, drop=None, act: str = "gelu"):
     """The pre-norm FFN sub-layer: (h, n) -> (h + drop(FFN2(gelu(FFN1(n)))), Norm(that sum)); ``gamma`` / ``beta``
     belong to the next layer's ``ln1``, or to the final norm after the last layer. ``act``: see ffn_block."""
-    _pre_norm_impl(impl)
-    return _PreFFNBlock.apply(h, n, w1, b1, w2, b2, gamma, beta, eps, impl, drop, act)
+    return pre_norm_block(ffn_core(act, impl), h, n, (w1, b1, w2, b2), (gamma, beta, eps), drop)
 
 
 class _Dropout(torch.autograd.Function):

@@ -292,7 +292,7 @@ def test_native_blocks_reject_rotary_with_fp8():
         pass
 
     with pytest.raises(ValueError, match="rotary"):
-        T._attn_fwd(None, None, None, None, None, None, 1, 1, 1, impl=NotBf16(), rope=(None, None))
+        T._attn_fwd(None, (None, None, None, None), None, T.AttnSpec(1, 1, 1, rope=(None, None)), impl=NotBf16())
 
 
 # ------------------------------------------------------------------------------------------------ the CLI
