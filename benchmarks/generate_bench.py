@@ -33,6 +33,11 @@ blocks (``BertConfig.pre_ln`` / ``norm``); the records carry ``"pre_ln"`` and ``
 with grouped-query attention (``BertConfig.kv_heads``); the model records then carry ``"kv_heads"``. ``--ffn swiglu``
 (``--intermediate F``) builds it with the gated feed-forward; the records carry ``"ffn"``, ``"intermediate"`` and, in
 the sampler A/B, ``"decode_glu"`` (``MLT_DECODE_GLU``: 0 = FFN1 and the gate as two launches).
+``--max-position P`` builds the model with ``BertConfig.max_position = P`` (with ``--rotary``: the rows of the table, so
+``--prompt`` + ``--new`` may reach P). ``--split-ab`` alternates two captured graphs of the device-sampler loop in one
+process, one captured under ``MLT_DECODE_SPLIT=0`` (the single decode attention kernel) and one under ``1`` (split +
+merge where ``ops.decode.decode_attn_path`` routes the cache there): medians, spreads, prefill outside the timed region.
+    python benchmarks/generate_bench.py --rotary --max-position 4224 --prompt 4096 --new 128 --split-ab --repeats 5
 Random weights and prompts (no network)."""
 from __future__ import annotations
 
@@ -69,6 +74,8 @@ def _model(args, dev):
         over["ffn"] = args.ffn
     if args.intermediate is not None:
         over["intermediate"] = args.intermediate
+    if args.max_position is not None:
+        over["max_position"] = args.max_position
     return BertLMHeadModel(bert_config(args.model, **over)).to(dev).eval()
 
 
@@ -205,6 +212,42 @@ def bench_sampler_ab(args, dev):
     return recs
 
 
+def bench_split_ab(args, dev):
+    """The graph-replayed token loop with the decode attention captured as the single kernel (MLT_DECODE_SPLIT=0) and
+    as routed (1), alternated in one process. ``GraphedDecoder`` reads the variable while capturing."""
+    from ml_trainer_amd.models.bert import GraphedDecoder
+    from ml_trainer_amd.ops.decode import decode_attn_path
+    m = _model(args, dev)
+    V, P, N = m.config.vocab_size, args.prompt, args.new
+    params = m._sampler_params(0.8, 50, 0.9, None, 1)
+    recs = []
+    for B in [int(b) for b in args.batch.split(",")]:
+        ids = torch.randint(5, V, (B, P), device=dev)
+        decs, paths = {}, {}
+        for s in ("0", "1"):
+            os.environ["MLT_DECODE_SPLIT"] = s
+            decs[s], paths[s] = GraphedDecoder(m, B, P + N, N, dev, m._decode_signature()), decode_attn_path(P + N)
+        t = {s: [] for s in decs}
+        for r in range(args.repeats + 1):  # round 0 is the warm-up
+            for s, dec in decs.items():
+                os.environ["MLT_DECODE_SPLIT"] = s  # the eager step of start() takes the path of its graph
+                z = dec.start(m, ids, None, params)
+                ms = _sync_ms(lambda: dec.run(m, z)) / (N - 1)
+                if r:
+                    t[s].append(ms)
+        os.environ.pop("MLT_DECODE_SPLIT")
+        rec = {"bench": "generate_split_ab", "model": args.model, "rotary": bool(args.rotary), "kv_heads": args.kv_heads,
+               "batch": B, "prompt": P, "new": N, "smax": P + N}
+        for s in decs:
+            rec.update({f"split{s}_path": paths[s], f"split{s}_ms_per_token": statistics.median(t[s]),
+                        f"split{s}_spread": _spread(t[s]), f"split{s}_runs": t[s]})
+        print(json.dumps(rec), flush=True)
+        recs.append(rec)
+        del decs
+        torch.cuda.empty_cache()
+    return recs
+
+
 def bench_sampler_kernel(args, dev):
     from ml_trainer_amd.ops import decode as DC
     V, Vp, reps = 30522, 30720, 200
@@ -336,6 +379,9 @@ def main():
     ap.add_argument("--sampler-ab", action="store_true",
                     help="alternate (eager, torch sampler), (eager, device sampler), (graph, device sampler)")
     ap.add_argument("--rotary", action="store_true", help="rotary positions in the model timings")
+    ap.add_argument("--max-position", type=int, default=None, help="BertConfig.max_position (with --rotary: table rows)")
+    ap.add_argument("--split-ab", action="store_true",
+                    help="alternate graphs captured under MLT_DECODE_SPLIT=0 / 1 (the device-sampler loop)")
     ap.add_argument("--ffn", choices=["gelu", "swiglu"], default="gelu",
                     help="BertConfig.ffn: the GELU or the gated SwiGLU feed-forward (records carry ffn)")
     ap.add_argument("--intermediate", type=int, default=None, help="BertConfig.intermediate (records carry it)")
@@ -352,7 +398,9 @@ def main():
     dev = torch.device("cuda", 0)
     if args.graph and args.sampler != "device":
         raise SystemExit("--graph needs --sampler device")
-    if args.sampler_kernel or args.sampler_ab:
+    if args.split_ab:
+        recs = bench_split_ab(args, dev)
+    elif args.sampler_kernel or args.sampler_ab:
         recs = bench_sampler_kernel(args, dev) if args.sampler_kernel else bench_sampler_ab(args, dev)
     else:
         recs = bench_linear(args, dev) if args.linear else bench_kernel(args, dev) if args.kernel else bench_model(args, dev)

@@ -29,17 +29,25 @@ def main(argv=None):
     p.add_argument("--top_k", type=int, default=None)
     p.add_argument("--lr", type=float, default=1e-3)
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--max_position", type=int, default=None,
+                   help="train with rotary positions and a table of this many rows: --new may then run past --seq_len, "
+                        "up to --prompt_len + --new = max_position (from 2048 rows the cache is long enough for the "
+                        "split decode attention kernels)")
     args = p.parse_args(argv)
-    if args.prompt_len + args.new > args.seq_len:
-        raise ValueError("--prompt_len + --new must not exceed --seq_len")
+    if args.prompt_len > args.seq_len or args.prompt_len + args.new > (args.max_position or args.seq_len):
+        raise ValueError("--prompt_len must not exceed --seq_len, --prompt_len + --new neither --seq_len nor, when "
+                         "given, --max_position")
     from ml_trainer_amd.data.text import SyntheticCausalLM
     from ml_trainer_amd.models import build_model
     from ml_trainer_amd.trainer import Trainer
     torch.manual_seed(args.seed)
-    model = build_model("bert-tiny", task="clm")
+    over = {} if args.max_position is None else dict(rotary=True, max_position=args.max_position)
+    model = build_model("bert-tiny", task="clm", **over)
     V = model.config.vocab_size
     train = SyntheticCausalLM(args.steps * args.batch_size, seq_len=args.seq_len, vocab_size=V, seed=args.seed)
-    val = SyntheticCausalLM(args.rows, seq_len=args.seq_len, vocab_size=V, seed=args.seed + 1)
+    # validation rows as long as the continuation: with --max_position it runs past the training length
+    val = SyntheticCausalLM(args.rows, seq_len=max(args.seq_len, args.prompt_len + args.new), vocab_size=V,
+                            seed=args.seed + 1)
     tr = Trainer(model, datasets=(train, val), epochs=1, batch_size=args.batch_size, optimizer="adamw", lr=args.lr,
                  criterion="clm", metric="accuracy", is_parallel=False, options={"progress": False})
     for i in range(args.steps):

@@ -92,6 +92,9 @@ def build_model_and_datasets(args):
         raise ValueError("--rotary / --rope_base apply to the BERT models; the LeNet models have no positions")
     if args.rope_base is not None and not args.rotary:
         raise ValueError("--rope_base applies to --rotary")
+    if args.max_position is not None and (not args.rotary or args.max_position < 1):
+        raise ValueError("--max_position applies to --rotary (a learned position table is as long as it was trained) "
+                         "and must be positive")
     if args.rope_base is not None and not args.rope_base > 0:
         raise ValueError(f"--rope_base must be > 0, got {args.rope_base}")
     if lenet and (args.pre_ln or args.norm != "layernorm"):
@@ -135,6 +138,8 @@ def build_model_and_datasets(args):
         over["rotary"] = True
         if args.rope_base is not None:
             over["rope_base"] = args.rope_base
+        if args.max_position is not None:
+            over["max_position"] = args.max_position
     if args.pre_ln:
         over["pre_ln"] = True
         over["norm"] = args.norm
@@ -156,9 +161,11 @@ def build_model_and_datasets(args):
         from ml_trainer_amd.data.text import SyntheticTextClassification
         c = model.config
         seq = min(args.seq_len, c.max_position)
-        if args.generate and args.prompt_len + args.generate > seq:
+        # a rotary model with --max_position generates past the training length, up to the table's rows
+        limit = c.max_position if args.max_position is not None else seq
+        if args.generate and (args.prompt_len > seq or args.prompt_len + args.generate > limit):
             raise ValueError(f"--prompt_len + --generate = {args.prompt_len + args.generate} exceeds the sequence "
-                             f"length {seq}")
+                             f"length {limit} (--prompt_len at most {seq})")
         n = args.synthetic_size or 4096
         var = {} if args.min_seq_len is None else {"min_len": min(args.min_seq_len, seq), "pad_id": pad_id}
         if clm:
@@ -292,6 +299,11 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--rope_base", type=float, default=None,
                         help="--rotary: the base of the angles, position p and pair i turn by "
                              "p * base ** (-2 i / 64) (default: 10000)")
+    parser.add_argument("--max_position", type=int, default=None,
+                        help="--rotary: rows of the rotary table = the longest sequence the model can be run at "
+                             "(default: the preset's). It may exceed --seq_len: --generate then continues past the "
+                             "training length, up to --prompt_len + --generate = max_position; from 2048 cache rows "
+                             "a decode step's attention takes the split kernels (MLT_DECODE_SPLIT=0: the single one)")
     parser.add_argument("--pre_ln", action="store_true",
                         help="BERT, any --task: pre-norm blocks h + f(norm(h)) and a final norm (final_ln) instead "
                              "of the post-LN blocks (not with the fp8 `large` preset). An error for the LeNet models")

@@ -1356,6 +1356,61 @@ void attn_decode_gqa(Tensor qkv_new, Tensor kv, Tensor pos, Tensor out, int64_t 
                          rp, (int)gc);
 }
 
+// The workspace of attn_decode_split for a cache of Smax rows: fp32 [B, H, ceil(Smax / C), 68] (attn_decode_split.hip).
+std::vector<int64_t> attn_decode_split_ws(int64_t B, int64_t H, int64_t Smax) {
+  TORCH_CHECK(B > 0 && H > 0 && Smax >= 1, "attn_decode_split_ws: B, H and Smax must be positive");
+  const int64_t C = attn_decode_split_keys();
+  return {B, H, (Smax + C - 1) / C, 68};
+}
+
+// attn_decode / attn_decode_gqa for long caches (attn_decode_split.hip): the cached keys split over workgroups,
+// C = attn_decode_split_keys() each, and a merge launch. kv [2, B, Hkv, Smax, 64], Hkv = kv.size(2) a divisor of H
+// (Hkv == H: multi-head, qkv_new [B, 3 * H * 64]). The checks are attn_decode_gqa's; ws is a contiguous fp32 device
+// tensor of the shape attn_decode_split_ws(B, H, Smax), 16-byte aligned; it needs no initialisation and holds
+// nothing the caller may rely on afterwards. Everything is checked before the first launch.
+void attn_decode_split(Tensor qkv_new, Tensor kv, Tensor pos, Tensor out, Tensor ws, int64_t H, double scale,
+                       c10::optional<Tensor> rope, int64_t gc) {
+  TORCH_CHECK(qkv_new.is_cuda() && qkv_new.dim() == 2 && qkv_new.scalar_type() == at::kBFloat16,
+              "attn_decode_split: qkv_new must be a bf16 [B, (H + 2 Hkv) * 64] device tensor");
+  const int64_t B = qkv_new.size(0), D = H * 64;
+  TORCH_CHECK(B > 0 && H > 0 && B <= 65535 && H <= 65535, "attention dims");
+  check_dev(kv, "kv", at::kBFloat16, 0);
+  TORCH_CHECK(kv.dim() == 5 && kv.size(0) == 2 && kv.size(1) == B && kv.size(2) >= 1 && kv.size(3) >= 1 &&
+                  kv.size(4) == 64,
+              "attn_decode_split: kv must be [2, B, Hkv, Smax, 64] with B = ", B);
+  const int64_t Hkv = kv.size(2), Smax = kv.size(3), W = (H + 2 * Hkv) * 64;
+  TORCH_CHECK(Hkv <= H && H % Hkv == 0, "attn_decode_split: the cache holds ", Hkv, " key/value heads, which does not ",
+              "divide H = ", H);
+  TORCH_CHECK(qkv_new.size(1) == W, "attn_decode_split: qkv_new has ", qkv_new.size(1),
+              " columns, expected (H + 2 Hkv) * 64 = ", W);
+  TORCH_CHECK(qkv_new.stride(1) == 1 && qkv_new.stride(0) >= W && qkv_new.stride(0) % 8 == 0,
+              "attn_decode_split: qkv_new needs unit column stride and a row stride that is a multiple of 8");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(qkv_new.data_ptr()) % 16 == 0, "qkv_new must be 16-byte aligned");
+  TORCH_CHECK(kv.numel() == 2 * B * Hkv * Smax * 64 && Smax <= 0x7fffffff, "attn_decode_split: kv size");
+  check_dev(pos, "pos", at::kInt, B, 4);
+  TORCH_CHECK(pos.numel() == B, "attn_decode_split: pos must have one entry per sequence");
+  check_bf16_2d(out, "out", B, D);
+  const std::vector<int64_t> shape = attn_decode_split_ws(B, H, Smax);
+  TORCH_CHECK(shape[2] <= 65535 && B * H <= 0x7fffffff, "attn_decode_split: ", shape[2], " splits x ", B * H,
+              " heads exceed the grid");
+  check_dev(ws, "ws", at::kFloat, 0, 16);
+  TORCH_CHECK(ws.sizes().vec() == shape, "attn_decode_split: ws has shape ", ws.sizes(), ", expected ",
+              at::IntArrayRef(shape), " (attn_decode_split_ws)");
+  const float* rp = nullptr;
+  if (rope.has_value()) {
+    check_dev(*rope, "rope table", at::kFloat, 64, 16);
+    TORCH_CHECK(rope->dim() == 3 && rope->size(1) == 32 && rope->size(2) == 2 && rope->size(0) >= Smax,
+                "attn_decode_split: the rope table must be [P >= Smax = ", Smax, ", 32, 2]");
+    rp = rope->data_ptr<float>();
+  }
+  const int64_t G = H / Hkv;
+  TORCH_CHECK(gc == 0 || ((gc == 1 || gc == 2 || gc == 3 || gc == 4 || gc == 6 || gc == 8) && G % gc == 0),
+              "attn_decode_split: gc = ", gc, " must be 0 or one of 1, 2, 3, 4, 6, 8 that divides H / Hkv = ", G);
+  launch_attn_decode_split(bf16_ptr(qkv_new), qkv_new.stride(0), (uint16_t*)kv.data_ptr(), pos.data_ptr<int>(),
+                           (uint16_t*)out.data_ptr(), ws.data_ptr<float>(), (int)B, (int)H, (int)Hkv, (int)Smax,
+                           (float)scale, cur_stream(), rp, (int)gc);
+}
+
 // The operands of gqa_expand / gqa_reduce (gqa.hip): compact bf16 [rows, (H + 2 Hkv) * 64], wide bf16
 // [rows, 3 * H * 64], both 2-D device tensors with unit column stride, a row stride that is a multiple of 8 and a
 // 16-byte aligned base (row-strided views pass).
@@ -2193,6 +2248,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_decode_gqa_chunk",
         [](int64_t G, int64_t Hkv, int64_t B) { return attn_decode_gqa_chunk((int)G, (int)Hkv, (int)B); }, py::arg("G"),
         py::arg("Hkv"), py::arg("B"));
+  m.def("attn_decode_split", &attn_decode_split, py::arg("qkv_new"), py::arg("kv"), py::arg("pos"), py::arg("out"),
+        py::arg("ws"), py::arg("H"), py::arg("scale"), py::arg("rope") = py::none(), py::arg("gc") = 0);
+  m.def("attn_decode_split_ws", &attn_decode_split_ws, py::arg("B"), py::arg("H"), py::arg("Smax"));
+  m.def("attn_decode_split_keys", []() { return (int64_t)attn_decode_split_keys(); });
   m.def("gqa_expand", &gqa_expand, py::arg("compact"), py::arg("wide"), py::arg("H"), py::arg("Hkv"));
   m.def("gqa_reduce", &gqa_reduce, py::arg("wide"), py::arg("compact"), py::arg("H"), py::arg("Hkv"));
   m.def("rope_qk", &rope_qk, py::arg("qkv"), py::arg("table"), py::arg("H"), py::arg("S"), py::arg("pos") = py::none(),

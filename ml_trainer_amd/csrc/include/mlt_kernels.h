@@ -439,6 +439,16 @@ int attn_decode_gqa_chunk(int G, int Hkv, int B);
 void launch_attn_decode_gqa(const uint16_t* qkv_new, int64_t ldq, uint16_t* kv, const int* pos, uint16_t* out, int B,
                             int H, int Hkv, int Smax, float scale, hipStream_t st, const float* rope = nullptr,
                             int gc = 0);
+// The same function for long caches (attn_decode_split.hip): the keys of a (batch, KV head) split over workgroups,
+// attn_decode_split_keys() = C of them each (a compile-time constant), and a second launch that merges the partial
+// states. Operands as launch_attn_decode_gqa (Hkv == H is multi-head attention: the compact row is then q | k | v),
+// plus ws fp32 [B][H][ceil(Smax / C)][68], 16-byte aligned, which needs no initialisation. Rows with pos[b] <= C
+// get the bits of the unsplit kernels; no bit depends on gc (0: attn_decode_gqa_chunk with B * ceil(Smax / C) in
+// place of B), on B or on Smax.
+int attn_decode_split_keys();
+void launch_attn_decode_split(const uint16_t* qkv_new, int64_t ldq, uint16_t* kv, const int* pos, uint16_t* out,
+                              float* ws, int B, int H, int Hkv, int Smax, float scale, hipStream_t st,
+                              const float* rope = nullptr, int gc = 0);
 // Grouped-query layouts around the flash attention kernels (gqa.hip). compact [rows][ldc >= 64 (H + 2 Hkv)], wide
 // [rows][ldw >= 3 * 64 H], both bf16, ld % 8 == 0, 16-byte aligned, H % Hkv == 0. expand: q copied, every k / v
 // head stored H / Hkv times (bitwise). reduce: dq copied, dk / dv summed over the group in ascending head order in

@@ -70,7 +70,10 @@ head-major cache (``ops.decode.KVCache``: ``[2, B, H, Smax, 64]`` per layer) and
 ``attn_decode`` kernel over the cache with the append fused in, out-projection + residual, LayerNorm, FFN,
 LayerNorm) and returns fp32 logits; ``generate`` loops it with greedy, temperature / top-k sampling and an EOS
 mask. The position of every sequence lives on the device (ragged prompts continue at their own length) and no
-step reads anything back. On the CPU the same runs in fp32 torch with an fp32 cache;
+step reads anything back. Over a cache of ``ops.decode.DECODE_SPLIT_MIN_SMAX`` rows or more the attention of a step is
+``C.attn_decode_split`` (the cached keys of a head split over workgroups, then a merge launch:
+``ops.decode.decode_attn_path``; ``MLT_DECODE_SPLIT=0`` keeps the single kernel). On the CPU the same runs in fp32
+torch with an fp32 cache;
 ``generate_reference`` / ``decode_logits_reference`` are the uncached oracle. Opt-in: ``sampler="device"`` (the
 ``sample_step`` kernel of ``ops.decode``: top-k / top-p and the EOS bookkeeping in one launch, integer-defined,
 independent of the batch), ``top_p``, and ``graph=True`` (``GraphedDecoder``: one captured graph of ``decode_step`` +
@@ -1102,7 +1105,8 @@ class BertLMHeadModel(BertForMaskedLM):
         it is decoded in. ``top_p`` (nucleus sampling inside the top-k set, applied as ``round(top_p * 65536) /
         65536``) needs it. ``graph=True`` (GPU, device sampler, no ``return_logits``) replays one captured graph
         of ``decode_step`` + ``sample_step`` per token (``GraphedDecoder``); the graph is captured on the first call
-        of a shape and again after a parameter changed, and ``MLT_DECODE_GEMM`` is read when it is captured."""
+        of a shape and again after a parameter changed, and ``MLT_DECODE_GEMM`` / ``MLT_DECODE_SPLIT`` are read when it is
+        captured."""
         self._check_generate(input_ids, max_new_tokens, temperature, top_k, top_p, sampler, graph, return_logits)
         B, S = input_ids.shape
         dev = input_ids.device
@@ -1166,8 +1170,9 @@ class GraphedDecoder:
     ``sample_step`` on the logits it returns: token t's sampling closes replay t, so a generation is one eager
     ``sample_step`` on the prompt's logits and ``T - 1`` replays. Captured on ONE side stream after one eager run
     of the body on it: the graph is a linear chain of kernel nodes, no branches. ``signature`` is the model's
-    ``_decode_signature()`` at capture; the model recaptures when it no longer matches. ``MLT_DECODE_GEMM`` is
-    read while capturing. Not supported: ``return_logits``, a graph for ``prefill``."""
+    ``_decode_signature()`` at capture; the model recaptures when it no longer matches. ``MLT_DECODE_GEMM`` and
+    ``MLT_DECODE_SPLIT`` (``ops.decode.decode_attn_path``: the split attention's two launches and its workspace are then
+    nodes and pool memory of the graph) are read while capturing. Not supported: ``return_logits``, a graph for ``prefill``."""
 
     def __init__(self, model, B, Smax, T, dev, signature):
         import time

@@ -8,7 +8,9 @@ has cached = the row its next token takes. Rows ``j > pos[b]`` are stale memory 
 ``attn_decode`` is the native kernel (csrc/kernels/attn_decode.hip: bf16 cache, the append of the new token
 fused in); ``attn_decode_reference`` the same function in plain fp32 torch (the CPU path and the oracle of the
 tests). ``fill_from_prefill`` copies a prompt's K / V out of the padded forward's QKV buffer with torch ops: once
-per layer per prompt, not a hot path.
+per layer per prompt, not a hot path. Over a long cache (``decode_attn_path``) ``attn_decode`` launches
+``C.attn_decode_split`` (csrc/kernels/attn_decode_split.hip): the cached keys of a head split over workgroups and a
+merge launch, so that the whole machine fetches the cache of a small batch.
 
 ``linear_small`` is the linear layer of a decode step (M = B rows): ``decode_linear_path`` sends it to the
 weight-streaming kernel ``C.gemm_skinny`` (csrc/kernels/gemm_skinny.hip) or to the planner's GEMM. With the skinny
@@ -41,6 +43,13 @@ ATTN_SCALE = 1.0 / 8.0  # 1/sqrt(head_dim = 64)
 # run-to-run spread. At 32 rows the vocabulary decoder ties (20.7 against 20.5 us), at 64 the decoder and FFN2
 # lose: every workgroup re-reads X from L2 (profiles/generate/README.md has the table).
 SKINNY_MAX_ROWS = 16
+# cache rows from which a decode step's attention takes the split kernels (decode_attn_path): the smallest measured
+# Smax (512, 2048, 8192, 32768; bert-base heads, Hkv 12 / 4 / 1) at which split + merge beat the single kernel at batch 1
+# AND at batch 8 by more than the single kernel's run-to-run spread. At 512 they lose everywhere (7.8 against 6.2 us at
+# batch 1: the second launch); at 2048 they win by 1.5 - 2.4 x, at 32768 by 2 - 10 x. At batch 64 with 12 KV heads the
+# single kernel already fills the machine and the split form is 1 - 4 % slower (profiles/decode_split/README.md):
+# the price of a routing that does not look at the batch; MLT_DECODE_SPLIT=0 is the switch.
+DECODE_SPLIT_MIN_SMAX = 2048
 
 
 @dataclass
@@ -85,16 +94,35 @@ def attn_decode(qkv_new, cache_layer, pos, H: int, scale: float = ATTN_SCALE, ro
     A cache of ``Hkv = cache_layer.shape[2] != H`` heads is grouped-query attention: ``qkv_new`` is then the compact
     [B, (H + 2 Hkv) * 64] row (ops/gqa.py) and the launch ``C.attn_decode_gqa``, which streams every cached row once
     for the ``H // Hkv`` query heads of its group and returns the bits ``C.attn_decode`` returns on the repeated
-    cache. ``Hkv`` must divide ``H``."""
+    cache. ``Hkv`` must divide ``H``.
+    A cache of ``Smax`` rows with ``decode_attn_path(Smax) == "split"`` takes ``C.attn_decode_split`` instead, for both
+    layouts: two launches, with a workspace allocated here beside ``out``."""
     C = require_native()
     out = torch.empty(qkv_new.shape[0], H * HEAD_DIM, dtype=torch.bfloat16, device=qkv_new.device)
-    if cache_layer.shape[2] != H:
+    if decode_attn_path(cache_layer.shape[3]) == "split":
+        # the workspace beside out: a captured step places both in the graph's pool, two kernel nodes in one chain
+        ws = torch.empty(C.attn_decode_split_ws(qkv_new.shape[0], H, cache_layer.shape[3]), dtype=torch.float32,
+                         device=qkv_new.device)
+        C.attn_decode_split(qkv_new, cache_layer, pos, out, ws, H, scale, rope=rope)
+    elif cache_layer.shape[2] != H:
         C.attn_decode_gqa(qkv_new, cache_layer, pos, out, H, scale, rope=rope)
     elif rope is None:
         C.attn_decode(qkv_new, cache_layer, pos, out, H, scale)
     else:
         C.attn_decode(qkv_new, cache_layer, pos, out, H, scale, rope=rope)
     return out
+
+
+def decode_attn_path(Smax: int) -> str:
+    """Which kernels a decode step's attention takes over a cache of ``Smax`` rows: ``"single"`` (``C.attn_decode`` /
+    ``C.attn_decode_gqa``: one workgroup walks all cached rows of its head) or ``"split"`` (``C.attn_decode_split``:
+    the cached keys split over workgroups, ``C.attn_decode_split_keys()`` each, and a merge launch). A pure function
+    of the cache geometry and of ``MLT_DECODE_SPLIT`` (read per call; ``0`` forces ``"single"``: the A/B baseline).
+    It does not look at the batch, so a sequence takes the same kernels, and gets the same bits, alone and in a
+    batch."""
+    if os.environ.get("MLT_DECODE_SPLIT", "1") == "0":
+        return "single"
+    return "split" if Smax >= DECODE_SPLIT_MIN_SMAX else "single"
 
 
 def attn_decode_reference(qkv_new, cache_layer, pos, H: int, scale: float = ATTN_SCALE, rope=None):
