@@ -33,7 +33,8 @@ is the next-token accuracy), ``--generate N`` (``--task clm``: after training, r
 validation rows from their first ``--prompt_len`` tokens by N tokens with the key/value cache, logs a
 ``generate`` record with the ``continuation_accuracy`` and writes ``model_dir/generated.json``;
 ``--temperature`` / ``--top_k`` sample instead of the greedy argmax; ``--sampler device`` takes the on-device
-sampler, which adds ``--top_p`` and, with ``--graph_decode``, a decode loop replayed from one captured graph).
+sampler, which adds ``--top_p`` and, with ``--graph_decode``, a decode loop replayed from one captured graph;
+``--kv_cache {bf16,fp8}``: the format of that cache, ``fp8`` = e4m3 codes with one scale per cached row).
 """
 from __future__ import annotations
 
@@ -121,6 +122,8 @@ def build_model_and_datasets(args):
         raise ValueError("--temperature / --top_k apply to --generate")
     if not args.generate and (args.top_p is not None or args.sampler is not None or args.graph_decode):
         raise ValueError("--top_p / --sampler / --graph_decode apply to --generate")
+    if args.kv_cache is not None and (lenet or not args.generate):
+        raise ValueError("--kv_cache applies to --generate (BERT models, --task clm): the LeNet models have no cache")
     if args.top_p is not None and args.sampler != "device":
         raise ValueError("--top_p needs --sampler device (nucleus sampling is part of the on-device sampler)")
     if args.top_p is not None and not 0.0 < args.top_p <= 1.0:
@@ -237,7 +240,7 @@ def generate_after_fit(args, trainer, val_set, rows: int = 8):
     tokens, _ = model.generate(ids[:, :P].to(dev), N, attention_mask=mask.to(dev),
                                temperature=args.temperature or 0.0, top_k=args.top_k, seed=args.seed,
                                top_p=args.top_p, sampler=args.sampler,
-                               graph=args.graph_decode and dev.type == "cuda")
+                               graph=args.graph_decode and dev.type == "cuda", kv_cache=args.kv_cache)
     tokens = tokens.cpu()
     at = plens[:, None] + torch.arange(N)[None, :]  # where the continuation sits in the row
     has = at < lengths[:, None]
@@ -359,6 +362,9 @@ def build_parser() -> argparse.ArgumentParser:
                              "of the batch); default: the torch sampler")
     parser.add_argument("--graph_decode", action="store_true",
                         help="--generate with --sampler device on a GPU: replay one captured graph per token")
+    parser.add_argument("--kv_cache", choices=["bf16", "fp8"], default=None,
+                        help="--generate: the key/value cache format; fp8 = OCP e4m3 codes with one power-of-two "
+                             "scale per cached row (0.53 x the bytes of the bf16 cache); default: bf16")
     parser.add_argument("--synthetic_size", type=int, default=0)
     parser.add_argument("--seq_len", type=int, default=512)
     parser.add_argument("--per_device_batch", action="store_true",

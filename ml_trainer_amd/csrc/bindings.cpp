@@ -1411,6 +1411,89 @@ void attn_decode_split(Tensor qkv_new, Tensor kv, Tensor pos, Tensor out, Tensor
                            (float)scale, cur_stream(), rp, (int)gc);
 }
 
+// The fp8 cache of one layer (attn_decode_f8.hip): kv8 uint8 [2, B, Hkv, Smax, 64] (OCP e4m3 codes), kv_scale fp32
+// [2, B, Hkv, Smax] (one scale per cached row), both contiguous device tensors, kv8 16-byte aligned. Returns (Hkv, Smax).
+static std::pair<int64_t, int64_t> check_kv8(const Tensor& kv8, const Tensor& kv_scale, int64_t B, int64_t H,
+                                             const char* who) {
+  check_dev(kv8, "kv8", at::kByte, 0);
+  TORCH_CHECK(kv8.dim() == 5 && kv8.size(0) == 2 && kv8.size(1) == B && kv8.size(2) >= 1 && kv8.size(3) >= 1 &&
+                  kv8.size(4) == 64,
+              who, ": kv8 must be [2, B, Hkv, Smax, 64] with B = ", B);
+  const int64_t Hkv = kv8.size(2), Smax = kv8.size(3);
+  TORCH_CHECK(Hkv <= H && H % Hkv == 0, who, ": the cache holds ", Hkv, " key/value heads, which does not divide H = ",
+              H);
+  TORCH_CHECK(Smax <= 0x7fffffff, who, ": kv8 size");
+  check_dev(kv_scale, "kv_scale", at::kFloat, 0, 4);  // read and written one word at a time
+  TORCH_CHECK(kv_scale.sizes().vec() == std::vector<int64_t>({2, B, Hkv, Smax}), who, ": kv_scale has shape ",
+              kv_scale.sizes(), ", expected one scale per cached row [2, ", B, ", ", Hkv, ", ", Smax, "]");
+  return {Hkv, Smax};
+}
+
+// attn_decode over an fp8 cache (attn_decode_f8.hip): qkv_new [B, (H + 2 Hkv) * 64] bf16 compact (Hkv == H: the
+// [B, 3 * H * 64] row; may be a row-strided view), kv8 / kv_scale as check_kv8, pos, out, rope and gc as
+// attn_decode_gqa. ws None: the single kernel; ws (fp32, the shape attn_decode_split_ws(B, H, Smax), 16-byte
+// aligned, no initialisation needed): the split kernel and the merge launch. Everything is checked before the first
+// launch.
+void attn_decode_f8(Tensor qkv_new, Tensor kv8, Tensor kv_scale, Tensor pos, Tensor out, int64_t H, double scale,
+                    c10::optional<Tensor> rope, c10::optional<Tensor> ws, int64_t gc) {
+  TORCH_CHECK(qkv_new.is_cuda() && qkv_new.dim() == 2 && qkv_new.scalar_type() == at::kBFloat16,
+              "attn_decode_f8: qkv_new must be a bf16 [B, (H + 2 Hkv) * 64] device tensor");
+  const int64_t B = qkv_new.size(0), D = H * 64;
+  TORCH_CHECK(B > 0 && H > 0 && B <= 65535 && H <= 65535, "attention dims");
+  const auto [Hkv, Smax] = check_kv8(kv8, kv_scale, B, H, "attn_decode_f8");
+  const int64_t W = (H + 2 * Hkv) * 64;
+  TORCH_CHECK(qkv_new.size(1) == W, "attn_decode_f8: qkv_new has ", qkv_new.size(1),
+              " columns, expected (H + 2 Hkv) * 64 = ", W);
+  TORCH_CHECK(qkv_new.stride(1) == 1 && qkv_new.stride(0) >= W && qkv_new.stride(0) % 8 == 0,
+              "attn_decode_f8: qkv_new needs unit column stride and a row stride that is a multiple of 8");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(qkv_new.data_ptr()) % 16 == 0, "qkv_new must be 16-byte aligned");
+  check_dev(pos, "pos", at::kInt, B, 4);
+  TORCH_CHECK(pos.numel() == B, "attn_decode_f8: pos must have one entry per sequence");
+  check_bf16_2d(out, "out", B, D);
+  float* wp = nullptr;
+  if (ws.has_value()) {
+    const std::vector<int64_t> shape = attn_decode_split_ws(B, H, Smax);
+    TORCH_CHECK(shape[2] <= 65535 && B * H <= 0x7fffffff, "attn_decode_f8: ", shape[2], " splits x ", B * H,
+                " heads exceed the grid");
+    check_dev(*ws, "ws", at::kFloat, 0, 16);
+    TORCH_CHECK(ws->sizes().vec() == shape, "attn_decode_f8: ws has shape ", ws->sizes(), ", expected ",
+                at::IntArrayRef(shape), " (attn_decode_split_ws)");
+    wp = ws->data_ptr<float>();
+  }
+  const float* rp = nullptr;
+  if (rope.has_value()) {
+    check_dev(*rope, "rope table", at::kFloat, 64, 16);
+    TORCH_CHECK(rope->dim() == 3 && rope->size(1) == 32 && rope->size(2) == 2 && rope->size(0) >= Smax,
+                "attn_decode_f8: the rope table must be [P >= Smax = ", Smax, ", 32, 2]");
+    rp = rope->data_ptr<float>();
+  }
+  const int64_t G = H / Hkv;
+  TORCH_CHECK(gc == 0 || ((gc == 1 || gc == 2 || gc == 3 || gc == 4 || gc == 6 || gc == 8) && G % gc == 0),
+              "attn_decode_f8: gc = ", gc, " must be 0 or one of 1, 2, 3, 4, 6, 8 that divides H / Hkv = ", G);
+  launch_attn_decode_f8(bf16_ptr(qkv_new), qkv_new.stride(0), kv8.data_ptr<uint8_t>(), kv_scale.data_ptr<float>(),
+                        pos.data_ptr<int>(), (uint16_t*)out.data_ptr(), wp, (int)B, (int)H, (int)Hkv, (int)Smax,
+                        (float)scale, cur_stream(), rp, (int)gc);
+}
+
+// The prefill fill of an fp8 cache (kv_fill_f8_kernel): rows 0 .. S - 1 of every (b, KV head) of kv8 / kv_scale from
+// a layer's padded, already rotated qkv [B * S, 3 * H * 64] (wide: every (H / Hkv)-th k / v head is taken) or
+// [B * S, (H + 2 Hkv) * 64] (compact) bf16; may be a row-strided view. S <= Smax.
+void kv_fill_f8(Tensor qkv, Tensor kv8, Tensor kv_scale, int64_t B, int64_t S, int64_t H) {
+  TORCH_CHECK(qkv.is_cuda() && qkv.dim() == 2 && qkv.scalar_type() == at::kBFloat16,
+              "kv_fill_f8: qkv must be a bf16 [B * S, 3 * H * 64 or (H + 2 Hkv) * 64] device tensor");
+  TORCH_CHECK(B > 0 && S > 0 && H > 0 && H <= 65535 && B * S <= 0x7fffffff, "kv_fill_f8: B, S, H");
+  const auto [Hkv, Smax] = check_kv8(kv8, kv_scale, B, H, "kv_fill_f8");
+  TORCH_CHECK(S <= Smax, "kv_fill_f8: a prompt of width ", S, " does not fit a cache of ", Smax, " rows");
+  const int64_t wide = 3 * H * 64, compact = (H + 2 * Hkv) * 64;
+  TORCH_CHECK(qkv.size(0) == B * S && (qkv.size(1) == wide || qkv.size(1) == compact), "kv_fill_f8: qkv is [",
+              qkv.size(0), ", ", qkv.size(1), "], expected [B * S = ", B * S, ", ", wide, " or ", compact, "]");
+  TORCH_CHECK(qkv.stride(1) == 1 && qkv.stride(0) >= qkv.size(1) && qkv.stride(0) % 8 == 0,
+              "kv_fill_f8: qkv needs unit column stride and a row stride that is a multiple of 8");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(qkv.data_ptr()) % 16 == 0, "qkv must be 16-byte aligned");
+  launch_kv_fill_f8(bf16_ptr(qkv), qkv.stride(0), qkv.size(1) != wide, kv8.data_ptr<uint8_t>(),
+                    kv_scale.data_ptr<float>(), (int)B, (int)S, (int)H, (int)Hkv, (int)Smax, cur_stream());
+}
+
 // The operands of gqa_expand / gqa_reduce (gqa.hip): compact bf16 [rows, (H + 2 Hkv) * 64], wide bf16
 // [rows, 3 * H * 64], both 2-D device tensors with unit column stride, a row stride that is a multiple of 8 and a
 // 16-byte aligned base (row-strided views pass).
@@ -2252,6 +2335,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("ws"), py::arg("H"), py::arg("scale"), py::arg("rope") = py::none(), py::arg("gc") = 0);
   m.def("attn_decode_split_ws", &attn_decode_split_ws, py::arg("B"), py::arg("H"), py::arg("Smax"));
   m.def("attn_decode_split_keys", []() { return (int64_t)attn_decode_split_keys(); });
+  m.def("attn_decode_f8", &attn_decode_f8, py::arg("qkv_new"), py::arg("kv8"), py::arg("kv_scale"), py::arg("pos"),
+        py::arg("out"), py::arg("H"), py::arg("scale"), py::arg("rope") = py::none(), py::arg("ws") = py::none(),
+        py::arg("gc") = 0);
+  m.def("kv_fill_f8", &kv_fill_f8, py::arg("qkv"), py::arg("kv8"), py::arg("kv_scale"), py::arg("B"), py::arg("S"),
+        py::arg("H"));
   m.def("gqa_expand", &gqa_expand, py::arg("compact"), py::arg("wide"), py::arg("H"), py::arg("Hkv"));
   m.def("gqa_reduce", &gqa_reduce, py::arg("wide"), py::arg("compact"), py::arg("H"), py::arg("Hkv"));
   m.def("rope_qk", &rope_qk, py::arg("qkv"), py::arg("table"), py::arg("H"), py::arg("S"), py::arg("pos") = py::none(),

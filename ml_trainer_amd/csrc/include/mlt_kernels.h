@@ -449,6 +449,23 @@ int attn_decode_split_keys();
 void launch_attn_decode_split(const uint16_t* qkv_new, int64_t ldq, uint16_t* kv, const int* pos, uint16_t* out,
                               float* ws, int B, int H, int Hkv, int Smax, float scale, hipStream_t st,
                               const float* rope = nullptr, int gc = 0);
+// The second launch of the split form alone (attn_decode_merge_kernel): ws [B][H][ceil(Smax / C)][68] as a split
+// kernel left it -> out [B][64 H] bf16. launch_attn_decode_split ends with it; launch_attn_decode_f8 too.
+void launch_attn_decode_merge(const float* ws, const int* pos, uint16_t* out, int B, int H, int Smax, hipStream_t st);
+// Decode attention over an fp8 cache (attn_decode_f8.hip): kv8 [2][B][Hkv][Smax][64] OCP e4m3 codes, kv_scale
+// [2][B][Hkv][Smax] fp32, one power-of-two scale per cached row (mlt_kv_f8.h has the format). qkv_new is compact
+// (Hkv == H: q | k | v); pos, out, rope and gc as launch_attn_decode_gqa. The new token's k / v are quantised first,
+// enter their own step dequantised and are stored as codes + scale at row pos[b]. ws == nullptr: one workgroup
+// walks all cached rows of its KV head; otherwise the split form over the workspace of launch_attn_decode_split,
+// finished by launch_attn_decode_merge. No bit of a row depends on gc, B or Smax.
+void launch_attn_decode_f8(const uint16_t* qkv_new, int64_t ldq, uint8_t* kv8, float* kv_scale, const int* pos,
+                           uint16_t* out, float* ws, int B, int H, int Hkv, int Smax, float scale, hipStream_t st,
+                           const float* rope = nullptr, int gc = 0);
+// The prefill fill of that cache: rows 0 .. S - 1 of every (b, KV head) from the padded, already rotated qkv
+// [B * S][ldq] bf16 (ldq % 8 == 0, 16-byte aligned), wide [.., 3 * 64 H] (every (H / Hkv)-th k / v head is taken)
+// or compact [.., 64 (H + 2 Hkv)]; S <= Smax. The quantiser is the append's, bit for bit.
+void launch_kv_fill_f8(const uint16_t* qkv, int64_t ldq, bool compact, uint8_t* kv8, float* kv_scale, int B, int S,
+                       int H, int Hkv, int Smax, hipStream_t st);
 // Grouped-query layouts around the flash attention kernels (gqa.hip). compact [rows][ldc >= 64 (H + 2 Hkv)], wide
 // [rows][ldw >= 3 * 64 H], both bf16, ld % 8 == 0, 16-byte aligned, H % Hkv == 0. expand: q copied, every k / v
 // head stored H / Hkv times (bitwise). reduce: dq copied, dk / dv summed over the group in ascending head order in

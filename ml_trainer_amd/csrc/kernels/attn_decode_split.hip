@@ -293,8 +293,13 @@ void launch_attn_decode_split(const uint16_t* qkv_new, int64_t ldq, uint16_t* kv
         rope != nullptr);
   });
   if (!hit) throw_no_kernel("launch_attn_decode_split", "GC", gc);
-  const int BH = B * H;
-  attn_decode_merge_kernel<<<dim3((BH + kDecWaves - 1) / kDecWaves), block, 0, st>>>(ws, pos, out, BH, H, Z, Smax);
+  launch_attn_decode_merge(ws, pos, out, B, H, Smax, st);
+}
+
+void launch_attn_decode_merge(const float* ws, const int* pos, uint16_t* out, int B, int H, int Smax, hipStream_t st) {
+  const int BH = B * H, Z = (Smax + kDecSplitKeys - 1) / kDecSplitKeys;
+  attn_decode_merge_kernel<<<dim3((BH + kDecWaves - 1) / kDecWaves), dim3(kDecWaves * 64), 0, st>>>(ws, pos, out, BH,
+                                                                                                  H, Z, Smax);
 }
 
 }  // namespace mlt

@@ -835,16 +835,19 @@ class BertLMHeadModel(BertForMaskedLM):
         return torch.arange(B, device=device) * S + last
 
     @torch.no_grad()
-    def prefill(self, input_ids, attention_mask=None, max_len: Optional[int] = None, cache=None):
+    def prefill(self, input_ids, attention_mask=None, max_len: Optional[int] = None, cache=None, kv_cache=None):
         """Run the prompt ``input_ids`` [B, S] (right-padded; lengths from ``attention_mask`` or ``pad_id``)
         through the padded causal forward, layer by layer, keep every layer's K / V in a cache of ``max_len``
         rows per sequence (default ``config.max_position``) and return the ``DecodeState``: the cache with
         ``pos = lens`` and the hidden row of each sequence's last real token. No gradients and no dropout,
         whatever mode the model is in; ``config.unpad`` has no effect (prompts are short). ``cache``: an existing
         ``KVCache`` of this shape to fill in place (its ``pos`` is overwritten with ``pos.copy_``, its tensors keep
-        their addresses: what a captured decode step needs) instead of a new one."""
+        their addresses: what a captured decode step needs) instead of a new one. ``kv_cache``: ``None`` / ``"bf16"``
+        (the cache as it is) or ``"fp8"`` (e4m3 codes and one scale per cached row, ``ops.decode.KVCache``); a given
+        ``cache`` must be of that format. ``decode_step`` takes the format from the cache."""
         from ml_trainer_amd.ops import decode as DC
         c = self.config
+        fp8 = DC.check_kv_cache(kv_cache)
         B, S = input_ids.shape
         Smax = c.max_position if max_len is None else int(max_len)
         if not S <= Smax <= c.max_position:
@@ -853,11 +856,13 @@ class BertLMHeadModel(BertForMaskedLM):
         dev = input_ids.device
         lens = self._lengths(input_ids, attention_mask)
         if cache is None:
-            cache = DC.KVCache.allocate(c.layers, B, c.num_kv_heads, Smax, dev)
+            cache = DC.KVCache.allocate(c.layers, B, c.num_kv_heads, Smax, dev, kv_cache=kv_cache)
         elif (cache.Smax != Smax or len(cache.kv) != c.layers or cache.pos.device != dev or
               tuple(cache.kv[0].shape) != (2, B, c.num_kv_heads, Smax, DC.HEAD_DIM)):
             raise ValueError(f"prefill: the given cache does not hold {c.layers} layers of [2, {B}, {c.num_kv_heads}, {Smax}, "
                              f"{DC.HEAD_DIM}] on {dev}")
+        elif (cache.scales is not None) != fp8:
+            raise ValueError(f"prefill: the given cache is {cache.kv_cache}, kv_cache = {kv_cache!r}")
         if input_ids.is_cuda:
             from ml_trainer_amd.ops import transformer as T
             x = T.embeddings(input_ids, None, self.word_embeddings.weight, self._pos_weight(),
@@ -944,7 +949,8 @@ class BertLMHeadModel(BertForMaskedLM):
             for l, L in enumerate(self.layers):  # (x, n and the sums as in prefill)
                 n = _norm_native(x, L.ln1) if c.pre_ln else x
                 qkv = DC.linear_small(n, T.bf16_weight(L.qkv.weight), L.qkv.bias)
-                ctx = DC.attn_decode(qkv, cache.kv[l], cache.pos, c.heads, rope=self.rope_table)
+                ctx = DC.attn_decode(qkv, cache.kv[l], cache.pos, c.heads, rope=self.rope_table,
+                                     kv_scale=cache.scale(l))
                 y = DC.linear_small(ctx, T.bf16_weight(L.out.weight), L.out.bias, res=x)
                 x = y if c.pre_ln else _norm_native(y, L.ln1)
                 n = _norm_native(x, L.ln2) if c.pre_ln else x
@@ -956,7 +962,8 @@ class BertLMHeadModel(BertForMaskedLM):
             x = self.emb_ln(self._embed_torch(ids, torch.zeros_like(ids), cache.pos.long()))
             for l, L in enumerate(self.layers):
                 n = L.ln1(x) if c.pre_ln else x
-                ctx = DC.attn_decode_reference(L.qkv(n), cache.kv[l], cache.pos, c.heads, rope=self.rope_table)
+                ctx = DC.attn_decode_reference(L.qkv(n), cache.kv[l], cache.pos, c.heads, rope=self.rope_table,
+                                               kv_scale=cache.scale(l))
                 y = L.out(ctx) + x
                 x = y if c.pre_ln else L.ln1(y)
                 y = L.ffn_torch(L.ln2(x) if c.pre_ln else x) + x
@@ -967,8 +974,10 @@ class BertLMHeadModel(BertForMaskedLM):
         return self._state_logits(state)
 
     def _check_generate(self, input_ids, max_new_tokens, temperature, top_k, top_p=None, sampler=None, graph=False,
-                        return_logits=False):
+                        return_logits=False, kv_cache=None):
+        from ml_trainer_amd.ops.decode import check_kv_cache
         S = input_ids.shape[1]
+        check_kv_cache(kv_cache)
         if sampler not in (None, "device"):
             raise ValueError(f"sampler must be None (the torch sampler) or 'device', got {sampler!r}")
         if top_p is not None:
@@ -1066,15 +1075,15 @@ class BertLMHeadModel(BertForMaskedLM):
         ffn = (c.ffn,) if c.ffn != "gelu" else ()  # (which FFN1 launch a step makes)
         return (c.pre_ln, c.norm) + gqa + ffn + tuple((p._version, p.data_ptr()) for p in self.parameters())
 
-    def _graphed_decoder(self, B, Smax, T, dev):
-        key = (B, Smax, T, str(dev))
+    def _graphed_decoder(self, B, Smax, T, dev, kv_cache=None):
+        key = (B, Smax, T, str(dev)) + (("fp8",) if kv_cache == "fp8" else ())  # (the cache a capture baked in)
         decoders = self.__dict__.setdefault("_graphed_decoders", {})
         dec = decoders.get(key)
         sig = self._decode_signature()
         if dec is None or dec.signature != sig:
             decoders.pop(key, None)  # free the stale graph's buffers before the new capture
             del dec
-            dec = decoders[key] = GraphedDecoder(self, B, Smax, T, dev, sig)
+            dec = decoders[key] = GraphedDecoder(self, B, Smax, T, dev, sig, kv_cache)
             self._decode_graph_captures = self.decode_graph_captures + 1
         return dec
 
@@ -1087,7 +1096,7 @@ class BertLMHeadModel(BertForMaskedLM):
     def generate(self, input_ids, max_new_tokens: int, attention_mask=None, temperature: float = 0.0,
                  top_k: Optional[int] = None, eos_id: Optional[int] = None, seed: Optional[int] = None,
                  return_logits: bool = False, top_p: Optional[float] = None, sampler: Optional[str] = None,
-                 graph: bool = False):
+                 graph: bool = False, kv_cache: Optional[str] = None):
         """Continue the prompts ``input_ids`` [B, S] (right-padded, ragged lengths allowed: sequence b's new
         tokens continue at position ``len_b``) by ``max_new_tokens`` tokens with a key/value cache: one
         ``prefill``, then one ``decode_step`` per token. Returns ``(tokens [B, max_new_tokens], lengths [B])``,
@@ -1106,15 +1115,21 @@ class BertLMHeadModel(BertForMaskedLM):
         65536``) needs it. ``graph=True`` (GPU, device sampler, no ``return_logits``) replays one captured graph
         of ``decode_step`` + ``sample_step`` per token (``GraphedDecoder``); the graph is captured on the first call
         of a shape and again after a parameter changed, and ``MLT_DECODE_GEMM`` / ``MLT_DECODE_SPLIT`` are read when it is
-        captured."""
-        self._check_generate(input_ids, max_new_tokens, temperature, top_k, top_p, sampler, graph, return_logits)
+        captured.
+
+        ``kv_cache="fp8"`` (opt-in; ``None`` / ``"bf16"`` change nothing): the cache holds OCP e4m3 codes and one
+        power-of-two scale per cached row (``ops.decode.kv_quantize_reference``), 0.53 x the bytes; a step's attention
+        is ``C.attn_decode_f8`` over the dequantised rows, the prompt is quantised by ``C.kv_fill_f8``. Works eager and
+        graph-replayed, with every block kind, ``rotary`` and ``kv_heads``."""
+        self._check_generate(input_ids, max_new_tokens, temperature, top_k, top_p, sampler, graph, return_logits,
+                             kv_cache)
         B, S = input_ids.shape
         dev = input_ids.device
         if graph:
-            dec = self._graphed_decoder(B, S + max_new_tokens, max_new_tokens, dev)
+            dec = self._graphed_decoder(B, S + max_new_tokens, max_new_tokens, dev, kv_cache)
             return dec.generate(self, input_ids, attention_mask,
                                 self._sampler_params(temperature, top_k, top_p, eos_id, seed))
-        state = self.prefill(input_ids, attention_mask, max_len=S + max_new_tokens)
+        state = self.prefill(input_ids, attention_mask, max_len=S + max_new_tokens, kv_cache=kv_cache)
         if sampler == "device":
             st = self._new_sampler(B, max_new_tokens, dev, temperature, top_k, top_p, eos_id, seed)
             return self._device_sampler_loop(lambda: self.decode_step(state), lambda tok: self.decode_step(state, tok),
@@ -1138,9 +1153,12 @@ class BertLMHeadModel(BertForMaskedLM):
     @torch.no_grad()
     def generate_reference(self, input_ids, max_new_tokens: int, attention_mask=None, temperature: float = 0.0,
                            top_k: Optional[int] = None, eos_id: Optional[int] = None, seed: Optional[int] = None,
-                           return_logits: bool = False, top_p: Optional[float] = None, sampler: Optional[str] = None):
-        """``generate`` without any cache: ``forward_reference`` over the growing sequence, once per token."""
-        self._check_generate(input_ids, max_new_tokens, temperature, top_k, top_p, sampler)
+                           return_logits: bool = False, top_p: Optional[float] = None, sampler: Optional[str] = None,
+                           kv_cache: Optional[str] = None):
+        """``generate`` without any cache: ``forward_reference`` over the growing sequence, once per token.
+        ``kv_cache`` is checked as ``generate`` checks it and changes nothing here: there is no cache to quantise, so
+        this stays the unquantised oracle of either format."""
+        self._check_generate(input_ids, max_new_tokens, temperature, top_k, top_p, sampler, kv_cache=kv_cache)
         B, S = input_ids.shape
         dev = input_ids.device
         lens = self._lengths(input_ids, attention_mask)
@@ -1164,7 +1182,8 @@ class BertLMHeadModel(BertForMaskedLM):
 
 class GraphedDecoder:
     """One captured decode loop body of a ``BertLMHeadModel`` for a fixed ``(B, Smax, T, device)``, and everything
-    the capture baked addresses of: the key/value cache (``prefill(cache=)`` refills it in place), the
+    the capture baked addresses of: the key/value cache (bf16, or codes + scales under ``kv_cache="fp8"``, which is
+    part of the decoder's key; ``prefill(cache=)`` refills it in place), the
     ``SamplerState`` (``set_params`` / ``reset`` rewrite it in place) and, inside the graph's own memory pool, the
     hidden rows and the logits buffer of a step. The body is ``decode_step(state, sampler.next_ids)`` followed by
     ``sample_step`` on the logits it returns: token t's sampling closes replay t, so a generation is one eager
@@ -1174,13 +1193,14 @@ class GraphedDecoder:
     ``MLT_DECODE_SPLIT`` (``ops.decode.decode_attn_path``: the split attention's two launches and its workspace are then
     nodes and pool memory of the graph) are read while capturing. Not supported: ``return_logits``, a graph for ``prefill``."""
 
-    def __init__(self, model, B, Smax, T, dev, signature):
+    def __init__(self, model, B, Smax, T, dev, signature, kv_cache=None):
         import time
         from ml_trainer_amd.ops import decode as DC
         c = model.config
         self.signature = signature
         self.B, self.Smax, self.T = B, Smax, T
-        self.cache = DC.KVCache.allocate(c.layers, B, c.num_kv_heads, Smax, dev)
+        self.kv_cache = kv_cache
+        self.cache = DC.KVCache.allocate(c.layers, B, c.num_kv_heads, Smax, dev, kv_cache=kv_cache)
         self.sampler = DC.SamplerState.allocate(B, T, dev)
         self.state = DC.DecodeState(self.cache, None)
         self.graph = None
@@ -1215,7 +1235,8 @@ class GraphedDecoder:
         arguments), the prompt prefilled into the captured cache. Returns the prompt's logits."""
         self.sampler.reset()
         self.sampler.set_params(**params)
-        return model.decode_step(model.prefill(input_ids, attention_mask, max_len=self.Smax, cache=self.cache))
+        return model.decode_step(model.prefill(input_ids, attention_mask, max_len=self.Smax, cache=self.cache,
+                                               kv_cache=self.kv_cache))
 
     def run(self, model, first_logits):
         """The token loop: one eager ``sample_step`` on the prompt's logits, then ``T - 1`` replays. Results are in

@@ -12,6 +12,11 @@ per layer per prompt, not a hot path. Over a long cache (``decode_attn_path``) `
 ``C.attn_decode_split`` (csrc/kernels/attn_decode_split.hip): the cached keys of a head split over workgroups and a
 merge launch, so that the whole machine fetches the cache of a small batch.
 
+The fp8 cache (``KVCache.allocate(kv_cache="fp8")``): ``kv`` holds uint8 OCP e4m3 codes and ``scales`` one fp32
+power-of-two scale per cached row. ``kv_quantize_reference`` / ``kv_dequantize_reference`` define the format;
+``attn_decode`` then launches ``C.attn_decode_f8`` (csrc/kernels/attn_decode_f8.hip, single and split forms) and
+``fill_from_prefill`` ``C.kv_fill_f8``; ``attn_decode_reference`` takes the same cache on the CPU.
+
 ``linear_small`` is the linear layer of a decode step (M = B rows): ``decode_linear_path`` sends it to the
 weight-streaming kernel ``C.gemm_skinny`` (csrc/kernels/gemm_skinny.hip) or to the planner's GEMM. With the skinny
 kernel every kernel of a step works row by row, so a sequence's logits do not depend on the batch it is decoded in.
@@ -52,24 +57,71 @@ SKINNY_MAX_ROWS = 16
 DECODE_SPLIT_MIN_SMAX = 2048
 
 
+KV_CACHE_FORMATS = (None, "bf16", "fp8")
+
+
+def check_kv_cache(kv_cache) -> bool:
+    """True for the fp8 cache, False for ``None`` / ``"bf16"`` (the cache as it always was); anything else raises."""
+    if kv_cache not in KV_CACHE_FORMATS:
+        raise ValueError(f"kv_cache must be None, 'bf16' or 'fp8', got {kv_cache!r}")
+    return kv_cache == "fp8"
+
+
 @dataclass
 class KVCache:
     """``kv[l]`` [2, B, H, Smax, 64] per layer (bf16 on the GPU, fp32 on the CPU), ``pos`` int32 [B] on the
-    same device, ``Smax`` the rows per sequence."""
+    same device, ``Smax`` the rows per sequence. The fp8 cache (``allocate(kv_cache="fp8")``, any device): ``kv[l]``
+    holds uint8 OCP e4m3 codes in the same layout and ``scales[l]`` fp32 [2, B, H, Smax] one power-of-two scale per
+    cached row (``kv_quantize_reference`` is the format's definition); 68 bytes per row and tensor instead of 128."""
     kv: List[torch.Tensor]
     pos: torch.Tensor
     Smax: int
+    scales: Optional[List[torch.Tensor]] = None
 
     @classmethod
-    def allocate(cls, layers: int, B: int, H: int, Smax: int, device, dtype=None) -> "KVCache":
+    def allocate(cls, layers: int, B: int, H: int, Smax: int, device, dtype=None, kv_cache=None) -> "KVCache":
         device = torch.device(device)
+        fp8 = check_kv_cache(kv_cache)
+        if fp8 and dtype is not None:
+            raise ValueError("an fp8 cache has uint8 codes and fp32 scales: dtype cannot be given with it")
         if dtype is None:
-            dtype = torch.bfloat16 if device.type == "cuda" else torch.float32
+            dtype = torch.uint8 if fp8 else torch.bfloat16 if device.type == "cuda" else torch.float32
         if Smax < 1:
             raise ValueError(f"a cache needs Smax >= 1, got {Smax}")
         # zeros, not empty: stale rows are never used, but a cache that is inspected should not show garbage
         kv = [torch.zeros(2, B, H, Smax, HEAD_DIM, dtype=dtype, device=device) for _ in range(layers)]
-        return cls(kv, torch.zeros(B, dtype=torch.int32, device=device), Smax)
+        scales = [torch.ones(2, B, H, Smax, dtype=torch.float32, device=device) for _ in range(layers)] if fp8 else None
+        return cls(kv, torch.zeros(B, dtype=torch.int32, device=device), Smax, scales)
+
+    @property
+    def kv_cache(self) -> str:
+        return "bf16" if self.scales is None else "fp8"
+
+    def scale(self, layer: int):
+        return None if self.scales is None else self.scales[layer]
+
+
+def kv_quantize_reference(x):
+    """(codes uint8 [..., 64], scales fp32 [...]) of rows ``x`` [..., 64] (bf16, or fp32 on the CPU path): the
+    definition of the fp8 cache format, which ``C.attn_decode_f8`` and ``C.kv_fill_f8`` equal byte for byte. Per row:
+    ``amax = max |x_d|``; ``d = 2^e`` with ``e = max(E - 7, -126)``, ``E`` the unbiased fp32 exponent of ``amax``, and
+    ``d = 1`` where ``amax`` is 0 or not finite (a NaN in the row makes it so); ``code_d = e4m3(x_d * 2^-e)``, round to
+    nearest even, saturating at +-448, NaN -> the NaN code. The scaled ``amax`` lies in [128, 256): nothing
+    saturates, and the product and ``value(code) * d`` are exact (one corner: an ``amax`` in fp32's last binade whose
+    scaled value rounds up to 256 dequantises to ``256 * 2^120``, an infinity)."""
+    xf = x.float()
+    amax = xf.abs().amax(-1)
+    e = (((amax.view(torch.int32) >> 23) & 0xFF) - 134).clamp(min=-126)
+    e = torch.where(torch.isfinite(amax) & (amax > 0), e, torch.zeros_like(e))
+    scales = ((e + 127) << 23).view(torch.float32)
+    inv = ((127 - e) << 23).view(torch.float32)
+    codes = (xf * inv[..., None]).clamp(-448.0, 448.0).to(torch.float8_e4m3fn).view(torch.uint8)
+    return codes, scales
+
+
+def kv_dequantize_reference(codes, scales):
+    """fp32 [..., 64] ``= value(code) * scale`` of uint8 e4m3 ``codes`` [..., 64] and fp32 ``scales`` [...]: exact."""
+    return codes.view(torch.float8_e4m3fn).float() * scales[..., None]
 
 
 @dataclass
@@ -84,7 +136,7 @@ class DecodeState:
         return self.cache.pos
 
 
-def attn_decode(qkv_new, cache_layer, pos, H: int, scale: float = ATTN_SCALE, rope=None):
+def attn_decode(qkv_new, cache_layer, pos, H: int, scale: float = ATTN_SCALE, rope=None, kv_scale=None):
     """out [B, H * 64] bf16 = attention of the B new tokens' queries over their cached keys and themselves;
     rows ``pos[b]`` of ``cache_layer`` become the new tokens' k / v (the native kernel). ``qkv_new``
     [B, 3 * H * 64] bf16 may be a row-strided view (row stride a multiple of 8). ``rope`` (the fp32 table of
@@ -96,10 +148,19 @@ def attn_decode(qkv_new, cache_layer, pos, H: int, scale: float = ATTN_SCALE, ro
     for the ``H // Hkv`` query heads of its group and returns the bits ``C.attn_decode`` returns on the repeated
     cache. ``Hkv`` must divide ``H``.
     A cache of ``Smax`` rows with ``decode_attn_path(Smax) == "split"`` takes ``C.attn_decode_split`` instead, for both
-    layouts: two launches, with a workspace allocated here beside ``out``."""
+    layouts: two launches, with a workspace allocated here beside ``out``.
+    ``kv_scale`` (fp32 [2, B, Hkv, Smax]): ``cache_layer`` is an fp8 cache (uint8 e4m3 codes) and the launch
+    ``C.attn_decode_f8`` (csrc/kernels/attn_decode_f8.hip), for every layout; the same ``decode_attn_path`` gives it the
+    workspace of the split form. The new k / v are quantised first and enter their own step dequantised."""
     C = require_native()
     out = torch.empty(qkv_new.shape[0], H * HEAD_DIM, dtype=torch.bfloat16, device=qkv_new.device)
-    if decode_attn_path(cache_layer.shape[3]) == "split":
+    if kv_scale is not None:
+        ws = None
+        if decode_attn_path(cache_layer.shape[3]) == "split":
+            ws = torch.empty(C.attn_decode_split_ws(qkv_new.shape[0], H, cache_layer.shape[3]), dtype=torch.float32,
+                             device=qkv_new.device)
+        C.attn_decode_f8(qkv_new, cache_layer, kv_scale, pos, out, H, scale, rope=rope, ws=ws)
+    elif decode_attn_path(cache_layer.shape[3]) == "split":
         # the workspace beside out: a captured step places both in the graph's pool, two kernel nodes in one chain
         ws = torch.empty(C.attn_decode_split_ws(qkv_new.shape[0], H, cache_layer.shape[3]), dtype=torch.float32,
                          device=qkv_new.device)
@@ -125,14 +186,16 @@ def decode_attn_path(Smax: int) -> str:
     return "split" if Smax >= DECODE_SPLIT_MIN_SMAX else "single"
 
 
-def attn_decode_reference(qkv_new, cache_layer, pos, H: int, scale: float = ATTN_SCALE, rope=None):
+def attn_decode_reference(qkv_new, cache_layer, pos, H: int, scale: float = ATTN_SCALE, rope=None, kv_scale=None):
     """``attn_decode`` in plain fp32 torch, on any device: appends into ``cache_layer`` (any float dtype) and
     returns out [B, H * 64] fp32. Stale rows are selected out (scores to -inf, values to 0), never multiplied
     by zero; nothing is read back from the device. ``rope`` (the table): q and the new k are rotated by
     ``pos[b]`` (clamped into the cache, as the kernel clamps it) before use, in ``qkv_new``'s own dtype (bf16 in:
     rounded to bf16 as the kernel rounds them; fp32 in: fp32). A cache of ``Hkv != H`` heads (``Hkv`` divides ``H``):
     grouped-query attention on the compact ``qkv_new`` [B, (H + 2 Hkv) * 64]; the Hkv new k / v heads are appended and
-    every query head reads KV head ``h // (H // Hkv)``."""
+    every query head reads KV head ``h // (H // Hkv)``. ``kv_scale`` (fp32 [2, B, Hkv, Smax]): the fp8 cache;
+    ``cache_layer`` holds uint8 codes, the new k (after rotation) and v are quantised by ``kv_quantize_reference``,
+    stored as codes + scale, and enter this step as the dequantised values: attention over the dequantised rows."""
     B = qkv_new.shape[0]
     Hkv, Smax = cache_layer.shape[2], cache_layer.shape[3]
     if Hkv != H:
@@ -146,12 +209,20 @@ def attn_decode_reference(qkv_new, cache_layer, pos, H: int, scale: float = ATTN
     G = H // Hkv
     idx = pos.long()
     ar = torch.arange(B, device=qkv_new.device)
-    cache_layer[0, ar, :, idx] = k[:, ::G].to(cache_layer.dtype)
-    cache_layer[1, ar, :, idx] = v[:, ::G].to(cache_layer.dtype)
+    if kv_scale is not None:
+        (kq, kd), (vq, vd) = kv_quantize_reference(k[:, ::G]), kv_quantize_reference(v[:, ::G])
+        cache_layer[0, ar, :, idx], cache_layer[1, ar, :, idx] = kq, vq
+        kv_scale[0, ar, :, idx], kv_scale[1, ar, :, idx] = kd, vd
+        k = kv_dequantize_reference(kq, kd).repeat_interleave(G, dim=1)  # what every later step will read
+        v = kv_dequantize_reference(vq, vd).repeat_interleave(G, dim=1)
+        Kc, Vc = kv_dequantize_reference(cache_layer, kv_scale).unbind(0)
+    else:
+        cache_layer[0, ar, :, idx] = k[:, ::G].to(cache_layer.dtype)
+        cache_layer[1, ar, :, idx] = v[:, ::G].to(cache_layer.dtype)
+        Kc, Vc = cache_layer[0].float(), cache_layer[1].float()
     j = torch.arange(Smax, device=qkv_new.device)
     cached = (j[None, :] < idx[:, None])[:, None, :]  # [B, 1, Smax]
     own = (j[None, :] == idx[:, None])[:, None, :]
-    Kc, Vc = cache_layer[0].float(), cache_layer[1].float()
     if G > 1:  # every query head sees its group's KV head
         Kc, Vc = Kc.repeat_interleave(G, dim=1), Vc.repeat_interleave(G, dim=1)
     K = torch.where(own[..., None], k[:, :, None, :], Kc)  # the new token from qkv_new itself
@@ -230,7 +301,9 @@ def fill_from_prefill(cache: KVCache, layer: int, qkv, lens: Optional[torch.Tens
     head-major cache. Rows at and past ``lens[b]`` receive the pad positions' projections: they are stale by
     the definition of ``pos`` (the caller sets ``pos = lens``) and never read. ``heads`` (default: the cache's own
     head count): the H of ``qkv`` when the cache holds fewer heads (grouped-query attention: ``qkv`` is the wide
-    buffer, whose k / v heads are equal within a group, and the cache takes every ``H // Hkv``-th of them)."""
+    buffer, whose k / v heads are equal within a group, and the cache takes every ``H // Hkv``-th of them).
+    An fp8 cache is filled by ``C.kv_fill_f8`` on the GPU (one launch per layer, the quantiser of the decode step's
+    append) and by ``kv_quantize_reference`` on the CPU."""
     kv = cache.kv[layer]
     H = kv.shape[2] if heads is None else heads
     G = H // kv.shape[2]
@@ -238,6 +311,13 @@ def fill_from_prefill(cache: KVCache, layer: int, qkv, lens: Optional[torch.Tens
         raise ValueError(f"a cache of {kv.shape[2]} heads does not divide heads = {H}")
     if S > cache.Smax:
         raise ValueError(f"a prompt of width {S} does not fit a cache of {cache.Smax} rows")
+    if cache.scales is not None:
+        if qkv.is_cuda:
+            require_native().kv_fill_f8(qkv.view(B * S, 3 * H * HEAD_DIM), kv, cache.scales[layer], B, S, H)
+        else:
+            x = qkv.view(B, S, 3, H, HEAD_DIM)[:, :, 1:, ::G].permute(2, 0, 3, 1, 4)  # [2, B, Hkv, S, 64]
+            kv[:, :, :, :S], cache.scales[layer][:, :, :, :S] = kv_quantize_reference(x)
+        return
     x = qkv.view(B, S, 3, H, HEAD_DIM)
     kv[0, :, :, :S] = x[:, :, 1, ::G].permute(0, 2, 1, 3).to(kv.dtype)
     kv[1, :, :, :S] = x[:, :, 2, ::G].permute(0, 2, 1, 3).to(kv.dtype)
