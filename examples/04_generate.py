@@ -72,6 +72,11 @@ def main(argv=None):
                                    seed=args.seed, sampler="device", graph=on_gpu)
     print(f"top-p 0.9 / top-k 20 / temperature 0.7{' (graph replay)' if on_gpu else ''}: row 0 -> "
           f"{sampled[0].tolist()}  agreement with the row {float((sampled.cpu() == want).float().mean()):.3f}")
+    if P >= 2:  # the prompt in two turns: half through prefill, the rest into the same cache through generate(past=)
+        state = tr.model.prefill(val.ids[:, :P // 2].to(tr.device), max_len=P + N)
+        again, _ = tr.model.generate(val.ids[:, P // 2:P].to(tr.device), N, temperature=args.temperature,
+                                     top_k=args.top_k, seed=args.seed, past=state)
+        print(f"prompt fed in two turns: {float((again.cpu() == tokens).float().mean()):.3f} of the tokens equal")
     return acc
 
 

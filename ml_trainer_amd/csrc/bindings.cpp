@@ -1411,6 +1411,77 @@ void attn_decode_split(Tensor qkv_new, Tensor kv, Tensor pos, Tensor out, Tensor
                            (float)scale, cur_stream(), rp, (int)gc);
 }
 
+// The workspace of attn_append's split form: fp32 [B * T, H, ceil(Smax / C), 68], attn_decode_split_ws over B * T rows.
+std::vector<int64_t> attn_append_ws(int64_t B, int64_t T, int64_t H, int64_t Smax) {
+  TORCH_CHECK(B > 0 && T > 0, "attn_append_ws: B and T must be positive");
+  return attn_decode_split_ws(B * T, H, Smax);
+}
+
+// Multi-token append attention (attn_append.hip): qkv_new [B * T, (H + 2 Hkv) * 64] bf16 (row b T + t = token t of
+// sequence b; may be a row-strided view), T = rows / B in 1 .. attn_append_max_tokens(); kv [2, B, Hkv, Smax, 64] bf16,
+// Hkv = kv.size(2) a divisor of H; pos int32 [B]; out [B * T, H * 64]. ws (fp32, the shape attn_append_ws(B, T, H,
+// Smax)) and row_pos (int32 [B * T]) given together select the split form, at any Smax; neither: one workgroup per
+// (KV head, chunk, batch) walks all keys. gc as attn_decode_gqa, from 1, 2, 3, 4. An fp8 (uint8) cache is refused.
+void attn_append(Tensor qkv_new, Tensor kv, Tensor pos, Tensor out, int64_t B, int64_t H, double scale,
+                 c10::optional<Tensor> rope, c10::optional<Tensor> ws, c10::optional<Tensor> row_pos, int64_t gc) {
+  TORCH_CHECK(qkv_new.is_cuda() && qkv_new.dim() == 2 && qkv_new.scalar_type() == at::kBFloat16,
+              "attn_append: qkv_new must be a bf16 [B * T, (H + 2 Hkv) * 64] device tensor");
+  const int64_t R = qkv_new.size(0), D = H * 64;
+  TORCH_CHECK(B > 0 && H > 0 && B <= 65535 && H <= 65535, "attention dims");
+  TORCH_CHECK(R > 0 && R % B == 0, "attn_append: qkv_new has ", R, " rows, not a multiple of B = ", B);
+  const int64_t T = R / B;
+  TORCH_CHECK(T >= 1 && T <= attn_append_max_tokens(), "attn_append: T = ", T, " new tokens per sequence, takes 1 .. ",
+              attn_append_max_tokens());
+  TORCH_CHECK(kv.defined() && kv.scalar_type() != at::kByte,
+              "attn_append: an fp8 (uint8) cache is not supported; the cache must be bf16");
+  check_dev(kv, "kv", at::kBFloat16, 0);
+  TORCH_CHECK(kv.dim() == 5 && kv.size(0) == 2 && kv.size(1) == B && kv.size(2) >= 1 && kv.size(3) >= 1 &&
+                  kv.size(4) == 64,
+              "attn_append: kv must be [2, B, Hkv, Smax, 64] with B = ", B);
+  const int64_t Hkv = kv.size(2), Smax = kv.size(3), W = (H + 2 * Hkv) * 64;
+  TORCH_CHECK(Hkv <= H && H % Hkv == 0, "attn_append: the cache holds ", Hkv, " key/value heads, which does not ",
+              "divide H = ", H);
+  TORCH_CHECK(T <= Smax, "attn_append: T = ", T, " tokens do not fit a cache of ", Smax, " rows");
+  TORCH_CHECK(qkv_new.size(1) == W, "attn_append: qkv_new has ", qkv_new.size(1),
+              " columns, expected (H + 2 Hkv) * 64 = ", W);
+  TORCH_CHECK(qkv_new.stride(1) == 1 && qkv_new.stride(0) >= W && qkv_new.stride(0) % 8 == 0,
+              "attn_append: qkv_new needs unit column stride and a row stride that is a multiple of 8");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(qkv_new.data_ptr()) % 16 == 0, "qkv_new must be 16-byte aligned");
+  TORCH_CHECK(kv.numel() == 2 * B * Hkv * Smax * 64 && Smax <= 0x7fffffff, "attn_append: kv size");
+  check_dev(pos, "pos", at::kInt, B, 4);
+  TORCH_CHECK(pos.numel() == B, "attn_append: pos must have one entry per sequence");
+  check_bf16_2d(out, "out", R, D);
+  TORCH_CHECK(ws.has_value() == row_pos.has_value(), "attn_append: ws and row_pos select the split form together: ",
+              "give both or neither");
+  float* wp = nullptr;
+  int* rpos = nullptr;
+  if (ws.has_value()) {
+    const std::vector<int64_t> shape = attn_append_ws(B, T, H, Smax);
+    TORCH_CHECK(shape[2] <= 65535 && R * H <= 0x7fffffff, "attn_append: ", shape[2], " splits x ", R * H,
+                " heads exceed the grid");
+    check_dev(*ws, "ws", at::kFloat, 0, 16);
+    TORCH_CHECK(ws->sizes().vec() == shape, "attn_append: ws has shape ", ws->sizes(), ", expected ",
+                at::IntArrayRef(shape), " (attn_append_ws)");
+    check_dev(*row_pos, "row_pos", at::kInt, R, 4);
+    TORCH_CHECK(row_pos->numel() == R, "attn_append: row_pos must have one entry per row of qkv_new");
+    wp = ws->data_ptr<float>();
+    rpos = row_pos->data_ptr<int>();
+  }
+  const float* rp = nullptr;
+  if (rope.has_value()) {
+    check_dev(*rope, "rope table", at::kFloat, 64, 16);
+    TORCH_CHECK(rope->dim() == 3 && rope->size(1) == 32 && rope->size(2) == 2 && rope->size(0) >= Smax,
+                "attn_append: the rope table must be [P >= Smax = ", Smax, ", 32, 2]");
+    rp = rope->data_ptr<float>();
+  }
+  const int64_t G = H / Hkv;
+  TORCH_CHECK(gc == 0 || (gc >= 1 && gc <= 4 && G % gc == 0), "attn_append: gc = ", gc,
+              " must be 0 or one of 1, 2, 3, 4 that divides H / Hkv = ", G);
+  launch_attn_append(bf16_ptr(qkv_new), qkv_new.stride(0), (uint16_t*)kv.data_ptr(), pos.data_ptr<int>(),
+                     (uint16_t*)out.data_ptr(), wp, rpos, (int)B, (int)T, (int)H, (int)Hkv, (int)Smax, (float)scale,
+                     cur_stream(), rp, (int)gc);
+}
+
 // The fp8 cache of one layer (attn_decode_f8.hip): kv8 uint8 [2, B, Hkv, Smax, 64] (OCP e4m3 codes), kv_scale fp32
 // [2, B, Hkv, Smax] (one scale per cached row), both contiguous device tensors, kv8 16-byte aligned. Returns (Hkv, Smax).
 static std::pair<int64_t, int64_t> check_kv8(const Tensor& kv8, const Tensor& kv_scale, int64_t B, int64_t H,
@@ -2335,6 +2406,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("ws"), py::arg("H"), py::arg("scale"), py::arg("rope") = py::none(), py::arg("gc") = 0);
   m.def("attn_decode_split_ws", &attn_decode_split_ws, py::arg("B"), py::arg("H"), py::arg("Smax"));
   m.def("attn_decode_split_keys", []() { return (int64_t)attn_decode_split_keys(); });
+  m.def("attn_append", &attn_append, py::arg("qkv_new"), py::arg("kv"), py::arg("pos"), py::arg("out"), py::arg("B"),
+        py::arg("H"), py::arg("scale"), py::arg("rope") = py::none(), py::arg("ws") = py::none(),
+        py::arg("row_pos") = py::none(), py::arg("gc") = 0);
+  m.def("attn_append_ws", &attn_append_ws, py::arg("B"), py::arg("T"), py::arg("H"), py::arg("Smax"));
+  m.def("attn_append_max_tokens", []() { return (int64_t)attn_append_max_tokens(); });
   m.def("attn_decode_f8", &attn_decode_f8, py::arg("qkv_new"), py::arg("kv8"), py::arg("kv_scale"), py::arg("pos"),
         py::arg("out"), py::arg("H"), py::arg("scale"), py::arg("rope") = py::none(), py::arg("ws") = py::none(),
         py::arg("gc") = 0);

@@ -452,6 +452,18 @@ void launch_attn_decode_split(const uint16_t* qkv_new, int64_t ldq, uint16_t* kv
 // The second launch of the split form alone (attn_decode_merge_kernel): ws [B][H][ceil(Smax / C)][68] as a split
 // kernel left it -> out [B][64 H] bf16. launch_attn_decode_split ends with it; launch_attn_decode_f8 too.
 void launch_attn_decode_merge(const float* ws, const int* pos, uint16_t* out, int B, int H, int Smax, hipStream_t st);
+// Multi-token append attention (attn_append.hip): T = 1 .. attn_append_max_tokens() = 16 new tokens per sequence,
+// qkv_new [B * T][ldq] (row b T + t = token t of sequence b, compact q | k | v as launch_attn_decode_gqa), attend to
+// the cached rows j < n = clamp(pos[b], 0, Smax - T) and causally to each other; rows n .. n + T - 1 of the cache
+// become their k / v (rotated by n + t under rope); out [B * T][64 H]; pos is not changed. MFMA scores and P . V, the
+// cache streamed once for the T tokens and the gc query heads of a workgroup. ws == nullptr: one workgroup walks all
+// keys of its (KV head, chunk). Otherwise the split form: ws fp32 [B * T][H][ceil(Smax / C)][68] and row_pos int32
+// [B * T] (both written here, no initialisation needed), finished by launch_attn_decode_merge over B * T rows.
+// gc: 0 (attn_decode_gqa_chunk) or one of 1, 2, 3, 4 that divides H / Hkv. No bit depends on gc, B or Smax.
+int attn_append_max_tokens();
+void launch_attn_append(const uint16_t* qkv_new, int64_t ldq, uint16_t* kv, const int* pos, uint16_t* out, float* ws,
+                        int* row_pos, int B, int T, int H, int Hkv, int Smax, float scale, hipStream_t st,
+                        const float* rope = nullptr, int gc = 0);
 // Decode attention over an fp8 cache (attn_decode_f8.hip): kv8 [2][B][Hkv][Smax][64] OCP e4m3 codes, kv_scale
 // [2][B][Hkv][Smax] fp32, one power-of-two scale per cached row (mlt_kv_f8.h has the format). qkv_new is compact
 // (Hkv == H: q | k | v); pos, out, rope and gc as launch_attn_decode_gqa. The new token's k / v are quantised first,

@@ -899,7 +899,7 @@ class BertLMHeadModel(BertForMaskedLM):
         x = x.index_select(0, self._last_rows(lens, B, S, dev))
         if c.pre_ln:  # rows are independent: the final norm of the last real rows only
             x = _norm_native(x, self.final_ln) if x.is_cuda else self.final_ln(x)
-        return DC.DecodeState(cache, x)
+        return DC.DecodeState(cache, x, width=S)
 
     def _state_logits(self, state):
         from ml_trainer_amd.ops import decode as DC
@@ -945,33 +945,116 @@ class BertLMHeadModel(BertForMaskedLM):
             C.embed_fwd(ids, None, T.bf16_weight(self.word_embeddings.weight),
                         None if c.rotary else T.bf16_weight(self.position_embeddings.weight),
                         T.bf16_weight(self.token_type_embeddings.weight), x, cache.Smax, pos=cache.pos)
-            x = _norm_native(x, self.emb_ln)
-            for l, L in enumerate(self.layers):  # (x, n and the sums as in prefill)
-                n = _norm_native(x, L.ln1) if c.pre_ln else x
-                qkv = DC.linear_small(n, T.bf16_weight(L.qkv.weight), L.qkv.bias)
-                ctx = DC.attn_decode(qkv, cache.kv[l], cache.pos, c.heads, rope=self.rope_table,
-                                     kv_scale=cache.scale(l))
-                y = DC.linear_small(ctx, T.bf16_weight(L.out.weight), L.out.bias, res=x)
-                x = y if c.pre_ln else _norm_native(y, L.ln1)
-                n = _norm_native(x, L.ln2) if c.pre_ln else x
-                y = DC.linear_small(self._ffn1_decode(L, n), T.bf16_weight(L.ffn2.weight), L.ffn2.bias, res=x)
-                x = y if c.pre_ln else _norm_native(y, L.ln2)
-            if c.pre_ln:  # state.hidden holds the normed rows, as after a post-LN layer
-                x = _norm_native(x, self.final_ln)
+            x = self._decode_layers(x, lambda l, qkv: DC.attn_decode(
+                qkv, cache.kv[l], cache.pos, c.heads, rope=self.rope_table, kv_scale=cache.scale(l)))
         else:
-            x = self.emb_ln(self._embed_torch(ids, torch.zeros_like(ids), cache.pos.long()))
-            for l, L in enumerate(self.layers):
-                n = L.ln1(x) if c.pre_ln else x
-                ctx = DC.attn_decode_reference(L.qkv(n), cache.kv[l], cache.pos, c.heads, rope=self.rope_table,
-                                               kv_scale=cache.scale(l))
-                y = L.out(ctx) + x
-                x = y if c.pre_ln else L.ln1(y)
-                y = L.ffn_torch(L.ln2(x) if c.pre_ln else x) + x
-                x = y if c.pre_ln else L.ln2(y)
-            x = self._final_norm(x)
+            x = self._embed_torch(ids, torch.zeros_like(ids), cache.pos.long())
+            x = self._decode_layers_torch(x, lambda l, qkv: DC.attn_decode_reference(
+                qkv, cache.kv[l], cache.pos, c.heads, rope=self.rope_table, kv_scale=cache.scale(l)))
         cache.pos.add_(1)
         state.hidden = x
+        if state.width is not None:
+            state.width += 1
         return self._state_logits(state)
+
+    def _decode_layers(self, x, attn):
+        """The native layer walk of ``decode_step`` and ``extend`` on the embedded bf16 rows ``x`` [M, h]: every kernel
+        works row by row except ``attn(l, qkv)``, the attention of layer l over the cache. Returns the rows
+        ``state.hidden`` holds (normed, as after a post-LN layer)."""
+        from ml_trainer_amd.ops import decode as DC
+        from ml_trainer_amd.ops import transformer as T
+        c = self.config
+        x = _norm_native(x, self.emb_ln)
+        for l, L in enumerate(self.layers):  # (x, n and the sums as in prefill)
+            n = _norm_native(x, L.ln1) if c.pre_ln else x
+            qkv = DC.linear_small(n, T.bf16_weight(L.qkv.weight), L.qkv.bias)
+            ctx = attn(l, qkv)
+            y = DC.linear_small(ctx, T.bf16_weight(L.out.weight), L.out.bias, res=x)
+            x = y if c.pre_ln else _norm_native(y, L.ln1)
+            n = _norm_native(x, L.ln2) if c.pre_ln else x
+            y = DC.linear_small(self._ffn1_decode(L, n), T.bf16_weight(L.ffn2.weight), L.ffn2.bias, res=x)
+            x = y if c.pre_ln else _norm_native(y, L.ln2)
+        if c.pre_ln:
+            x = _norm_native(x, self.final_ln)
+        return x
+
+    def _decode_layers_torch(self, x, attn):
+        """``_decode_layers`` on the modules (the CPU path), from the embedding sum ``x``."""
+        c = self.config
+        x = self.emb_ln(x)
+        for l, L in enumerate(self.layers):
+            n = L.ln1(x) if c.pre_ln else x
+            y = L.out(attn(l, L.qkv(n))) + x
+            x = y if c.pre_ln else L.ln1(y)
+            y = L.ffn_torch(L.ln2(x) if c.pre_ln else x) + x
+            x = y if c.pre_ln else L.ln2(y)
+        return self._final_norm(x)
+
+    def _rows_logits(self, x):
+        """fp32 [M, V] of the hidden rows ``x`` [M, h]: ``decode_logits`` where both its linears route "skinny"."""
+        from ml_trainer_amd.ops import decode as DC
+        from ml_trainer_amd.ops import mlm as M
+        rows, h = x.shape
+        Vp = M._round_up(self.config.vocab_size, M.VOCAB_MULTIPLE)
+        if (x.is_cuda and x.dtype == torch.bfloat16 and DC.decode_linear_path(rows, h, h) == "skinny" and
+                DC.decode_linear_path(rows, Vp, h) == "skinny"):
+            return M.decode_logits(x, self.mlm_params())
+        return self.mlm_logits(x, torch.arange(rows, device=x.device))
+
+    @torch.no_grad()
+    def extend(self, state, token_ids, counts=None):
+        """fp32 logits [B, T, V] of ``token_ids`` [B, T] pushed into a live cache in one pass: token t of sequence b
+        enters at position ``state.pos[b] + t`` and sees the cache and the tokens before it (a new chat turn, a
+        prompt fed in pieces, the verification pass of speculative decoding). The walk is ``decode_step``'s on
+        ``B * T`` rows with ``ops.decode.attn_append`` as the attention; ``T > 16`` runs in pieces of at most 16
+        tokens, each seeing the previous ones in the cache. Then ``state.pos += counts`` (int32 [B] on the device,
+        ``0 <= counts[b] <= T``, default T): rows past ``counts[b]`` were written but stay above ``pos``, stale by
+        definition, so accepting fewer tokens than were scored costs nothing. ``state.hidden`` becomes the row of
+        token ``counts[b] - 1`` (unchanged where ``counts[b] == 0``). Nothing is read back from the device. The
+        caller keeps ``state.pos[b] + T <= Smax``, as with ``decode_step``. An fp8 cache and ``T < 1`` raise
+        ``ValueError``."""
+        from ml_trainer_amd.ops import decode as DC
+        c = self.config
+        cache = state.cache
+        if cache.scales is not None:
+            raise ValueError("extend takes a bf16 cache: the fp8 cache has no multi-token attention kernel")
+        if token_ids.dim() != 2 or token_ids.shape[1] < 1 or token_ids.shape[0] != cache.pos.numel():
+            raise ValueError(f"extend takes token_ids [B = {cache.pos.numel()}, T >= 1], got {tuple(token_ids.shape)}")
+        B, T = token_ids.shape
+        dev = token_ids.device
+        counts = (torch.full((B,), T, dtype=torch.int32, device=dev) if counts is None
+                  else counts.to(device=dev, dtype=torch.int32).clamp(0, T))
+        ar = torch.arange(B, device=dev)
+        logits = []
+        for t0 in range(0, T, DC.APPEND_MAX_TOKENS):
+            ids = token_ids[:, t0:t0 + DC.APPEND_MAX_TOKENS].to(torch.int64)
+            Tp = ids.shape[1]
+            ids = ids.reshape(-1).contiguous()
+            # every piece sits at pos + t0 whatever counts says, so all T rows of logits are those of their positions;
+            # pos itself moves once, at the end, by counts
+            base = cache.pos + t0
+            tpos = (base[:, None] + torch.arange(Tp, dtype=torch.int32, device=dev)[None, :]).reshape(-1)
+            if ids.is_cuda:
+                from ml_trainer_amd.ops import transformer as TR
+                x = torch.empty(B * Tp, c.hidden, dtype=torch.bfloat16, device=dev)
+                TR.require_native().embed_fwd(ids, None, TR.bf16_weight(self.word_embeddings.weight),
+                                              None if c.rotary else TR.bf16_weight(self.position_embeddings.weight),
+                                              TR.bf16_weight(self.token_type_embeddings.weight), x, cache.Smax,
+                                              pos=tpos.contiguous())
+                x = self._decode_layers(x, lambda l, qkv: DC.attn_append(qkv, cache.kv[l], base, B, c.heads,
+                                                                         rope=self.rope_table))
+            else:
+                x = self._embed_torch(ids, torch.zeros_like(ids), tpos.long())
+                x = self._decode_layers_torch(x, lambda l, qkv: DC.attn_append_reference(
+                    qkv, cache.kv[l], base, B, c.heads, rope=self.rope_table))
+            sel = (counts.long() - 1 - t0)  # token counts - 1, where it falls in this piece (on the device)
+            last = x.view(B, Tp, -1)[ar, sel.clamp(0, Tp - 1)]
+            state.hidden = torch.where(((sel >= 0) & (sel < Tp))[:, None], last, state.hidden.to(last.dtype))
+            logits.append(self._rows_logits(x).float().reshape(B, Tp, -1))
+        cache.pos.add_(counts)
+        if state.width is not None:
+            state.width += T
+        return logits[0] if len(logits) == 1 else torch.cat(logits, 1)
 
     def _check_generate(self, input_ids, max_new_tokens, temperature, top_k, top_p=None, sampler=None, graph=False,
                         return_logits=False, kv_cache=None):
@@ -1096,7 +1179,7 @@ class BertLMHeadModel(BertForMaskedLM):
     def generate(self, input_ids, max_new_tokens: int, attention_mask=None, temperature: float = 0.0,
                  top_k: Optional[int] = None, eos_id: Optional[int] = None, seed: Optional[int] = None,
                  return_logits: bool = False, top_p: Optional[float] = None, sampler: Optional[str] = None,
-                 graph: bool = False, kv_cache: Optional[str] = None):
+                 graph: bool = False, kv_cache: Optional[str] = None, past=None):
         """Continue the prompts ``input_ids`` [B, S] (right-padded, ragged lengths allowed: sequence b's new
         tokens continue at position ``len_b``) by ``max_new_tokens`` tokens with a key/value cache: one
         ``prefill``, then one ``decode_step`` per token. Returns ``(tokens [B, max_new_tokens], lengths [B])``,
@@ -1120,16 +1203,34 @@ class BertLMHeadModel(BertForMaskedLM):
         ``kv_cache="fp8"`` (opt-in; ``None`` / ``"bf16"`` change nothing): the cache holds OCP e4m3 codes and one
         power-of-two scale per cached row (``ops.decode.kv_quantize_reference``), 0.53 x the bytes; a step's attention
         is ``C.attn_decode_f8`` over the dequantised rows, the prompt is quantised by ``C.kv_fill_f8``. Works eager and
-        graph-replayed, with every block kind, ``rotary`` and ``kv_heads``."""
+        graph-replayed, with every block kind, ``rotary`` and ``kv_heads``.
+
+        ``past`` (a ``DecodeState`` of an earlier ``prefill`` / ``generate`` turn over the same batch): ``input_ids``
+        are then the NEW turn only; they enter ``past``'s cache through ``extend`` instead of ``prefill``, the first
+        logits are those of each sequence's last real new token, and decoding continues into ``past``'s cache (the
+        state is advanced in place and can be passed again). Not with ``graph=True`` (the captured decoder owns its
+        cache) or an fp8 cache. The cache must have room for ``pos[b] + S + max_new_tokens`` rows: checked against
+        ``past.width`` where the state records it, otherwise the caller's duty, as with ``decode_step``."""
         self._check_generate(input_ids, max_new_tokens, temperature, top_k, top_p, sampler, graph, return_logits,
                              kv_cache)
         B, S = input_ids.shape
         dev = input_ids.device
-        if graph:
+        if past is not None:
+            if graph:
+                raise ValueError("generate(past=) cannot run graph=True: the captured decoder owns its cache")
+            if kv_cache == "fp8" or past.cache.scales is not None:
+                raise ValueError("generate(past=) takes a bf16 cache: extend has no fp8 form")
+            if (past.width if past.width is not None else 0) + S + max_new_tokens > past.cache.Smax:
+                raise ValueError(f"generate(past=): {S} new columns + {max_new_tokens} tokens do not fit the cache of "
+                                 f"{past.cache.Smax} rows after {past.width or 0} cached columns")
+            self.extend(past, input_ids, counts=self._lengths(input_ids, attention_mask))
+            state = past
+        elif graph:
             dec = self._graphed_decoder(B, S + max_new_tokens, max_new_tokens, dev, kv_cache)
             return dec.generate(self, input_ids, attention_mask,
                                 self._sampler_params(temperature, top_k, top_p, eos_id, seed))
-        state = self.prefill(input_ids, attention_mask, max_len=S + max_new_tokens, kv_cache=kv_cache)
+        else:
+            state = self.prefill(input_ids, attention_mask, max_len=S + max_new_tokens, kv_cache=kv_cache)
         if sampler == "device":
             st = self._new_sampler(B, max_new_tokens, dev, temperature, top_k, top_p, eos_id, seed)
             return self._device_sampler_loop(lambda: self.decode_step(state), lambda tok: self.decode_step(state, tok),

@@ -17,6 +17,13 @@ power-of-two scale per cached row. ``kv_quantize_reference`` / ``kv_dequantize_r
 ``attn_decode`` then launches ``C.attn_decode_f8`` (csrc/kernels/attn_decode_f8.hip, single and split forms) and
 ``fill_from_prefill`` ``C.kv_fill_f8``; ``attn_decode_reference`` takes the same cache on the CPU.
 
+``attn_append`` is the multi-token form (csrc/kernels/attn_append.hip): T = 1 .. 16 new tokens per sequence in one
+launch, attending to the cache and causally to each other, their k / v appended at rows ``pos[b] .. pos[b] + T - 1``;
+``pos`` is the caller's to advance, so accepting ``a <= T`` of them is ``pos += a`` and the rest is stale by
+definition. It streams the cache once for the T tokens where T ``attn_decode`` launches stream it T times, on the
+matrix cores; the bf16 cache only. ``attn_append_reference`` is its definition and CPU path;
+``BertLMHeadModel.extend`` the model-level caller.
+
 ``linear_small`` is the linear layer of a decode step (M = B rows): ``decode_linear_path`` sends it to the
 weight-streaming kernel ``C.gemm_skinny`` (csrc/kernels/gemm_skinny.hip) or to the planner's GEMM. With the skinny
 kernel every kernel of a step works row by row, so a sequence's logits do not depend on the batch it is decoded in.
@@ -55,6 +62,8 @@ SKINNY_MAX_ROWS = 16
 # single kernel already fills the machine and the split form is 1 - 4 % slower (profiles/decode_split/README.md):
 # the price of a routing that does not look at the batch; MLT_DECODE_SPLIT=0 is the switch.
 DECODE_SPLIT_MIN_SMAX = 2048
+# new tokens per sequence one attn_append launch takes (C.attn_append_max_tokens(): the 16 columns of the MFMA tile)
+APPEND_MAX_TOKENS = 16
 
 
 KV_CACHE_FORMATS = (None, "bf16", "fp8")
@@ -127,9 +136,12 @@ def kv_dequantize_reference(codes, scales):
 @dataclass
 class DecodeState:
     """What ``prefill`` hands to ``decode_step``: the cache (with ``pos``) and the hidden row [B, h] of every
-    sequence's last token, from which the next token's logits come."""
+    sequence's last token, from which the next token's logits come. ``width`` is a host-side upper bound of every
+    ``pos[b]`` (the prompt's width plus the columns fed since), kept so that ``generate(past=)`` can check the room
+    left in the cache without reading ``pos`` back; ``None``: not recorded."""
     cache: KVCache
     hidden: torch.Tensor
+    width: Optional[int] = None
 
     @property
     def pos(self) -> torch.Tensor:
@@ -233,6 +245,84 @@ def attn_decode_reference(qkv_new, cache_layer, pos, H: int, scale: float = ATTN
     V = torch.where(valid[..., None], V, torch.zeros_like(V))
     p = torch.softmax(s, -1)
     return (p[:, :, None, :] @ V)[:, :, 0, :].reshape(B, H * HEAD_DIM)
+
+
+def _append_tokens(qkv_new, B: int, Smax: int, kv_scale=None, fp8: bool = False) -> int:
+    """T of an ``attn_append`` call, or the ``ValueError`` both the native op and its reference raise."""
+    if kv_scale is not None or fp8:
+        raise ValueError("attn_append takes a bf16 cache: the fp8 cache has no multi-token kernel")
+    rows = qkv_new.shape[0]
+    T = rows // B if B > 0 else 0
+    if B < 1 or T * B != rows or not 1 <= T <= APPEND_MAX_TOKENS:
+        raise ValueError(f"attn_append takes 1 .. {APPEND_MAX_TOKENS} new tokens per sequence, got {rows} rows for "
+                         f"B = {B}")
+    if T > Smax:
+        raise ValueError(f"attn_append: {T} new tokens do not fit a cache of {Smax} rows")
+    return T
+
+
+def attn_append(qkv_new, cache_layer, pos, B: int, H: int, scale: float = ATTN_SCALE, rope=None, kv_scale=None):
+    """out [B * T, H * 64] bf16 = attention of T = rows / B new tokens per sequence (row ``b * T + t`` of ``qkv_new``
+    is token t of sequence b; 1 <= T <= 16) over the cached rows ``j < pos[b]`` and, causally, over each other; rows
+    ``pos[b] .. pos[b] + T - 1`` of ``cache_layer`` become their k / v; ``pos`` is not changed. One launch of
+    ``C.attn_append`` (csrc/kernels/attn_append.hip: MFMA scores and P . V, the cache streamed once for all T tokens
+    and the query heads of a group), or over a cache with ``decode_attn_path(Smax) == "split"`` its split form and the
+    decode merge launch, with the workspace and ``row_pos`` allocated here beside ``out``. ``qkv_new``, ``rope`` and a
+    cache of ``Hkv != H`` heads as in ``attn_decode``; the token at row ``pos[b] + t`` is rotated by that position.
+    The caller keeps ``pos[b] + T <= Smax`` (the kernel clamps). An fp8 cache (``kv_scale``) and a ``T`` out of range
+    raise ``ValueError``. A non-finite value in a new token may reach the rows of earlier tokens of its sequence
+    (the matrix cores multiply masked probabilities, 0 * NaN): finite inputs are the caller's duty."""
+    Smax = cache_layer.shape[3]
+    T = _append_tokens(qkv_new, B, Smax, kv_scale, cache_layer.dtype == torch.uint8)
+    C = require_native()
+    out = torch.empty(B * T, H * HEAD_DIM, dtype=torch.bfloat16, device=qkv_new.device)
+    ws = row_pos = None
+    if decode_attn_path(Smax) == "split":
+        ws = torch.empty(C.attn_append_ws(B, T, H, Smax), dtype=torch.float32, device=qkv_new.device)
+        row_pos = torch.empty(B * T, dtype=torch.int32, device=qkv_new.device)
+    C.attn_append(qkv_new, cache_layer, pos, out, B, H, scale, rope=rope, ws=ws, row_pos=row_pos)
+    return out
+
+
+def attn_append_reference(qkv_new, cache_layer, pos, B: int, H: int, scale: float = ATTN_SCALE, rope=None,
+                          kv_scale=None):
+    """``attn_append`` in plain fp32 torch, on any device (the CPU path and the definition): appends into
+    ``cache_layer`` (any float dtype) and returns out [B * T, H * 64] fp32. With ``n = clamp(pos[b], 0, Smax - T)``,
+    token t of sequence b sees the cached rows ``j < n`` and the new tokens ``t' <= t``; stale rows and invisible
+    tokens are selected out (scores to -inf, values to 0), never multiplied by zero, and the new k / v enter from
+    ``qkv_new`` itself. ``rope`` and grouped-query caches as in ``attn_decode_reference``, token t at position
+    ``n + t``. It equals T successive ``attn_decode_reference`` calls up to the summation order."""
+    Hkv, Smax = cache_layer.shape[2], cache_layer.shape[3]
+    T = _append_tokens(qkv_new, B, Smax, kv_scale, cache_layer.dtype == torch.uint8)
+    dev = qkv_new.device
+    if Hkv != H:
+        from ml_trainer_amd.ops.gqa import check_kv_heads, gqa_expand_reference
+        check_kv_heads(H, Hkv)
+        qkv_new = gqa_expand_reference(qkv_new, H, Hkv)
+    n = pos.long().clamp(0, Smax - T)
+    rows = n[:, None] + torch.arange(T, device=dev)[None, :]  # [B, T]: the cache row = the position of every token
+    if rope is not None:
+        from ml_trainer_amd.ops.rope import rope_qk_reference
+        qkv_new = rope_qk_reference(qkv_new, rope, H, pos=rows.reshape(-1))
+    q, k, v = qkv_new.float().view(B, T, 3, H, HEAD_DIM).unbind(2)  # [B, T, H, 64]
+    G = H // Hkv
+    ar = torch.arange(B, device=dev)[:, None]
+    cache_layer[0, ar, :, rows] = k[:, :, ::G].to(cache_layer.dtype)
+    cache_layer[1, ar, :, rows] = v[:, :, ::G].to(cache_layer.dtype)
+    Kc, Vc = cache_layer[0].float(), cache_layer[1].float()
+    if G > 1:
+        Kc, Vc = Kc.repeat_interleave(G, dim=1), Vc.repeat_interleave(G, dim=1)
+    cached = (torch.arange(Smax, device=dev)[None, :] < n[:, None])[:, None, None, :]  # [B, 1, 1, Smax]
+    t = torch.arange(T, device=dev)
+    tri = (t[None, :] <= t[:, None])[None, None]  # [1, 1, T(query), T(key)]
+    qh, kh, vh = (x.permute(0, 2, 1, 3) for x in (q, k, v))  # [B, H, T, 64]
+    neg = torch.tensor(float("-inf"), device=dev)
+    sc = torch.where(cached, (qh @ Kc.transpose(-1, -2)) * scale, neg)
+    sn = torch.where(tri, (qh @ kh.transpose(-1, -2)) * scale, neg)
+    p = torch.softmax(torch.cat((sc, sn), -1), -1)
+    Vc = torch.where(cached.transpose(-1, -2), Vc, torch.zeros_like(Vc))
+    o = p[..., :Smax] @ Vc + p[..., Smax:] @ vh
+    return o.permute(0, 2, 1, 3).reshape(B * T, H * HEAD_DIM)
 
 
 def decode_linear_path(M: int, N: int, K: int) -> str:
