@@ -1411,6 +1411,90 @@ void attn_decode_split(Tensor qkv_new, Tensor kv, Tensor pos, Tensor out, Tensor
                            (float)scale, cur_stream(), rp, (int)gc);
 }
 
+// The operands both paged launches share (attn_decode_paged.hip): pool bf16 [2, P, Hkv, R, 64] contiguous with R =
+// attn_decode_paged_page_rows(), block_table int32 [B, max_pages >= 1] contiguous on the device, Hkv a divisor of H.
+// The entries of the table are the caller's to keep in [0, P): they are not read back here. Returns
+// (P, Hkv, max_pages).
+static std::tuple<int64_t, int64_t, int64_t> check_paged(const Tensor& pool, const Tensor& block_table, int64_t B,
+                                                         int64_t H, const char* who) {
+  const int64_t R = attn_decode_paged_page_rows();
+  check_dev(pool, "pool", at::kBFloat16, 0);
+  TORCH_CHECK(pool.dim() == 5 && pool.size(0) == 2 && pool.size(1) >= 1 && pool.size(2) >= 1 && pool.size(3) == R &&
+                  pool.size(4) == 64,
+              who, ": pool must be [2, P, Hkv, ", R, ", 64], got ", pool.sizes());
+  const int64_t P = pool.size(1), Hkv = pool.size(2);
+  TORCH_CHECK(P <= 0x7fffffff && Hkv <= H && H % Hkv == 0, who, ": the pool holds ", Hkv,
+              " key/value heads, which does not divide H = ", H);
+  check_dev(block_table, "block_table", at::kInt, B, 4);
+  TORCH_CHECK(block_table.dim() == 2 && block_table.size(0) == B && block_table.size(1) >= 1 &&
+                  block_table.size(1) <= 0x7fffffff / R,
+              who, ": block_table must be int32 [B = ", B, ", max_pages >= 1], got ", block_table.sizes());
+  return {P, Hkv, block_table.size(1)};
+}
+
+// Decode attention over a paged cache (attn_decode_paged.hip): attn_decode_split with (pool, block_table) in place
+// of kv. qkv_new bf16 [B, (H + 2 Hkv) * 64] (may be a row-strided view), pos int32 [B], out bf16 [B, H * 64], ws the
+// shape attn_decode_split_ws(B, H, max_pages * R), rope [>= max_pages * R, 32, 2]. Everything is checked before the
+// first launch.
+void attn_decode_paged(Tensor qkv_new, Tensor pool, Tensor block_table, Tensor pos, Tensor out, Tensor ws, int64_t H,
+                       double scale, c10::optional<Tensor> rope, int64_t gc) {
+  TORCH_CHECK(qkv_new.is_cuda() && qkv_new.dim() == 2 && qkv_new.scalar_type() == at::kBFloat16,
+              "attn_decode_paged: qkv_new must be a bf16 [B, (H + 2 Hkv) * 64] device tensor");
+  const int64_t B = qkv_new.size(0), D = H * 64;
+  TORCH_CHECK(B > 0 && H > 0 && B <= 65535 && H <= 65535, "attention dims");
+  const auto [P, Hkv, max_pages] = check_paged(pool, block_table, B, H, "attn_decode_paged");
+  const int64_t Smax = max_pages * attn_decode_paged_page_rows(), W = (H + 2 * Hkv) * 64;
+  TORCH_CHECK(qkv_new.size(1) == W, "attn_decode_paged: qkv_new has ", qkv_new.size(1),
+              " columns, expected (H + 2 Hkv) * 64 = ", W);
+  TORCH_CHECK(qkv_new.stride(1) == 1 && qkv_new.stride(0) >= W && qkv_new.stride(0) % 8 == 0,
+              "attn_decode_paged: qkv_new needs unit column stride and a row stride that is a multiple of 8");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(qkv_new.data_ptr()) % 16 == 0, "qkv_new must be 16-byte aligned");
+  check_dev(pos, "pos", at::kInt, B, 4);
+  TORCH_CHECK(pos.numel() == B, "attn_decode_paged: pos must have one entry per sequence");
+  check_bf16_2d(out, "out", B, D);
+  const std::vector<int64_t> shape = attn_decode_split_ws(B, H, Smax);
+  TORCH_CHECK(shape[2] <= 65535 && B * H <= 0x7fffffff, "attn_decode_paged: ", shape[2], " splits x ", B * H,
+              " heads exceed the grid");
+  check_dev(ws, "ws", at::kFloat, 0, 16);
+  TORCH_CHECK(ws.sizes().vec() == shape, "attn_decode_paged: ws has shape ", ws.sizes(), ", expected ",
+              at::IntArrayRef(shape), " (attn_decode_split_ws over max_pages * ", attn_decode_paged_page_rows(),
+              " rows)");
+  const float* rp = nullptr;
+  if (rope.has_value()) {
+    check_dev(*rope, "rope table", at::kFloat, 64, 16);
+    TORCH_CHECK(rope->dim() == 3 && rope->size(1) == 32 && rope->size(2) == 2 && rope->size(0) >= Smax,
+                "attn_decode_paged: the rope table must be [rows >= max_pages * ", attn_decode_paged_page_rows(), " = ",
+                Smax, ", 32, 2]");
+    rp = rope->data_ptr<float>();
+  }
+  const int64_t G = H / Hkv;
+  TORCH_CHECK(gc == 0 || ((gc == 1 || gc == 2 || gc == 3 || gc == 4 || gc == 6 || gc == 8) && G % gc == 0),
+              "attn_decode_paged: gc = ", gc, " must be 0 or one of 1, 2, 3, 4, 6, 8 that divides H / Hkv = ", G);
+  launch_attn_decode_paged(bf16_ptr(qkv_new), qkv_new.stride(0), (uint16_t*)pool.data_ptr(),
+                           block_table.data_ptr<int>(), pos.data_ptr<int>(), (uint16_t*)out.data_ptr(),
+                           ws.data_ptr<float>(), (int)B, (int)H, (int)Hkv, (int)max_pages, (int)P, (float)scale,
+                           cur_stream(), rp, (int)gc);
+}
+
+// The prefill fill of a paged cache (kv_fill_paged_kernel): rows 0 .. S - 1 of every (b, KV head) from a layer's
+// padded, already rotated wide qkv [B * S, 3 * H * 64] bf16 (may be a row-strided view) into the pages the table
+// names; S <= max_pages * R.
+void kv_fill_paged(Tensor qkv, Tensor pool, Tensor block_table, int64_t B, int64_t S, int64_t H) {
+  TORCH_CHECK(qkv.is_cuda() && qkv.dim() == 2 && qkv.scalar_type() == at::kBFloat16,
+              "kv_fill_paged: qkv must be a bf16 [B * S, 3 * H * 64] device tensor");
+  TORCH_CHECK(B > 0 && S > 0 && H > 0 && H <= 65535 && B * S <= 0x7fffffff, "kv_fill_paged: B, S, H");
+  const auto [P, Hkv, max_pages] = check_paged(pool, block_table, B, H, "kv_fill_paged");
+  TORCH_CHECK(S <= max_pages * attn_decode_paged_page_rows(), "kv_fill_paged: a prompt of width ", S,
+              " does not fit a table of ", max_pages, " pages");
+  TORCH_CHECK(qkv.size(0) == B * S && qkv.size(1) == 3 * H * 64, "kv_fill_paged: qkv is [", qkv.size(0), ", ",
+              qkv.size(1), "], expected [B * S = ", B * S, ", ", 3 * H * 64, "]");
+  TORCH_CHECK(qkv.stride(1) == 1 && qkv.stride(0) >= qkv.size(1) && qkv.stride(0) % 8 == 0,
+              "kv_fill_paged: qkv needs unit column stride and a row stride that is a multiple of 8");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(qkv.data_ptr()) % 16 == 0, "qkv must be 16-byte aligned");
+  launch_kv_fill_paged(bf16_ptr(qkv), qkv.stride(0), (uint16_t*)pool.data_ptr(), block_table.data_ptr<int>(), (int)B,
+                       (int)S, (int)H, (int)Hkv, (int)max_pages, (int)P, cur_stream());
+}
+
 // The workspace of attn_append's split form: fp32 [B * T, H, ceil(Smax / C), 68], attn_decode_split_ws over B * T rows.
 std::vector<int64_t> attn_append_ws(int64_t B, int64_t T, int64_t H, int64_t Smax) {
   TORCH_CHECK(B > 0 && T > 0, "attn_append_ws: B and T must be positive");
@@ -2406,6 +2490,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("ws"), py::arg("H"), py::arg("scale"), py::arg("rope") = py::none(), py::arg("gc") = 0);
   m.def("attn_decode_split_ws", &attn_decode_split_ws, py::arg("B"), py::arg("H"), py::arg("Smax"));
   m.def("attn_decode_split_keys", []() { return (int64_t)attn_decode_split_keys(); });
+  m.def("attn_decode_paged", &attn_decode_paged, py::arg("qkv_new"), py::arg("pool"), py::arg("block_table"),
+        py::arg("pos"), py::arg("out"), py::arg("ws"), py::arg("H"), py::arg("scale"), py::arg("rope") = py::none(),
+        py::arg("gc") = 0);
+  m.def("attn_decode_paged_page_rows", []() { return (int64_t)attn_decode_paged_page_rows(); });
+  m.def("kv_fill_paged", &kv_fill_paged, py::arg("qkv"), py::arg("pool"), py::arg("block_table"), py::arg("B"),
+        py::arg("S"), py::arg("H"));
   m.def("attn_append", &attn_append, py::arg("qkv_new"), py::arg("kv"), py::arg("pos"), py::arg("out"), py::arg("B"),
         py::arg("H"), py::arg("scale"), py::arg("rope") = py::none(), py::arg("ws") = py::none(),
         py::arg("row_pos") = py::none(), py::arg("gc") = 0);

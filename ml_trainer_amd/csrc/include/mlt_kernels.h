@@ -452,6 +452,21 @@ void launch_attn_decode_split(const uint16_t* qkv_new, int64_t ldq, uint16_t* kv
 // The second launch of the split form alone (attn_decode_merge_kernel): ws [B][H][ceil(Smax / C)][68] as a split
 // kernel left it -> out [B][64 H] bf16. launch_attn_decode_split ends with it; launch_attn_decode_f8 too.
 void launch_attn_decode_merge(const float* ws, const int* pos, uint16_t* out, int B, int H, int Smax, hipStream_t st);
+// Decode attention over a paged cache (attn_decode_paged.hip): pool [2][P][Hkv][R][64] bf16 with R =
+// attn_decode_paged_page_rows() = 64 rows per page, block_table int32 [B][max_pages] on the device (entry i = the
+// page of rows R i .. R i + R - 1 of sequence b; every entry in [0, P), page 0 the null page that no sequence owns).
+// Always split + merge over the workspace of launch_attn_decode_split for Smax = max_pages R; qkv_new, pos, out,
+// rope and gc as there. out and the appended row (row pos[b] % R of page block_table[b][pos[b] / R]) have the bits
+// of launch_attn_decode_split on the cache gathered into contiguous form, wherever the pages lie.
+int attn_decode_paged_page_rows();
+void launch_attn_decode_paged(const uint16_t* qkv_new, int64_t ldq, uint16_t* pool, const int* block_table,
+                              const int* pos, uint16_t* out, float* ws, int B, int H, int Hkv, int max_pages, int P,
+                              float scale, hipStream_t st, const float* rope = nullptr, int gc = 0);
+// The prefill fill of the pages: row s < S <= max_pages R of (b, KV head) from the padded, already rotated wide qkv
+// [B * S][ldq >= 3 * 64 H] bf16 (ldq % 8 == 0, 16-byte aligned; every (H / Hkv)-th k / v head is taken) to row
+// s % R of page block_table[b][s / R].
+void launch_kv_fill_paged(const uint16_t* qkv, int64_t ldq, uint16_t* pool, const int* block_table, int B, int S,
+                          int H, int Hkv, int max_pages, int P, hipStream_t st);
 // Multi-token append attention (attn_append.hip): T = 1 .. attn_append_max_tokens() = 16 new tokens per sequence,
 // qkv_new [B * T][ldq] (row b T + t = token t of sequence b, compact q | k | v as launch_attn_decode_gqa), attend to
 // the cached rows j < n = clamp(pos[b], 0, Smax - T) and causally to each other; rows n .. n + T - 1 of the cache

@@ -835,7 +835,8 @@ class BertLMHeadModel(BertForMaskedLM):
         return torch.arange(B, device=device) * S + last
 
     @torch.no_grad()
-    def prefill(self, input_ids, attention_mask=None, max_len: Optional[int] = None, cache=None, kv_cache=None):
+    def prefill(self, input_ids, attention_mask=None, max_len: Optional[int] = None, cache=None, kv_cache=None,
+                pool=None):
         """Run the prompt ``input_ids`` [B, S] (right-padded; lengths from ``attention_mask`` or ``pad_id``)
         through the padded causal forward, layer by layer, keep every layer's K / V in a cache of ``max_len``
         rows per sequence (default ``config.max_position``) and return the ``DecodeState``: the cache with
@@ -844,18 +845,27 @@ class BertLMHeadModel(BertForMaskedLM):
         ``KVCache`` of this shape to fill in place (its ``pos`` is overwritten with ``pos.copy_``, its tensors keep
         their addresses: what a captured decode step needs) instead of a new one. ``kv_cache``: ``None`` / ``"bf16"``
         (the cache as it is) or ``"fp8"`` (e4m3 codes and one scale per cached row, ``ops.decode.KVCache``); a given
-        ``cache`` must be of that format. ``decode_step`` takes the format from the cache."""
+        ``cache`` must be of that format. ``decode_step`` takes the format from the cache. ``pool`` (an
+        ``ops.decode.PagePool`` of this model's layers and KV heads on the prompts' device): the state's cache is a
+        ``PagedKVCache`` over it with a table of ``ceil(max(max_len or S, S) / 64)`` pages, of which it owns those of
+        the S prompt rows; ``decode_step`` reserves more as the sequences grow, past ``max_len`` too, and
+        ``state.release()`` returns them. Not with ``cache=`` or ``kv_cache="fp8"``."""
         from ml_trainer_amd.ops import decode as DC
         c = self.config
         fp8 = DC.check_kv_cache(kv_cache)
         B, S = input_ids.shape
+        if pool is not None:
+            self._check_pool(pool, input_ids.device, fp8, cache)
         Smax = c.max_position if max_len is None else int(max_len)
         if not S <= Smax <= c.max_position:
             raise ValueError(f"prefill: prompt width {S} <= max_len {Smax} <= max_position {c.max_position} "
                              f"does not hold")
         dev = input_ids.device
         lens = self._lengths(input_ids, attention_mask)
-        if cache is None:
+        if pool is not None:
+            cache = DC.PagedKVCache(pool, B, -(-max(int(max_len or S), S) // DC.PAGE_ROWS))
+            cache.reserve(S)
+        elif cache is None:
             cache = DC.KVCache.allocate(c.layers, B, c.num_kv_heads, Smax, dev, kv_cache=kv_cache)
         elif (cache.Smax != Smax or len(cache.kv) != c.layers or cache.pos.device != dev or
               tuple(cache.kv[0].shape) != (2, B, c.num_kv_heads, Smax, DC.HEAD_DIM)):
@@ -901,6 +911,27 @@ class BertLMHeadModel(BertForMaskedLM):
             x = _norm_native(x, self.final_ln) if x.is_cuda else self.final_ln(x)
         return DC.DecodeState(cache, x, width=S)
 
+    def _check_pool(self, pool, dev, fp8=False, cache=None):
+        """The ``ValueError`` cases of ``prefill(pool=)`` / ``generate(pool=)``."""
+        c = self.config
+        if fp8:
+            raise ValueError("pool= takes a bf16 cache: there are no fp8 pages (kv_cache='fp8' cannot be given with it)")
+        if cache is not None:
+            raise ValueError("pool= builds its own PagedKVCache: cache= cannot be given with it")
+        if len(pool.kv) != c.layers or pool.Hkv != c.num_kv_heads or pool.device != dev:
+            raise ValueError(f"the page pool holds {len(pool.kv)} layers of {pool.Hkv} KV heads on {pool.device}, the "
+                             f"model needs {c.layers} layers of {c.num_kv_heads} on {dev}")
+
+    def _reserve_paged(self, state, rows: int):
+        """Before a step over a paged state: pages for ``rows`` rows per sequence, by the host bound ``state.width``."""
+        c = self.config
+        if rows > c.max_position:
+            raise ValueError(f"a paged state of {rows} rows exceeds max_position {c.max_position}")
+        state.cache.reserve(rows)
+        if self.rope_table is not None and state.cache.Smax > self.rope_table.shape[0]:
+            raise ValueError(f"a block table of {state.cache.max_pages} pages names {state.cache.Smax} rows, the rotary "
+                             f"table has max_position = {self.rope_table.shape[0]}: make it a multiple of 64")
+
     def _state_logits(self, state):
         from ml_trainer_amd.ops import decode as DC
         from ml_trainer_amd.ops import mlm as M
@@ -938,19 +969,33 @@ class BertLMHeadModel(BertForMaskedLM):
         cache = state.cache
         ids = token_ids.reshape(-1).to(torch.int64).contiguous()
         B = ids.numel()
+        paged = isinstance(cache, DC.PagedKVCache)
+        if paged:  # pages for the row this step appends; the table may be a new, wider tensor afterwards
+            if state.width is None:
+                raise ValueError("a paged state needs its width (the host bound pages are reserved by)")
+            self._reserve_paged(state, state.width + 1)
         if ids.is_cuda:
             from ml_trainer_amd.ops import transformer as T
             C = T.require_native()
             x = torch.empty(B, c.hidden, dtype=torch.bfloat16, device=ids.device)
             C.embed_fwd(ids, None, T.bf16_weight(self.word_embeddings.weight),
                         None if c.rotary else T.bf16_weight(self.position_embeddings.weight),
-                        T.bf16_weight(self.token_type_embeddings.weight), x, cache.Smax, pos=cache.pos)
-            x = self._decode_layers(x, lambda l, qkv: DC.attn_decode(
-                qkv, cache.kv[l], cache.pos, c.heads, rope=self.rope_table, kv_scale=cache.scale(l)))
+                        T.bf16_weight(self.token_type_embeddings.weight), x,
+                        min(cache.Smax, c.max_position) if paged else cache.Smax, pos=cache.pos)
+            if paged:
+                x = self._decode_layers(x, lambda l, qkv: DC.attn_decode(
+                    qkv, cache.kv[l], cache.pos, c.heads, rope=self.rope_table, block_table=cache.block_table))
+            else:
+                x = self._decode_layers(x, lambda l, qkv: DC.attn_decode(
+                    qkv, cache.kv[l], cache.pos, c.heads, rope=self.rope_table, kv_scale=cache.scale(l)))
         else:
             x = self._embed_torch(ids, torch.zeros_like(ids), cache.pos.long())
-            x = self._decode_layers_torch(x, lambda l, qkv: DC.attn_decode_reference(
-                qkv, cache.kv[l], cache.pos, c.heads, rope=self.rope_table, kv_scale=cache.scale(l)))
+            if paged:
+                x = self._decode_layers_torch(x, lambda l, qkv: DC.attn_decode_paged_reference(
+                    qkv, cache.kv[l], cache.block_table, cache.pos, c.heads, rope=self.rope_table))
+            else:
+                x = self._decode_layers_torch(x, lambda l, qkv: DC.attn_decode_reference(
+                    qkv, cache.kv[l], cache.pos, c.heads, rope=self.rope_table, kv_scale=cache.scale(l)))
         cache.pos.add_(1)
         state.hidden = x
         if state.width is not None:
@@ -1018,6 +1063,8 @@ class BertLMHeadModel(BertForMaskedLM):
         cache = state.cache
         if cache.scales is not None:
             raise ValueError("extend takes a bf16 cache: the fp8 cache has no multi-token attention kernel")
+        if isinstance(cache, DC.PagedKVCache):
+            raise ValueError("extend takes a contiguous cache: the paged cache has no multi-token attention kernel")
         if token_ids.dim() != 2 or token_ids.shape[1] < 1 or token_ids.shape[0] != cache.pos.numel():
             raise ValueError(f"extend takes token_ids [B = {cache.pos.numel()}, T >= 1], got {tuple(token_ids.shape)}")
         B, T = token_ids.shape
@@ -1055,6 +1102,18 @@ class BertLMHeadModel(BertForMaskedLM):
         if state.width is not None:
             state.width += T
         return logits[0] if len(logits) == 1 else torch.cat(logits, 1)
+
+    def _feed_paged(self, state, token_ids, counts):
+        """What ``extend`` does for ``generate(past=)``, over a paged state: the columns of ``token_ids`` [B, T] one
+        ``decode_step`` each (the paged cache has no multi-token kernel). A sequence with ``counts[b] <= t`` takes
+        column t back: its ``pos`` and hidden row stay, and the row it wrote lies at ``pos[b]``, stale by definition."""
+        counts = counts.to(device=token_ids.device, dtype=torch.int32)
+        for t in range(token_ids.shape[1]):
+            hidden = state.hidden
+            self.decode_step(state, token_ids[:, t])
+            live = counts > t
+            state.cache.pos.sub_((~live).to(torch.int32))
+            state.hidden = torch.where(live[:, None], state.hidden, hidden.to(state.hidden.dtype))
 
     def _check_generate(self, input_ids, max_new_tokens, temperature, top_k, top_p=None, sampler=None, graph=False,
                         return_logits=False, kv_cache=None):
@@ -1179,7 +1238,7 @@ class BertLMHeadModel(BertForMaskedLM):
     def generate(self, input_ids, max_new_tokens: int, attention_mask=None, temperature: float = 0.0,
                  top_k: Optional[int] = None, eos_id: Optional[int] = None, seed: Optional[int] = None,
                  return_logits: bool = False, top_p: Optional[float] = None, sampler: Optional[str] = None,
-                 graph: bool = False, kv_cache: Optional[str] = None, past=None):
+                 graph: bool = False, kv_cache: Optional[str] = None, past=None, pool=None):
         """Continue the prompts ``input_ids`` [B, S] (right-padded, ragged lengths allowed: sequence b's new
         tokens continue at position ``len_b``) by ``max_new_tokens`` tokens with a key/value cache: one
         ``prefill``, then one ``decode_step`` per token. Returns ``(tokens [B, max_new_tokens], lengths [B])``,
@@ -1210,33 +1269,56 @@ class BertLMHeadModel(BertForMaskedLM):
         logits are those of each sequence's last real new token, and decoding continues into ``past``'s cache (the
         state is advanced in place and can be passed again). Not with ``graph=True`` (the captured decoder owns its
         cache) or an fp8 cache. The cache must have room for ``pos[b] + S + max_new_tokens`` rows: checked against
-        ``past.width`` where the state records it, otherwise the caller's duty, as with ``decode_step``."""
+        ``past.width`` where the state records it, otherwise the caller's duty, as with ``decode_step``.
+
+        ``pool`` (an ``ops.decode.PagePool``; eager, either sampler, bf16): the cache is a ``PagedKVCache`` over it
+        (``prefill(pool=)``) that owns pages for the rows it holds and takes more as it grows; its pages go back to the
+        pool before this returns. A paged ``past`` (from ``prefill(pool=)``) simply grows, past the ``max_len`` it was
+        made with: the new turn enters it one ``decode_step`` per column, the "does not fit" error is the contiguous
+        cache's alone, and the state stays the caller's to ``release()``. Tokens and logits are those of the
+        contiguous cache, bit for bit while fewer than 256 rows are cached (one active split)."""
         self._check_generate(input_ids, max_new_tokens, temperature, top_k, top_p, sampler, graph, return_logits,
                              kv_cache)
         B, S = input_ids.shape
         dev = input_ids.device
+        from ml_trainer_amd.ops.decode import PagedKVCache
+        if pool is not None:
+            if graph:
+                raise ValueError("generate(pool=) runs eager: a captured decoder bakes in its cache's addresses")
+            self._check_pool(pool, dev, kv_cache == "fp8")
+            if past is not None and (not isinstance(past.cache, PagedKVCache) or past.cache.pool is not pool):
+                raise ValueError("generate(past=, pool=): the state's cache is not a paged cache over that pool")
         if past is not None:
             if graph:
                 raise ValueError("generate(past=) cannot run graph=True: the captured decoder owns its cache")
             if kv_cache == "fp8" or past.cache.scales is not None:
                 raise ValueError("generate(past=) takes a bf16 cache: extend has no fp8 form")
-            if (past.width if past.width is not None else 0) + S + max_new_tokens > past.cache.Smax:
+            if isinstance(past.cache, PagedKVCache):
+                lens = self._lengths(input_ids, attention_mask)
+                self._feed_paged(past, input_ids, torch.full((B,), S, device=dev) if lens is None else lens)
+            elif (past.width if past.width is not None else 0) + S + max_new_tokens > past.cache.Smax:
                 raise ValueError(f"generate(past=): {S} new columns + {max_new_tokens} tokens do not fit the cache of "
                                  f"{past.cache.Smax} rows after {past.width or 0} cached columns")
-            self.extend(past, input_ids, counts=self._lengths(input_ids, attention_mask))
+            else:
+                self.extend(past, input_ids, counts=self._lengths(input_ids, attention_mask))
             state = past
         elif graph:
             dec = self._graphed_decoder(B, S + max_new_tokens, max_new_tokens, dev, kv_cache)
             return dec.generate(self, input_ids, attention_mask,
                                 self._sampler_params(temperature, top_k, top_p, eos_id, seed))
         else:
-            state = self.prefill(input_ids, attention_mask, max_len=S + max_new_tokens, kv_cache=kv_cache)
-        if sampler == "device":
-            st = self._new_sampler(B, max_new_tokens, dev, temperature, top_k, top_p, eos_id, seed)
-            return self._device_sampler_loop(lambda: self.decode_step(state), lambda tok: self.decode_step(state, tok),
-                                             st, max_new_tokens, return_logits)
-        return self._generate_loop(lambda: self.decode_step(state), lambda tok: self.decode_step(state, tok), B,
-                                   dev, max_new_tokens, temperature, top_k, eos_id, seed, return_logits)
+            state = self.prefill(input_ids, attention_mask, max_len=S + max_new_tokens, kv_cache=kv_cache, pool=pool)
+        try:
+            if sampler == "device":
+                st = self._new_sampler(B, max_new_tokens, dev, temperature, top_k, top_p, eos_id, seed)
+                return self._device_sampler_loop(lambda: self.decode_step(state),
+                                                 lambda tok: self.decode_step(state, tok), st, max_new_tokens,
+                                                 return_logits)
+            return self._generate_loop(lambda: self.decode_step(state), lambda tok: self.decode_step(state, tok), B,
+                                       dev, max_new_tokens, temperature, top_k, eos_id, seed, return_logits)
+        finally:
+            if pool is not None and past is None:  # the state made here; a caller's state stays the caller's
+                state.release()
 
     @torch.no_grad()
     def decode_logits_reference(self, ids, lens):

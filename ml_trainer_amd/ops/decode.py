@@ -24,6 +24,15 @@ definition. It streams the cache once for the T tokens where T ``attn_decode`` l
 matrix cores; the bf16 cache only. ``attn_append_reference`` is its definition and CPU path;
 ``BertLMHeadModel.extend`` the model-level caller.
 
+The paged cache (``PagePool`` / ``PagedKVCache``): the rows live in pages of ``PAGE_ROWS = 64`` rows drawn from one
+pool, ``kv[l]`` [2, P, Hkv, 64, 64], and a sequence names its pages in a row of ``block_table`` (int32
+[B, max_pages], on the device, written by the host; page 0 is the null page of every unowned entry). A sequence pays
+for the rows it holds, grows past the reservation it started with and returns its pages when it is done.
+``attn_decode(block_table=)`` launches ``C.attn_decode_paged`` (csrc/kernels/attn_decode_paged.hip: always split +
+merge, the bits of ``C.attn_decode_split`` on the gathered cache), ``fill_from_prefill`` ``C.kv_fill_paged``;
+``attn_decode_paged_reference`` is the definition and the CPU path. Paging is a layout, not a format: it is reached
+through ``pool=`` / ``block_table=``, never through ``kv_cache=``.
+
 ``linear_small`` is the linear layer of a decode step (M = B rows): ``decode_linear_path`` sends it to the
 weight-streaming kernel ``C.gemm_skinny`` (csrc/kernels/gemm_skinny.hip) or to the planner's GEMM. With the skinny
 kernel every kernel of a step works row by row, so a sequence's logits do not depend on the batch it is decoded in.
@@ -64,6 +73,9 @@ SKINNY_MAX_ROWS = 16
 DECODE_SPLIT_MIN_SMAX = 2048
 # new tokens per sequence one attn_append launch takes (C.attn_append_max_tokens(): the 16 columns of the MFMA tile)
 APPEND_MAX_TOKENS = 16
+# rows of one page of a paged cache (C.attn_decode_paged_page_rows(): a compile-time constant of the kernels). A
+# wave's 32-key run of the decode kernels lies inside one page, and a split of 256 keys is 4 pages.
+PAGE_ROWS = 64
 
 
 KV_CACHE_FORMATS = (None, "bf16", "fp8")
@@ -133,12 +145,115 @@ def kv_dequantize_reference(codes, scales):
     return codes.view(torch.float8_e4m3fn).float() * scales[..., None]
 
 
+class PagePool:
+    """The memory of a paged cache: ``kv[l]`` [2, P, Hkv, 64, 64] per layer (keys / values, page, KV head, row in
+    page, dim; bf16 on the GPU, fp32 on the CPU, as ``KVCache`` chooses), shared by every ``PagedKVCache`` built on
+    it. A page id names the same page in every layer. Page 0 is the null page: never handed out, and what every
+    unowned block-table entry points at, so a stale or clamped position cannot land outside the pool or in another
+    sequence's rows. The free list lives on the host: ``alloc`` / ``free`` touch no device memory."""
+
+    def __init__(self, layers: int, pages: int, Hkv: int, device, dtype=None):
+        device = torch.device(device)
+        if layers < 1 or pages < 2 or Hkv < 1:
+            raise ValueError(f"a page pool needs layers >= 1, pages >= 2 (page 0 is the null page) and Hkv >= 1, got "
+                             f"{layers}, {pages}, {Hkv}")
+        if dtype is None:
+            dtype = torch.bfloat16 if device.type == "cuda" else torch.float32
+        self.kv = [torch.zeros(2, pages, Hkv, PAGE_ROWS, HEAD_DIM, dtype=dtype, device=device) for _ in range(layers)]
+        self.pages, self.Hkv = pages, Hkv
+        self._free = list(range(pages - 1, 0, -1))  # a stack: alloc hands out 1, 2, ... first
+        self._owned = [False] * pages
+
+    @property
+    def device(self) -> torch.device:
+        return self.kv[0].device
+
+    @property
+    def num_free(self) -> int:
+        return len(self._free)
+
+    def alloc(self, n: int) -> List[int]:
+        """``n`` page ids off the free list, or ``RuntimeError`` with the list unchanged."""
+        if n > len(self._free):
+            raise RuntimeError(f"page pool exhausted: {n} pages asked, {len(self._free)} of {self.pages - 1} free")
+        ids = [self._free.pop() for _ in range(n)]
+        for i in ids:
+            self._owned[i] = True
+        return ids
+
+    def free(self, ids) -> None:
+        for i in ids:
+            if not 0 < i < self.pages or not self._owned[i]:
+                raise ValueError(f"page {i} is not an allocated page of this pool")
+            self._owned[i] = False
+            self._free.append(i)
+
+
+class PagedKVCache:
+    """A cache of B sequences over a ``PagePool``: ``block_table`` int32 [B, max_pages] on the device (entry i = the
+    page of rows ``64 i .. 64 i + 63``; 0 = the null page = not owned), ``pos`` int32 [B] as in ``KVCache``, ``Smax =
+    max_pages * 64`` the rows the table can name. ``kv`` is the pool's, ``scales`` is None and ``kv_cache`` "bf16", so
+    code that asks a ``KVCache`` those questions gets the same answers. ``pages[b]`` (host) are the ids sequence b
+    owns, in row order. The host writes the table, so every entry lies in [0, P): the kernels rely on it."""
+
+    def __init__(self, pool: PagePool, B: int, max_pages: int):
+        if B < 1 or max_pages < 1:
+            raise ValueError(f"a paged cache needs B >= 1 and max_pages >= 1, got {B}, {max_pages}")
+        self.pool, self.max_pages = pool, int(max_pages)
+        self.block_table = torch.zeros(B, self.max_pages, dtype=torch.int32, device=pool.device)
+        self.pos = torch.zeros(B, dtype=torch.int32, device=pool.device)
+        self.pages: List[List[int]] = [[] for _ in range(B)]
+        self.scales = None
+
+    @property
+    def kv(self) -> List[torch.Tensor]:
+        return self.pool.kv
+
+    @property
+    def Smax(self) -> int:
+        return self.max_pages * PAGE_ROWS
+
+    @property
+    def kv_cache(self) -> str:
+        return "bf16"
+
+    def scale(self, layer: int):
+        return None
+
+    def reserve(self, rows: int) -> None:
+        """Make every sequence own ``ceil(rows / 64)`` pages (never fewer than it has). Host-side: ``rows`` comes
+        from a host bound such as ``DecodeState.width``, ``pos`` is not read back. New ids reach the device in one
+        small host-to-device copy of the table, which is replaced by a wider one when ``rows > Smax``. An exhausted
+        pool raises ``RuntimeError`` before the table or the free list changed."""
+        need = -(-int(rows) // PAGE_ROWS)
+        short = [max(0, need - len(p)) for p in self.pages]
+        if not any(short):
+            return
+        ids = self.pool.alloc(sum(short))
+        for p, k in zip(self.pages, short):
+            p.extend(ids.pop() for _ in range(k))
+        self.max_pages = max(self.max_pages, need)
+        host = torch.tensor([p + [0] * (self.max_pages - len(p)) for p in self.pages], dtype=torch.int32)
+        if self.block_table.shape[1] == self.max_pages:
+            self.block_table.copy_(host)
+        else:
+            self.block_table = host.to(self.pool.device)
+
+    def release(self) -> None:
+        """Give every page back to the pool and zero the table (every entry the null page again)."""
+        for p in self.pages:
+            self.pool.free(p)
+            p.clear()
+        self.block_table.zero_()
+
+
 @dataclass
 class DecodeState:
     """What ``prefill`` hands to ``decode_step``: the cache (with ``pos``) and the hidden row [B, h] of every
     sequence's last token, from which the next token's logits come. ``width`` is a host-side upper bound of every
     ``pos[b]`` (the prompt's width plus the columns fed since), kept so that ``generate(past=)`` can check the room
-    left in the cache without reading ``pos`` back; ``None``: not recorded."""
+    left in the cache without reading ``pos`` back; ``None``: not recorded. Over a ``PagedKVCache`` it is what
+    ``decode_step`` reserves pages by, and ``release()`` returns the pages to the pool."""
     cache: KVCache
     hidden: torch.Tensor
     width: Optional[int] = None
@@ -147,8 +262,14 @@ class DecodeState:
     def pos(self) -> torch.Tensor:
         return self.cache.pos
 
+    def release(self) -> None:
+        """Return a paged cache's pages to its pool; a contiguous cache owns its memory: nothing to do."""
+        if isinstance(self.cache, PagedKVCache):
+            self.cache.release()
 
-def attn_decode(qkv_new, cache_layer, pos, H: int, scale: float = ATTN_SCALE, rope=None, kv_scale=None):
+
+def attn_decode(qkv_new, cache_layer, pos, H: int, scale: float = ATTN_SCALE, rope=None, kv_scale=None,
+                block_table=None):
     """out [B, H * 64] bf16 = attention of the B new tokens' queries over their cached keys and themselves;
     rows ``pos[b]`` of ``cache_layer`` become the new tokens' k / v (the native kernel). ``qkv_new``
     [B, 3 * H * 64] bf16 may be a row-strided view (row stride a multiple of 8). ``rope`` (the fp32 table of
@@ -163,10 +284,20 @@ def attn_decode(qkv_new, cache_layer, pos, H: int, scale: float = ATTN_SCALE, ro
     layouts: two launches, with a workspace allocated here beside ``out``.
     ``kv_scale`` (fp32 [2, B, Hkv, Smax]): ``cache_layer`` is an fp8 cache (uint8 e4m3 codes) and the launch
     ``C.attn_decode_f8`` (csrc/kernels/attn_decode_f8.hip), for every layout; the same ``decode_attn_path`` gives it the
-    workspace of the split form. The new k / v are quantised first and enter their own step dequantised."""
+    workspace of the split form. The new k / v are quantised first and enter their own step dequantised.
+    ``block_table`` (int32 [B, max_pages] on the device): the paged cache. ``cache_layer`` is then a ``PagePool``
+    layer [2, P, Hkv, 64, 64] and the launch ``C.attn_decode_paged`` (csrc/kernels/attn_decode_paged.hip), always
+    split + merge over ``max_pages * 64`` rows (``decode_attn_path`` is not consulted), with the bits of
+    ``C.attn_decode_split`` on the gathered cache. There is no fp8 page: ``kv_scale`` with it raises ``ValueError``."""
+    if block_table is not None and kv_scale is not None:
+        raise ValueError("attn_decode: a paged cache is bf16, kv_scale cannot be given with block_table")
     C = require_native()
     out = torch.empty(qkv_new.shape[0], H * HEAD_DIM, dtype=torch.bfloat16, device=qkv_new.device)
-    if kv_scale is not None:
+    if block_table is not None:
+        ws = torch.empty(C.attn_decode_split_ws(qkv_new.shape[0], H, block_table.shape[1] * PAGE_ROWS),
+                         dtype=torch.float32, device=qkv_new.device)
+        C.attn_decode_paged(qkv_new, cache_layer, block_table, pos, out, ws, H, scale, rope=rope)
+    elif kv_scale is not None:
         ws = None
         if decode_attn_path(cache_layer.shape[3]) == "split":
             ws = torch.empty(C.attn_decode_split_ws(qkv_new.shape[0], H, cache_layer.shape[3]), dtype=torch.float32,
@@ -247,8 +378,32 @@ def attn_decode_reference(qkv_new, cache_layer, pos, H: int, scale: float = ATTN
     return (p[:, :, None, :] @ V)[:, :, 0, :].reshape(B, H * HEAD_DIM)
 
 
-def _append_tokens(qkv_new, B: int, Smax: int, kv_scale=None, fp8: bool = False) -> int:
+def gather_pages(pool_layer, block_table):
+    """The contiguous cache [2, B, Hkv, max_pages * 64, 64] a block table names in ``pool_layer`` [2, P, Hkv, 64, 64]
+    (a copy; unowned entries show the null page)."""
+    B, mp = block_table.shape
+    g = pool_layer[:, block_table.long()]  # [2, B, max_pages, Hkv, 64, 64]
+    return g.permute(0, 1, 3, 2, 4, 5).reshape(2, B, pool_layer.shape[2], mp * PAGE_ROWS, HEAD_DIM)
+
+
+def attn_decode_paged_reference(qkv_new, pool_layer, block_table, pos, H: int, scale: float = ATTN_SCALE, rope=None):
+    """``attn_decode`` over a paged cache in plain torch, on any device (the CPU path and the definition): gather
+    the pages into the contiguous cache (``gather_pages``), ``attn_decode_reference`` on it, and the one new row per
+    (b, KV head) written back to row ``pos[b] % 64`` of page ``block_table[b, pos[b] // 64]``. Returns out
+    [B, H * 64] fp32."""
+    kv = gather_pages(pool_layer, block_table)
+    out = attn_decode_reference(qkv_new, kv, pos, H, scale, rope)
+    n = pos.long()
+    ar = torch.arange(n.numel(), device=n.device)
+    page = block_table.long()[ar, n // PAGE_ROWS]
+    pool_layer[:, page, :, n % PAGE_ROWS] = kv[:, ar, :, n]  # both [B, 2, Hkv, 64]
+    return out
+
+
+def _append_tokens(qkv_new, B: int, Smax: int, kv_scale=None, fp8: bool = False, block_table=None) -> int:
     """T of an ``attn_append`` call, or the ``ValueError`` both the native op and its reference raise."""
+    if block_table is not None:
+        raise ValueError("attn_append takes a contiguous cache: the paged cache has no multi-token kernel")
     if kv_scale is not None or fp8:
         raise ValueError("attn_append takes a bf16 cache: the fp8 cache has no multi-token kernel")
     rows = qkv_new.shape[0]
@@ -261,7 +416,8 @@ def _append_tokens(qkv_new, B: int, Smax: int, kv_scale=None, fp8: bool = False)
     return T
 
 
-def attn_append(qkv_new, cache_layer, pos, B: int, H: int, scale: float = ATTN_SCALE, rope=None, kv_scale=None):
+def attn_append(qkv_new, cache_layer, pos, B: int, H: int, scale: float = ATTN_SCALE, rope=None, kv_scale=None,
+                block_table=None):
     """out [B * T, H * 64] bf16 = attention of T = rows / B new tokens per sequence (row ``b * T + t`` of ``qkv_new``
     is token t of sequence b; 1 <= T <= 16) over the cached rows ``j < pos[b]`` and, causally, over each other; rows
     ``pos[b] .. pos[b] + T - 1`` of ``cache_layer`` become their k / v; ``pos`` is not changed. One launch of
@@ -270,10 +426,11 @@ def attn_append(qkv_new, cache_layer, pos, B: int, H: int, scale: float = ATTN_S
     decode merge launch, with the workspace and ``row_pos`` allocated here beside ``out``. ``qkv_new``, ``rope`` and a
     cache of ``Hkv != H`` heads as in ``attn_decode``; the token at row ``pos[b] + t`` is rotated by that position.
     The caller keeps ``pos[b] + T <= Smax`` (the kernel clamps). An fp8 cache (``kv_scale``) and a ``T`` out of range
-    raise ``ValueError``. A non-finite value in a new token may reach the rows of earlier tokens of its sequence
-    (the matrix cores multiply masked probabilities, 0 * NaN): finite inputs are the caller's duty."""
+    raise ``ValueError``, and so does ``block_table`` (a paged cache: it has no multi-token kernel). A non-finite
+    value in a new token may reach the rows of earlier tokens of its sequence (the matrix cores multiply masked
+    probabilities, 0 * NaN): finite inputs are the caller's duty."""
     Smax = cache_layer.shape[3]
-    T = _append_tokens(qkv_new, B, Smax, kv_scale, cache_layer.dtype == torch.uint8)
+    T = _append_tokens(qkv_new, B, Smax, kv_scale, cache_layer.dtype == torch.uint8, block_table)
     C = require_native()
     out = torch.empty(B * T, H * HEAD_DIM, dtype=torch.bfloat16, device=qkv_new.device)
     ws = row_pos = None
@@ -285,7 +442,7 @@ def attn_append(qkv_new, cache_layer, pos, B: int, H: int, scale: float = ATTN_S
 
 
 def attn_append_reference(qkv_new, cache_layer, pos, B: int, H: int, scale: float = ATTN_SCALE, rope=None,
-                          kv_scale=None):
+                          kv_scale=None, block_table=None):
     """``attn_append`` in plain fp32 torch, on any device (the CPU path and the definition): appends into
     ``cache_layer`` (any float dtype) and returns out [B * T, H * 64] fp32. With ``n = clamp(pos[b], 0, Smax - T)``,
     token t of sequence b sees the cached rows ``j < n`` and the new tokens ``t' <= t``; stale rows and invisible
@@ -293,7 +450,7 @@ def attn_append_reference(qkv_new, cache_layer, pos, B: int, H: int, scale: floa
     ``qkv_new`` itself. ``rope`` and grouped-query caches as in ``attn_decode_reference``, token t at position
     ``n + t``. It equals T successive ``attn_decode_reference`` calls up to the summation order."""
     Hkv, Smax = cache_layer.shape[2], cache_layer.shape[3]
-    T = _append_tokens(qkv_new, B, Smax, kv_scale, cache_layer.dtype == torch.uint8)
+    T = _append_tokens(qkv_new, B, Smax, kv_scale, cache_layer.dtype == torch.uint8, block_table)
     dev = qkv_new.device
     if Hkv != H:
         from ml_trainer_amd.ops.gqa import check_kv_heads, gqa_expand_reference
@@ -393,7 +550,9 @@ def fill_from_prefill(cache: KVCache, layer: int, qkv, lens: Optional[torch.Tens
     head count): the H of ``qkv`` when the cache holds fewer heads (grouped-query attention: ``qkv`` is the wide
     buffer, whose k / v heads are equal within a group, and the cache takes every ``H // Hkv``-th of them).
     An fp8 cache is filled by ``C.kv_fill_f8`` on the GPU (one launch per layer, the quantiser of the decode step's
-    append) and by ``kv_quantize_reference`` on the CPU."""
+    append) and by ``kv_quantize_reference`` on the CPU. A ``PagedKVCache`` (which must own pages for S rows:
+    ``reserve``) is filled by ``C.kv_fill_paged`` on the GPU, one launch per layer, and by torch indexing on the CPU:
+    row s of sequence b goes to row ``s % 64`` of page ``block_table[b, s // 64]``."""
     kv = cache.kv[layer]
     H = kv.shape[2] if heads is None else heads
     G = H // kv.shape[2]
@@ -401,6 +560,18 @@ def fill_from_prefill(cache: KVCache, layer: int, qkv, lens: Optional[torch.Tens
         raise ValueError(f"a cache of {kv.shape[2]} heads does not divide heads = {H}")
     if S > cache.Smax:
         raise ValueError(f"a prompt of width {S} does not fit a cache of {cache.Smax} rows")
+    if isinstance(cache, PagedKVCache):
+        if min(len(p) for p in cache.pages) * PAGE_ROWS < S:
+            raise ValueError(f"a prompt of width {S} needs pages reserved for it (PagedKVCache.reserve)")
+        if qkv.is_cuda:
+            require_native().kv_fill_paged(qkv.view(B * S, 3 * H * HEAD_DIM), kv, cache.block_table, B, S, H)
+        else:
+            x = qkv.view(B, S, 3, H, HEAD_DIM)
+            s = torch.arange(S, device=qkv.device)
+            page = cache.block_table.long()[:, s // PAGE_ROWS]  # [B, S]
+            kv[0][page, :, s % PAGE_ROWS] = x[:, :, 1, ::G].to(kv.dtype)  # both [B, S, Hkv, 64]
+            kv[1][page, :, s % PAGE_ROWS] = x[:, :, 2, ::G].to(kv.dtype)
+        return
     if cache.scales is not None:
         if qkv.is_cuda:
             require_native().kv_fill_f8(qkv.view(B * S, 3 * H * HEAD_DIM), kv, cache.scales[layer], B, S, H)
