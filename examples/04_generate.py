@@ -72,6 +72,10 @@ def main(argv=None):
                                    seed=args.seed, sampler="device", graph=on_gpu)
     print(f"top-p 0.9 / top-k 20 / temperature 0.7{' (graph replay)' if on_gpu else ''}: row 0 -> "
           f"{sampled[0].tolist()}  agreement with the row {float((sampled.cpu() == want).float().mean()):.3f}")
+    # weight-only fp8 for the decode steps: the layer linears stream e4m3 codes and one scale per output row
+    f8w, _ = tr.model.generate(val.ids[:, :P].to(tr.device), N, temperature=args.temperature, top_k=args.top_k,
+                               seed=args.seed, weights="fp8")
+    print(f"fp8 layer weights: {float((f8w.cpu() == tokens).float().mean()):.3f} of the tokens equal")
     if P >= 2:  # the prompt in two turns: half through prefill, the rest into the same cache through generate(past=)
         state = tr.model.prefill(val.ids[:, :P // 2].to(tr.device), max_len=P + N)
         again, _ = tr.model.generate(val.ids[:, P // 2:P].to(tr.device), N, temperature=args.temperature,

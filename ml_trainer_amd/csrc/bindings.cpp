@@ -602,6 +602,77 @@ void gemm_skinny_glu(Tensor X, Tensor W, Tensor Y, c10::optional<Tensor> bias) {
                          W.stride(0), Y.stride(0), bp, cur_stream());
 }
 
+// The fp8 weight of gemm_skinny_f8 / gemm_skinny_glu_f8: W8 uint8 [rows, K] e4m3 codes with unit column stride and
+// 16-byte aligned rows, wscale fp32 [rows] contiguous (exactly one scale per row).
+static void check_w8(const Tensor& W8, const Tensor& wscale, const char* who) {
+  TORCH_CHECK(W8.defined() && W8.is_cuda() && W8.dim() == 2 && W8.scalar_type() == at::kByte, who,
+              ": W8 must be a 2-D uint8 device tensor of e4m3 codes");
+  TORCH_CHECK(W8.stride(1) == 1 && W8.stride(0) % 16 == 0 && reinterpret_cast<uintptr_t>(W8.data_ptr()) % 16 == 0, who,
+              ": W8 needs unit column stride and 16-byte aligned rows (leading dimension a multiple of 16)");
+  TORCH_CHECK(wscale.defined() && wscale.is_cuda() && wscale.scalar_type() == at::kFloat && wscale.dim() == 1 &&
+                  wscale.is_contiguous() && wscale.size(0) == W8.size(0),
+              who, ": wscale must be a contiguous fp32 device vector with one scale per row of W8 (", W8.size(0), ")");
+}
+
+// gemm_skinny on fp8 weights (gemm_skinny_f8.hip): Y [M, N] = epilogue((X [M, K] . value(W8 [N, K])^T) * wscale [N]).
+// The operand checks of gemm_skinny plus check_w8; no fall-back to another kernel.
+void gemm_skinny_f8(Tensor X, Tensor W8, Tensor wscale, Tensor Y, c10::optional<Tensor> bias,
+                    c10::optional<Tensor> aux, c10::optional<Tensor> res, int mode) {
+  static const GemmOperandText tx{"gemm_skinny_f8", "gemm_skinny_f8 operands must be device tensors",
+                                  "gemm_skinny_f8 operands need unit column stride (k-contiguous X)",
+                                  "gemm_skinny_f8 leading dimensions must be multiples of 8"};
+  check_gemm_operand(X, tx, 8);
+  check_gemm_operand(Y, tx, 0);
+  check_w8(W8, wscale, "gemm_skinny_f8");
+  TORCH_CHECK(X.scalar_type() == at::kBFloat16, "gemm_skinny_f8 X must be bf16");
+  TORCH_CHECK(Y.scalar_type() == at::kBFloat16 || Y.scalar_type() == at::kFloat,
+              "gemm_skinny_f8 Y must be bf16 or fp32");
+  const int64_t M = X.size(0), K = X.size(1), N = W8.size(0);
+  TORCH_CHECK(W8.size(1) == K, "gemm_skinny_f8 inner dimensions differ: ", K, " vs ", W8.size(1));
+  TORCH_CHECK(Y.size(0) == M && Y.size(1) == N, "gemm_skinny_f8 Y shape mismatch");
+  TORCH_CHECK(M >= 1 && M <= kSkinnyMaxRows, "gemm_skinny_f8 takes 1 .. ", kSkinnyMaxRows, " rows, got ", M);
+  TORCH_CHECK(N % 16 == 0 && K % 32 == 0 && N > 0 && K > 0, "gemm_skinny_f8 needs N % 16 == 0 and K % 32 == 0, got N = ",
+              N, ", K = ", K);
+  TORCH_CHECK(N < (1LL << 31) && K < (1LL << 31), "gemm_skinny_f8 dims too large");
+  TORCH_CHECK(mode == 0 || mode == 1, "gemm_skinny_f8 mode (0 none, 1 gelu)");
+  TORCH_CHECK(X.stride(0) >= K && W8.stride(0) >= K && Y.stride(0) >= N, "gemm_skinny_f8 rows overlap");
+  const GemmEpiOperands ep = check_gemm_epilogue(bias, aux, res, M, N, mode, true, "gemm_skinny_f8 GELU mode needs aux",
+                                                 "aux must be bf16 [M,N] with 16-byte aligned rows");
+  launch_gemm_skinny_f8(bf16_ptr(X), W8.data_ptr<uint8_t>(), wscale.data_ptr<float>(), Y.data_ptr(),
+                        Y.scalar_type() == at::kFloat, (int)M, (int)N, (int)K, X.stride(0), W8.stride(0), Y.stride(0),
+                        ep.bias, ep.aux, ep.ldaux, ep.res, ep.ldres, mode, cur_stream());
+}
+
+// gemm_skinny_glu on fp8 weights (gemm_skinny_glu_f8_kernel): W8 [2F, K], wscale [2F]. Bit for bit gemm_skinny_f8
+// (N = 2F) followed by swiglu_fwd.
+void gemm_skinny_glu_f8(Tensor X, Tensor W8, Tensor wscale, Tensor Y, c10::optional<Tensor> bias) {
+  static const GemmOperandText tx{"gemm_skinny_glu_f8", "gemm_skinny_glu_f8 operands must be device tensors",
+                                  "gemm_skinny_glu_f8 operands need unit column stride (k-contiguous X)",
+                                  "gemm_skinny_glu_f8 leading dimensions must be multiples of 8"};
+  check_gemm_operand(X, tx, 8);
+  check_gemm_operand(Y, tx, 8);
+  check_w8(W8, wscale, "gemm_skinny_glu_f8");
+  TORCH_CHECK(X.scalar_type() == at::kBFloat16 && Y.scalar_type() == at::kBFloat16,
+              "gemm_skinny_glu_f8 X/Y must be bf16");
+  const int64_t M = X.size(0), K = X.size(1), F = Y.size(1);
+  TORCH_CHECK(W8.size(1) == K, "gemm_skinny_glu_f8 inner dimensions differ: ", K, " vs ", W8.size(1));
+  TORCH_CHECK(W8.size(0) == 2 * F, "gemm_skinny_glu_f8 W8 must hold gate and up rows: W8.shape[0] = ", W8.size(0),
+              ", expected 2 * Y.shape[1] = ", 2 * F);
+  TORCH_CHECK(Y.size(0) == M, "gemm_skinny_glu_f8 Y shape mismatch");
+  TORCH_CHECK(M >= 1 && M <= kSkinnyMaxRows, "gemm_skinny_glu_f8 takes 1 .. ", kSkinnyMaxRows, " rows, got ", M);
+  TORCH_CHECK(F % 16 == 0 && K % 32 == 0 && F > 0 && K > 0,
+              "gemm_skinny_glu_f8 needs F % 16 == 0 and K % 32 == 0, got F = ", F, ", K = ", K);
+  TORCH_CHECK(F < (1LL << 30) && K < (1LL << 31), "gemm_skinny_glu_f8 dims too large");
+  TORCH_CHECK(X.stride(0) >= K && W8.stride(0) >= K && Y.stride(0) >= F, "gemm_skinny_glu_f8 rows overlap");
+  const float* bp = nullptr;
+  if (bias.has_value()) {
+    check_dev(*bias, "bias", at::kFloat, 2 * F, 4);
+    bp = bias->data_ptr<float>();
+  }
+  launch_gemm_skinny_glu_f8(bf16_ptr(X), W8.data_ptr<uint8_t>(), wscale.data_ptr<float>(), (uint16_t*)Y.data_ptr(),
+                            (int)M, (int)F, (int)K, X.stride(0), W8.stride(0), Y.stride(0), bp, cur_stream());
+}
+
 // The bf16 operands of swiglu_fwd / swiglu_bwd (swiglu.hip): 2-D device tensors with unit column stride, a row
 // stride that is a multiple of 8 and a 16-byte aligned base (row-strided views pass).
 static void check_glu(const Tensor& t, const char* name, int64_t rows, int64_t cols, const char* who) {
@@ -2392,6 +2463,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("aux") = py::none(), py::arg("res") = py::none(), py::arg("mode") = 0);
   m.def("gemm_skinny_max_rows", []() { return kSkinnyMaxRows; });
   m.def("gemm_skinny_glu", &gemm_skinny_glu, py::arg("X"), py::arg("W"), py::arg("Y"), py::arg("bias") = py::none());
+  m.def("gemm_skinny_f8", &gemm_skinny_f8, py::arg("X"), py::arg("W8"), py::arg("wscale"), py::arg("Y"),
+        py::arg("bias") = py::none(), py::arg("aux") = py::none(), py::arg("res") = py::none(), py::arg("mode") = 0);
+  m.def("gemm_skinny_glu_f8", &gemm_skinny_glu_f8, py::arg("X"), py::arg("W8"), py::arg("wscale"), py::arg("Y"),
+        py::arg("bias") = py::none());
   m.def("swiglu_fwd", &swiglu_fwd, py::arg("H1"), py::arg("A"));
   m.def("swiglu_bwd", &swiglu_bwd, py::arg("dA"), py::arg("H1"), py::arg("dH1"), py::arg("part"), py::arg("db1"),
         py::arg("accumulate") = false);

@@ -226,6 +226,16 @@ void launch_gemm_skinny(const uint16_t* X, const uint16_t* W, void* Y, bool out_
 // launch_gemm_skinny with N = 2F followed by launch_swiglu_fwd.
 void launch_gemm_skinny_glu(const uint16_t* X, const uint16_t* W, uint16_t* Y, int M, int F, int K, int64_t ldx,
                             int64_t ldw, int64_t ldy, const float* bias, hipStream_t st);
+// The fp8-weight forms (gemm_skinny_f8.hip): W8 [N][K] (gated: [2F][K]) OCP e4m3 codes, k-contiguous, rows 16-byte
+// aligned (ldw % 16 == 0), wscale fp32 [N] ([2F]) one power-of-two scale per output row; the result is
+// epilogue((X . value(W8)^T) * wscale). Everything else as the two launchers above, whose partition rules they keep
+// (a function of (N, K) alone); launch_gemm_skinny_glu_f8 equals launch_gemm_skinny_f8 with N = 2F followed by
+// launch_swiglu_fwd bit for bit.
+void launch_gemm_skinny_f8(const uint16_t* X, const uint8_t* W8, const float* wscale, void* Y, bool out_f32, int M,
+                           int N, int K, int64_t ldx, int64_t ldw, int64_t ldy, const float* bias, const uint16_t* aux,
+                           int64_t ldaux, const uint16_t* res, int64_t ldres, int mode, hipStream_t st);
+void launch_gemm_skinny_glu_f8(const uint16_t* X, const uint8_t* W8, const float* wscale, uint16_t* Y, int M, int F,
+                               int K, int64_t ldx, int64_t ldw, int64_t ldy, const float* bias, hipStream_t st);
 // SwiGLU (swiglu.hip, definition in mlt_swiglu.h): H1 [rows][ldh >= 2F] bf16 = gate | up, A [rows][F], F % 8 == 0,
 // row strides multiples of 8, 16-byte aligned bases. The backward also writes part [swiglu_bwd_row_blocks(rows)][2F]
 // fp32, the column sums of the rounded dH1 per block of 64 rows (reduced by launch_reduce_rows).

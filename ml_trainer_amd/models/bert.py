@@ -323,14 +323,17 @@ class BertLayer(nn.Module):
                 x = T.post_norm_block(core, x, params, _norm_args(norm), drop)
         return x, n
 
-    def ffn_torch(self, x, round_bf16=False):
+    def ffn_torch(self, x, round_bf16=False, lin=None):
         """``ffn2(act(ffn1(x)))`` in plain torch: GELU, or the SwiGLU of ops/swiglu.py on ffn1's gate | up columns.
-        ``round_bf16`` (the eager bf16 baseline): h1 and a rounded to bf16, as the native path stores them."""
-        h1 = self.ffn1(x)
+        ``round_bf16`` (the eager bf16 baseline): h1 and a rounded to bf16, as the native path stores them.
+        ``lin(module, x)`` (default: call the module) applies the two linears: the decode steps on fp8 weights."""
+        if lin is None:
+            lin = lambda m, v: m(v)
+        h1 = lin(self.ffn1, x)
         if self.c.ffn != "swiglu":
-            return self.ffn2(F.gelu(h1))
+            return lin(self.ffn2, F.gelu(h1))
         from ml_trainer_amd.ops.swiglu import swiglu
-        return self.ffn2(swiglu(h1.to(torch.bfloat16) if round_bf16 else h1))
+        return lin(self.ffn2, swiglu(h1.to(torch.bfloat16) if round_bf16 else h1))
 
     def forward_reference(self, x, mask, B, S, drop=None, attn_drop=None, packed=None, rope=None):
         """fp32 torch reference. x [B*S, h]; mask [B, S] bool (True = valid key); drop and attn_drop
@@ -836,7 +839,7 @@ class BertLMHeadModel(BertForMaskedLM):
 
     @torch.no_grad()
     def prefill(self, input_ids, attention_mask=None, max_len: Optional[int] = None, cache=None, kv_cache=None,
-                pool=None):
+                pool=None, weights=None):
         """Run the prompt ``input_ids`` [B, S] (right-padded; lengths from ``attention_mask`` or ``pad_id``)
         through the padded causal forward, layer by layer, keep every layer's K / V in a cache of ``max_len``
         rows per sequence (default ``config.max_position``) and return the ``DecodeState``: the cache with
@@ -849,10 +852,13 @@ class BertLMHeadModel(BertForMaskedLM):
         ``ops.decode.PagePool`` of this model's layers and KV heads on the prompts' device): the state's cache is a
         ``PagedKVCache`` over it with a table of ``ceil(max(max_len or S, S) / 64)`` pages, of which it owns those of
         the S prompt rows; ``decode_step`` reserves more as the sequences grow, past ``max_len`` too, and
-        ``state.release()`` returns them. Not with ``cache=`` or ``kv_cache="fp8"``."""
+        ``state.release()`` returns them. Not with ``cache=`` or ``kv_cache="fp8"``. ``weights``: ``None`` /
+        ``"bf16"`` or ``"fp8"``, recorded in the state for ``decode_step`` and ``extend`` (``generate`` documents the
+        option); the prompt itself always runs on the bf16 tile GEMMs and the full weights."""
         from ml_trainer_amd.ops import decode as DC
         c = self.config
         fp8 = DC.check_kv_cache(kv_cache)
+        DC.check_weights(weights)
         B, S = input_ids.shape
         if pool is not None:
             self._check_pool(pool, input_ids.device, fp8, cache)
@@ -909,7 +915,7 @@ class BertLMHeadModel(BertForMaskedLM):
         x = x.index_select(0, self._last_rows(lens, B, S, dev))
         if c.pre_ln:  # rows are independent: the final norm of the last real rows only
             x = _norm_native(x, self.final_ln) if x.is_cuda else self.final_ln(x)
-        return DC.DecodeState(cache, x, width=S)
+        return DC.DecodeState(cache, x, width=S, weights=weights)
 
     def _check_pool(self, pool, dev, fp8=False, cache=None):
         """The ``ValueError`` cases of ``prefill(pool=)`` / ``generate(pool=)``."""
@@ -942,15 +948,16 @@ class BertLMHeadModel(BertForMaskedLM):
             return M.decode_logits(state.hidden, self.mlm_params())  # B rows, no gather into a 256-row tile
         return self.mlm_logits(state.hidden, torch.arange(B, device=state.hidden.device))
 
-    def _ffn1_decode(self, L, x):
+    def _ffn1_decode(self, L, x, fp8=False):
         """act(ffn1(x)) [B, F] bf16 of a native decode step: FFN1 with the GELU epilogue, or under SwiGLU the gated
-        skinny GEMM (``ops.decode.linear_small_glu``)."""
+        skinny GEMM (``ops.decode.linear_small_glu``). ``fp8``: on the fp8 weight rows."""
         from ml_trainer_amd.ops import decode as DC
         from ml_trainer_amd.ops.transformer import bf16_weight
+        w8 = DC.fp8_weight_rows(L.ffn1.weight) if fp8 else None
         if self.config.ffn == "swiglu":
-            return DC.linear_small_glu(x, bf16_weight(L.ffn1.weight), L.ffn1.bias)
+            return DC.linear_small_glu(x, bf16_weight(L.ffn1.weight), L.ffn1.bias, w8=w8)
         pre = torch.empty(x.shape[0], L.ffn1.weight.shape[0], dtype=torch.bfloat16, device=x.device)
-        return DC.linear_small(x, bf16_weight(L.ffn1.weight), L.ffn1.bias, gelu_aux=pre)
+        return DC.linear_small(x, bf16_weight(L.ffn1.weight), L.ffn1.bias, gelu_aux=pre, w8=w8)
 
     @torch.no_grad()
     def decode_step(self, state, token_ids=None):
@@ -967,6 +974,7 @@ class BertLMHeadModel(BertForMaskedLM):
         from ml_trainer_amd.ops import decode as DC
         c = self.config
         cache = state.cache
+        fp8w = DC.check_weights(state.weights)
         ids = token_ids.reshape(-1).to(torch.int64).contiguous()
         B = ids.numel()
         paged = isinstance(cache, DC.PagedKVCache)
@@ -984,54 +992,66 @@ class BertLMHeadModel(BertForMaskedLM):
                         min(cache.Smax, c.max_position) if paged else cache.Smax, pos=cache.pos)
             if paged:
                 x = self._decode_layers(x, lambda l, qkv: DC.attn_decode(
-                    qkv, cache.kv[l], cache.pos, c.heads, rope=self.rope_table, block_table=cache.block_table))
+                    qkv, cache.kv[l], cache.pos, c.heads, rope=self.rope_table, block_table=cache.block_table), fp8w)
             else:
                 x = self._decode_layers(x, lambda l, qkv: DC.attn_decode(
-                    qkv, cache.kv[l], cache.pos, c.heads, rope=self.rope_table, kv_scale=cache.scale(l)))
+                    qkv, cache.kv[l], cache.pos, c.heads, rope=self.rope_table, kv_scale=cache.scale(l)), fp8w)
         else:
             x = self._embed_torch(ids, torch.zeros_like(ids), cache.pos.long())
             if paged:
                 x = self._decode_layers_torch(x, lambda l, qkv: DC.attn_decode_paged_reference(
-                    qkv, cache.kv[l], cache.block_table, cache.pos, c.heads, rope=self.rope_table))
+                    qkv, cache.kv[l], cache.block_table, cache.pos, c.heads, rope=self.rope_table), fp8w)
             else:
                 x = self._decode_layers_torch(x, lambda l, qkv: DC.attn_decode_reference(
-                    qkv, cache.kv[l], cache.pos, c.heads, rope=self.rope_table, kv_scale=cache.scale(l)))
+                    qkv, cache.kv[l], cache.pos, c.heads, rope=self.rope_table, kv_scale=cache.scale(l)), fp8w)
         cache.pos.add_(1)
         state.hidden = x
         if state.width is not None:
             state.width += 1
         return self._state_logits(state)
 
-    def _decode_layers(self, x, attn):
+    def _decode_layers(self, x, attn, fp8=False):
         """The native layer walk of ``decode_step`` and ``extend`` on the embedded bf16 rows ``x`` [M, h]: every kernel
         works row by row except ``attn(l, qkv)``, the attention of layer l over the cache. Returns the rows
-        ``state.hidden`` holds (normed, as after a post-LN layer)."""
+        ``state.hidden`` holds (normed, as after a post-LN layer). ``fp8`` (``DecodeState.weights == "fp8"``): the four
+        layer linears read ``ops.decode.fp8_weight_rows`` of their weights; the attention call is untouched."""
         from ml_trainer_amd.ops import decode as DC
         from ml_trainer_amd.ops import transformer as T
         c = self.config
+        w8 = (lambda m: DC.fp8_weight_rows(m.weight)) if fp8 else (lambda m: None)
         x = _norm_native(x, self.emb_ln)
         for l, L in enumerate(self.layers):  # (x, n and the sums as in prefill)
             n = _norm_native(x, L.ln1) if c.pre_ln else x
-            qkv = DC.linear_small(n, T.bf16_weight(L.qkv.weight), L.qkv.bias)
+            qkv = DC.linear_small(n, T.bf16_weight(L.qkv.weight), L.qkv.bias, w8=w8(L.qkv))
             ctx = attn(l, qkv)
-            y = DC.linear_small(ctx, T.bf16_weight(L.out.weight), L.out.bias, res=x)
+            y = DC.linear_small(ctx, T.bf16_weight(L.out.weight), L.out.bias, res=x, w8=w8(L.out))
             x = y if c.pre_ln else _norm_native(y, L.ln1)
             n = _norm_native(x, L.ln2) if c.pre_ln else x
-            y = DC.linear_small(self._ffn1_decode(L, n), T.bf16_weight(L.ffn2.weight), L.ffn2.bias, res=x)
+            y = DC.linear_small(self._ffn1_decode(L, n, fp8), T.bf16_weight(L.ffn2.weight), L.ffn2.bias, res=x,
+                                w8=w8(L.ffn2))
             x = y if c.pre_ln else _norm_native(y, L.ln2)
         if c.pre_ln:
             x = _norm_native(x, self.final_ln)
         return x
 
-    def _decode_layers_torch(self, x, attn):
-        """``_decode_layers`` on the modules (the CPU path), from the embedding sum ``x``."""
+    def _decode_layers_torch(self, x, attn, fp8=False):
+        """``_decode_layers`` on the modules (the CPU path), from the embedding sum ``x``. ``fp8``: the four layer
+        linears as ``F.linear`` on their dequantised fp8 weight rows, otherwise the same operations in the same order."""
         c = self.config
+        if fp8:
+            from ml_trainer_amd.ops import decode as DC
+
+            def lin(m, v):
+                return F.linear(v, DC.w8_dequantized(DC.fp8_weight_rows(m.weight), v.dtype), m.bias)
+        else:
+            def lin(m, v):
+                return m(v)
         x = self.emb_ln(x)
         for l, L in enumerate(self.layers):
             n = L.ln1(x) if c.pre_ln else x
-            y = L.out(attn(l, L.qkv(n))) + x
+            y = lin(L.out, attn(l, lin(L.qkv, n))) + x
             x = y if c.pre_ln else L.ln1(y)
-            y = L.ffn_torch(L.ln2(x) if c.pre_ln else x) + x
+            y = L.ffn_torch(L.ln2(x) if c.pre_ln else x, lin=lin) + x
             x = y if c.pre_ln else L.ln2(y)
         return self._final_norm(x)
 
@@ -1061,6 +1081,7 @@ class BertLMHeadModel(BertForMaskedLM):
         from ml_trainer_amd.ops import decode as DC
         c = self.config
         cache = state.cache
+        fp8w = DC.check_weights(state.weights)
         if cache.scales is not None:
             raise ValueError("extend takes a bf16 cache: the fp8 cache has no multi-token attention kernel")
         if isinstance(cache, DC.PagedKVCache):
@@ -1089,11 +1110,11 @@ class BertLMHeadModel(BertForMaskedLM):
                                               TR.bf16_weight(self.token_type_embeddings.weight), x, cache.Smax,
                                               pos=tpos.contiguous())
                 x = self._decode_layers(x, lambda l, qkv: DC.attn_append(qkv, cache.kv[l], base, B, c.heads,
-                                                                         rope=self.rope_table))
+                                                                         rope=self.rope_table), fp8w)
             else:
                 x = self._embed_torch(ids, torch.zeros_like(ids), tpos.long())
                 x = self._decode_layers_torch(x, lambda l, qkv: DC.attn_append_reference(
-                    qkv, cache.kv[l], base, B, c.heads, rope=self.rope_table))
+                    qkv, cache.kv[l], base, B, c.heads, rope=self.rope_table), fp8w)
             sel = (counts.long() - 1 - t0)  # token counts - 1, where it falls in this piece (on the device)
             last = x.view(B, Tp, -1)[ar, sel.clamp(0, Tp - 1)]
             state.hidden = torch.where(((sel >= 0) & (sel < Tp))[:, None], last, state.hidden.to(last.dtype))
@@ -1116,10 +1137,11 @@ class BertLMHeadModel(BertForMaskedLM):
             state.hidden = torch.where(live[:, None], state.hidden, hidden.to(state.hidden.dtype))
 
     def _check_generate(self, input_ids, max_new_tokens, temperature, top_k, top_p=None, sampler=None, graph=False,
-                        return_logits=False, kv_cache=None):
-        from ml_trainer_amd.ops.decode import check_kv_cache
+                        return_logits=False, kv_cache=None, weights=None):
+        from ml_trainer_amd.ops.decode import check_kv_cache, check_weights
         S = input_ids.shape[1]
         check_kv_cache(kv_cache)
+        check_weights(weights)
         if sampler not in (None, "device"):
             raise ValueError(f"sampler must be None (the torch sampler) or 'device', got {sampler!r}")
         if top_p is not None:
@@ -1209,23 +1231,26 @@ class BertLMHeadModel(BertForMaskedLM):
         out = (sampler.tokens, sampler.lengths)
         return out + (torch.stack(kept, 1),) if return_logits else out
 
-    def _decode_signature(self):
+    def _decode_signature(self, weights=None):
         """What a captured decode step baked in of the parameters: an in-place edit bumps ``_version`` (and makes
-        ``bf16_weight`` / ``padded_decoder`` hand out new tensors), a re-allocation moves ``data_ptr``."""
+        ``bf16_weight`` / ``padded_decoder`` / ``fp8_weight_rows`` hand out new tensors), a re-allocation moves
+        ``data_ptr``. ``weights="fp8"`` adds the format (which linears a step launches); without it no value changes."""
         c = self.config  # (the block kind decides which kernels a step launches)
         gqa = (c.kv_heads,) if c.num_kv_heads != c.heads else ()  # (the attention launch and the cache shape)
         ffn = (c.ffn,) if c.ffn != "gelu" else ()  # (which FFN1 launch a step makes)
-        return (c.pre_ln, c.norm) + gqa + ffn + tuple((p._version, p.data_ptr()) for p in self.parameters())
+        w8 = ("w-fp8",) if weights == "fp8" else ()
+        return (c.pre_ln, c.norm) + gqa + ffn + w8 + tuple((p._version, p.data_ptr()) for p in self.parameters())
 
-    def _graphed_decoder(self, B, Smax, T, dev, kv_cache=None):
+    def _graphed_decoder(self, B, Smax, T, dev, kv_cache=None, weights=None):
         key = (B, Smax, T, str(dev)) + (("fp8",) if kv_cache == "fp8" else ())  # (the cache a capture baked in)
+        key += ("w-fp8",) if weights == "fp8" else ()  # (and the weight tensors its linears read)
         decoders = self.__dict__.setdefault("_graphed_decoders", {})
         dec = decoders.get(key)
-        sig = self._decode_signature()
+        sig = self._decode_signature(weights)
         if dec is None or dec.signature != sig:
             decoders.pop(key, None)  # free the stale graph's buffers before the new capture
             del dec
-            dec = decoders[key] = GraphedDecoder(self, B, Smax, T, dev, sig, kv_cache)
+            dec = decoders[key] = GraphedDecoder(self, B, Smax, T, dev, sig, kv_cache, weights)
             self._decode_graph_captures = self.decode_graph_captures + 1
         return dec
 
@@ -1238,7 +1263,8 @@ class BertLMHeadModel(BertForMaskedLM):
     def generate(self, input_ids, max_new_tokens: int, attention_mask=None, temperature: float = 0.0,
                  top_k: Optional[int] = None, eos_id: Optional[int] = None, seed: Optional[int] = None,
                  return_logits: bool = False, top_p: Optional[float] = None, sampler: Optional[str] = None,
-                 graph: bool = False, kv_cache: Optional[str] = None, past=None, pool=None):
+                 graph: bool = False, kv_cache: Optional[str] = None, past=None, pool=None,
+                 weights: Optional[str] = None):
         """Continue the prompts ``input_ids`` [B, S] (right-padded, ragged lengths allowed: sequence b's new
         tokens continue at position ``len_b``) by ``max_new_tokens`` tokens with a key/value cache: one
         ``prefill``, then one ``decode_step`` per token. Returns ``(tokens [B, max_new_tokens], lengths [B])``,
@@ -1264,6 +1290,16 @@ class BertLMHeadModel(BertForMaskedLM):
         is ``C.attn_decode_f8`` over the dequantised rows, the prompt is quantised by ``C.kv_fill_f8``. Works eager and
         graph-replayed, with every block kind, ``rotary`` and ``kv_heads``.
 
+        ``weights="fp8"`` (opt-in; ``None`` / ``"bf16"`` change nothing): weight-only quantisation of the decode steps.
+        The four layer linears of every step (QKV, out-projection, FFN1 including the gated form, FFN2) read e4m3
+        codes and one power-of-two scale per output row (``ops.decode.weight_quantize_reference``, made once per
+        weight version by ``fp8_weight_rows``) through ``C.gemm_skinny_f8`` / ``C.gemm_skinny_glu_f8``: half the
+        bytes of a step's largest stream, activations bf16, accumulation fp32. A step is exactly the bf16 step on
+        the dequantised weights. Not covered: the prompt (compute-bound: the bf16 tile GEMMs on the full weights),
+        the head (the transform and the tied vocabulary decoder stay bf16; the decoder shares its table with the
+        embedding lookup) and memory (the fp32 and bf16 weights remain, the codes are a third copy). Works eager and
+        graph-replayed, with every cache kind, ``past=`` (``None`` keeps the state's own setting) and ``pool=``.
+
         ``past`` (a ``DecodeState`` of an earlier ``prefill`` / ``generate`` turn over the same batch): ``input_ids``
         are then the NEW turn only; they enter ``past``'s cache through ``extend`` instead of ``prefill``, the first
         logits are those of each sequence's last real new token, and decoding continues into ``past``'s cache (the
@@ -1278,7 +1314,7 @@ class BertLMHeadModel(BertForMaskedLM):
         cache's alone, and the state stays the caller's to ``release()``. Tokens and logits are those of the
         contiguous cache, bit for bit while fewer than 256 rows are cached (one active split)."""
         self._check_generate(input_ids, max_new_tokens, temperature, top_k, top_p, sampler, graph, return_logits,
-                             kv_cache)
+                             kv_cache, weights)
         B, S = input_ids.shape
         dev = input_ids.device
         from ml_trainer_amd.ops.decode import PagedKVCache
@@ -1293,6 +1329,8 @@ class BertLMHeadModel(BertForMaskedLM):
                 raise ValueError("generate(past=) cannot run graph=True: the captured decoder owns its cache")
             if kv_cache == "fp8" or past.cache.scales is not None:
                 raise ValueError("generate(past=) takes a bf16 cache: extend has no fp8 form")
+            if weights is not None:
+                past.weights = weights
             if isinstance(past.cache, PagedKVCache):
                 lens = self._lengths(input_ids, attention_mask)
                 self._feed_paged(past, input_ids, torch.full((B,), S, device=dev) if lens is None else lens)
@@ -1303,11 +1341,12 @@ class BertLMHeadModel(BertForMaskedLM):
                 self.extend(past, input_ids, counts=self._lengths(input_ids, attention_mask))
             state = past
         elif graph:
-            dec = self._graphed_decoder(B, S + max_new_tokens, max_new_tokens, dev, kv_cache)
+            dec = self._graphed_decoder(B, S + max_new_tokens, max_new_tokens, dev, kv_cache, weights)
             return dec.generate(self, input_ids, attention_mask,
                                 self._sampler_params(temperature, top_k, top_p, eos_id, seed))
         else:
-            state = self.prefill(input_ids, attention_mask, max_len=S + max_new_tokens, kv_cache=kv_cache, pool=pool)
+            state = self.prefill(input_ids, attention_mask, max_len=S + max_new_tokens, kv_cache=kv_cache, pool=pool,
+                                 weights=weights)
         try:
             if sampler == "device":
                 st = self._new_sampler(B, max_new_tokens, dev, temperature, top_k, top_p, eos_id, seed)
@@ -1337,11 +1376,12 @@ class BertLMHeadModel(BertForMaskedLM):
     def generate_reference(self, input_ids, max_new_tokens: int, attention_mask=None, temperature: float = 0.0,
                            top_k: Optional[int] = None, eos_id: Optional[int] = None, seed: Optional[int] = None,
                            return_logits: bool = False, top_p: Optional[float] = None, sampler: Optional[str] = None,
-                           kv_cache: Optional[str] = None):
+                           kv_cache: Optional[str] = None, weights: Optional[str] = None):
         """``generate`` without any cache: ``forward_reference`` over the growing sequence, once per token.
-        ``kv_cache`` is checked as ``generate`` checks it and changes nothing here: there is no cache to quantise, so
-        this stays the unquantised oracle of either format."""
-        self._check_generate(input_ids, max_new_tokens, temperature, top_k, top_p, sampler, kv_cache=kv_cache)
+        ``kv_cache`` and ``weights`` are checked as ``generate`` checks them and change nothing here: there is no
+        cache and no decode step to quantise, so this stays the unquantised oracle of every format."""
+        self._check_generate(input_ids, max_new_tokens, temperature, top_k, top_p, sampler, kv_cache=kv_cache,
+                             weights=weights)
         B, S = input_ids.shape
         dev = input_ids.device
         lens = self._lengths(input_ids, attention_mask)
@@ -1376,16 +1416,16 @@ class GraphedDecoder:
     ``MLT_DECODE_SPLIT`` (``ops.decode.decode_attn_path``: the split attention's two launches and its workspace are then
     nodes and pool memory of the graph) are read while capturing. Not supported: ``return_logits``, a graph for ``prefill``."""
 
-    def __init__(self, model, B, Smax, T, dev, signature, kv_cache=None):
+    def __init__(self, model, B, Smax, T, dev, signature, kv_cache=None, weights=None):
         import time
         from ml_trainer_amd.ops import decode as DC
         c = model.config
         self.signature = signature
         self.B, self.Smax, self.T = B, Smax, T
-        self.kv_cache = kv_cache
+        self.kv_cache, self.weights = kv_cache, weights
         self.cache = DC.KVCache.allocate(c.layers, B, c.num_kv_heads, Smax, dev, kv_cache=kv_cache)
         self.sampler = DC.SamplerState.allocate(B, T, dev)
-        self.state = DC.DecodeState(self.cache, None)
+        self.state = DC.DecodeState(self.cache, None, weights=weights)
         self.graph = None
         self.capture_seconds = 0.0
         if T < 2:
@@ -1396,7 +1436,8 @@ class GraphedDecoder:
             DC.sample_step(model.decode_step(self.state, self.sampler.next_ids), V, self.sampler)
 
         # The zeroed cache and sampler are a valid state (token 0 at position 0, column 0): the eager run warms the
-        # bf16 weight copies and the allocator, the capture records the same launches. Both leave marks in the
+        # bf16 weight copies (the fp8 weight rows under weights="fp8", whose quantiser copies between host and device
+        # and must not run inside a capture) and the allocator, the capture records the same launches. Both leave marks in the
         # state; every generation starts by resetting it.
         torch.cuda.synchronize(dev)
         t0 = time.perf_counter()
@@ -1419,7 +1460,7 @@ class GraphedDecoder:
         self.sampler.reset()
         self.sampler.set_params(**params)
         return model.decode_step(model.prefill(input_ids, attention_mask, max_len=self.Smax, cache=self.cache,
-                                               kv_cache=self.kv_cache))
+                                               kv_cache=self.kv_cache, weights=self.weights))
 
     def run(self, model, first_logits):
         """The token loop: one eager ``sample_step`` on the prompt's logits, then ``T - 1`` replays. Results are in

@@ -38,6 +38,14 @@ weight-streaming kernel ``C.gemm_skinny`` (csrc/kernels/gemm_skinny.hip) or to t
 kernel every kernel of a step works row by row, so a sequence's logits do not depend on the batch it is decoded in.
 ``linear_small_glu`` is the gated FFN1 of a SwiGLU model's step: ``C.gemm_skinny_glu``, or the unfused pair.
 
+fp8 layer weights (``DecodeState.weights = "fp8"``, set by ``prefill`` / ``generate(weights="fp8")``): weight-only
+quantisation of the four layer linears of a decode step. ``weight_quantize_reference`` defines the format (e4m3
+codes and one power-of-two scale per output row of the bf16-rounded weight), ``fp8_weight_rows`` caches it per
+parameter, and ``linear_small(w8=)`` / ``linear_small_glu(w8=)`` launch ``C.gemm_skinny_f8`` /
+``C.gemm_skinny_glu_f8`` (csrc/kernels/gemm_skinny_f8.hip), which stream half the bytes. The quantised layer is
+exactly the bf16 layer on the dequantised weight. Prefill and the head keep the bf16 weights, and the fp32 masters
+and bf16 copies remain: the option halves a step's weight traffic, it does not save memory.
+
 ``sample_step`` is the on-device sampler (csrc/kernels/sample.hip): greedy / temperature / top-k / top-p and the
 token / EOS bookkeeping of ``generate`` in one launch per step, over a ``SamplerState``. Its result is defined in
 integers (the definition is the header of csrc/include/mlt_sample.h and the docstring of
@@ -129,7 +137,8 @@ def kv_quantize_reference(x):
     ``d = 1`` where ``amax`` is 0 or not finite (a NaN in the row makes it so); ``code_d = e4m3(x_d * 2^-e)``, round to
     nearest even, saturating at +-448, NaN -> the NaN code. The scaled ``amax`` lies in [128, 256): nothing
     saturates, and the product and ``value(code) * d`` are exact (one corner: an ``amax`` in fp32's last binade whose
-    scaled value rounds up to 256 dequantises to ``256 * 2^120``, an infinity)."""
+    scaled value rounds up to 256 dequantises to ``256 * 2^120``, an infinity). The body is generic in the last
+    dimension: ``weight_quantize_reference`` applies it to the [N, K] rows of a linear layer's weight."""
     xf = x.float()
     amax = xf.abs().amax(-1)
     e = (((amax.view(torch.int32) >> 23) & 0xFF) - 134).clamp(min=-126)
@@ -143,6 +152,58 @@ def kv_quantize_reference(x):
 def kv_dequantize_reference(codes, scales):
     """fp32 [..., 64] ``= value(code) * scale`` of uint8 e4m3 ``codes`` [..., 64] and fp32 ``scales`` [...]: exact."""
     return codes.view(torch.float8_e4m3fn).float() * scales[..., None]
+
+
+WEIGHT_FORMATS = (None, "bf16", "fp8")
+
+
+def check_weights(weights) -> bool:
+    """True for fp8 layer weights, False for ``None`` / ``"bf16"`` (the weights as they always were); anything else
+    raises."""
+    if weights not in WEIGHT_FORMATS:
+        raise ValueError(f"weights must be None, 'bf16' or 'fp8', got {weights!r}")
+    return weights == "fp8"
+
+
+def weight_quantize_reference(w):
+    """(codes uint8 [N, K], scales fp32 [N]) of a linear layer's weight ``w`` [N, K]: the definition of the fp8
+    weight format of the decode steps. ``w`` is first rounded to bf16 (the weight the bf16 step multiplies by, and
+    what makes every device produce the same codes), then every output row is quantised by the rules of
+    ``kv_quantize_reference`` with K in place of 64: one power-of-two scale ``d = 2^max(E - 7, -126)`` per row,
+    ``code = e4m3(w * 2^-e)``. ``value(code)`` has 3 mantissa bits, so it is a bf16 number, and ``d`` is a power of
+    two, so a layer on these weights is EXACTLY the bf16 layer whose weight is
+    ``kv_dequantize_reference(codes, scales)``: ``|dequant - bf16(w)| <= 2^-4 |bf16(w)| + 2^-10 d`` per entry
+    (half a unit of 3 mantissa bits, or half the smallest subnormal ``2^-9`` of the scaled row)."""
+    return kv_quantize_reference(w.to(torch.bfloat16))
+
+
+def fp8_weight_rows(p: torch.Tensor):
+    """``weight_quantize_reference`` of parameter ``p`` [N, K] on ``p``'s device, cached on the parameter and keyed
+    as ``bf16_weight`` keys its copy (version counters and address): a captured graph sees stable tensors until
+    the weight changes. Quantising runs on the CPU, from the bf16 copy, and the result is copied over (the float8
+    casts are not relied on on the GPU build); once per weight version, not a hot path."""
+    from ml_trainer_amd.ops.transformer import bf16_weight
+    from ml_trainer_amd.utils.flat import FlatParams
+    fp = FlatParams.owner(p)
+    key = ((fp.generation, fp.data._version, p._version) if fp is not None else p._version, p.data_ptr())
+    cache = getattr(p, "_mlt_f8_rows", None)
+    if cache is not None and cache[0] == key:
+        return cache[1]
+    codes, scales = weight_quantize_reference(bf16_weight(p).detach().cpu())
+    w8 = (codes.to(p.device).contiguous(), scales.to(p.device).contiguous())
+    p._mlt_f8_rows = (key, w8)
+    return w8
+
+
+def w8_dequantized(w8, dtype):
+    """The dequantised weight of a ``(codes, scales)`` pair on its device in ``dtype`` (exact in bf16 and fp32),
+    kept beside the codes: what a decode linear multiplies by where it does not take the fp8 kernel."""
+    codes, scales = w8
+    cache = getattr(codes, "_mlt_deq", None)
+    if cache is None or cache.dtype != dtype:
+        cache = kv_dequantize_reference(codes.cpu(), scales.cpu()).to(dtype).to(codes.device)
+        codes._mlt_deq = cache
+    return cache
 
 
 class PagePool:
@@ -253,10 +314,14 @@ class DecodeState:
     sequence's last token, from which the next token's logits come. ``width`` is a host-side upper bound of every
     ``pos[b]`` (the prompt's width plus the columns fed since), kept so that ``generate(past=)`` can check the room
     left in the cache without reading ``pos`` back; ``None``: not recorded. Over a ``PagedKVCache`` it is what
-    ``decode_step`` reserves pages by, and ``release()`` returns the pages to the pool."""
+    ``decode_step`` reserves pages by, and ``release()`` returns the pages to the pool. ``weights``: ``None`` /
+    ``"bf16"`` (the layer weights as they are) or ``"fp8"`` (``decode_step`` and ``extend`` take the four layer
+    linears through ``fp8_weight_rows``; the head and everything in ``prefill`` stay bf16), checked by
+    ``check_weights`` where a step reads it."""
     cache: KVCache
     hidden: torch.Tensor
     width: Optional[int] = None
+    weights: Optional[str] = None
 
     @property
     def pos(self) -> torch.Tensor:
@@ -494,13 +559,25 @@ def decode_linear_path(M: int, N: int, K: int) -> str:
     return "gemm"
 
 
-def linear_small(x, w16, bias=None, gelu_aux=None, res=None, out=None):
+def linear_small(x, w16, bias=None, gelu_aux=None, res=None, out=None, w8=None):
     """``y = epilogue(x . w16^T)`` for the few rows of a decode step: x [M, K] bf16, w16 [N, K] bf16 (the layout
     of ``bf16_weight``), fp32 ``bias`` [N], ``gelu_aux`` [M, N] bf16 (GELU epilogue; receives the pre-activation),
     ``res`` [M, N] bf16 added last, ``out`` [M, N] bf16 or fp32 (default: a new bf16 tensor). The skinny kernel
     where ``decode_linear_path`` says so, otherwise the launches of ``transformer.linear_fwd``. On the CPU:
-    ``F.linear`` and the same epilogue in fp32."""
+    ``F.linear`` and the same epilogue in fp32.
+    ``w8`` (the ``(codes, scales)`` pair of ``fp8_weight_rows``; ``w16`` is then not read and may be ``None``): the
+    layer on the dequantised weight. Where the path is ``"skinny"`` it is ``C.gemm_skinny_f8``
+    (csrc/kernels/gemm_skinny_f8.hip), which streams the codes; elsewhere the dequantised bf16 weight goes through
+    the path above, so it is the same function at every M; on the CPU ``F.linear`` on the dequantised fp32 weight."""
     M, K = x.shape
+    if w8 is not None:
+        if x.is_cuda and decode_linear_path(M, w8[0].shape[0], K) == "skinny":
+            if out is None:
+                out = torch.empty(M, w8[0].shape[0], dtype=torch.bfloat16, device=x.device)
+            require_native().gemm_skinny_f8(x, w8[0], w8[1], out, bias=bias, aux=gelu_aux, res=res,
+                                            mode=1 if gelu_aux is not None else 0)
+            return out
+        w16 = w8_dequantized(w8, torch.bfloat16 if x.is_cuda else torch.float32)
     N = w16.shape[0]
     if not x.is_cuda:
         y = F.linear(x.float(), w16.float(), None if bias is None else bias.float())
@@ -523,23 +600,29 @@ def linear_small(x, w16, bias=None, gelu_aux=None, res=None, out=None):
     return out
 
 
-def linear_small_glu(x, w16, bias=None):
+def linear_small_glu(x, w16, bias=None, w8=None):
     """The gated FFN1 of a SwiGLU decode step: ``swiglu(x . w16^T + bias)`` [M, F] for x [M, K] bf16 and w16 [2F, K]
     bf16 (gate rows, then up rows: ops/swiglu.py), fp32 ``bias`` [2F]. Where ``decode_linear_path(M, F, K)`` says
     ``"skinny"`` it is ONE launch, ``C.gemm_skinny_glu`` (two weight streams, the activation in the epilogue);
     otherwise, and with ``MLT_DECODE_GLU=0`` (read per call: the A/B baseline), ``linear_small`` into the [M, 2F]
     intermediate followed by ``swiglu_fwd``. The two agree bit for bit. On the CPU: ``F.linear`` and the torch
-    definition."""
+    definition. ``w8`` as in ``linear_small``: the one launch is then ``C.gemm_skinny_glu_f8``, and the unfused pair
+    and the CPU path take the dequantised weight."""
     from ml_trainer_amd.ops import swiglu as SG
     M, K = x.shape
-    Fh = w16.shape[0] // 2
+    Fh = (w16 if w8 is None else w8[0]).shape[0] // 2
     if not x.is_cuda:
+        if w8 is not None:
+            w16 = w8_dequantized(w8, torch.float32)
         return SG.swiglu_reference(F.linear(x.float(), w16.float(), None if bias is None else bias.float()))
     if os.environ.get("MLT_DECODE_GLU", "1") != "0" and decode_linear_path(M, Fh, K) == "skinny":
         out = torch.empty(M, Fh, dtype=torch.bfloat16, device=x.device)
-        require_native().gemm_skinny_glu(x, w16, out, bias=bias)
+        if w8 is not None:
+            require_native().gemm_skinny_glu_f8(x, w8[0], w8[1], out, bias=bias)
+        else:
+            require_native().gemm_skinny_glu(x, w16, out, bias=bias)
         return out
-    return SG.swiglu_fwd(linear_small(x, w16, bias))
+    return SG.swiglu_fwd(linear_small(x, w16, bias, w8=w8))
 
 
 def fill_from_prefill(cache: KVCache, layer: int, qkv, lens: Optional[torch.Tensor], B: int, S: int,
